@@ -6,14 +6,20 @@ Metric (BASELINE.json): real-time factor (+ utterances/s) of UNIVERSE++ 16 kHz, 
   step      = one `enhance` call over one batch of synthetic 4 s utterances (default batch 1 per GPU = configs[1])
   value     = whole-job audio seconds enhanced per wall second (inputs already resident in HBM), measured in the
               PRODUCT DEFAULT mode (`model.check_status = True`: the stream is synchronised and the device status word
-              read after every call); the free-running mode (no host sync inside the loop) is reported beside it
-  roofline  = the dominant conv kernel (the one with the most device time per enhance among conv_direct_kernel,
+              read after every call); with --full the free-running mode (no host sync inside the loop) is reported beside it
+  roofline  = (--full) the dominant conv kernel (the one with the most device time per enhance among conv_direct_kernel,
               conv_mfma_kernel and conv_chain_kernel): algorithmic FLOPs of its launches / their device-side durations,
               against the fp32 MFMA peak (157.3 TFLOP/s) -- plus the HBM view, the other conv kernels and the
               whole-score-forward fractions (the unit of work is one score-network forward)
-  cpu_baseline = the CPU oracle (plain-PyTorch restatement of the reference path) on this box's host cores
+  cpu_baseline = (--full) the CPU oracle (plain-PyTorch restatement of the reference path) on the host's cores
 
-Usage: python bench.py --gpus N --steps K --warmup W
+Usage: python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+  A plain run sets up, warms up, times exactly K steps and prints the headline line (metric, value, unit, ms_per_step, ...).
+  --full adds everything else the benchmark measures or checks: the free-running loop, per-rank times, the batch sweep, the
+  sustained leg, the ragged-set leg, host enqueue / hipGraph times, the profiled roofline pass, the CPU baseline and the
+  weight-broadcast / RCCL report.
+  --dump-outputs DIR writes what the timed path returned in its last timed step as DIR/enhanced.npy (float32; rank r > 0:
+  enhanced_rank<r>.npy); inputs, weights and noise are seeded, so two builds can be compared output for output.
   N > 1 without a launcher: the script re-executes itself under `torch.distributed.run` with N ranks (one per GPU);
   under a launcher (RANK / WORLD_SIZE set) it asserts WORLD_SIZE == N.
 """
@@ -291,11 +297,35 @@ def gru_roofline(gru_recs, args, ms_per_enhance):
                       "the conv launches); floor = tools/ubench/xchg_latency.hip (859 cycles at 2.4 GHz)"}
 
 
+# --dump-outputs: at most this many bytes over all ranks (a larger output is cut to a fixed, seeded sample of its elements)
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(dirname, out, rank, world):
+    """What the timed path handed its caller in the last timed step (this rank's enhanced batch, (B, T)) as float32 .npy.
+    Beyond DUMP_LIMIT_BYTES / world bytes per rank: the elements at a seeded random subset of flat indices (sorted), 1-D."""
+    import numpy as np
+
+    a = out.detach().to(torch.float32).cpu().contiguous()
+    budget = DUMP_LIMIT_BYTES // world // 4
+    if a.numel() > budget:
+        idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:budget].sort().values
+        a = a.reshape(-1)[idx]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "enhanced.npy" if rank == 0 else f"enhanced_rank{rank}.npy"), a.numpy())
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (enhance calls) of the headline loop")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg (free-running loop, per-rank times, batch sweep, sustained, ragged sets, "
+                         "host enqueue / hipGraph, profiled roofline pass, CPU baseline, weight-broadcast / RCCL report); "
+                         "without it only the headline loop runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the enhanced batch of the last timed step to DIR/enhanced.npy (float32)")
     ap.add_argument("--batch", type=int, default=1, help="utterances per GPU per step (configs[1]: 1)")
     ap.add_argument("--model", default="PP16", choices=["PP16", "OR16", "PP24"])
     ap.add_argument("--n_steps", type=int, default=8, help="diffusion steps")
@@ -303,8 +333,8 @@ def parse_args(argv=None):
     ap.add_argument("--varlen", action="store_true",
                     help="variable-length batch (configs[4]): lengths seconds*U(0.25,2) s, right-zero-padded to the batch "
                          "maximum like the reference's max_collator (datasets/datamodule.py:24-42)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--profile-steps", type=int, default=2)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--profile-steps", type=int, default=2, help="(--full) enhance calls of the profiled roofline pass")
     ap.add_argument("--share-devices", action="store_true",
                     help="allow more ranks than visible GPUs (ranks wrap around the devices, gloo rendezvous): "
                          "exercises the N > 1 path on a 1-GPU box; not a scaling measurement")
@@ -312,22 +342,25 @@ def parse_args(argv=None):
                     help="create the nccl (= RCCL) process group even with ONE rank: communicator set-up, the environment RCCL "
                          "needs and the device-side weight broadcast then execute on a 1-GPU box exactly as on a node")
     ap.add_argument("--sustained-s", type=float, default=10.0,
-                    help="length of the sustained leg (back-to-back free-running enhance calls with the device clock and power "
-                         "sampled beside them); 0 = off")
+                    help="(--full) length of the sustained leg (back-to-back free-running enhance calls with the device clock "
+                         "and power sampled beside them); 0 = off")
     ap.add_argument("--in-flight", default="4",
-                    help="lanes of the ragged-set leg (32 utterances of 32 different lengths through "
+                    help="(--full) lanes of the ragged-set leg (32 utterances of 32 different lengths through "
                          "distributed.enhance_sharded, serial loop vs K calls in flight); '' = off")
     ap.add_argument("--option", action="append", default=[], metavar="KEY=VALUE",
                     help="ou_set_option on every model of the run (tuning / A-B runs, e.g. --option split=0 --option no_overlap=1); "
                          "recorded in the line as `options`")
     ap.add_argument("--ragged-batch", default="8,16,32",
-                    help="batch sizes of the ragged-set leg's exact-batching runs (ou_enhance_var); empty: skip")
+                    help="(--full) batch sizes of the ragged-set leg's exact-batching runs (ou_enhance_var); empty: skip")
     ap.add_argument("--batch-sweep", default="1,4,8,16",
-                    help="also time these per-GPU batch sizes (short loops after the main one): one invocation gives the "
+                    help="(--full) also time these per-GPU batch sizes (short loops after the main one): one invocation gives the "
                          "utterances/s curve of configs[1] (batch 1) and of the batched throughput mode; '' = off")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-budget", type=float, default=30.0, help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def timed_loop(step, steps, world, device):
@@ -414,7 +447,7 @@ def main():
     t_pack_bcast = time.perf_counter() - t_b0
     bcast = None
     grouped = torch.distributed.is_initialized()
-    if grouped:
+    if grouped and args.full:
         # the collective alone (the first call above also folds / packs on rank 0 and sets the communicator up)
         xb = blob if torch.distributed.get_backend() == "nccl" else blob.cpu()
         torch.distributed.barrier()
@@ -429,7 +462,8 @@ def main():
         bcast = {"bytes": int(blob.numel() * 4), "seconds": t_b, "GBs": blob.numel() * 4 / t_b / 1e9,
                  "pack_plus_first_broadcast_s": t_pack_bcast, "identical_on_all_ranks": len(set(csum)) == 1,
                  "backend": torch.distributed.get_backend(), "ranks": world}
-    rccl = D.rccl_report(device)  # ranks, distinct physical GPUs (UUIDs), backend -- what a SCALE record has to prove
+    # ranks, distinct physical GPUs (UUIDs), backend -- what a SCALE record has to prove
+    rccl = D.rccl_report(device) if args.full else None
     cls = UniverseGAN if spec.kind == "universe_gan" else Universe
     forced = {}
     for kv in args.option:
@@ -459,17 +493,21 @@ def main():
         step()
     model.check_status = True   # product default: sync + device status word after every enhance
     dt, out = timed_loop(step, args.steps, world, device)
-    model.check_status = False  # free-running: calls are only enqueued, status checked once afterwards
-    dt_async, out = timed_loop(step, args.steps, world, device)
-    model.check_status = True
-    model._status()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
     assert torch.isfinite(out).all()
     launches = model.launch_stats()
-    rank_ms = per_rank_ms(step, max(2, args.steps // 2), world, device)
+    if args.full:
+        model.check_status = False  # free-running: calls are only enqueued, status checked once afterwards
+        dt_async, out = timed_loop(step, args.steps, world, device)
+        model.check_status = True
+        model._status()
+        assert torch.isfinite(out).all()
+        rank_ms = per_rank_ms(step, max(2, args.steps // 2), world, device)
     # ---- N > 1: the same loop on rank 0 ALONE (the other ranks wait at a barrier with idle GPUs) -- the one-GPU figure of THIS
     # invocation mode (same process layout, host-thread cap, backend), so that a multi-GPU record describes itself
     solo_ms = None
-    if world > 1:
+    if world > 1 and args.full:
         torch.cuda.synchronize()
         torch.distributed.barrier()
         if rank == 0:
@@ -483,7 +521,7 @@ def main():
 
     # ---- other per-GPU batch sizes, same model / length / step count (short loops; every rank takes part) ----
     batch_sweep = {}
-    for bs in [int(b) for b in args.batch_sweep.split(",") if b.strip()] if not args.varlen else []:
+    for bs in [int(b) for b in args.batch_sweep.split(",") if b.strip()] if args.full and not args.varlen else []:
         if bs == args.batch:
             batch_sweep[str(bs)] = {"ms_per_step": 1e3 * dt / args.steps,
                                     "utterances_per_s": args.steps * args.batch * world / dt, "steps": args.steps}
@@ -495,11 +533,12 @@ def main():
         k = max(3, args.steps // 2)
         dt_b, _ = timed_loop(step_b, k, world, device)
         batch_sweep[str(bs)] = {"ms_per_step": 1e3 * dt_b / k, "utterances_per_s": k * bs * world / dt_b, "steps": k}
-    step()  # back on the headline shape (workspace of the main configuration is current again)
+    if args.full:
+        step()  # back on the headline shape (workspace of the main configuration is current again)
 
     # ---- sustained rate: >= args.sustained_s of back-to-back free-running calls, per-window rates, sclk / power beside them
     sustained = None
-    if rank == 0 and world == 1 and args.sustained_s > 0 and not args.varlen:
+    if args.full and rank == 0 and world == 1 and args.sustained_s > 0 and not args.varlen:
         model.check_status = False
         win = 100
         per_call = dt_async / args.steps
@@ -534,7 +573,7 @@ def main():
 
     # ---- ragged utterance sets (the reference CLI's real workload): serial loop vs K calls in flight (lanes) -------------
     in_flight = None
-    if rank == 0 and world == 1 and args.in_flight.strip() and not args.varlen and args.batch == 1:
+    if args.full and rank == 0 and world == 1 and args.in_flight.strip() and not args.varlen and args.batch == 1:
         n_utt = 32
         gl = torch.Generator().manual_seed(17)
         lens = set()
@@ -588,7 +627,7 @@ def main():
 
     # ---- host side: time to ENQUEUE one enhance (no sync), eager walk of the network vs one hipGraph replay ----
     host_enqueue = None
-    if rank == 0 and not args.varlen:
+    if args.full and rank == 0 and not args.varlen:
         model.check_status = False
 
         def enqueue_ms(fn, reps=10):
@@ -613,8 +652,6 @@ def main():
             return 1e3 * (time.perf_counter() - t0) / args.steps
 
         try:
-            if os.environ.get("OU_BENCH_NO_GRAPH"):  # (tools/hwq_probe.sh: which leg hangs under GPU_MAX_HW_QUEUES=2)
-                raise RuntimeError("hipGraph legs skipped (OU_BENCH_NO_GRAPH)")
             # the capturable form: one chain on one stream (OU_ENH_SERIAL); and, for the record, the eager call's own
             # fork / join structure captured as it is
             run = model.graphed_enhance(args.batch, T, n_steps=args.n_steps, serial=True)
@@ -636,7 +673,7 @@ def main():
 
     # ---- roofline of the dominant kernel: per-launch device-side timing (separate profiled pass, same workload) ----
     roofline = None
-    if rank == 0:
+    if args.full and rank == 0:
         model.check_status = False
         model.profile(True)
         for _ in range(max(1, args.profile_steps)):
@@ -816,12 +853,6 @@ def main():
             "unit": "x_realtime",
             "utterances_per_s": args.steps * args.batch * world / dt,
             "utterances_per_s_per_gpu": args.steps * args.batch / dt,
-            "rank0_alone": None if solo_ms is None else {
-                "ms_per_step": solo_ms, "utterances_per_s": 1e3 * args.batch / solo_ms,
-                "per_gpu_rate_vs_rank0_alone": (args.steps * args.batch / dt) / (1e3 * args.batch / solo_ms),
-                "note": "the same loop on rank 0 while the other ranks wait at a barrier (their GPUs idle), same process layout "
-                        "and host-thread cap: the one-GPU figure of this invocation mode; the ratio is the per-GPU rate of the "
-                        "N-rank loop (MAX over ranks) over it"},
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
@@ -830,16 +861,6 @@ def main():
             "scaling": "weak",
             "vs_baseline": None,
             "dtype": "f32",
-            "bf16_split_launches_per_enhance": split_launches // max(1, args.profile_steps),
-            "dtype_note": "fp32 tensors and fp32 accumulation everywhere; the timed configuration (batch %d; from the kernel variants "
-                          "recorded in the profiled pass) runs %s" % (
-                args.batch, "some of its k3 / k5 convs of the 256- / 512-channel levels on the BF16 matrix pipe with every fp32 operand as three "
-                "bf16 pieces and six piece products per fp32 product (conv_split_kernel, DESIGN.md 4.1f: fp32-class accuracy, measured "
-                "1 dB better than an fp32 fmaf chain against a double evaluation; option split = 0 keeps everything on the f32 MFMAs)"
-                if split_launches else
-                "every convolution on the f32-input MFMAs (exact fp32 products); from batch 16 -- the '16' entry of batch_sweep -- the "
-                "256- / 512-channel k3 / k5 convs go to conv_split_kernel (three bf16 pieces per fp32 operand on the BF16 pipe, "
-                "fp32-class accuracy, DESIGN.md 4.1f)"),
             "data": "synthetic (seeded AM-sine + noise waveforms; seeded random weights with the reference key schema)",
             "config": {
                 "workload": f"{what}, {args.n_steps} diffusion steps, batch={args.batch} utterance(s) of "
@@ -857,25 +878,44 @@ def main():
             },
             "options": {"forced": forced, "note": "ou_set_option values that differ from the defaults in this run (--option); the "
                                                   "library reads no environment variable"},
-            "per_rank_ms_per_step": rank_ms,
-            "rccl": rccl,
             "host_threads_per_rank": host_threads,
-            "weight_broadcast": bcast,
-            "batch_sweep": dict(batch_sweep, note="utterances/s of the whole job at other per-GPU batch sizes (same model, "
-                                                  "length and step count; MAX over ranks like the headline)"),
             "status_mode": "value / ms_per_step: product default (stream sync + device status read after every enhance)",
-            "free_running": {"value": audio_s / dt_async, "ms_per_step": 1e3 * dt_async / args.steps,
-                             "note": "model.check_status = False: no host sync inside the timed loop, status checked after it"},
-            "host_enqueue": host_enqueue,
-            "sustained": sustained,
-            "in_flight": in_flight,
-            "gru_exchange": dict(model.gru_exchange_stats(),
-                                 note="hand-offs the GRU clusters had to repeat / waves that finished a pass with "
-                                      "system-scope publishes (DESIGN.md 4.4), whole process; both 0 on a healthy device"),
-            "roofline": roofline,
         }
-        if not args.no_cpu_baseline:
-            res["cpu_baseline"] = cpu_baseline(args.model, args.n_steps, args.seconds)
+        if args.full:
+            res.update({
+                "rank0_alone": None if solo_ms is None else {
+                    "ms_per_step": solo_ms, "utterances_per_s": 1e3 * args.batch / solo_ms,
+                    "per_gpu_rate_vs_rank0_alone": (args.steps * args.batch / dt) / (1e3 * args.batch / solo_ms),
+                    "note": "the same loop on rank 0 while the other ranks wait at a barrier (their GPUs idle), same process layout "
+                            "and host-thread cap: the one-GPU figure of this invocation mode; the ratio is the per-GPU rate of the "
+                            "N-rank loop (MAX over ranks) over it"},
+                "bf16_split_launches_per_enhance": split_launches // max(1, args.profile_steps),
+                "dtype_note": "fp32 tensors and fp32 accumulation everywhere; the timed configuration (batch %d; from the kernel variants "
+                              "recorded in the profiled pass) runs %s" % (
+                    args.batch, "some of its k3 / k5 convs of the 256- / 512-channel levels on the BF16 matrix pipe with every fp32 operand as three "
+                    "bf16 pieces and six piece products per fp32 product (conv_split_kernel, DESIGN.md 4.1f: fp32-class accuracy, measured "
+                    "1 dB better than an fp32 fmaf chain against a double evaluation; option split = 0 keeps everything on the f32 MFMAs)"
+                    if split_launches else
+                    "every convolution on the f32-input MFMAs (exact fp32 products); from batch 16 -- the '16' entry of batch_sweep -- the "
+                    "256- / 512-channel k3 / k5 convs go to conv_split_kernel (three bf16 pieces per fp32 operand on the BF16 pipe, "
+                    "fp32-class accuracy, DESIGN.md 4.1f)"),
+                "per_rank_ms_per_step": rank_ms,
+                "rccl": rccl,
+                "weight_broadcast": bcast,
+                "batch_sweep": dict(batch_sweep, note="utterances/s of the whole job at other per-GPU batch sizes (same model, "
+                                                      "length and step count; MAX over ranks like the headline)"),
+                "free_running": {"value": audio_s / dt_async, "ms_per_step": 1e3 * dt_async / args.steps,
+                                 "note": "model.check_status = False: no host sync inside the timed loop, status checked after it"},
+                "host_enqueue": host_enqueue,
+                "sustained": sustained,
+                "in_flight": in_flight,
+                "gru_exchange": dict(model.gru_exchange_stats(),
+                                     note="hand-offs the GRU clusters had to repeat / waves that finished a pass with "
+                                          "system-scope publishes (DESIGN.md 4.4), whole process; both 0 on a healthy device"),
+                "roofline": roofline,
+            })
+            if not args.no_cpu_baseline:
+                res["cpu_baseline"] = cpu_baseline(args.model, args.n_steps, args.seconds)
         print(json.dumps(res), flush=True)
     if grouped:
         torch.distributed.barrier()

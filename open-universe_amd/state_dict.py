@@ -9,8 +9,8 @@ This module re-derives, from a `ModelSpec`, the ordered list of tensors the refe
     universe_gan.py:136-143) back onto names,
   * generate seeded synthetic checkpoints (no trained checkpoint is reachable offline),
   * validate a checkpoint before it is handed to the C ABI.
-The schema is checked against the imported reference in tests/test_oracle_vs_reference.py and against
-the committed key lists in tests/golden/.
+The schema is checked against the reference's recorded key shapes and buffers in tests/test_oracle_vs_reference.py
+and against the committed key lists in tests/golden/.
 """
 import math
 from typing import Dict, List, Tuple

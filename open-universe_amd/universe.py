@@ -751,7 +751,7 @@ class Universe:
         n_steps = self.diff_kwargs.n_steps if n_steps is None else int(n_steps)
         epsilon = self.diff_kwargs.epsilon if epsilon is None else float(epsilon)
         if not serial:
-            # Measured (tools/hwq_probe.sh, profiles/r05_final_hwq_probe.txt): with GPU_MAX_HW_QUEUES below 4 the HIP runtime
+            # Measured (profiles/r05_final_hwq_probe.txt): with GPU_MAX_HW_QUEUES below 4 the HIP runtime
             # SEGFAULTS replaying a captured graph that has this call's four-stream fork / join structure (round 4 recorded it
             # as a hang of bench.py); the eager call and the serial-chain capture are fine with 1, 2 or 4 queues.
             import os

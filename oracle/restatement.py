@@ -11,9 +11,9 @@ Only `tests/`, `__graft_entry__.smoke()` and `bench.py`'s cpu_baseline leg may i
 as the checker / the timed CPU baseline -- never as the thing shipped.  The product path
 (`open_universe_amd`) does not import it and fails loudly when the HIP library is missing.
 
-Pinning: validated in the build container against the *imported* reference itself
-(`oracle/ref_import.py`, `tests/test_oracle_vs_reference.py`) and against the committed golden vectors
-generated from that import (`tests/golden/`).  The reference has no tests / golden vectors of its own
+Pinning: validated against recorded reference outputs -- the committed golden vectors under `tests/golden/`, generated
+by `tests/golden/make_golden.py` from the reference itself imported through `oracle/ref_import.py`, and checked by
+`tests/test_oracle_vs_reference.py` and `tests/test_oracle_golden.py`.  The reference has no tests / golden vectors of its own
 (SURVEY.md section 4).  torchaudio (MelSpectrogram, Resample) is absent from the image: those two pieces are
 restated from torchaudio's documented algorithm and are therefore "parity unpinned" at that third-party
 boundary (the mel window / filterbank / resample kernels are checkpoint buffers, so with a real checkpoint

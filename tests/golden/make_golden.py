@@ -25,7 +25,10 @@ Fixtures are DATA only: inputs are regenerated from seeds, outputs are stored as
                          run row 0 alone = the batch-1 dispatch, and rows 0-1 inside a batch of 16 = the throughput dispatch).
                          Beside every output the REFERENCE'S OWN SELF-AGREEMENT on those weights as scalars: 1 thread vs 8
                          threads and fp32 vs fp64 (SI-SDR / SNR in dB, row 0) -- the yardstick for the HIP path's figures
-Run:  python tests/golden/make_golden.py [base] [stress] [configs] [transform] [loud] [fullstress]      (default: base)
+    live_ref.npz/.json   what tests/test_oracle_vs_reference.py holds the oracle against: resolved model configs, state-dict key
+                         shapes and 3-step enhance outputs (plain and oracle-score mode) of width-8 models, the buffers of the
+                         default model, the STFT windows of the transform classes
+Run:  python tests/golden/make_golden.py [base] [stress] [configs] [transform] [loud] [fullstress] [live]      (default: base)
 """
 import json
 import os
@@ -239,9 +242,79 @@ def make_transform():
     print("transform", {k: v.shape for k, v in out.items()})
 
 
+LIVE_CASES = {"PP16": "default", "OR16": "universe_original", "PP24": "universepp_24k"}
+LIVE_OV = {"score_model.n_channels": 8, "condition_model.n_channels": 8}
+LIVE_EDM_OV = dict(LIVE_OV, **{"edm.data_level_db": -20.0, "normalization_kwargs.ref": "noisy"})
+
+
+def _live_model(m, spec):
+    """Loads the seed-5 synthetic weights of `spec` into the reference model `m`; returns their key shapes in the reference."""
+    shapes = {k: list(v.shape) for k, v in m.state_dict().items()}
+    sd = S.synthetic_state_dict(spec, seed=5)
+    missing, unexpected = m.load_state_dict(sd, strict=False)
+    assert not unexpected and all(k.startswith("loss_") for k in missing)
+    if m.ema is not None:
+        m.ema.shadow_params = [p.clone().detach() for p in m.model_parameters()]
+    m.eval()
+    return shapes
+
+
+def _live_enhance(m, mix, tgt):
+    with torch.no_grad():
+        ref = m.enhance(mix, n_steps=3, rng=torch.Generator().manual_seed(3))
+        fake = m.enhance(mix[:, None, :], n_steps=3, target=tgt, fake_score_snr=10.0, rng=torch.Generator().manual_seed(3))
+    return ref.numpy(), fake.numpy()
+
+
+def make_live():
+    """live_ref.npz / live_ref.json: what tests/test_oracle_vs_reference.py holds the oracle against -- the reference's
+    resolved model configs, state-dict key shapes and enhance outputs of reduced-width models (seed-5 weights, 3 steps,
+    rng seed 3; plain and oracle-score mode), its buffers of the default model, and the STFT windows of its transform classes."""
+    from open_universe_amd import config as C
+
+    from helpers import TRANSFORM_CASES
+
+    arrays, meta = {}, {"cases": {}}
+    for name, ref_cfg in LIVE_CASES.items():
+        spec = C.spec_from_config(C.builtin_config(name, **{"score_model.n_channels": 8}))
+        m, cfg = R.build_reference_model(ref_cfg, LIVE_OV)
+        shapes = _live_model(m, spec)
+        mix = synth_mix(spec, 2, spec.tot_ds * 10 + 13)
+        arrays[name + "_enh"], arrays[name + "_fake"] = _live_enhance(m, mix, 0.5 * mix[:, None, :])
+        meta["cases"][name] = {"ref_cfg": ref_cfg, "model_cfg": json.loads(json.dumps(cfg)), "state_dict_shapes": shapes}
+    # config options no shipped yaml sets
+    m, cfg = R.build_reference_model("default", LIVE_EDM_OV)
+    spec = C.spec_from_config({"model": cfg})
+    shapes = _live_model(m, spec)
+    mix = synth_mix(spec, 2, spec.tot_ds * 6 + 5)
+    arrays["edm_enh"], arrays["edm_fake"] = _live_enhance(m, mix, 0.5 * mix[:, None, :] + 0.01)
+    meta["edm"] = {"model_cfg": json.loads(json.dumps(cfg)), "state_dict_shapes": shapes}
+    # buffers (non-parameters) of the full default model
+    m, cfg = R.build_reference_model("default")
+    pn = set(n for n, _ in m.named_parameters())
+    for k, v in m.state_dict().items():
+        if k not in pn and not k.startswith("loss_"):
+            arrays["buf:" + k] = v.numpy()
+    # the windows the reference's transform classes build
+    import importlib
+
+    drc = importlib.import_module("open_universe.layers.dyn_range_comp")
+    for tag, stft_kw, spec_kw, pad_block in TRANSFORM_CASES:
+        t = (drc.CompressedMagSTFT(dict(stft_kw), dict(spec_kw)) if pad_block is None
+             else drc.CompressedMagSTFTPadded(dict(stft_kw), dict(spec_kw), pad_block=pad_block))
+        arrays["window:" + tag] = t.stft_window.numpy()
+    np.savez_compressed(os.path.join(HERE, "live_ref.npz"), **arrays)
+    with open(os.path.join(HERE, "live_ref.json"), "w") as f:
+        json.dump(meta, f)
+    print("live", {k: v.shape for k, v in arrays.items() if not k.startswith("buf:")},
+          sum(1 for k in arrays if k.startswith("buf:")), "buffers")
+
+
 def main():
     torch.set_num_threads(8)
     what = set(sys.argv[1:]) or {"base"}
+    if "live" in what:
+        make_live()
     if "transform" in what:
         make_transform()
     if "stress" in what:

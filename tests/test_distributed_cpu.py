@@ -185,6 +185,24 @@ def test_pick_backend_uses_the_local_world_size(monkeypatch):
     assert D.pick_backend(2) == "nccl" and D.pick_backend(9) == "gloo"
 
 
+def test_cap_host_threads_default_and_omp_override(monkeypatch):
+    """min(8, logical CPUs / local ranks) by default; OMP_NUM_THREADS, when set, is taken as it is."""
+    sys.path.insert(0, ROOT)
+    import open_universe_amd  # noqa: F401
+    from open_universe_amd import distributed as D
+
+    before = torch.get_num_threads()
+    ncpu = os.cpu_count() or 8
+    try:
+        monkeypatch.delenv("OMP_NUM_THREADS", raising=False)
+        assert D.cap_host_threads(local_world=1) == min(8, ncpu) == torch.get_num_threads()
+        assert D.cap_host_threads(local_world=4 * ncpu) == 1
+        monkeypatch.setenv("OMP_NUM_THREADS", "3")
+        assert D.cap_host_threads(local_world=1) == 3 == torch.get_num_threads()
+    finally:
+        torch.set_num_threads(before)
+
+
 def _bad_ckpt_worker(rank, world, port, q, path):
     sys.path.insert(0, ROOT)
     os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",

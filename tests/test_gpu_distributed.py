@@ -126,9 +126,9 @@ def test_two_ranks_batched_shards():
     assert min(float(O.si_sdr(singles[i].cpu(), padded[i].cpu())) for i in (1, 4, 8)) < 60.0
 
 
-def _run(cmd, timeout=900):
+def _run(cmd, timeout=900, unset=()):
     env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""), HSA_ENABLE_IPC_MODE_LEGACY="0")
-    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT") + tuple(unset):
         env.pop(k, None)
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=timeout)
     if r.returncode != 0:  # keep the whole story: pytest's assertion message truncates it
@@ -252,9 +252,10 @@ def test_world_size_1_nccl_group_end_to_end(tmp_path):
 def test_bench_force_nccl_line_carries_the_rccl_block():
     """`bench.py --gpus 1 --force-nccl`: the headline loop under an initialised RCCL group of one rank; the JSON line carries
     `rccl: {ranks, distinct_device_uuids, backend}` (what a SCALE record needs to prove N GPUs were seen) and the
-    explicit host-thread cap per rank."""
-    r = _run([sys.executable, "bench.py", "--gpus", "1", "--force-nccl", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-              "--profile-steps", "1", "--sustained-s", "0", "--in-flight", "", "--batch-sweep", ""])
+    explicit host-thread cap per rank (the default cap: OMP_NUM_THREADS, which overrides it, is not passed on)."""
+    r = _run([sys.executable, "bench.py", "--gpus", "1", "--force-nccl", "--steps", "2", "--warmup", "1", "--full",
+              "--no-cpu-baseline", "--profile-steps", "1", "--sustained-s", "0", "--in-flight", "", "--batch-sweep", ""],
+             unset=("OMP_NUM_THREADS",))
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     res = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert res["n_gpus"] == 1 and res["config"]["backend"] == "nccl"
@@ -268,7 +269,7 @@ def test_bench_two_gpus_over_rccl():
     """The day-one multi-GPU run: `bench.py --gpus 2` on two real devices must take the nccl (= RCCL) branch, put every
     rank on its own GPU, hand every rank rank 0's packed blob (checksum compared across ranks) and report per-rank
     times, the broadcast rate and the batch-1 / batch-4 utterance rates in one line."""
-    r = _run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+    r = _run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
               "--profile-steps", "1"])
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     res = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -283,7 +284,7 @@ def test_bench_two_gpus_over_rccl():
 
 def test_bench_spawns_its_own_ranks():
     """`python bench.py --gpus 2` without a launcher: two ranks, n_gpus = 2 in the JSON line, per-rank device ids."""
-    r = _run([sys.executable, "bench.py", "--gpus", "2", "--share-devices", "--steps", "2", "--warmup", "1",
+    r = _run([sys.executable, "bench.py", "--gpus", "2", "--share-devices", "--steps", "2", "--warmup", "1", "--full",
               "--no-cpu-baseline", "--profile-steps", "1"])
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]

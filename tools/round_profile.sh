@@ -3,7 +3,7 @@
 # kernel stats of the headline command, PMC passes (FETCH_SIZE / WRITE_SIZE, separate runs) for the conv kernels' memory-side
 # traffic of the headline AND the throughput configurations, SQ counters of one deep-level layer (split-K kernel) and one
 # throughput layer (no-split-K kernel) in isolation, GRU per-step cycle stamps, the micro-benchmarks behind the design
-# decisions, the two-ranks-on-one-GPU stress loop.  Everything lands under gpurun_out/final/; tools/collect_profiles.py copies
+# decisions.  Everything lands under $O (set below); tools/collect_profiles.py copies
 # what should be judged into profiles/.
 set -u
 export TMPDIR=/tmp
@@ -12,32 +12,32 @@ rm -rf $O
 mkdir -p $O
 R=${GRAFT_REPO_ROOT:-$PWD}
 timeout 120 python tools/box_health.py 2>&1 | grep "box health" | tee $O/box_health.txt
-timeout 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 tail -c 400 $O/bench_default.json
 # the same loop under an initialised RCCL group of ONE rank (communicator set-up, device-side weight broadcast, `rccl` block)
-timeout 300 python bench.py --gpus 1 --force-nccl --sustained-s 0 --in-flight "" --batch-sweep "" --no-cpu-baseline --steps 10 --warmup 2 > $O/bench_force_nccl.json 2>> $O/bench_default.err
+timeout 300 python bench.py --full --gpus 1 --force-nccl --sustained-s 0 --in-flight "" --batch-sweep "" --no-cpu-baseline --steps 10 --warmup 2 > $O/bench_force_nccl.json 2>> $O/bench_default.err
 python - $O/bench_force_nccl.json <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
 print("force-nccl:", d["ms_per_step"], {k: d["rccl"][k] for k in ("ranks", "distinct_device_uuids", "backend", "rccl_version")}, d["weight_broadcast"]["backend"])
 PY
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- \
-  python bench.py --sustained-s 0 --in-flight "" --steps 10 --warmup 2 --no-cpu-baseline --batch-sweep "" > $O/bench_under_rocprof.json 2> $O/rocprof.err
+  python bench.py --full --sustained-s 0 --in-flight "" --steps 10 --warmup 2 --no-cpu-baseline --batch-sweep "" > $O/bench_under_rocprof.json 2> $O/rocprof.err
 python tools/kstats.py $O/prof/bench_kernel_trace.csv | head -16 | tee $O/kstats_PP16_B1.txt
 # the same command as ONE serial chain (option no_overlap = 1: no side streams inside the call) -- every kernel alone on the device;
 # the default run above times the first score-encoder pass beside the conditioner, like bench.py's own per-launch pass does
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_serial -o bench -- \
-  python bench.py --option no_overlap=1 --sustained-s 0 --in-flight "" --steps 10 --warmup 2 --no-cpu-baseline --batch-sweep "" > $O/bench_under_rocprof_serial.json 2>> $O/rocprof.err
+  python bench.py --full --option no_overlap=1 --sustained-s 0 --in-flight "" --steps 10 --warmup 2 --no-cpu-baseline --batch-sweep "" > $O/bench_under_rocprof_serial.json 2>> $O/rocprof.err
 python tools/kstats.py $O/prof_serial/bench_kernel_trace.csv | head -16 | tee $O/kstats_PP16_B1_serial.txt
 rm -rf $O/prof_serial
 # the other BASELINE configurations (per-GPU shapes): C3 PP16 64 steps B=4, C4 OR16 32 steps B=16, C5 PP24 varlen B=8
-timeout 900 python bench.py --sustained-s 0 --in-flight "" --batch 4 --n_steps 64 --steps 5 --warmup 1 --batch-sweep "" > $O/bench_C3_PP16_n64_b4.json 2>> $O/bench_default.err
-timeout 900 python bench.py --sustained-s 0 --in-flight "" --model OR16 --batch 16 --n_steps 32 --steps 5 --warmup 1 --batch-sweep "" > $O/bench_C4_OR16_n32_b16.json 2>> $O/bench_default.err
-timeout 900 python bench.py --sustained-s 0 --in-flight "" --model PP24 --batch 8 --varlen --steps 5 --warmup 1 > $O/bench_C5_PP24_varlen_b8.json 2>> $O/bench_default.err
-timeout 900 python bench.py --sustained-s 0 --in-flight "" --batch 8 --steps 10 --warmup 2 --no-cpu-baseline --batch-sweep "" > $O/bench_PP16_b8.json 2>> $O/bench_default.err
-timeout 900 python bench.py --sustained-s 0 --in-flight "" --batch 4 --steps 10 --warmup 2 --no-cpu-baseline --batch-sweep "" > $O/bench_PP16_b4.json 2>> $O/bench_default.err
-timeout 900 python bench.py --sustained-s 0 --in-flight "" --batch 16 --steps 6 --warmup 1 --no-cpu-baseline --batch-sweep "" > $O/bench_PP16_b16.json 2>> $O/bench_default.err
-timeout 900 python bench.py --sustained-s 0 --in-flight "" --batch 32 --steps 4 --warmup 1 --no-cpu-baseline --batch-sweep "" > $O/bench_PP16_b32.json 2>> $O/bench_default.err
+timeout 900 python bench.py --full --sustained-s 0 --in-flight "" --batch 4 --n_steps 64 --steps 5 --warmup 1 --batch-sweep "" > $O/bench_C3_PP16_n64_b4.json 2>> $O/bench_default.err
+timeout 900 python bench.py --full --sustained-s 0 --in-flight "" --model OR16 --batch 16 --n_steps 32 --steps 5 --warmup 1 --batch-sweep "" > $O/bench_C4_OR16_n32_b16.json 2>> $O/bench_default.err
+timeout 900 python bench.py --full --sustained-s 0 --in-flight "" --model PP24 --batch 8 --varlen --steps 5 --warmup 1 > $O/bench_C5_PP24_varlen_b8.json 2>> $O/bench_default.err
+timeout 900 python bench.py --full --sustained-s 0 --in-flight "" --batch 8 --steps 10 --warmup 2 --no-cpu-baseline --batch-sweep "" > $O/bench_PP16_b8.json 2>> $O/bench_default.err
+timeout 900 python bench.py --full --sustained-s 0 --in-flight "" --batch 4 --steps 10 --warmup 2 --no-cpu-baseline --batch-sweep "" > $O/bench_PP16_b4.json 2>> $O/bench_default.err
+timeout 900 python bench.py --full --sustained-s 0 --in-flight "" --batch 16 --steps 6 --warmup 1 --no-cpu-baseline --batch-sweep "" > $O/bench_PP16_b16.json 2>> $O/bench_default.err
+timeout 900 python bench.py --full --sustained-s 0 --in-flight "" --batch 32 --steps 4 --warmup 1 --no-cpu-baseline --batch-sweep "" > $O/bench_PP16_b32.json 2>> $O/bench_default.err
 for f in C3_PP16_n64_b4 C4_OR16_n32_b16 C5_PP24_varlen_b8 PP16_b8 PP16_b4 PP16_b16 PP16_b32; do python - $O/bench_$f.json $f <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
@@ -46,7 +46,7 @@ PY
 done
 for cfgname in "PP16_B8 --batch 8 --steps 2 --warmup 1" "PP16_B16 --batch 16 --steps 2 --warmup 1" "C3 --batch 4 --n_steps 64 --steps 2 --warmup 1" "C4 --model OR16 --batch 16 --n_steps 32 --steps 2 --warmup 1" "C5 --model PP24 --batch 8 --varlen --steps 2 --warmup 1"; do
   set -- $cfgname; name=$1; shift
-  timeout 900 rocprofv3 --kernel-trace --output-format csv -d $O/prof_$name -o k -- python bench.py --sustained-s 0 --in-flight "" "$@" --no-cpu-baseline --profile-steps 1 --batch-sweep "" > /dev/null 2>> $O/rocprof.err
+  timeout 900 rocprofv3 --kernel-trace --output-format csv -d $O/prof_$name -o k -- python bench.py --full --sustained-s 0 --in-flight "" "$@" --no-cpu-baseline --profile-steps 1 --batch-sweep "" > /dev/null 2>> $O/rocprof.err
   python tools/kstats.py $O/prof_$name/k_kernel_trace.csv | head -12 > $O/kstats_$name.txt
   rm -rf $O/prof_$name
 done
@@ -55,7 +55,7 @@ for cfgname in "PP16_b1 " "PP16_b8 --batch 8" "PP16_b16 --batch 16" "PP24_b8_var
   set -- $cfgname; tag=$1; shift
   for c in FETCH_SIZE WRITE_SIZE; do
     timeout 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmc_${tag}_$c -o p -- \
-      python bench.py --sustained-s 0 --in-flight "" "$@" --steps 2 --warmup 1 --no-cpu-baseline --profile-steps 1 --batch-sweep "" > /dev/null 2> $O/pmc_${tag}_$c.err
+      python bench.py --full --sustained-s 0 --in-flight "" "$@" --steps 2 --warmup 1 --no-cpu-baseline --profile-steps 1 --batch-sweep "" > /dev/null 2> $O/pmc_${tag}_$c.err
     # per-family averages now, the raw per-dispatch CSV (tens of MB per pass) stays on the box: gpurun returns 64 MiB at most
     python tools/collect_profiles.py --reduce $O/pmc_${tag}_$c/p_counter_collection.csv $O/pmc_${tag}_$c.json && rm -rf $O/pmc_${tag}_$c
   done
@@ -86,10 +86,9 @@ for K in 1 2 4; do timeout 300 python tools/lanes_timeline.py $K 32 2>&1 | grep 
 timeout 600 python tools/lanes_batch.py 64 2>&1 | grep -v amdgpu.ids > $O/lanes_batch.txt
 { timeout 300 python tools/free_run.py; OU_NO_OVERLAP=1 timeout 300 python tools/free_run.py; } 2>&1 | grep -v amdgpu.ids > $O/free_run.txt
 # round 5: the wide-load split-K family per layer (8 / 4 slices, minimal filtering, 16-row tiles, XCD ownerships), phase stamps of
-# the minimal-filtering fused ConvBlock bodies, the two open questions of round 4 (GPU_MAX_HW_QUEUES=2, three lanes)
+# the minimal-filtering fused ConvBlock bodies
 timeout 600 python tools/d2_sweep.py PP16 1 -1,2,3 2>&1 | grep -v amdgpu.ids | cut -c1-420 > $O/d2_sweep_PP16_B1.txt; tail -3 $O/d2_sweep_PP16_B1.txt | cut -c1-200
 { timeout 300 python tools/chainw_ts.py score.enc0; timeout 300 python tools/chainw_ts.py score.dec4; timeout 300 python tools/chainw_ts.py score.enc1; } 2>&1 | grep -v amdgpu.ids | cut -c1-330 > $O/chainw_ts.txt; cat $O/chainw_ts.txt
-bash tools/hwq_probe.sh $O/hwq > /dev/null 2>&1; cp $O/hwq/hwq_probe.txt $O/hwq_probe.txt; cp $O/hwq/lanes3_probe.txt $O/lanes_three_probe.txt; rm -rf $O/hwq; cat $O/hwq_probe.txt | cut -c1-200
 # microbenchmarks behind the design decisions
 for u in xchg_latency launch_overhead vmem_issue; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 tools/ubench/$u.hip -o /tmp/$u 2>> $O/rocprof.err && timeout 150 /tmp/$u > $O/ubench_$u.txt 2>&1
@@ -98,16 +97,6 @@ done
 echo "--- one process" > $O/xcc_migrate.txt; timeout 60 /tmp/xcc_migrate 200 2 >> $O/xcc_migrate.txt
 echo "--- three processes at once" >> $O/xcc_migrate.txt
 for i in 1 2 3; do timeout 120 /tmp/xcc_migrate 300 6 >> $O/xcc_migrate.txt 2>&1 & done; wait
-# two ranks on ONE GPU, repeated (the arrangement that produced the GRU time-outs of round 2)
-ok=0; bad=0
-for i in $(seq 1 30); do
-  if timeout 120 python bench.py --sustained-s 0 --in-flight "" --gpus 2 --share-devices --steps 3 --warmup 1 --no-cpu-baseline --profile-steps 1 --batch-sweep "" > $O/st.out 2> $O/st.err; then ok=$((ok+1)); else bad=$((bad+1)); grep -h RuntimeError $O/st.err | head -2 | cut -c1-700 >> $O/stress_two_ranks.txt; fi
-done
-echo "two ranks on one GPU, bench.py --gpus 2 --share-devices --steps 3: ok=$ok failed=$bad of 30" | tee -a $O/stress_two_ranks.txt
-python - >> $O/stress_two_ranks.txt <<PY
-import json
-d=json.loads([l for l in open("$O/st.out") if l.startswith("{")][-1]); print("last run:", d["ms_per_step"], d["gru_exchange"])
-PY
 # per-layer tables: the library's own per-launch records paired with its OU_TRACE lines in launch order (tools/layer_table.py)
 timeout 600 python tools/layer_table.py PP16 1 2>&1 | grep -v amdgpu.ids > $O/layers_PP16_B1.txt; tail -2 $O/layers_PP16_B1.txt
 OU_NO_OVERLAP=1 timeout 600 python tools/layer_table.py PP16 1 2>&1 | grep -v amdgpu.ids > $O/layers_PP16_B1_serial.txt
@@ -124,7 +113,7 @@ timeout 600 python tools/split_clock.py 4 2>&1 | grep -v amdgpu.ids > $O/split_c
 Q="--sustained-s 0 --in-flight= --no-cpu-baseline --batch-sweep= --profile-steps 0"
 for s in 0 -1 0 -1; do
   for cfg in "--batch 16 --steps 5 --warmup 1" "--batch 32 --steps 3 --warmup 1" "--model OR16 --batch 16 --n_steps 32 --steps 3 --warmup 1"; do
-    echo "OU_SPLIT=$s $cfg: $(timeout 600 python bench.py --option split=$s $Q $cfg 2>/dev/null | python -c 'import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print("%.2f ms per step, %.1f utt/s" % (d["ms_per_step"], d["utterances_per_s"]))')"
+    echo "OU_SPLIT=$s $cfg: $(timeout 600 python bench.py --full --option split=$s $Q $cfg 2>/dev/null | python -c 'import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print("%.2f ms per step, %.1f utt/s" % (d["ms_per_step"], d["utterances_per_s"]))')"
   done
 done > $O/split_ab.txt 2>&1; cat $O/split_ab.txt
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O2 -o /tmp/cumask_probe tools/ubench/cumask_probe.hip 2>> $O/rocprof.err && timeout 120 /tmp/cumask_probe > $O/cumask_probe.txt 2>&1
