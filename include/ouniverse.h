@@ -150,7 +150,9 @@ int ou_aux_to_wav(ou_handle* h, float* wav_out, int32_t B, int32_t T, void* ws, 
 #define OU_ENH_SERIAL 8u         /* everything on the caller's stream, no side streams inside the call: the form to capture
                                   * into a hipGraph (a captured fork / join replays slower than the serial chain) */
 
-/* Universe.enhance(mix, n_steps, epsilon, rng=...) -- universe.py:231-375, for a (B, T_raw) batch:
+/* Universe.enhance(mix, n_steps, epsilon, rng=...) -- universe.py:231-375, for a (B, T_raw) batch.  An input whose padded length
+ * would make a per-row plane of the walk reach 2^32 bytes (its kernels address a plane with 32-bit descriptors) is refused with
+ * OU_EINVAL before anything is launched -- ou_enhance_segments takes it:
  * pad (:219-223) -> normalize (utils/norm.py:47-87) -> conditioner -> x0 = sigma_0 * noise[0] ->
  * N-1 x { score; x += sigma_n^2*eta*score + beta*sigma_{n+1}*noise[n+1] } -> last clean step ->
  * unpad -> [keep_rms] -> peak guard.  Ensemble replication / reduction stays with the caller.
@@ -180,6 +182,43 @@ int ou_enhance(ou_handle* h, const float* mix, float* out, const float* noise, i
 int ou_enhance_var(ou_handle* h, const float* mix, float* out, const float* noise, int32_t B, int32_t T_raw_max,
                    const int32_t* t_raw, int32_t n_steps, double epsilon, const float* sigma_host, int32_t warm_start,
                    uint32_t flags, void* ws, size_t ws_bytes, ou_stream_t stream);
+
+/* ---- segmented enhance: recordings of any length in bounded memory (extension; the reference runs a whole file per call)
+ * A long row is cut into overlapping windows that run as one batch through the walk of ou_enhance; whatever the reference
+ * computes over the whole utterance is still computed over the whole row:
+ *   - pad split, mean and gain (utils/norm.py:47-87) and mix_rms over the whole padded row; window k's input is exactly
+ *     xn[s_k : s_k + L] of the normalised padded row xn;
+ *   - ONE mel normalisation per row (condition.py:105-106) over the mel frames of the whole row;
+ *   - window k's noise is noise[..., s_k : s_k + L] of the whole-row noise, so a generator advances as in ou_enhance;
+ *   - the window outputs are crossfaded (complementary raised cosine over the last `overlap` samples of window k; the weights
+ *     sum to 1) into the padded row, then unpad, keep_rms (whole-row mix_rms) and the peak guard (max over the whole row).
+ * Only the network's receptive field and the bidirectional GRUs see a window instead of the row.  A row that fits into one
+ * window gives the ou_enhance result.
+ *
+ * Plan (pure host function of T_raw, tot_ds, segment, overlap): segment and overlap are rounded down to multiples of tot_ds,
+ * 0 <= overlap <= segment / 2.  T_pad = T_raw + (tot_ds - T_raw % tot_ds).  T_pad <= segment: one window [0, T_pad).  Else every
+ * window has L = segment samples, window k starts at k * (segment - overlap), the last one at T_pad - L (shifted to stay inside);
+ * the crossfade between windows k and k + 1 covers [s_k + L - overlap, s_k + L), and core k (the samples where window k has
+ * weight >= 1/2) runs from the middle of one crossfade to the next: the cores tile [0, T_pad).
+ * `capacity`: entries of the four arrays (all four may be NULL: then only n_windows / overlap_used / T_pad are returned). */
+int ou_segment_plan(int32_t tot_ds, int64_t T_raw, int32_t segment, int32_t overlap, int32_t capacity, int64_t* starts,
+                    int32_t* lengths, int64_t* core_begin, int64_t* core_end, int32_t* n_windows, int32_t* overlap_used,
+                    int64_t* T_pad);
+/* Workspace of ou_enhance_segments for C rows of T_raw samples: the workspace of the walk for (batch, length) -- batch <=
+ * max_batch windows of `length` samples per group -- plus a small area for the whole-row statistics (C rows x 24 KiB), one
+ * step of gathered noise (batch x length floats) and one carried window.  It depends on C, max_batch and segment, NOT on T_raw
+ * (beyond T_raw's share of a segment).  Prepare the buffer with ou_workspace_init(h, batch, length, ws, nbytes, stream). */
+int ou_segments_workspace_bytes(const ou_handle* h, int32_t C, int64_t T_raw, int32_t segment, int32_t overlap,
+                                int32_t max_batch, size_t* nbytes, int32_t* batch, int32_t* length);
+/* Universe.enhance of C independent rows of T_raw samples, in windows (see above):
+ *   mix, out : (C, T_raw) device (out also serves as scratch for the whole-row mel frame energies before the first window)
+ *   noise    : (n_steps, C, T_pad) standard-normal, device, the draw order of ou_enhance (x0, z_0 .. z_{N-2})
+ *   flags    : OU_ENH_KEEP_RMS, OU_ENH_NO_PEAK_GUARD; warm_start must be -1 and OU_ENH_USE_AUX_SIGNAL is refused (OU_EINVAL).
+ * Everything is enqueued on `stream` (no side streams). */
+int ou_enhance_segments(ou_handle* h, const float* mix, float* out, const float* noise, int32_t C, int64_t T_raw,
+                        int32_t segment, int32_t overlap, int32_t max_batch, int32_t n_steps, double epsilon,
+                        const float* sigma_host, int32_t warm_start, uint32_t flags, void* ws, size_t ws_bytes,
+                        ou_stream_t stream);
 
 /* One sampler update on caller-owned buffers, for bindings that keep the reference's Python loop
  * (universe.py:339 `x = x + s_now^2 * eta * score + beta * z`, :343 `x = x + s_last^2 * score`):

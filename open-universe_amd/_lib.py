@@ -97,6 +97,11 @@ def load():
         "ou_aux_to_wav": (i32, [vp, vp, i32, i32, vp, sz, vp]),
         "ou_enhance": (i32, [vp, vp, vp, vp, i32, i32, i32, c_double, POINTER(c_float), i32, c_uint32, vp, sz, vp]),
         "ou_enhance_var": (i32, [vp, vp, vp, vp, i32, i32, POINTER(i32), i32, c_double, POINTER(c_float), i32, c_uint32, vp, sz, vp]),
+        "ou_segment_plan": (i32, [i32, c_int64, i32, i32, i32, POINTER(c_int64), POINTER(i32), POINTER(c_int64),
+                                  POINTER(c_int64), POINTER(i32), POINTER(i32), POINTER(c_int64)]),
+        "ou_segments_workspace_bytes": (i32, [vp, i32, c_int64, i32, i32, i32, POINTER(sz), POINTER(i32), POINTER(i32)]),
+        "ou_enhance_segments": (i32, [vp, vp, vp, vp, i32, c_int64, i32, i32, i32, i32, c_double, POINTER(c_float), i32,
+                                      c_uint32, vp, sz, vp]),
         "ou_check_device_status": (i32, [vp, vp]),
         "ou_set_option": (i32, [vp, c_char_p, c_double]),
         "ou_get_option": (i32, [vp, c_char_p, POINTER(c_double)]),
@@ -140,6 +145,7 @@ EXPORTED_SYMBOLS = [
     "ou_version", "ou_last_error", "ou_packer_last_error", "ou_packer_create", "ou_packer_set", "ou_packer_finish",
     "ou_packer_destroy", "ou_packed_bytes", "ou_create", "ou_destroy", "ou_workspace_bytes", "ou_schedule",
     "ou_condition", "ou_score", "ou_aux_to_wav", "ou_enhance", "ou_enhance_var", "ou_check_device_status",
+    "ou_segment_plan", "ou_segments_workspace_bytes", "ou_enhance_segments",
     "ou_set_option", "ou_get_option", "ou_reset_options", "ou_option_count", "ou_option_name", "ou_option_doc", "ou_option_default", "ou_plan_json",
     "ou_packer_plan_json", "ou_tensor", "ou_launch_stats", "ou_workspace_init", "ou_sampler_step",
     "ou_set_gru_publish_mode", "ou_get_gru_publish_mode", "ou_set_lanes", "ou_set_lane_batch", "ou_lane_capacity",
@@ -175,6 +181,50 @@ def option_names():
 def option_defaults():
     L = load()
     return {L.ou_option_name(i).decode(): L.ou_option_default(i) for i in range(L.ou_option_count())}
+
+
+def segment_plan(tot_ds, T_raw, segment, overlap):
+    """The library's window plan of a segmented enhance (ou_segment_plan): dict of numpy arrays `starts`, `lengths`,
+    `core_begin`, `core_end` (one entry per window) and the ints `overlap` (as used) and `T_pad`.  Pure host code."""
+    import numpy as np
+
+    L = load()
+    n, ov, tp = c_int32(), c_int32(), c_int64()
+    check(L.ou_segment_plan(int(tot_ds), int(T_raw), int(segment), int(overlap), 0, None, None, None, None, byref(n),
+                            byref(ov), byref(tp)))
+    k = n.value
+    starts, ce0, ce1 = (c_int64 * k)(), (c_int64 * k)(), (c_int64 * k)()
+    lens = (c_int32 * k)()
+    check(L.ou_segment_plan(int(tot_ds), int(T_raw), int(segment), int(overlap), k, starts, lens, ce0, ce1, byref(n),
+                            byref(ov), byref(tp)))
+    return {"starts": np.ctypeslib.as_array(starts).copy(), "lengths": np.ctypeslib.as_array(lens).copy(),
+            "core_begin": np.ctypeslib.as_array(ce0).copy(), "core_end": np.ctypeslib.as_array(ce1).copy(),
+            "overlap": ov.value, "T_pad": tp.value}
+
+
+def segment_weights(plan, k):
+    """Crossfade weight of window k over its own samples (float32), as the stitch applies it: a(i) = 0.5 - 0.5 cos(pi (i + 0.5)
+    / O) over the crossfade [e_{k-1} - O, e_{k-1}) with the window in front (which gets 1 - a(i)), 1 on the rest of what the
+    window writes, 0 on samples that a shifted last window covers but does not write."""
+    import numpy as np
+
+    s, n, O = plan["starts"], len(plan["starts"]), plan["overlap"]
+    L = int(plan["lengths"][k])
+    u = np.arange(s[k], s[k] + L, dtype=np.int64)
+    w = np.zeros(L, dtype=np.float32)
+    ramp = lambda i: (np.float32(0.5) - np.float32(0.5) * np.cos(
+        np.float32(np.pi) * ((i.astype(np.float32) + np.float32(0.5)) / np.float32(O)))).astype(np.float32)
+    w0 = 0 if k == 0 else s[k - 1] + L - O
+    w1 = plan["T_pad"] if k == n - 1 else s[k] + L - O
+    own = (u >= w0) & (u < w1)
+    w[own] = 1.0
+    if k > 0 and O > 0:
+        m = own & (u < s[k - 1] + L)
+        w[m] = ramp(u[m] - w0)
+    if k < n - 1 and O > 0:
+        m = u >= w1
+        w[m] = np.float32(1.0) - ramp(u[m] - w1)
+    return w
 
 
 def make_config(spec, fir_fold=0, split_copy=True):

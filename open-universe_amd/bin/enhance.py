@@ -94,6 +94,12 @@ def build_parser():
                         help="Keep this many enhance calls in flight side by side on the device (one stream and workspace "
                              "each, 1..8): same result as the file-by-file loop, bit for bit, at a multiple of its "
                              "throughput (--batch-size reaches a higher rate, equal to fp32 round-off)")
+    parser.add_argument("--segment-seconds", type=float, default=None,
+                        help="Enhance every file longer than this many seconds in overlapping windows of this length "
+                             "(Universe.enhance_long: bounded memory for recordings of any length; normalisation, mel scale, "
+                             "noise and output level stay those of the whole file).  Off by default")
+    parser.add_argument("--segment-overlap", type=float, default=None,
+                        help="With --segment-seconds: overlap of consecutive windows in seconds (default 1.0)")
     parser.add_argument("--pad-batch", action="store_true",
                         help="With --batch-size: files of different lengths are zero-padded to the longest WITHOUT a mask "
                              "(the reference's batch semantics: the padding changes every result)")
@@ -117,6 +123,42 @@ def group_files(todo, infos, batch_size, pad_batch=False):
     if cur:
         groups.append(cur)
     return groups
+
+
+def check_segment_args(args, enhance_kwargs):
+    """--segment-seconds / --segment-overlap: refused with what they cannot be combined with."""
+    if args.segment_seconds is None:
+        if args.segment_overlap is not None:
+            raise ValueError("--segment-overlap needs --segment-seconds")
+        return
+    if not args.segment_seconds > 0:
+        raise ValueError("--segment-seconds must be positive")
+    ov = 1.0 if args.segment_overlap is None else args.segment_overlap
+    if ov < 0 or 2 * ov > args.segment_seconds:
+        raise ValueError("--segment-overlap must lie in [0, segment-seconds / 2]")
+    if args.pad_batch:
+        raise ValueError("--segment-seconds cannot be combined with --pad-batch")
+    if args.batch_size > 1 or args.in_flight > 1:
+        raise ValueError("--segment-seconds runs one file per call: it cannot be combined with --batch-size or --in-flight")
+    for key in ("ensemble", "target", "warm_start"):
+        if enhance_kwargs.get(key) is not None:
+            raise ValueError(f"--segment-seconds cannot be combined with --{key}")
+    if enhance_kwargs.get("use_aux_signal"):
+        raise ValueError("--segment-seconds cannot be combined with --use-aux-signal")
+
+
+def enhance_file(model, audio, args, enhance_kwargs, rng):
+    """One file of the serial loop: `enhance`, or `enhance_long` when --segment-seconds is set and the file is longer."""
+    if args.segment_seconds is not None and audio.shape[-1] > args.segment_seconds * model.fs:
+        ov = 1.0 if args.segment_overlap is None else args.segment_overlap
+        kw = {k: v for k, v in enhance_kwargs.items() if k in ("n_steps", "epsilon", "keep_rms")}
+        return model.enhance_long(audio, segment_s=args.segment_seconds, overlap_s=ov, rng=rng, **kw)
+    try:
+        return model.enhance(audio, **dict(enhance_kwargs, rng=rng))
+    except ValueError as e:
+        if "ou_enhance_segments" in str(e):
+            raise ValueError(f"{e} -- this file is too long for one pass: run with --segment-seconds (e.g. 8)") from e
+        raise
 
 
 def main(argv=None, model=None):
@@ -156,6 +198,7 @@ def main(argv=None, model=None):
         if group.title == "enhance":
             enhance_kwargs = {a.dest: getattr(args, a.dest, None) for a in group._group_actions}
 
+    check_segment_args(args, enhance_kwargs)
     files, rel_path, dir_proc = find_files(args.input)
     per_file_seed = args.per_file_seed or world > 1
     rng = torch.Generator(device=device)
@@ -231,7 +274,7 @@ def main(argv=None, model=None):
                 rng.manual_seed(args.seed + k)
             with torch.no_grad():
                 audio = resample(audio, fs, model.fs)
-                enh = model.enhance(audio, **dict(enhance_kwargs, rng=rng))
+                enh = enhance_file(model, audio, args, enhance_kwargs, rng)
                 enh = resample(enh, model.fs, fs)
             save(output_path, enh.cpu(), fs)
             done.append(output_path)

@@ -90,6 +90,9 @@ struct ou_handle {
   // launches of all lanes have to be resident together
   int lanes = 1, lane = 0;
   int lane_max_b = 0;  // ou_set_lane_batch: largest batch size any lane of the pool runs (0: every call's own B)
+  // length guard of ou_enhance / ou_enhance_var: bytes per padded sample of the largest per-row plane of the walk (dry walk of
+  // the conditioner and one score pass, every plane a multiple of T; 0 = not measured yet) and of the decoupling scratch
+  double plane_per_sample = 0.0, wav_plane_per_sample = 0.0;
   // A workspace prepared for (B, T0) serves every T of the same batch size that fits into it: everything ou_workspace_init
   // prepares (status words, tag epochs, GRU exchange areas) lies in a header whose layout depends on B alone, and the tag
   // epochs advance monotonically whatever the length of a pass -- a directory of files of different lengths runs on ONE
@@ -184,6 +187,8 @@ struct Runner {
   hipError_t herr = hipSuccess;
   bool oom = false;
   const char* where = "";
+  size_t max_plane = 0;            // largest (C, T) plane of one batch row that alloc() handed out (length guard)
+  bool mel_scale_preset = false;   // the caller wrote the per-row mel scale (segmented enhance: whole-file scale)
 
   Runner(ou_handle* h_, void* ws, size_t cap_, bool dry_, hipStream_t st_, int B_)
       : h(h_), env(h_->opt), base((char*)ws), cap(cap_), dry(dry_), st(st_), B(B_), main_st(st_) {
@@ -203,6 +208,7 @@ struct Runner {
     size_t o = off;
     Tensor t;
     t.p = alloc_raw((size_t)B * C * T);
+    if ((size_t)C * T * 4 > max_plane) max_plane = (size_t)C * T * 4;
     t.C = C;
     t.T = T;
     if (!name.empty()) h->tensors[name] = TensorRef{o, C, T};
@@ -701,6 +707,7 @@ Persist layout_persist(Runner& r, int T) {
   P.lens = (int*)r.alloc_raw((size_t)r.B * kMaxLenLevels);
   P.xchg = (unsigned long long*)r.alloc_raw(gru_granules(r.B, m.OC / 2) * 2);
   P.xchg2 = (unsigned long long*)r.alloc_raw(gru_granules(r.B, m.OC / 2) * 2);
+  r.h->tensors["mel_scale"] = TensorRef{r.off, 1, 1};  // (B, 1, 1): the conditioner's mel normalisation of each row
   P.mel_scale = r.alloc_raw(r.B);
   P.g = r.alloc_raw((size_t)ncoef * m.film.D);
   P.film = r.alloc_raw((size_t)ncoef * m.film.rows);
@@ -736,7 +743,7 @@ void run_condition(Runner& r, Persist& P, const float* mix_norm, int T) {
   if (!r.dry && r.ok()) {
     r.chk(launch_mel(mix_norm, r.W(m.mel.win_off), r.W(m.mel.tw_off), r.W(m.mel.fb_off), mel.p, esum, r.B, T,
                      m.mel.n_fft, m.mel.hop, m.mel.pad_left, m.mel.n_freq, m.mel.n_mels, L, r.st), "mel");
-    r.chk(launch_mel_scale(esum, P.mel_scale, r.B, L, r.st, r.lens_of(L)), "mel_scale");
+    if (!r.mel_scale_preset) r.chk(launch_mel_scale(esum, P.mel_scale, r.B, L, r.st, r.lens_of(L)), "mel_scale");
     r.mask(mel);  // (frames behind a row's end still see its last samples)
   }
   Runner::Epi em;
@@ -932,6 +939,8 @@ void upload_coefs(Runner& r, StepCoef* dst, const std::vector<StepCoef>& rows) {
     r.chk(launch_upload_coef(dst + i, blk, n, r.st), "upload coef");
   }
 }
+
+long long max_walk_length(ou_handle* h, bool need_wav);
 
 int finish(ou_handle* h, Runner& r) {
   if (r.oom) return fail(h, OU_ENOMEM, "workspace too small: need " + std::to_string(r.off) + " bytes");
@@ -1139,6 +1148,9 @@ int ou_workspace_bytes(const ou_handle* hc, int32_t B, int32_t T, size_t* nbytes
   ou_handle* h = const_cast<ou_handle*>(hc);
   if (!h || !nbytes || B < 1 || T < 1) return fail(h, OU_EINVAL, "bad argument");
   if (T % h->m.tot_ds) return fail(h, OU_EINVAL, "T must be a multiple of the total down-sampling factor");
+  if (T > max_walk_length(h, false))  // (the length guard of ou_enhance: refused before a caller allocates for it)
+    return fail(h, OU_EINVAL, "input too long for one pass: a plane of the walk would reach 2^32 bytes; ou_enhance_segments "
+                              "enhances it in windows");
   auto saved = h->tensors;
   Runner r(h, nullptr, 0, true, nullptr, B);
   Persist P = layout_persist(r, T);
@@ -1228,6 +1240,29 @@ int ou_aux_to_wav(ou_handle* h, float* wav_out, int32_t B, int32_t T, void* ws, 
 }  // extern "C"
 
 namespace {
+// Length guard: the kernels of the walk address one batch row's (C, T) plane with 32-bit buffer descriptors, so no plane may
+// reach 2^32 bytes.  Every plane is (channels) x (T * num / den): one dry walk (conditioner + one score pass, batch 1) gives the
+// largest plane per padded sample, cached in the handle.  Returns the largest padded length the walk takes.
+long long max_walk_length(ou_handle* h, bool need_wav) {
+  if (h->plane_per_sample == 0.0) {
+    const int T0 = h->m.tot_ds * 64;
+    auto keep = h->tensors;
+    Runner d(h, nullptr, 0, true, nullptr, 1);
+    Persist Pd = layout_persist(d, T0);
+    run_condition(d, Pd, nullptr, T0);
+    run_score(d, Pd, nullptr, nullptr, nullptr, OUT_UPDATE, nullptr, 0, nullptr, 0, T0);
+    h->tensors = keep;
+    h->plane_per_sample = (double)d.max_plane / T0;
+    h->wav_plane_per_sample = (double)h->m.C0 * 2 * 4;  // decoupling scratch: (C0, 2 T) per row
+  }
+  double per = h->plane_per_sample;
+  if (need_wav && h->wav_plane_per_sample > per) per = h->wav_plane_per_sample;
+  // (4 KiB of head room: the padded descriptors of the up-sampling kernels reach a few samples in front of the plane)
+  const double lim = (4294967296.0 - 4096.0) / per;
+  long long t = (long long)lim;
+  return t - t % h->m.tot_ds;
+}
+
 // ou_enhance / ou_enhance_var.  `t_raw`: host array of B row lengths (max = T_raw) or null (every row T_raw samples long).
 int enhance_impl(ou_handle* h, const float* mix, float* out, const float* noise, int32_t B, int32_t T_raw,
                  const int32_t* t_raw, int32_t n_steps, double epsilon, const float* sigma_host, int32_t warm_start,
@@ -1260,6 +1295,13 @@ int enhance_impl(ou_handle* h, const float* mix, float* out, const float* noise,
   const int pad = tot - T_raw % tot;  // universe.py:219-223 (a full block when already a multiple)
   const int pad_left = pad / 2;
   const int T = T_raw + pad;
+  {
+    const long long t_max = max_walk_length(h, use_aux || warm_start >= 0);
+    if (T > t_max)
+      return fail(h, OU_EINVAL, "input too long for one pass: " + std::to_string(T_raw) + " samples padded to " +
+                                    std::to_string(T) + " make a plane of the walk reach 2^32 bytes (at most " +
+                                    std::to_string(t_max) + " padded samples); ou_enhance_segments enhances it in windows");
+  }
   if (!h->ws_ok(ws, ws_bytes, B, T))
     return fail(h, OU_EINVAL, "workspace was not prepared by ou_workspace_init for this (B, T_raw + pad)");
   h->tensors.clear();
@@ -1424,6 +1466,212 @@ int ou_enhance_var(ou_handle* h, const float* mix, float* out, const float* nois
   if (!t_raw) return fail(h, OU_EINVAL, "ou_enhance_var: t_raw must be given (ou_enhance takes batches of equal lengths)");
   return enhance_impl(h, mix, out, noise, B, T_raw_max, t_raw, n_steps, epsilon, sigma_host, warm_start, flags, ws, ws_bytes,
                       stream);
+}
+
+}  // extern "C"
+
+namespace {
+// Segment plan (include/ouniverse.h, ou_segment_plan): a pure function of (T_raw, tot_ds, segment, overlap).
+struct SegPlan {
+  SegGeom g;
+  std::string err;
+};
+bool seg_plan(int tot, long long T_raw, long long segment, long long overlap, SegPlan& p) {
+  if (tot < 1 || T_raw < 1) { p.err = "segment plan: T_raw >= 1 and tot_ds >= 1"; return false; }
+  const long long S = segment - segment % tot, O = overlap - overlap % tot;
+  if (S < tot) { p.err = "segment must be at least one total down-sampling factor (" + std::to_string(tot) + " samples)"; return false; }
+  if (O < 0 || 2 * O > S) { p.err = "overlap must lie in [0, segment / 2]"; return false; }
+  SegGeom& g = p.g;
+  const long long pad = tot - T_raw % tot;  // universe.py:219-223
+  g.T_raw = T_raw;
+  g.T_pad = T_raw + pad;
+  g.pad_left = pad / 2;
+  if (g.T_pad <= S) {
+    g.L = g.T_pad; g.hop = g.T_pad; g.overlap = 0; g.n_win = 1;
+  } else {
+    g.L = S; g.hop = S - O; g.overlap = O;
+    g.n_win = (g.T_pad - S + g.hop - 1) / g.hop + 1;
+  }
+  g.n_entries = g.n_win;  // (per row; the caller multiplies by the rows)
+  return true;
+}
+long long seg_start_host(const SegGeom& g, long long k) { return k < g.n_win - 1 ? k * g.hop : g.T_pad - g.L; }
+// batch size of every group: the entries spread evenly over ceil(E / max_batch) groups
+int seg_batch(long long entries, int max_batch) {
+  const long long groups = (entries + max_batch - 1) / max_batch;
+  return (int)((entries + groups - 1) / groups);
+}
+// bytes of the segmented call's own area behind the walk's workspace
+struct SegArea {
+  size_t stats, row_scale, part, zbuf, carry, total;
+};
+SegArea seg_area(int C, int B, long long L) {
+  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+  SegArea a;
+  size_t off = 0;
+  a.stats = off; off += al((size_t)C * 4 * 4);
+  a.row_scale = off; off += al((size_t)C * 4);
+  a.part = off; off += al((size_t)C * 1024 * 3 * 8);
+  a.zbuf = off; off += al((size_t)B * L * 4);
+  a.carry = off; off += al((size_t)L * 4);
+  a.total = off;
+  return a;
+}
+}  // namespace
+
+extern "C" {
+
+int ou_segment_plan(int32_t tot_ds, int64_t T_raw, int32_t segment, int32_t overlap, int32_t capacity, int64_t* starts,
+                    int32_t* lengths, int64_t* core_begin, int64_t* core_end, int32_t* n_windows, int32_t* overlap_used,
+                    int64_t* T_pad) {
+  SegPlan p;
+  if (!seg_plan(tot_ds, T_raw, segment, overlap, p)) return fail(nullptr, OU_EINVAL, p.err);
+  const SegGeom& g = p.g;
+  if (g.n_win > 0x7fffffffll) return fail(nullptr, OU_EINVAL, "segment plan: too many windows");
+  if (n_windows) *n_windows = (int32_t)g.n_win;
+  if (overlap_used) *overlap_used = (int32_t)g.overlap;
+  if (T_pad) *T_pad = g.T_pad;
+  if (!starts && !lengths && !core_begin && !core_end) return OU_OK;
+  if (capacity < g.n_win) return fail(nullptr, OU_EINVAL, "segment plan: capacity smaller than the number of windows");
+  // core k = [m_{k-1}, m_k): m_k = the middle of the crossfade between windows k and k + 1, [e_k - O, e_k)
+  for (long long k = 0; k < g.n_win; k++) {
+    const long long s = seg_start_host(g, k);
+    if (starts) starts[k] = s;
+    if (lengths) lengths[k] = (int32_t)g.L;
+    const long long m0 = k == 0 ? 0 : seg_start_host(g, k - 1) + g.L - g.overlap + g.overlap / 2;
+    const long long m1 = k == g.n_win - 1 ? g.T_pad : s + g.L - g.overlap + g.overlap / 2;
+    if (core_begin) core_begin[k] = m0;
+    if (core_end) core_end[k] = m1;
+  }
+  return OU_OK;
+}
+
+int ou_segments_workspace_bytes(const ou_handle* hc, int32_t C, int64_t T_raw, int32_t segment, int32_t overlap,
+                                int32_t max_batch, size_t* nbytes, int32_t* batch, int32_t* length) {
+  ou_handle* h = const_cast<ou_handle*>(hc);
+  if (!h || !nbytes || C < 1 || max_batch < 1) return fail(h, OU_EINVAL, "bad argument");
+  SegPlan p;
+  if (!seg_plan(h->m.tot_ds, T_raw, segment, overlap, p)) return fail(h, OU_EINVAL, p.err);
+  if (p.g.L > 0x7fffffffll) return fail(h, OU_EINVAL, "segment too long");
+  const int B = seg_batch((long long)C * p.g.n_win, max_batch);
+  size_t walk = 0;
+  const int rc = ou_workspace_bytes(h, B, (int32_t)p.g.L, &walk);
+  if (rc != OU_OK) return rc;
+  walk = (walk + 255) & ~size_t(255);
+  *nbytes = walk + seg_area(C, B, p.g.L).total;
+  if (batch) *batch = B;
+  if (length) *length = (int32_t)p.g.L;
+  return OU_OK;
+}
+
+int ou_enhance_segments(ou_handle* h, const float* mix, float* out, const float* noise, int32_t C, int64_t T_raw,
+                        int32_t segment, int32_t overlap, int32_t max_batch, int32_t n_steps, double epsilon,
+                        const float* sigma_host, int32_t warm_start, uint32_t flags, void* ws, size_t ws_bytes,
+                        ou_stream_t stream) {
+  if (!h || !mix || !out || !noise || !ws || C < 1 || T_raw < 1 || max_batch < 1) return fail(h, OU_EINVAL, "bad argument");
+  if (warm_start >= 0 || (flags & OU_ENH_USE_AUX_SIGNAL))
+    return fail(h, OU_EINVAL, "ou_enhance_segments: warm_start and use_aux_signal are not supported");
+  if (n_steps < 2 || n_steps > kMaxSteps) return fail(h, OU_EINVAL, "n_steps must be in [2, 256]");
+  SegPlan plan;
+  if (!seg_plan(h->m.tot_ds, T_raw, segment, overlap, plan)) return fail(h, OU_EINVAL, plan.err);
+  SegGeom g = plan.g;
+  g.n_entries = (long long)C * g.n_win;
+  if (g.L > max_walk_length(h, false))
+    return fail(h, OU_EINVAL, "ou_enhance_segments: segment too long for one pass of the walk");
+  const int B = seg_batch(g.n_entries, max_batch);
+  const int L = (int)g.L;
+  size_t walk = 0;
+  {
+    const int rc = ou_workspace_bytes(h, B, L, &walk);
+    if (rc != OU_OK) return rc;
+    walk = (walk + 255) & ~size_t(255);
+  }
+  const SegArea A = seg_area(C, B, g.L);
+  if (ws_bytes < walk + A.total) return fail(h, OU_ENOMEM, "workspace too small: need " + std::to_string(walk + A.total) +
+                                                               " bytes (ou_segments_workspace_bytes)");
+  if (!h->ws_ok(ws, ws_bytes, B, L))
+    return fail(h, OU_EINVAL, "workspace was not prepared by ou_workspace_init for (batch, length) of ou_segments_workspace_bytes");
+  char* seg = (char*)ws + walk;
+  float* stats = (float*)(seg + A.stats);
+  float* row_scale = (float*)(seg + A.row_scale);
+  double* part = (double*)(seg + A.part);
+  float* zbuf = (float*)(seg + A.zbuf);
+  float* carry = (float*)(seg + A.carry);
+
+  const bool saved_overlap = h->overlap;
+  struct OverlapGuard { ou_handle* h; bool v; ~OverlapGuard() { h->overlap = v; } } overlap_guard{h, saved_overlap};
+  h->overlap = false;  // one chain on the caller's stream
+  h->tensors.clear();
+  h->n_launch = h->n_conv = 0;
+  h->ev_used = 0;
+  hipStream_t st = (hipStream_t)stream;
+  const Model& m = h->m;
+
+  // ---- whole-file statistics and mel scale (the output buffer holds the frame energies until the first stitch)
+  const float level = (float)std::pow(10.0, (double)m.cfg.level_db / 20.0);
+  const long long Lf = g.T_pad / m.tot_ds;  // mel frames of the whole file (run_condition)
+  if (Lf > g.T_raw) return fail(h, OU_EINVAL, "internal: mel frames do not fit into the output row");
+  auto chk = [&](hipError_t e, const char* w) -> bool {
+    h->n_launch++;
+    if (e != hipSuccess) { fail(h, OU_EHIP, std::string("HIP error at ") + w + ": " + hipGetErrorString(e)); return false; }
+    return true;
+  };
+  if (!chk(launch_seg_stats(mix, part, stats, C, g.T_raw, g.T_pad, level, st), "segment stats")) return OU_EHIP;
+  if (!chk(launch_seg_mel_energy(mix, stats, h->W + m.mel.win_off, h->W + m.mel.tw_off, h->W + m.mel.fb_off, out, C, g.T_raw,
+                                 g.T_pad, g.pad_left, m.mel.n_fft, m.mel.hop, m.mel.pad_left, m.mel.n_freq, m.mel.n_mels, Lf,
+                                 st), "segment mel energy"))
+    return OU_EHIP;
+  if (Lf > 0x7fffffffll) return fail(h, OU_EINVAL, "input too long");
+  if (!chk(launch_mel_scale(out, row_scale, C, (int)Lf, st), "segment mel scale")) return OU_EHIP;
+
+  // ---- sampler constants (as ou_enhance)
+  std::vector<float> sigma(n_steps);
+  double eta, beta;
+  schedule(m.cfg, n_steps, epsilon, sigma.data(), &eta, &beta);
+  if (sigma_host) std::memcpy(sigma.data(), sigma_host, sizeof(float) * n_steps);
+  std::vector<StepCoef> rows;
+  for (int n = 0; n < n_steps; n++)
+    rows.push_back(make_coef(m.cfg, sigma[n], n == n_steps - 1, eta, beta, n + 1 < n_steps ? sigma[n + 1] : 0.f));
+
+  // ---- the windows, B at a time, through the plain walk of ou_enhance
+  const size_t nBL = (size_t)B * L;
+  const size_t step_noise = (size_t)C * g.T_pad;  // one step of the whole-file noise
+  bool coefs_up = false;
+  for (long long e0 = 0; e0 < g.n_entries; e0 += B) {
+    const int n_real = (int)std::min<long long>(B, g.n_entries - e0);
+    Runner r(h, ws, walk, false, st, B);
+    r.mel_scale_preset = true;
+    Persist P = layout_persist(r, L);
+    if (r.oom) return finish(h, r);
+    if (!coefs_up) {  // (the persistent area of the workspace keeps them from group to group)
+      upload_coefs(r, P.coef, rows);
+      r.chk(launch_sigma_embed(P.coef, n_steps, r.W(m.sigma.p_off), m.sigma.simple, m.sigma.n_rff, m.film.D, P.g, st), "sigma");
+      r.chk(launch_film(P.g, r.W(m.film.w_off), r.W(m.film.b_off), P.film, n_steps, m.film.rows, m.film.D, st), "film");
+      coefs_up = true;
+    }
+    r.chk(launch_seg_gather_input(mix, stats, row_scale, P.mixn.p, P.mel_scale, g, e0, B, st), "segment gather");
+    run_condition(r, P, P.mixn.p, L);
+    r.chk(launch_seg_gather_noise(noise, zbuf, g, e0, B, st), "segment noise");
+    r.chk(launch_init_x(zbuf, nullptr, sigma[0], P.x.p, nBL, st), "init x");  // universe.py:325-327
+    const size_t step_mark = r.off;
+    for (int n = 0; n < n_steps && r.ok(); n++) {
+      const bool last = n == n_steps - 1;
+      if (!last) r.chk(launch_seg_gather_noise(noise + (size_t)(n + 1) * step_noise, zbuf, g, e0, B, st), "segment noise");
+      r.off = step_mark;
+      run_score(r, P, P.x.p, last ? nullptr : zbuf, P.x.p, OUT_UPDATE, P.coef + n, 0, P.film + (size_t)n * m.film.rows, 0, L);
+    }
+    if (r.ok()) r.chk(launch_seg_stitch(P.x.p, carry, out, g, e0, n_real, st), "segment stitch");
+    if (r.ok() && e0 + B < g.n_entries)  // the window in front of the next group
+      r.chk(hipMemcpyAsync(carry, P.x.p + (size_t)(n_real - 1) * L, (size_t)L * 4, hipMemcpyDeviceToDevice, st), "carry");
+    const int rc = finish(h, r);
+    if (rc != OU_OK) return rc;
+  }
+  h->cond_B = 0;  // (the operator seams see a whole-file batch only)
+  h->cond_T = L;
+  const int keep_rms = (flags & OU_ENH_KEEP_RMS) ? 1 : 0;
+  const int peak = (flags & OU_ENH_NO_PEAK_GUARD) ? 0 : 1;
+  if (!chk(launch_seg_post(out, part, stats, C, g.T_raw, keep_rms, peak, st), "segment post")) return OU_EHIP;
+  return OU_OK;
 }
 
 int ou_transform_frames(int32_t T, int32_t n_fft, int32_t hop) {

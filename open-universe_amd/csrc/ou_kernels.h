@@ -181,6 +181,34 @@ hipError_t launch_mel(const float* x, const float* win, const float* tw, const f
 // (`lens`: frames per row of a ragged batch or null -- the mean runs over the row's own frames)
 hipError_t launch_mel_scale(const float* esum, float* scale, int B, int L, hipStream_t st, const int* lens = nullptr);
 
+// ---- segmented enhance (ou_segment.hip): long rows cut into overlapping windows of L samples --------------------------------
+// Window k of a row starts at k * hop (the last one at T_pad - L); the entries of a call are (row, window) pairs in row-major
+// order, e = row * n_win + k.  Every offset into a long row is 64-bit.
+struct SegGeom {
+  long long T_raw, T_pad, pad_left;
+  long long L, hop, overlap;
+  long long n_win, n_entries;
+};
+// blocks per row of the whole-row reductions (their partials: [C][nb][3] doubles for the statistics, [C][nb][2] for the post)
+int seg_reduce_blocks(long long T_raw);
+// stats[c] = {mean, gain, mix_rms, 0} of the padded whole row (pad_normalize_kernel's layout and arithmetic)
+hipError_t launch_seg_stats(const float* mix, double* part, float* stats, int C, long long T_raw, long long T_pad, float level,
+                            hipStream_t st);
+// esum[c][f] = frame energies of the mel front-end over the whole normalised row (mel_kernel without the mel output)
+hipError_t launch_seg_mel_energy(const float* mix, const float* stats, const float* win, const float* tw, const float* fb,
+                                 float* esum, int C, long long T_raw, long long T_pad, long long pad_left, int n_fft, int hop,
+                                 int mel_pad, int n_freq, int n_mels, long long L, hipStream_t st);
+// the B windows e0 .. e0 + B - 1 of a group: normalised input (B, L) and each entry's row mel scale; one step's noise (B, L)
+hipError_t launch_seg_gather_input(const float* mix, const float* stats, const float* row_mel_scale, float* mixn,
+                                   float* mel_scale, const SegGeom& g, long long e0, int B, hipStream_t st);
+hipError_t launch_seg_gather_noise(const float* noise, float* z, const SegGeom& g, long long e0, int B, hipStream_t st);
+// crossfade the group's n_real window outputs (and `carry`, the window in front of the group) into the unpadded long output
+hipError_t launch_seg_stitch(const float* y, const float* carry, float* out, const SegGeom& g, long long e0, int n_real,
+                             hipStream_t st);
+// keep_rms + peak guard over whole long rows, in place (universe.py:349-357)
+hipError_t launch_seg_post(float* out, double* part, const float* stats, int C, long long T_raw, int keep_rms, int peak_guard,
+                           hipStream_t st);
+
 // space-to-depth + PReLU for the conditioner's strided "st" convs: y[b][ci*R + k][q] = prelu(x[b][ci][q*R + k])
 hipError_t launch_s2d(const float* x, const float* alpha, float* y, int B, int C, int T, int R, hipStream_t st);
 // (`lens` of launch_in_conv / launch_out_conv / launch_fir: per-row valid lengths of a ragged batch or null, see ConvArgs::lens)

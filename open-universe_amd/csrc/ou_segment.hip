@@ -1,0 +1,313 @@
+// Segmented enhance (ou_enhance_segments): whole-file statistics, window gathers, crossfade stitch and post step over LONG
+// rows.  Every index into a long row is 64-bit and no kernel here builds a buffer descriptor, so nothing wraps past 2^32 bytes
+// per row.  Reductions run in a fixed order (per-block partials in double, summed in block order by whoever needs the
+// total): two runs give the same bits.  With one block per row the order is exactly that of pad_normalize_kernel /
+// post_kernel, so a file that fits into one window gets the whole-file call's statistics bit for bit.
+#include "ou_internal.h"
+
+namespace ou {
+namespace {
+
+template <typename T>
+__device__ __forceinline__ T seg_wave_sum(T v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ float seg_wave_max(float v) {
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  return v;
+}
+template <typename T>
+__device__ T seg_block_sum(T v, T* sh) {  // blockDim multiple of 64, <= 1024 (same order as block_sum, ou_small.hip)
+  v = seg_wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  T r = 0;
+  for (int i = 0; i < (int)(blockDim.x >> 6); i++) r += sh[i];
+  return r;
+}
+__device__ float seg_block_max(float v, float* sh) {
+  v = seg_wave_max(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float r = sh[0];
+  for (int i = 1; i < (int)(blockDim.x >> 6); i++) r = fmaxf(r, sh[i]);
+  return r;
+}
+
+// start of window k (SegGeom, ou_kernels.h): k * hop, the last one shifted to end at T_pad
+__device__ __forceinline__ long long seg_start(const SegGeom& g, long long k) {
+  return k < g.n_win - 1 ? k * g.hop : g.T_pad - g.L;
+}
+
+// ---- whole-file statistics (utils/norm.py:47-87, universe.py:259) ------------------------------------------------------
+// pass 1: per-block sum and sum of squares of the raw row.  grid (nb, C)
+__global__ __launch_bounds__(1024) void seg_stats1_kernel(const float* __restrict__ mix, double* __restrict__ part,
+                                                          long long T_raw, int nb) {
+  __shared__ double shd[16];
+  const int j = blockIdx.x, c = blockIdx.y;
+  const float* xb = mix + (size_t)c * T_raw;
+  double s = 0, sq = 0;
+  for (long long t = (long long)j * 1024 + threadIdx.x; t < T_raw; t += (long long)nb * 1024) {
+    const double d = xb[t];
+    s += d; sq += d * d;
+  }
+  s = seg_block_sum(s, shd);
+  sq = seg_block_sum(sq, shd);
+  if (threadIdx.x == 0) { part[((size_t)c * nb + j) * 3 + 0] = s; part[((size_t)c * nb + j) * 3 + 1] = sq; }
+}
+// pass 2: per-block sum of (x - mean)^2 around the mean of the padded row (each block sums the partials of pass 1 in order)
+__global__ __launch_bounds__(1024) void seg_stats2_kernel(const float* __restrict__ mix, double* __restrict__ part,
+                                                          long long T_raw, long long T_pad, int nb) {
+  __shared__ double shd[16];
+  const int j = blockIdx.x, c = blockIdx.y;
+  const double* pc = part + (size_t)c * nb * 3;
+  double s = pc[0];
+  for (int i = 1; i < nb; i++) s += pc[i * 3];
+  const float mean = (float)(s / (double)T_pad);  // norm.py:62  (mean over the padded signal)
+  const float* xb = mix + (size_t)c * T_raw;
+  double ss = 0;
+  for (long long t = (long long)j * 1024 + threadIdx.x; t < T_raw; t += (long long)nb * 1024) {
+    const double d = (double)(xb[t] - mean);
+    ss += d * d;
+  }
+  ss = seg_block_sum(ss, shd);
+  if (threadIdx.x == 0) part[((size_t)c * nb + j) * 3 + 2] = ss;
+}
+// finish: stats[c] = {mean, gain, mix_rms, 0}  (the layout of pad_normalize_kernel's stats)
+__global__ void seg_stats_finish_kernel(const double* __restrict__ part, float* __restrict__ stats, long long T_raw,
+                                        long long T_pad, int nb, float level) {
+  const int c = blockIdx.x;
+  if (threadIdx.x != 0) return;
+  const double* pc = part + (size_t)c * nb * 3;
+  double s = pc[0], sq = pc[1], ss = pc[2];
+  for (int i = 1; i < nb; i++) { s += pc[i * 3]; sq += pc[i * 3 + 1]; ss += pc[i * 3 + 2]; }
+  const float mean = (float)(s / (double)T_pad);
+  ss += (double)(T_pad - T_raw) * (double)(0.f - mean) * (double)(0.f - mean);
+  float sd = (float)sqrt(ss / (double)(T_pad - 1));  // unbiased std, norm.py:22-23
+  sd = fmaxf(sd, 1e-5f);
+  stats[c * 4 + 0] = mean;
+  stats[c * 4 + 1] = level / sd;
+  stats[c * 4 + 2] = (float)sqrt(sq / (double)T_raw);
+  stats[c * 4 + 3] = 0.f;
+}
+
+// ---- whole-file mel normalisation (condition.py:105-106) ---------------------------------------------------------------
+// The frame energies of mel_kernel over the whole normalised file, without the mel output: the normalisation (x - mean) * gain
+// and the pad split are applied on the fly to the raw row.  Same arithmetic, same order as mel_kernel.  grid (L, C)
+__global__ __launch_bounds__(512) void seg_mel_energy_kernel(const float* __restrict__ mix, const float* __restrict__ stats,
+                                                             const float* __restrict__ win, const float* __restrict__ tw,
+                                                             const float* __restrict__ fb, float* __restrict__ esum,
+                                                             long long T_raw, long long T_pad, long long pad_left,
+                                                             int n_fft, int hop, int mel_pad, int n_freq, int n_mels,
+                                                             long long L) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  float* sx = sm;
+  float* tc = sx + n_fft;
+  float* ts = tc + n_fft;
+  float* pw = ts + n_fft;
+  __shared__ float shf[8];
+  const long long f = blockIdx.x;
+  const int c = blockIdx.y, tid = threadIdx.x;
+  const float mean = stats[c * 4 + 0], gain = stats[c * 4 + 1];
+  const float* xb = mix + (size_t)c * T_raw;
+  for (int n = tid; n < n_fft; n += 512) {
+    const long long t = f * hop + n - mel_pad;
+    float v = 0.f;
+    if (t >= 0 && t < T_pad) {
+      const long long tr = t - pad_left;
+      v = ((tr >= 0 && tr < T_raw) ? xb[tr] : 0.f);
+      v = (v - mean) * gain;
+    }
+    sx[n] = v * win[n];
+    tc[n] = tw[n];
+    ts[n] = tw[n_fft + n];
+  }
+  __syncthreads();
+  for (int k = tid; k < n_freq; k += 512) {
+    float re = 0.f, im = 0.f;
+    int idx = 0;
+    for (int n = 0; n < n_fft; n++) {
+      float v = sx[n];
+      re = fmaf(v, tc[idx], re);
+      im = fmaf(-v, ts[idx], im);
+      idx += k;
+      if (idx >= n_fft) idx -= n_fft;
+    }
+    pw[k] = re * re + im * im;
+  }
+  __syncthreads();
+  float e = 0.f;
+  for (int m = tid; m < n_mels; m += 512) {
+    float acc = 0.f;
+    for (int k = 0; k < n_freq; k++) acc = fmaf(pw[k], fb[(size_t)k * n_mels + m], acc);
+    e += acc * acc;
+  }
+  e = seg_block_sum(e, shf);
+  if (tid == 0) esum[(size_t)c * L + f] = e;
+}
+
+// ---- window gathers ----------------------------------------------------------------------------------------------------
+// mixn[j][t] = (x[c_j][s_j + t - pad_left] - mean_c) * gain_c (0 outside the raw row: the whole-file pad split), and
+// mel_scale[j] = the whole-file mel scale of row c_j.  Entries e0 + j past the last real one repeat it.  grid (ceil(L/1024), B)
+__global__ __launch_bounds__(256) void seg_gather_input_kernel(const float* __restrict__ mix, const float* __restrict__ stats,
+                                                               const float* __restrict__ row_mel_scale, float* __restrict__ mixn,
+                                                               float* __restrict__ mel_scale, SegGeom g, long long e0) {
+  const int j = blockIdx.y;
+  long long e = e0 + j;
+  if (e > g.n_entries - 1) e = g.n_entries - 1;
+  const long long c = e / g.n_win, k = e - c * g.n_win;
+  const long long s = seg_start(g, k);
+  const float mean = stats[c * 4 + 0], gain = stats[c * 4 + 1];
+  const float* xb = mix + (size_t)c * g.T_raw;
+  float* yb = mixn + (size_t)j * g.L;
+  for (long long t = (long long)blockIdx.x * 1024 + threadIdx.x; t < (long long)(blockIdx.x + 1) * 1024 && t < g.L; t += 256) {
+    const long long tr = s + t - g.pad_left;
+    const float v = (tr >= 0 && tr < g.T_raw) ? xb[tr] : 0.f;
+    yb[t] = (v - mean) * gain;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) mel_scale[j] = row_mel_scale[c];
+}
+// z[j][t] = noise[c_j][s_j + t]   (one step's (C, T_pad) slice of the whole-file noise)
+__global__ __launch_bounds__(256) void seg_gather_noise_kernel(const float* __restrict__ noise, float* __restrict__ z, SegGeom g,
+                                                               long long e0) {
+  const int j = blockIdx.y;
+  long long e = e0 + j;
+  if (e > g.n_entries - 1) e = g.n_entries - 1;
+  const long long c = e / g.n_win, k = e - c * g.n_win;
+  const float* src = noise + (size_t)c * g.T_pad + seg_start(g, k);
+  float* dst = z + (size_t)j * g.L;
+  for (long long t = (long long)blockIdx.x * 1024 + threadIdx.x; t < (long long)(blockIdx.x + 1) * 1024 && t < g.L; t += 256)
+    dst[t] = src[t];
+}
+
+// ---- crossfade stitch ----------------------------------------------------------------------------------------------------
+// Entry k of a row writes the samples [w_k, w_{k+1}) of the padded row (w_0 = 0, w_k = e_{k-1} - O, w_n = T_pad, e_k = end of
+// window k), unpadded into out.  On [w_k, e_{k-1}) it crossfades with window k - 1 (the previous entry of the group, or `carry`
+// for the first entry of a group): weight a(i) = 0.5 - 0.5 cos(pi (i + 0.5) / O) for window k, 1 - a(i) for window k - 1.
+// grid (ceil(L / 1024), n_real)
+__global__ __launch_bounds__(256) void seg_stitch_kernel(const float* __restrict__ y, const float* __restrict__ carry,
+                                                         float* __restrict__ out, SegGeom g, long long e0) {
+  const int j = blockIdx.y;
+  const long long e = e0 + j;
+  const long long c = e / g.n_win, k = e - c * g.n_win;
+  const long long s = seg_start(g, k);
+  const long long w0 = k == 0 ? 0 : seg_start(g, k - 1) + g.L - g.overlap;
+  const long long w1 = k == g.n_win - 1 ? g.T_pad : s + g.L - g.overlap;
+  const long long e_prev = k == 0 ? 0 : seg_start(g, k - 1) + g.L;
+  const float* yk = y + (size_t)j * g.L;
+  const float* yp = j > 0 ? y + (size_t)(j - 1) * g.L : carry;
+  const long long s_prev = k == 0 ? 0 : seg_start(g, k - 1);
+  float* ob = out + (size_t)c * g.T_raw;
+  for (long long t = (long long)blockIdx.x * 1024 + threadIdx.x; t < (long long)(blockIdx.x + 1) * 1024 && t < g.L; t += 256) {
+    const long long u = s + t;  // position in the padded row
+    if (u < w0 || u >= w1) continue;
+    const long long tr = u - g.pad_left;
+    if (tr < 0 || tr >= g.T_raw) continue;
+    float v = yk[t];
+    if (u < e_prev) {
+      const float a = 0.5f - 0.5f * cosf(3.14159265358979f * ((float)(u - w0) + 0.5f) / (float)g.overlap);
+      v = (1.f - a) * yp[u - s_prev] + a * v;
+    }
+    ob[tr] = v;
+  }
+}
+
+// ---- post step over the whole row (universe.py:349-357) ----------------------------------------------------------------
+// per-block sum of squares (double) and max |x|: grid (nb, C)
+__global__ __launch_bounds__(1024) void seg_post_reduce_kernel(const float* __restrict__ out, double* __restrict__ part,
+                                                               long long T_raw, int nb) {
+  __shared__ double shd[16];
+  __shared__ float shf[16];
+  const int j = blockIdx.x, c = blockIdx.y;
+  const float* xb = out + (size_t)c * T_raw;
+  double sq = 0;
+  float mx = 0.f;
+  for (long long t = (long long)j * 1024 + threadIdx.x; t < T_raw; t += (long long)nb * 1024) {
+    const float v = xb[t];
+    const double d = v;
+    sq += d * d;
+    mx = fmaxf(mx, fabsf(v));
+  }
+  sq = seg_block_sum(sq, shd);
+  mx = seg_block_max(mx, shf);
+  if (threadIdx.x == 0) { part[((size_t)c * nb + j) * 2 + 0] = sq; part[((size_t)c * nb + j) * 2 + 1] = (double)mx; }
+}
+// keep_rms gain g = mix_rms / max(x_rms, 1e-5), peak m = max|x| * g (rounding is monotonic: = max|x * g|), x <- x * g [/ m]
+__global__ __launch_bounds__(256) void seg_post_scale_kernel(float* __restrict__ out, const double* __restrict__ part,
+                                                             const float* __restrict__ stats, long long T_raw, int nb,
+                                                             int keep_rms, int peak_guard) {
+  const int c = blockIdx.y;
+  const double* pc = part + (size_t)c * nb * 2;
+  double sq = pc[0];
+  float mxa = (float)pc[1];
+  for (int i = 1; i < nb; i++) { sq += pc[i * 2]; mxa = fmaxf(mxa, (float)pc[i * 2 + 1]); }
+  float g = 1.f;
+  if (keep_rms) {
+    const float x_rms = fmaxf((float)sqrt(sq / (double)T_raw), 1e-5f);
+    g = stats[c * 4 + 2] / x_rms;
+  }
+  const float mx = mxa * g;
+  const bool div = peak_guard && mx > 1.0f;
+  if (!keep_rms && !div) return;
+  float* xb = out + (size_t)c * T_raw;
+  for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < T_raw; t += (long long)gridDim.x * 256) {
+    float v = xb[t] * g;
+    if (div) v = v / mx;
+    xb[t] = v;
+  }
+}
+
+}  // namespace
+
+int seg_reduce_blocks(long long T_raw) {
+  long long nb = (T_raw + (1ll << 18) - 1) >> 18;  // one block per 256 Ki samples: one block per row up to 16 s at 16 kHz
+  return (int)(nb < 1 ? 1 : nb > 1024 ? 1024 : nb);
+}
+
+hipError_t launch_seg_stats(const float* mix, double* part, float* stats, int C, long long T_raw, long long T_pad, float level,
+                            hipStream_t st) {
+  const int nb = seg_reduce_blocks(T_raw);
+  hipLaunchKernelGGL(seg_stats1_kernel, dim3(nb, C), dim3(1024), 0, st, mix, part, T_raw, nb);
+  hipLaunchKernelGGL(seg_stats2_kernel, dim3(nb, C), dim3(1024), 0, st, mix, part, T_raw, T_pad, nb);
+  hipLaunchKernelGGL(seg_stats_finish_kernel, dim3(C), dim3(64), 0, st, part, stats, T_raw, T_pad, nb, level);
+  return hipGetLastError();
+}
+hipError_t launch_seg_mel_energy(const float* mix, const float* stats, const float* win, const float* tw, const float* fb,
+                                 float* esum, int C, long long T_raw, long long T_pad, long long pad_left, int n_fft, int hop,
+                                 int mel_pad, int n_freq, int n_mels, long long L, hipStream_t st) {
+  if (L > 0x7fffffffll) return hipErrorInvalidValue;
+  const size_t smem = (size_t)(3 * n_fft + n_freq) * 4;
+  hipLaunchKernelGGL(seg_mel_energy_kernel, dim3((unsigned)L, C), dim3(512), smem, st, mix, stats, win, tw, fb, esum, T_raw,
+                     T_pad, pad_left, n_fft, hop, mel_pad, n_freq, n_mels, L);
+  return hipGetLastError();
+}
+hipError_t launch_seg_gather_input(const float* mix, const float* stats, const float* row_mel_scale, float* mixn,
+                                   float* mel_scale, const SegGeom& g, long long e0, int B, hipStream_t st) {
+  hipLaunchKernelGGL(seg_gather_input_kernel, dim3((unsigned)((g.L + 1023) / 1024), B), dim3(256), 0, st, mix, stats,
+                     row_mel_scale, mixn, mel_scale, g, e0);
+  return hipGetLastError();
+}
+hipError_t launch_seg_gather_noise(const float* noise, float* z, const SegGeom& g, long long e0, int B, hipStream_t st) {
+  hipLaunchKernelGGL(seg_gather_noise_kernel, dim3((unsigned)((g.L + 1023) / 1024), B), dim3(256), 0, st, noise, z, g, e0);
+  return hipGetLastError();
+}
+hipError_t launch_seg_stitch(const float* y, const float* carry, float* out, const SegGeom& g, long long e0, int n_real,
+                             hipStream_t st) {
+  hipLaunchKernelGGL(seg_stitch_kernel, dim3((unsigned)((g.L + 1023) / 1024), n_real), dim3(256), 0, st, y, carry, out, g, e0);
+  return hipGetLastError();
+}
+hipError_t launch_seg_post(float* out, double* part, const float* stats, int C, long long T_raw, int keep_rms, int peak_guard,
+                           hipStream_t st) {
+  const int nb = seg_reduce_blocks(T_raw);
+  hipLaunchKernelGGL(seg_post_reduce_kernel, dim3(nb, C), dim3(1024), 0, st, out, part, T_raw, nb);
+  long long nsb = (T_raw + 256 * 64 - 1) / (256 * 64);  // ~64 samples per thread
+  if (nsb > 8192) nsb = 8192;
+  hipLaunchKernelGGL(seg_post_scale_kernel, dim3((unsigned)nsb, C), dim3(256), 0, st, out, part, stats, T_raw, nb, keep_rms,
+                     peak_guard);
+  return hipGetLastError();
+}
+
+}  // namespace ou

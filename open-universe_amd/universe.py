@@ -739,6 +739,84 @@ class Universe:
         for _ in range(n_noise):
             torch.randn((int(channels), 1, T), dtype=torch.float32, device=self.device, generator=rng)
 
+    # ---- recordings of any length: segmented enhance (ou_enhance_segments) ---------------------------------------------
+    SEGMENT_S = 8.0
+    OVERLAP_S = 1.0
+
+    def draw_noise_like_enhance(self, rng, channels, length, n_steps=None):
+        """The noise `enhance` draws for a (channels, length) input -- x0, then one z per noisy step, each (channels, 1, length
+        + pad) -- in ONE (n_steps, channels, length + pad) tensor, drawn in that order from `rng`."""
+        n_steps = self.diff_kwargs.n_steps if n_steps is None else int(n_steps)
+        T = int(length) + (self.tot_ds - int(length) % self.tot_ds)
+        noise = torch.empty((n_steps, int(channels), T), dtype=torch.float32, device=self.device)
+        for k in range(n_steps):
+            torch.randn((int(channels), 1, T), generator=rng, out=noise[k].view(int(channels), 1, T))
+        return noise
+
+    @torch.no_grad()
+    def enhance_long(self, mix, segment_s: float = SEGMENT_S, overlap_s: float = OVERLAP_S, max_batch: int = 32,
+                     rng: Optional[torch.Generator] = None, n_steps: Optional[int] = None, epsilon: Optional[float] = None,
+                     keep_rms: Optional[bool] = False, **other) -> torch.Tensor:
+        """`enhance` of a recording of any length in bounded memory (extension).  `mix`: (T,) or (C, T); rows are independent
+        signals, as channels are everywhere else.  The signal is cut into windows of `segment_s` seconds that overlap by
+        `overlap_s` seconds and run `max_batch` at a time through the walk of `enhance`; normalisation, mel scale, noise,
+        keep_rms and the peak guard stay those of the whole file (include/ouniverse.h, ou_enhance_segments).  The noise is
+        drawn exactly as `enhance` draws it for this input, so a shared generator advances identically.  A file that fits into
+        one window gets the `enhance` result.  Workspace: ou_segments_workspace_bytes -- set by max_batch and segment_s."""
+        for k in ("target", "ensemble", "fake_score_snr", "warm_start"):
+            if other.get(k) is not None:
+                raise ValueError(f"enhance_long does not take `{k}`")
+        if other.get("use_aux_signal"):
+            raise ValueError("enhance_long does not take `use_aux_signal`")
+        unknown = set(other) - {"target", "ensemble", "fake_score_snr", "warm_start", "use_aux_signal", "ensemble_stat"}
+        if unknown:
+            raise TypeError(f"enhance_long() got unexpected keyword argument(s): {sorted(unknown)}")
+        self._sync_env()
+        self._poll_deferred_status()
+        if mix.ndim not in (1, 2):
+            raise ValueError("enhance_long takes (T,) or (C, T) signals")
+        x = self._prep(mix if mix.ndim == 2 else mix[None, :])
+        C, T_raw = x.shape
+        if T_raw < 1:
+            raise ValueError("enhance_long: empty input signal")
+        n_steps = self.diff_kwargs.n_steps if n_steps is None else int(n_steps)
+        if epsilon is None:
+            epsilon = self.diff_kwargs.epsilon
+        segment = int(round(float(segment_s) * self.fs))
+        overlap = int(round(float(overlap_s) * self.fs))
+        need, B, L = c_size_t(), c_int32(), c_int32()
+        _lib.check(self._L.ou_segments_workspace_bytes(self._handle, C, T_raw, segment, overlap, int(max_batch), byref(need),
+                                                        byref(B), byref(L)), self._handle)
+        noise = self.draw_noise_like_enhance(rng, C, T_raw, n_steps)
+        skey = (int(n_steps), float(self.diff_kwargs.sigma_min), float(self.diff_kwargs.sigma_max))
+        sigma = self._sigma_cache.get(skey)
+        if sigma is None:
+            time = torch.linspace(0, 1, n_steps).to(torch.float32).flip(dims=[0])
+            sigma = self._sigma_cache[skey] = self.get_std_dev(time).to(torch.float32).contiguous()
+        ws = self._segments_workspace(B.value, L.value, need.value)
+        out = torch.empty(C, T_raw, dtype=torch.float32, device=self.device)
+        flags = _lib.OU_ENH_KEEP_RMS if keep_rms else 0
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.ou_enhance_segments(
+                self._handle, c_void_p(x.data_ptr()), c_void_p(out.data_ptr()), c_void_p(noise.data_ptr()), C, T_raw,
+                segment, overlap, int(max_batch), n_steps, float(epsilon), ctypes.cast(sigma.data_ptr(), ctypes.POINTER(c_float)),
+                -1, flags, c_void_p(ws.data_ptr()), c_size_t(ws.numel()), self._stream()), self._handle)
+        self._status()
+        return out if mix.ndim == 2 else out[0]
+
+    def _segments_workspace(self, B, L, need):
+        """The workspace of enhance_long: one buffer kept for re-use (outside the per-batch-size cache of `enhance`)."""
+        cur = getattr(self, "_seg_ws", None)
+        if cur is None or cur[0] != B or cur[1].numel() < need:
+            self._seg_ws = None
+            ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            with torch.cuda.device(self.device):
+                _lib.check(self._L.ou_workspace_init(self._handle, B, L, c_void_p(ws.data_ptr()), c_size_t(need),
+                                                     self._stream()), self._handle)
+            cur = self._seg_ws = (B, ws)
+        self._adopt_workspace(cur[1], B, L)
+        return cur[1]
+
     # ---- hipGraph replay of the hot path ------------------------------------------------------------------------
     def graphed_enhance(self, batch, length, n_steps=None, epsilon=None, keep_rms=False, serial=True):
         """-> callable `run(mix, rng=None)` equivalent to `enhance(mix, n_steps, epsilon, rng=rng, keep_rms=keep_rms)`
