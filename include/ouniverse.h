@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define OU_ABI_VERSION 5 /* 5: ou_enhance_var (batches whose rows have lengths of their own), workspace header carries the per-row geometry; ou_set_option / ou_get_option replace every OU_* environment switch (the library reads no environment variable), ou_config.fir_fold; 4: the packed blob carries a bf16-split weight copy (conv_split_kernel); 3: a Winograd-domain copy (round 5), ou_set_lane_batch, ou_lane_capacity */
+#define OU_ABI_VERSION 6 /* 6: counter-based sampler noise (ou_set_noise_source, ou_noise_scratch_bytes, ou_noise_fill); existing entry points unchanged; 5: ou_enhance_var (batches whose rows have lengths of their own), workspace header carries the per-row geometry; ou_set_option / ou_get_option replace every OU_* environment switch (the library reads no environment variable), ou_config.fir_fold; 4: the packed blob carries a bf16-split weight copy (conv_split_kernel); 3: a Winograd-domain copy (round 5), ou_set_lane_batch, ou_lane_capacity */
 
 enum {
   OU_OK = 0,
@@ -158,7 +158,8 @@ int ou_aux_to_wav(ou_handle* h, float* wav_out, int32_t B, int32_t T, void* ws, 
  * unpad -> [keep_rms] -> peak guard.  Ensemble replication / reduction stays with the caller.
  *   mix, out : (B, T_raw) device
  *   noise    : (n_steps - warm_start, B, T_pad) standard-normal, device, in the reference's draw order
- *              (x0, z_0 .. z_{N-2}); T_pad = T_raw + (tot_ds - T_raw % tot_ds)
+ *              (x0, z_0 .. z_{N-2}); T_pad = T_raw + (tot_ds - T_raw % tot_ds).  NULL when a noise source is set
+ *              (ou_set_noise_source)
  *   sigma_host: n_steps floats or NULL (then computed as ou_schedule does)
  *   warm_start: -1, or the step index to start from with x = aux_to_wav(aux) + noise (universe.py:328-331) */
 int ou_enhance(ou_handle* h, const float* mix, float* out, const float* noise, int32_t B, int32_t T_raw,
@@ -219,6 +220,56 @@ int ou_enhance_segments(ou_handle* h, const float* mix, float* out, const float*
                         int32_t segment, int32_t overlap, int32_t max_batch, int32_t n_steps, double epsilon,
                         const float* sigma_host, int32_t warm_start, uint32_t flags, void* ws, size_t ws_bytes,
                         ou_stream_t stream);
+
+/* ---- counter-based sampler noise (extension; the reference draws its noise with torch.randn on the model's device) --------
+ * By default every enhance entry point reads its noise from a tensor the caller has drawn.  With a noise SOURCE set on the
+ * handle the library produces the noise itself, one step's (B, T) plane at a time, from a pure function
+ *
+ *     z(seed, stream, draw, t)      -- a standard normal, fp32
+ *
+ * so that a row's noise depends on nothing but those four numbers: not on the batch it shares, the lane, the rank or the
+ * window it is computed in, and nobody holds n_steps planes of it.  The definition (ou_noise.hip and the numpy restatement
+ * open_universe_amd/noise.py follow it):
+ *   - Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11; multipliers D2511F53 / CD9E8D57,
+ *     key increments 9E3779B9 / BB67AE85).  Key = (seed & 0xffffffff, seed >> 32).  With the quad index q = t >> 2 the counter is
+ *         c0 = q & 0xffffffff    c1 = ((q >> 32) & 0xffff) | (draw << 16)    c2 = stream & 0xffffffff    c3 = stream >> 32
+ *     (q < 2^48, i.e. t < 2^50; draw < 2^16).  One block (w0, w1, w2, w3) yields the normals of the positions 4q .. 4q + 3.
+ *   - word -> uniform in the open interval (0, 1): u(w) = ((w >> 8) + 0.5) * 2^-24.
+ *   - Box-Muller: r = sqrt(-2 ln u(w0)); z(4q) = r cos(2 pi u(w1)), z(4q + 1) = r sin(2 pi u(w1)); the same with (w2, w3) for
+ *     z(4q + 2), z(4q + 3).  |z| <= sqrt(50 ln 2) = 5.887.  Evaluated with the precise fp32 device functions on exact
+ *     arguments (for w >> 8 >= 2^23 through the mirror image 1 - u, whose numerator is an fp32 number: ln u = log1p(-(1 - u)),
+ *     cos(2 pi u) = cos(2 pi (1 - u)), sin(2 pi u) = -sin(2 pi (1 - u))): within 1e-5 of the real-valued definition.
+ *   - draw: 0 = the initial draw (x0, universe.py:326, or the warm-start noise, :330); n + 1 = z_n of the ABSOLUTE step n (:338),
+ *     so a warm start at step k uses the draws 0, k + 1, k + 2, ..
+ *   - t: position in the row's OWN padded signal (column of its T_pad = t_raw + pad samples): ou_enhance, a row of
+ *     ou_enhance_var and a window of ou_enhance_segments (t = s_k + i) agree.
+ *   - stream: one 64-bit id per row, the caller's choice (the Python layer: (utterance index << 16) | channel). */
+typedef struct ou_noise_spec {
+  uint64_t seed;           /* the key */
+  const uint64_t* streams; /* HOST, one id per row: B of ou_enhance / ou_enhance_var, C of ou_enhance_segments (copied by the call) */
+  int32_t n_streams;
+  void* scratch;           /* DEVICE, caller-owned, 16-byte aligned, alive as long as the source is set: two (B, T_pad) planes */
+  size_t scratch_bytes;    /* >= ou_noise_scratch_bytes(h, B, T_pad) of every ou_enhance / ou_enhance_var call that follows;
+                            * ou_enhance_segments needs none (its workspace already holds one step's plane): NULL / 0 is fine */
+} ou_noise_spec;
+/* Noise source of the NEXT forward calls of this handle; NULL: back to the noise tensor (the default).  While a source is set
+ *   - `noise` must be NULL in ou_enhance / ou_enhance_var / ou_enhance_segments (OU_EINVAL otherwise: an argument is never
+ *     silently ignored), n_streams must equal the call's rows (OU_EINVAL), a scratch that is too small is OU_ENOMEM;
+ *   - the library fills a plane right in front of the launch that reads it (x0 in front of the init, z_n in front of the score
+ *     pass of step n) on the caller's stream, ping-pong between the two planes of the scratch -- the hot kernels read a
+ *     (B, T) plane through the pointer they always got; ou_enhance_segments fills its workspace plane per window group where it
+ *     gathered from the tensor before.  Stream ids and positions travel as kernel arguments: no allocation, no host
+ *     synchronisation, capturable like the rest.  A captured graph keeps the source it was captured with.
+ * The tensor mode enqueues exactly what it did before; ou_workspace_bytes / ou_segments_workspace_bytes are unchanged.
+ * ou_plan_json reports the source as "noise_source": "tensor" | "counter". */
+int ou_set_noise_source(ou_handle* h, const ou_noise_spec* spec);
+int ou_noise_scratch_bytes(const ou_handle* h, int32_t B, int32_t T_pad, size_t* nbytes);
+/* The function itself, for tests and for bindings that keep the reference's Python loop (cf. ou_sampler_step):
+ *   out[j * row_stride + i] = i < len[j] ? z(seed, streams[j], draw, t0[j] + i) : 0      for 0 <= i < cols, 0 <= j < rows
+ * out: device; streams_host / t0_host / len_host: `rows` entries on the HOST (0 <= len[j] <= cols <= row_stride, t0[j] >= 0,
+ * t0[j] + len[j] <= 2^50, 0 <= draw < 2^16).  Enqueued on `stream`, 64 rows per launch. */
+int ou_noise_fill(float* out, int64_t row_stride, int64_t cols, int32_t rows, const uint64_t* streams_host,
+                  const int64_t* t0_host, const int64_t* len_host, uint64_t seed, int32_t draw, ou_stream_t stream);
 
 /* One sampler update on caller-owned buffers, for bindings that keep the reference's Python loop
  * (universe.py:339 `x = x + s_now^2 * eta * score + beta * z`, :343 `x = x + s_last^2 * score`):

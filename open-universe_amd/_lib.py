@@ -6,10 +6,11 @@ shared library is missing (not built) every entry point raises, loudly.
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, byref, c_char_p, c_double, c_float, c_int32, c_int64, c_size_t, c_uint32, c_void_p
+from ctypes import (POINTER, Structure, byref, c_char_p, c_double, c_float, c_int32, c_int64, c_size_t, c_uint32, c_uint64,
+                    c_void_p)
 
 OU_MAX_RATES = 8
-OU_ABI_VERSION = 5
+OU_ABI_VERSION = 6
 OU_OK, OU_EINVAL, OU_ENOTIMPL, OU_EMISSING, OU_ESHAPE, OU_EHIP, OU_ENOMEM, OU_ESYNC = 0, -1, -2, -3, -4, -5, -6, -7
 OU_KIND_UNIVERSE, OU_KIND_UNIVERSE_GAN = 0, 1
 OU_ACT_NONE, OU_ACT_PRELU, OU_ACT_SNAKE = 0, 1, 2
@@ -52,6 +53,17 @@ class Config(Structure):
         ("edm_data_level_db", c_float),
         ("fir_fold", c_int32),
         ("no_split_copy", c_int32),
+    ]
+
+
+class NoiseSpec(Structure):
+    """ou_noise_spec: counter-based noise source of a handle (include/ouniverse.h)."""
+    _fields_ = [
+        ("seed", c_uint64),
+        ("streams", POINTER(c_uint64)),
+        ("n_streams", c_int32),
+        ("scratch", c_void_p),
+        ("scratch_bytes", c_size_t),
     ]
 
 
@@ -102,6 +114,10 @@ def load():
         "ou_segments_workspace_bytes": (i32, [vp, i32, c_int64, i32, i32, i32, POINTER(sz), POINTER(i32), POINTER(i32)]),
         "ou_enhance_segments": (i32, [vp, vp, vp, vp, i32, c_int64, i32, i32, i32, i32, c_double, POINTER(c_float), i32,
                                       c_uint32, vp, sz, vp]),
+        "ou_set_noise_source": (i32, [vp, POINTER(NoiseSpec)]),
+        "ou_noise_scratch_bytes": (i32, [vp, i32, i32, POINTER(sz)]),
+        "ou_noise_fill": (i32, [vp, c_int64, c_int64, i32, POINTER(c_uint64), POINTER(c_int64), POINTER(c_int64), c_uint64,
+                                i32, vp]),
         "ou_check_device_status": (i32, [vp, vp]),
         "ou_set_option": (i32, [vp, c_char_p, c_double]),
         "ou_get_option": (i32, [vp, c_char_p, POINTER(c_double)]),
@@ -146,6 +162,7 @@ EXPORTED_SYMBOLS = [
     "ou_packer_destroy", "ou_packed_bytes", "ou_create", "ou_destroy", "ou_workspace_bytes", "ou_schedule",
     "ou_condition", "ou_score", "ou_aux_to_wav", "ou_enhance", "ou_enhance_var", "ou_check_device_status",
     "ou_segment_plan", "ou_segments_workspace_bytes", "ou_enhance_segments",
+    "ou_set_noise_source", "ou_noise_scratch_bytes", "ou_noise_fill",
     "ou_set_option", "ou_get_option", "ou_reset_options", "ou_option_count", "ou_option_name", "ou_option_doc", "ou_option_default", "ou_plan_json",
     "ou_packer_plan_json", "ou_tensor", "ou_launch_stats", "ou_workspace_init", "ou_sampler_step",
     "ou_set_gru_publish_mode", "ou_get_gru_publish_mode", "ou_set_lanes", "ou_set_lane_batch", "ou_lane_capacity",

@@ -83,6 +83,12 @@ def build_parser():
     parser.add_argument("--per-file-seed", action="store_true",
                         help="Seed the generator of file k with seed + k instead of sharing one generator across files "
                              "(always on when the files are sharded over several processes)")
+    parser.add_argument("--noise", choices=("generator", "counter"), default="generator",
+                        help="Where the sampler's noise comes from.  generator (default): torch.randn from the seeded generator, "
+                             "as the reference draws it.  counter: a counter-based function of (--seed, file index in the sorted "
+                             "list, channel, step, sample) evaluated on the device (an extension; the reference has no such "
+                             "mode): a file's result then does not depend on batching, lanes, segmenting or sharding, and no "
+                             "noise tensor is held in memory")
     parser.add_argument("--batch-size", type=int, default=1,
                         help="Enhance up to this many consecutive files of equal sample rate (any lengths) in one call; "
                              "every file gets the result it would get alone")
@@ -147,6 +153,26 @@ def check_segment_args(args, enhance_kwargs):
         raise ValueError("--segment-seconds cannot be combined with --use-aux-signal")
 
 
+def check_noise_args(args, enhance_kwargs):
+    """--noise counter: refused with what it cannot be combined with."""
+    if args.noise != "counter":
+        return
+    if enhance_kwargs.get("target") is not None:
+        raise ValueError("--noise counter cannot be combined with --target (the oracle-score path draws from a generator)")
+    if args.per_file_seed:
+        raise ValueError("--per-file-seed selects generator seeds: with --noise counter file k is stream k of --seed already")
+    if args.seed < 0:
+        raise ValueError("--noise counter takes a non-negative --seed (it is the 64-bit key)")
+
+
+def file_noise(args, k):
+    """--noise counter: the source of file k of the sorted list -- key --seed, stream k -- whatever process, batch, lane or
+    window the file ends up in (noise.plan_streams)."""
+    from ..noise import plan_streams
+
+    return plan_streams(k + 1, args.seed, [k])[k]
+
+
 def enhance_file(model, audio, args, enhance_kwargs, rng):
     """One file of the serial loop: `enhance`, or `enhance_long` when --segment-seconds is set and the file is longer."""
     if args.segment_seconds is not None and audio.shape[-1] > args.segment_seconds * model.fs:
@@ -199,8 +225,11 @@ def main(argv=None, model=None):
             enhance_kwargs = {a.dest: getattr(args, a.dest, None) for a in group._group_actions}
 
     check_segment_args(args, enhance_kwargs)
+    check_noise_args(args, enhance_kwargs)
+    counter = args.noise == "counter"
     files, rel_path, dir_proc = find_files(args.input)
-    per_file_seed = args.per_file_seed or world > 1
+    # (counter mode: the file index is part of the noise function -- nothing to force for sharded runs, nothing to re-draw)
+    per_file_seed = (args.per_file_seed or world > 1) and not counter
     rng = torch.Generator(device=device)
     rng.manual_seed(args.seed)
 
@@ -246,7 +275,9 @@ def main(argv=None, model=None):
                 output_path = out_path(path)
                 audio, fs = load(path)
                 audio = audio.to(device)
-                if per_file_seed:
+                if counter:
+                    file_rng = file_noise(args, k)
+                elif per_file_seed:
                     # a generator of its own per file: the draws of a call in flight must not see the next file's re-seed
                     file_rng = torch.Generator(device=device)
                     file_rng.manual_seed(args.seed + k)
@@ -274,7 +305,7 @@ def main(argv=None, model=None):
                 rng.manual_seed(args.seed + k)
             with torch.no_grad():
                 audio = resample(audio, fs, model.fs)
-                enh = enhance_file(model, audio, args, enhance_kwargs, rng)
+                enh = enhance_file(model, audio, args, enhance_kwargs, file_noise(args, k) if counter else rng)
                 enh = resample(enh, model.fs, fs)
             save(output_path, enh.cpu(), fs)
             done.append(output_path)
@@ -291,7 +322,7 @@ def main(argv=None, model=None):
     # Sorting a window by length needs a generator per file that starts where the serial loop's shared generator would stand
     # in front of that file: with per-file seeds by construction, with the shared generator by taking its state file by file
     # in processing order and advancing it by the file's draws (Universe.advance_generator_like_enhance).
-    can_sort = per_file_seed or hasattr(model, "advance_generator_like_enhance")
+    can_sort = counter or per_file_seed or hasattr(model, "advance_generator_like_enhance")
     if not can_sort:
         window_size = min(window_size, args.batch_size)
 
@@ -304,7 +335,9 @@ def main(argv=None, model=None):
             items = []
             for k, path, a, _ in window:
                 sig = resample(a.to(device), fs, model.fs)
-                if per_file_seed:
+                if counter:
+                    g = file_noise(args, k)
+                elif per_file_seed:
                     g = torch.Generator(device=device)
                     g.manual_seed(args.seed + k)
                 elif can_sort:

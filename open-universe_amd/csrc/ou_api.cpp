@@ -90,6 +90,14 @@ struct ou_handle {
   // launches of all lanes have to be resident together
   int lanes = 1, lane = 0;
   int lane_max_b = 0;  // ou_set_lane_batch: largest batch size any lane of the pool runs (0: every call's own B)
+  // ou_set_noise_source: counter-based noise (include/ouniverse.h).  Off: the forward calls read the caller's noise tensor.
+  struct NoiseSource {
+    bool on = false;
+    unsigned long long seed = 0;
+    std::vector<unsigned long long> streams;  // host copy, one id per row
+    float* scratch = nullptr;                 // two (B, T_pad) planes (caller-owned, device)
+    size_t scratch_bytes = 0;
+  } noise_src;
   // length guard of ou_enhance / ou_enhance_var: bytes per padded sample of the largest per-row plane of the walk (dry walk of
   // the conditioner and one score pass, every plane a multiple of T; 0 = not measured yet) and of the decoupling scratch
   double plane_per_sample = 0.0, wav_plane_per_sample = 0.0;
@@ -1018,6 +1026,7 @@ const char* ou_plan_json(const ou_handle* hc) {
     o += buf;
   }
   o += "}";
+  o += std::string(", \"noise_source\": \"") + (h->noise_src.on ? "counter" : "tensor") + "\"";
   const std::string& j = h->m.json;
   const size_t close = j.rfind('}');
   h->plan_with_options = close == std::string::npos ? "{" + o + "}" : j.substr(0, close) + ", " + o + j.substr(close);
@@ -1263,6 +1272,21 @@ long long max_walk_length(ou_handle* h, bool need_wav) {
   return t - t % h->m.tot_ds;
 }
 
+// One plane of counter-based noise: dst[j][i] = i < len(j) ? z(seed, stream(j), draw, t0(j) + i) : 0 for the n_rows rows of a
+// call, 64 rows per launch; `row(j, stream, t0, len)` describes row j.
+template <typename RowFn>
+void fill_noise_plane(Runner& r, float* dst, long long cols, int n_rows, unsigned long long seed, int draw, RowFn row) {
+  for (int off = 0; off < n_rows && r.ok(); off += kNoiseRowsPerLaunch) {
+    NoiseRows blk;
+    const int n = n_rows - off < kNoiseRowsPerLaunch ? n_rows - off : kNoiseRowsPerLaunch;
+    for (int i = 0; i < kNoiseRowsPerLaunch; i++) {
+      blk.stream[i] = 0; blk.t0[i] = 0; blk.len[i] = 0;
+      if (i < n) row(off + i, blk.stream[i], blk.t0[i], blk.len[i]);
+    }
+    r.chk(launch_noise_fill(dst + (size_t)off * cols, cols, cols, blk, n, seed, draw, r.st), "noise fill");
+  }
+}
+
 // ou_enhance / ou_enhance_var.  `t_raw`: host array of B row lengths (max = T_raw) or null (every row T_raw samples long).
 int enhance_impl(ou_handle* h, const float* mix, float* out, const float* noise, int32_t B, int32_t T_raw,
                  const int32_t* t_raw, int32_t n_steps, double epsilon, const float* sigma_host, int32_t warm_start,
@@ -1287,7 +1311,13 @@ int enhance_impl(ou_handle* h, const float* mix, float* out, const float* noise,
   // four streams each alias there -- measured: 4 lanes 122 utt/s with side streams (87 % of the time ONE kernel on the
   // device), 209 utt/s as four chains (serial loop: 132).
   if ((flags & OU_ENH_SERIAL) || h->lanes > 1) h->overlap = false;
-  if (!use_aux && !noise) return fail(h, OU_EINVAL, "noise must be given");
+  const bool counter = h->noise_src.on;
+  if (counter && noise)
+    return fail(h, OU_EINVAL, "a noise source is set on this handle (ou_set_noise_source): `noise` must be NULL");
+  if (counter && (int)h->noise_src.streams.size() != B)
+    return fail(h, OU_EINVAL, "noise source: n_streams (" + std::to_string(h->noise_src.streams.size()) +
+                                  ") must equal the rows of the call (" + std::to_string(B) + ")");
+  if (!use_aux && !noise && !counter) return fail(h, OU_EINVAL, "noise must be given");
   if (n_steps < 2 || n_steps > kMaxSteps) return fail(h, OU_EINVAL, "n_steps must be in [2, 256]");
   if (warm_start >= n_steps) return fail(h, OU_EINVAL, "warm_start must be < n_steps");
   const Model& m = h->m;
@@ -1304,6 +1334,9 @@ int enhance_impl(ou_handle* h, const float* mix, float* out, const float* noise,
   }
   if (!h->ws_ok(ws, ws_bytes, B, T))
     return fail(h, OU_EINVAL, "workspace was not prepared by ou_workspace_init for this (B, T_raw + pad)");
+  if (counter && !use_aux && (!h->noise_src.scratch || h->noise_src.scratch_bytes < (size_t)2 * B * T * sizeof(float)))
+    return fail(h, OU_ENOMEM, "noise source: scratch too small: need " + std::to_string((size_t)2 * B * T * sizeof(float)) +
+                                  " bytes (ou_noise_scratch_bytes)");
   h->tensors.clear();
   h->n_launch = h->n_conv = 0;
   h->ev_used = 0;
@@ -1359,6 +1392,19 @@ int enhance_impl(ou_handle* h, const float* mix, float* out, const float* noise,
   if (need_wav && (!m.dec.present || m.dec.act != OU_ACT_SNAKE))
     return fail(h, OU_ENOTIMPL, "aux_to_wav needs the snake signal-decoupling layer (UNIVERSE++)");
   const int n_start = warm_start >= 0 ? warm_start : 0;
+  // Counter mode: draw d (0: the initial draw, n + 1: z_n of the absolute step n) is filled into plane d & 1 of the scratch right
+  // in front of the launch that reads it, on the caller's stream -- the simplest place: the launches that read a plane are
+  // untouched, and at step n_start the fill runs beside the first score-encoder pass on its side stream.  Row b's positions are
+  // the columns of its own padded signal, the tail of a shorter row is 0.
+  auto noise_plane = [&](int draw) -> const float* {
+    float* dst = h->noise_src.scratch + (size_t)(draw & 1) * nBT;
+    fill_noise_plane(r, dst, T, B, h->noise_src.seed, draw, [&](int b, unsigned long long& sid, long long& t0, long long& len) {
+      sid = h->noise_src.streams[b];
+      t0 = 0;
+      len = t_raw ? t_raw[b] + (tot - t_raw[b] % tot) : T;
+    });
+    return dst;
+  };
 
   // Where the conditioner's scratch ends (= where the per-step score scratch starts): layout is a pure function of
   // (config, B, T), so a dry walk gives it before anything is launched.
@@ -1387,7 +1433,7 @@ int enhance_impl(ou_handle* h, const float* mix, float* out, const float* noise,
                          gru_ring_batch_cap(m.c_gru0.H, h->num_cu, share2, 0, B, h->lanes) >= 1;
     if (warm_start < 0 && h->overlap && gru_fit) {
       r.gru_shared = true;
-      r.chk(launch_init_x(noise, nullptr, sigma[n_start], P.x.p, nBT, st), "init x");  // universe.py:325-327
+      r.chk(launch_init_x(counter ? noise_plane(0) : noise, nullptr, sigma[n_start], P.x.p, nBT, st), "init x");  // universe.py:325-327
       r.mask(P.x);
       const size_t save = r.off;
       r.fork(st, 2);
@@ -1427,13 +1473,14 @@ int enhance_impl(ou_handle* h, const float* mix, float* out, const float* noise,
   }
   // universe.py:325-331
   if (!have_e0) {
-    r.chk(launch_init_x(noise, warm_start >= 0 ? P.wav.p : nullptr, sigma[n_start], P.x.p, nBT, st), "init x");
+    r.chk(launch_init_x(counter ? noise_plane(0) : noise, warm_start >= 0 ? P.wav.p : nullptr, sigma[n_start], P.x.p, nBT, st),
+          "init x");
     r.mask(P.x);
   }
   const size_t step_mark = r.off;
   for (int n = n_start; n < n_steps; n++) {
     const bool last = n == n_steps - 1;
-    const float* z = last ? nullptr : noise + (size_t)(n - n_start + 1) * nBT;
+    const float* z = last ? nullptr : counter ? noise_plane(n + 1) : noise + (size_t)(n - n_start + 1) * nBT;
     const StepCoef* cf = P.coef + n;
     const float* fr = P.film + (size_t)n * m.film.rows;
     if (n == n_start && have_e0) {
@@ -1568,7 +1615,14 @@ int ou_enhance_segments(ou_handle* h, const float* mix, float* out, const float*
                         int32_t segment, int32_t overlap, int32_t max_batch, int32_t n_steps, double epsilon,
                         const float* sigma_host, int32_t warm_start, uint32_t flags, void* ws, size_t ws_bytes,
                         ou_stream_t stream) {
-  if (!h || !mix || !out || !noise || !ws || C < 1 || T_raw < 1 || max_batch < 1) return fail(h, OU_EINVAL, "bad argument");
+  if (!h || !mix || !out || !ws || C < 1 || T_raw < 1 || max_batch < 1) return fail(h, OU_EINVAL, "bad argument");
+  const bool counter = h->noise_src.on;
+  if (counter && noise)
+    return fail(h, OU_EINVAL, "a noise source is set on this handle (ou_set_noise_source): `noise` must be NULL");
+  if (counter && (int)h->noise_src.streams.size() != C)
+    return fail(h, OU_EINVAL, "noise source: n_streams (" + std::to_string(h->noise_src.streams.size()) +
+                                  ") must equal the rows of the call (" + std::to_string(C) + ")");
+  if (!counter && !noise) return fail(h, OU_EINVAL, "noise must be given");
   if (warm_start >= 0 || (flags & OU_ENH_USE_AUX_SIGNAL))
     return fail(h, OU_EINVAL, "ou_enhance_segments: warm_start and use_aux_signal are not supported");
   if (n_steps < 2 || n_steps > kMaxSteps) return fail(h, OU_EINVAL, "n_steps must be in [2, 256]");
@@ -1651,12 +1705,27 @@ int ou_enhance_segments(ou_handle* h, const float* mix, float* out, const float*
     }
     r.chk(launch_seg_gather_input(mix, stats, row_scale, P.mixn.p, P.mel_scale, g, e0, B, st), "segment gather");
     run_condition(r, P, P.mixn.p, L);
-    r.chk(launch_seg_gather_noise(noise, zbuf, g, e0, B, st), "segment noise");
+    // One step's noise of the group's windows: a slice of the caller's whole-row tensor, or -- counter mode -- the same
+    // positions (window k of row c: t = s_k + i, stream of row c) straight from the function; no whole-row noise exists then.
+    auto step_noise_plane = [&](int draw) {
+      if (!counter) {
+        r.chk(launch_seg_gather_noise(noise + (size_t)draw * step_noise, zbuf, g, e0, B, st), "segment noise");
+        return;
+      }
+      fill_noise_plane(r, zbuf, L, B, h->noise_src.seed, draw, [&](int j, unsigned long long& sid, long long& t0, long long& len) {
+        const long long e = std::min<long long>(e0 + j, g.n_entries - 1);  // (the filler rows of a short last group)
+        const long long c = e / g.n_win;
+        sid = h->noise_src.streams[c];
+        t0 = seg_start_host(g, e - c * g.n_win);
+        len = L;
+      });
+    };
+    step_noise_plane(0);
     r.chk(launch_init_x(zbuf, nullptr, sigma[0], P.x.p, nBL, st), "init x");  // universe.py:325-327
     const size_t step_mark = r.off;
     for (int n = 0; n < n_steps && r.ok(); n++) {
       const bool last = n == n_steps - 1;
-      if (!last) r.chk(launch_seg_gather_noise(noise + (size_t)(n + 1) * step_noise, zbuf, g, e0, B, st), "segment noise");
+      if (!last) step_noise_plane(n + 1);
       r.off = step_mark;
       run_score(r, P, P.x.p, last ? nullptr : zbuf, P.x.p, OUT_UPDATE, P.coef + n, 0, P.film + (size_t)n * m.film.rows, 0, L);
     }
@@ -1773,6 +1842,54 @@ int ou_get_gru_publish_mode(const ou_handle* h) { return h ? h->gru_agent_stores
 int ou_set_gru_publish_mode(ou_handle* h, int32_t agent_scope) {
   if (!h) return fail(h, OU_EINVAL, "bad argument");
   h->gru_agent_stores = agent_scope ? 1 : 0;
+  return OU_OK;
+}
+
+int ou_set_noise_source(ou_handle* h, const ou_noise_spec* spec) {
+  if (!h) return fail(h, OU_EINVAL, "bad argument");
+  if (!spec) {
+    h->noise_src = ou_handle::NoiseSource();
+    return OU_OK;
+  }
+  if (!spec->streams || spec->n_streams < 1) return fail(h, OU_EINVAL, "ou_set_noise_source: one stream id per row must be given");
+  if ((spec->scratch == nullptr) != (spec->scratch_bytes == 0))
+    return fail(h, OU_EINVAL, "ou_set_noise_source: scratch and scratch_bytes must be given together");
+  if (reinterpret_cast<uintptr_t>(spec->scratch) % 16 != 0)
+    return fail(h, OU_EINVAL, "ou_set_noise_source: scratch must be 16-byte aligned");
+  h->noise_src.on = true;
+  h->noise_src.seed = spec->seed;
+  h->noise_src.streams.assign(spec->streams, spec->streams + spec->n_streams);
+  h->noise_src.scratch = (float*)spec->scratch;
+  h->noise_src.scratch_bytes = spec->scratch_bytes;
+  return OU_OK;
+}
+
+int ou_noise_scratch_bytes(const ou_handle* h, int32_t B, int32_t T_pad, size_t* nbytes) {
+  if (!h || !nbytes || B < 1 || T_pad < 1) return fail(const_cast<ou_handle*>(h), OU_EINVAL, "bad argument");
+  *nbytes = (size_t)2 * B * T_pad * sizeof(float);  // two planes, ping-pong
+  return OU_OK;
+}
+
+int ou_noise_fill(float* out, int64_t row_stride, int64_t cols, int32_t rows, const uint64_t* streams_host,
+                  const int64_t* t0_host, const int64_t* len_host, uint64_t seed, int32_t draw, ou_stream_t stream) {
+  if (!out || !streams_host || !t0_host || !len_host || rows < 1 || cols < 1 || row_stride < cols)
+    return fail(nullptr, OU_EINVAL, "ou_noise_fill: bad argument");
+  if (draw < 0 || draw >= (1 << 16)) return fail(nullptr, OU_EINVAL, "ou_noise_fill: 0 <= draw < 2^16");
+  for (int j = 0; j < rows; j++)
+    if (len_host[j] < 0 || len_host[j] > cols || t0_host[j] < 0 || t0_host[j] > (1ll << 50) - len_host[j])
+      return fail(nullptr, OU_EINVAL, "ou_noise_fill: 0 <= len[j] <= cols, t0[j] >= 0, t0[j] + len[j] <= 2^50");
+  for (int off = 0; off < rows; off += kNoiseRowsPerLaunch) {
+    NoiseRows blk;
+    const int n = rows - off < kNoiseRowsPerLaunch ? rows - off : kNoiseRowsPerLaunch;
+    for (int i = 0; i < kNoiseRowsPerLaunch; i++) {
+      blk.stream[i] = i < n ? streams_host[off + i] : 0;
+      blk.t0[i] = i < n ? t0_host[off + i] : 0;
+      blk.len[i] = i < n ? len_host[off + i] : 0;
+    }
+    const hipError_t e = launch_noise_fill(out + (size_t)off * (size_t)row_stride, row_stride, cols, blk, n, seed, draw,
+                                           (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, OU_EHIP, std::string("HIP error at noise fill: ") + hipGetErrorString(e));
+  }
   return OU_OK;
 }
 

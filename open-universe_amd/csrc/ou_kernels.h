@@ -209,6 +209,18 @@ hipError_t launch_seg_stitch(const float* y, const float* carry, float* out, con
 hipError_t launch_seg_post(float* out, double* part, const float* stats, int C, long long T_raw, int keep_rms, int peak_guard,
                            hipStream_t st);
 
+// Counter-based sampler noise (ou_noise.hip; the function z(seed, stream, draw, t) is defined in include/ouniverse.h).
+// One launch fills up to 64 rows: out[j][col] = col < len[j] ? z(seed, stream[j], draw, t0[j] + col) : 0 for col < cols.
+// The per-row values travel as kernel arguments (capturable, no host memory involved).
+constexpr int kNoiseRowsPerLaunch = 64;
+struct NoiseRows {
+  unsigned long long stream[kNoiseRowsPerLaunch];
+  long long t0[kNoiseRowsPerLaunch];
+  long long len[kNoiseRowsPerLaunch];
+};
+hipError_t launch_noise_fill(float* out, long long row_stride, long long cols, const NoiseRows& rows, int n_rows,
+                             unsigned long long seed, int draw, hipStream_t st);
+
 // space-to-depth + PReLU for the conditioner's strided "st" convs: y[b][ci*R + k][q] = prelu(x[b][ci][q*R + k])
 hipError_t launch_s2d(const float* x, const float* alpha, float* y, int B, int C, int T, int R, hipStream_t st);
 // (`lens` of launch_in_conv / launch_out_conv / launch_fir: per-row valid lengths of a ragged batch or null, see ConvArgs::lens)

@@ -229,8 +229,21 @@ def plan_batches(lengths, indices, batch_size, pad_batch=False, equal_only=False
     return groups
 
 
+def utterance_noise(device, seed, index, noise="generator"):
+    """The noise source of utterance `index` of a set: its own generator (`utterance_generator`), or -- noise="counter" -- the
+    counter-based source with the utterance's GLOBAL index as stream (`noise.CounterNoise(seed, index)`): the noise is then a pure
+    function of (seed, index, channel, step, sample), the same on 1 rank and on N, alone and in a batch."""
+    if noise == "counter":
+        from .noise import CounterNoise
+
+        return CounterNoise(seed, index)
+    if noise != "generator":
+        raise ValueError("noise must be 'generator' or 'counter'")
+    return utterance_generator(device, seed, index)
+
+
 def enhance_sharded(model, signals, seed=1028282, gather=True, batch_size=1, pad_batch=False, in_flight=1,
-                    equal_only=False, **enhance_kwargs):
+                    equal_only=False, noise="generator", **enhance_kwargs):
     """Enhance a list of 1-D signals (any lengths) across the ranks of the current process group.
 
     Rank r takes its LPT shard (`shard_utterances`) and walks it in `plan_batches` groups: up to `batch_size`
@@ -248,12 +261,17 @@ def enhance_sharded(model, signals, seed=1028282, gather=True, batch_size=1, pad
     launches of one utterance with the kernels of the others (batch_size=1: the route for ragged sets before exact
     batching, 143 -> 238 utt/s; batching reaches the batched kernels' rate instead).
 
+    noise="counter" (extension, noise.py): utterance i draws from `CounterNoise(seed, i)` instead of a generator seeded
+    seed + i -- streams that are independent by construction, nothing drawn or stored on the host side (`utterance_noise`).
+
     Results are gathered on rank 0 in the original order (None on the other ranks; with gather=False every rank
     returns {index: tensor} of its shard)."""
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
     lengths = [int(s.shape[-1]) for s in signals]
     mine = shard_utterances(lengths, world)[rank]
+    if noise not in ("generator", "counter"):
+        raise ValueError("noise must be 'generator' or 'counter'")
     outs = {}
     batched_ok = not any(enhance_kwargs.get(k) is not None for k in ("target", "ensemble"))
     groups = plan_batches(lengths, mine, batch_size if batched_ok else 1, pad_batch, equal_only)
@@ -261,9 +279,9 @@ def enhance_sharded(model, signals, seed=1028282, gather=True, batch_size=1, pad
     def run_group(m, group):
         if len(group) == 1:
             i = group[0]
-            return [m.enhance(signals[i].to(m.device), rng=utterance_generator(m.device, seed, i), **enhance_kwargs)]
+            return [m.enhance(signals[i].to(m.device), rng=utterance_noise(m.device, seed, i, noise), **enhance_kwargs)]
         return m.enhance_many([signals[i].to(m.device) for i in group],
-                              [utterance_generator(m.device, seed, i) for i in group], pad_batch=pad_batch,
+                              [utterance_noise(m.device, seed, i, noise) for i in group], pad_batch=pad_batch,
                               **enhance_kwargs)
 
     in_flight = max(1, int(in_flight))

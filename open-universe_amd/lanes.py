@@ -54,7 +54,8 @@ class LanePool:
 
     def submit(self, fn, *inputs):
         """Run `fn(model)` -- device work only, e.g. `lambda m: m.enhance(x, rng=g)` -- on the next lane's stream and return
-        (lane index, whatever fn returned).  Nothing is waited for; the result may be used after `wait(lane)` /
+        (lane index, whatever fn returned).  (`rng=noise.CounterNoise(seed, u)` inside fn: the utterance's noise is a function of
+        (seed, u) alone, so it does not matter which lane, or in which order, the pool runs it.)  Nothing is waited for; the result may be used after `wait(lane)` /
         `synchronize()`.  `inputs`: device tensors fn reads that were produced on the caller's stream (the lane waits for
         that stream and the tensors are kept from being recycled until the lane is done with them)."""
         k = self._next

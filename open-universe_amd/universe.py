@@ -9,10 +9,12 @@ inference_utils/signature_to_parser.py:45), `.eval()`, `.to()`, `.condition_mode
 
 Everything numerical happens in libouniverse.so (HIP, gfx950) through the C ABI; this class only reshapes,
 draws the noise with `torch.randn(generator=rng)` in the reference's order (so a shared generator advances
-identically, bin/enhance.py:147-166), owns the device buffers (PyTorch = device memory + streams) and maps C
+identically, bin/enhance.py:147-166) -- or, with `rng=noise.CounterNoise(..)`, hands the library a key and one stream id per row
+and draws nothing (extension, noise.py) --, owns the device buffers (PyTorch = device memory + streams) and maps C
 status codes to the reference's exception types.  No torch compute fallback exists: without the library or
 without a GPU construction fails.
 """
+import contextlib
 import ctypes
 import math
 import weakref
@@ -23,6 +25,7 @@ import torch
 
 from . import _lib
 from .config import ModelSpec
+from .noise import CounterNoise, is_counter
 
 
 def randn(x, sigma, rng=None):
@@ -297,6 +300,7 @@ class Universe:
         self._ws_key = None
         self._cond_key = None
         self._status_ws = None
+        self.__dict__.pop("_noise_scratch", None)  # (the planes of the counter-based noise: re-made on demand)
 
     def _raise_on_status(self):
         self._status_event = None
@@ -502,6 +506,50 @@ class Universe:
         self._status()
         return out
 
+    # ---- counter-based noise (noise.py; ou_set_noise_source) ------------------------------------------------------------
+    @contextlib.contextmanager
+    def _counter_source(self, seed, stream_ids, B=0, T=0):
+        """The handle draws its noise from z(seed, stream_ids[row], draw, t) for the forward calls inside the `with` block and is
+        back on the noise tensor (the default every other entry point expects) behind it.  (B, T) > 0: the call needs the
+        two-plane scratch of ou_noise_scratch_bytes (ou_enhance / ou_enhance_var); ou_enhance_segments needs none."""
+        n = len(stream_ids)
+        spec = _lib.NoiseSpec()
+        spec.seed = int(seed)
+        spec.streams = (ctypes.c_uint64 * n)(*[int(v) for v in stream_ids])
+        spec.n_streams = n
+        if B and T:
+            need = c_size_t()
+            _lib.check(self._L.ou_noise_scratch_bytes(self._handle, int(B), int(T), byref(need)), self._handle)
+            buf = self.__dict__.get("_noise_scratch")
+            if buf is None or buf.numel() < need.value:  # kept and grown like the workspace
+                self._noise_scratch = None
+                buf = self._noise_scratch = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+            spec.scratch = buf.data_ptr()
+            spec.scratch_bytes = buf.numel()
+        _lib.check(self._L.ou_set_noise_source(self._handle, byref(spec)), self._handle)
+        try:
+            yield
+        finally:
+            self._L.ou_set_noise_source(self._handle, None)
+
+    def noise_fill(self, streams, t0, lengths, seed, draw, cols=None, out=None):
+        """z(seed, streams[j], draw, t0[j] + i) for i < lengths[j] (0 behind it) as a (rows, cols) float32 tensor on this
+        model's device -- the library's own evaluation of the counter-based noise (ou_noise_fill), e.g. to hand the noise of a
+        `CounterNoise` run to something that takes tensors."""
+        n = len(streams)
+        cols = int(max(lengths) if cols is None else cols)
+        if out is None:
+            out = torch.empty((n, cols), dtype=torch.float32, device=self.device)
+        if out.shape != (n, cols) or out.dtype != torch.float32 or out.stride(1) != 1 or not out.is_cuda:
+            raise ValueError("noise_fill: out must be a (rows, cols) float32 device tensor with unit column stride")
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.ou_noise_fill(c_void_p(out.data_ptr()), out.stride(0), cols, n,
+                                             (ctypes.c_uint64 * n)(*[int(v) for v in streams]),
+                                             (ctypes.c_int64 * n)(*[int(v) for v in t0]),
+                                             (ctypes.c_int64 * n)(*[int(v) for v in lengths]), int(seed), int(draw),
+                                             self._stream()))
+        return out
+
     # ---- the hot path ------------------------------------------------------------------------------
     def enhance(
         self,
@@ -517,15 +565,22 @@ class Universe:
         ensemble_stat: Optional[str] = "median",
         warm_start: Optional[int] = None,
     ) -> torch.Tensor:
-        """Universe.enhance, universe.py:231-375 (same arguments, same return convention)."""
+        """Universe.enhance, universe.py:231-375 (same arguments, same return convention).
+
+        Extension: `rng=noise.CounterNoise(seed, stream=u)` -- the noise comes from the counter-based function of noise.py
+        instead of a generator: row (channel) c of the input draws from stream id `(u << 16) | c`, nothing is drawn or stored
+        on the Python side and no generator advances.  With `ensemble=E` member e draws from the ids of the input plus
+        `e << 48`, so the members differ as they do with a generator.  `target` (the oracle-score debug path, pure torch) keeps
+        its generator and refuses a CounterNoise."""
         return self._enhance(mix, n_steps, epsilon, target, fake_score_snr, rng, use_aux_signal, keep_rms, ensemble,
                              ensemble_stat, warm_start, None)
 
     @torch.no_grad()
     def _enhance(self, mix, n_steps, epsilon, target, fake_score_snr, rng, use_aux_signal, keep_rms, ensemble,
-                 ensemble_stat, warm_start, noise, t_raw=None):
+                 ensemble_stat, warm_start, noise, t_raw=None, counter=None):
         """`t_raw`: per-row lengths of a batch whose rows are utterances of different lengths (enhance_many, exact
-        batching -> ou_enhance_var); `mix` is then (B, 1, max length) and `noise` a (n, B, 1, T) tensor."""
+        batching -> ou_enhance_var); `mix` is then (B, 1, max length) and `noise` a (n, B, 1, T) tensor.
+        `counter`: (seed, [one stream id per row]) -- counter-based noise (noise.py) instead of `noise` / `rng`."""
         self._sync_env()
         self._poll_deferred_status()
         if epsilon is None:
@@ -554,6 +609,14 @@ class Universe:
         B, _, mix_len = mix.shape
         pad = self.tot_ds - mix_len % self.tot_ds
         T = mix_len + pad
+        if is_counter(rng):
+            if target is not None:
+                raise ValueError("`target` (the oracle-score path) draws from a torch.Generator: it does not take a CounterNoise")
+            if noise is not None or counter is not None:
+                raise ValueError("give either a CounterNoise or a noise tensor")
+            counter = (rng.seed, rng.stream_ids(B if ensemble is None else B // int(ensemble), ensemble))
+        if counter is not None and len(counter[1]) != B:
+            raise ValueError("counter-based noise needs one stream id per row of the batch")
 
         if target is not None:
             x = self._enhance_with_oracle_score(mix, target, n_steps, epsilon, fake_score_snr, rng, pad)
@@ -564,8 +627,12 @@ class Universe:
                 if ensemble is not None:
                     raise ValueError("per-row lengths and `ensemble` do not combine (call enhance per input)")
                 noise_t = noise
-                if n_noise and (noise_t is None or tuple(noise_t.shape) != (n_noise, B, 1, T)):
+                if counter is not None:
+                    noise_t = None
+                elif n_noise and (noise_t is None or tuple(noise_t.shape) != (n_noise, B, 1, T)):
                     raise ValueError(f"noise must be a tensor of shape {(n_noise, B, 1, T)}")
+            elif counter is not None:
+                noise_t = None  # the library fills one step's plane at a time (ou_set_noise_source)
             elif noise is None:
                 # draw order of the reference: x0, then z_n for n = n_start .. N-2 (universe.py:326,330,338)
                 # (each draw lands in its slice of the tensor the C ABI takes: the same n separate (B, 1, T) draws -- generator
@@ -595,7 +662,8 @@ class Universe:
             out = torch.empty(B, 1, mix_len, dtype=torch.float32, device=self.device)
             ws = self._workspace(B, T)
             flags = (_lib.OU_ENH_KEEP_RMS if keep_rms else 0) | (_lib.OU_ENH_USE_AUX_SIGNAL if use_aux_signal else 0)
-            with torch.cuda.device(self.device):
+            source = self._counter_source(counter[0], counter[1], B, T) if counter is not None else contextlib.nullcontext()
+            with torch.cuda.device(self.device), source:
                 if t_raw is not None:
                     if len(t_raw) != B:
                         raise ValueError("t_raw must have one entry per row of the batch")
@@ -646,7 +714,9 @@ class Universe:
                      keep_rms=False, warm_start=None, **other):
         """Several independent inputs in ONE `enhance` call (extension; the reference's CLI loops over files one by one,
         bin/enhance.py:173-192).  `signals`: list of (L,) or (C, L) tensors -- a (C, L) entry is a file whose channels
-        are rows of the batch, as in the reference.  `rngs`: one generator per entry, ONE shared generator, or None.
+        are rows of the batch, as in the reference.  `rngs`: one generator per entry, ONE shared generator, or None -- or
+        `noise.CounterNoise` objects (one per entry with one seed, or ONE shared: entry i is then utterance `stream + i`); channel
+        c of an entry draws from stream id `(utterance << 16) | c`, and nothing is drawn here (no noise tensor exists).
         The noise of entry i is drawn from its generator entry by entry, step by step, with the shapes a call on that
         entry alone would use ((C_i, 1, T), x0 first) -- with a shared generator the draws come in exactly the order
         of the serial loop, so its state advances as the reference's does.
@@ -683,15 +753,19 @@ class Universe:
         if n_start >= n_steps:
             raise ValueError("warm_start must be < n_steps")
         n_noise = 0 if use_aux_signal else n_steps - n_start
+        counter = self._counter_plan(rngs, [r.shape[0] for r in rows])
+        extra = {} if counter is None else {"counter": counter}
         if not pad_batch and any(n != l_max for n in lens):
             # exact batching of different lengths: per-row geometry through the whole path
             B = sum(r.shape[0] for r in rows)
-            noise_t = torch.zeros((n_noise, B, 1, T), dtype=torch.float32, device=self.device) if n_noise else None
+            noise_t = None
+            if n_noise and counter is None:
+                noise_t = torch.zeros((n_noise, B, 1, T), dtype=torch.float32, device=self.device)
             t_raw, r0 = [], 0
             for i, (r, n) in enumerate(zip(rows, lens)):
                 g = rngs[i] if isinstance(rngs, (list, tuple)) else rngs
                 Ti = n + (self.tot_ds - n % self.tot_ds)
-                for k in range(n_noise):  # the draws of the call on this entry alone, in its order (x0 first)
+                for k in range(n_noise if counter is None else 0):  # the draws of the call on this entry alone (x0 first)
                     dst = noise_t[k, r0:r0 + r.shape[0], :, :Ti]
                     if dst.is_contiguous():  # (one row: the draw goes straight to its place)
                         torch.randn((r.shape[0], 1, Ti), generator=g, out=dst)
@@ -701,7 +775,7 @@ class Universe:
                 r0 += r.shape[0]
             mix = torch.cat([torch.nn.functional.pad(r, (0, l_max - r.shape[-1])) for r in rows], dim=0)[:, None, :]
             out = self._enhance(mix, n_steps, epsilon, None, None, None, use_aux_signal, keep_rms, None, "median",
-                                warm_start, noise_t, t_raw=t_raw)
+                                warm_start, noise_t, t_raw=t_raw, **extra)
             res, r0 = [], 0
             for r, nd, n in zip(rows, dims, lens):
                 o = out[r0:r0 + r.shape[0], 0, :n]
@@ -710,22 +784,46 @@ class Universe:
             return res
         # entry by entry, step by step (the serial loop's draw order), every draw straight into its rows of the step's tensor
         B = sum(r.shape[0] for r in rows)
-        noise = torch.empty((n_noise, B, 1, T), dtype=torch.float32, device=self.device)
-        r0 = 0
-        for i, r in enumerate(rows):
-            g = rngs[i] if isinstance(rngs, (list, tuple)) else rngs
-            for k in range(n_noise):
-                torch.randn((r.shape[0], 1, T), generator=g, out=noise[k, r0:r0 + r.shape[0]])
-            r0 += r.shape[0]
+        noise = None
+        if counter is None:
+            noise = torch.empty((n_noise, B, 1, T), dtype=torch.float32, device=self.device)
+            r0 = 0
+            for i, r in enumerate(rows):
+                g = rngs[i] if isinstance(rngs, (list, tuple)) else rngs
+                for k in range(n_noise):
+                    torch.randn((r.shape[0], 1, T), generator=g, out=noise[k, r0:r0 + r.shape[0]])
+                r0 += r.shape[0]
         mix = torch.cat([torch.nn.functional.pad(r, (0, l_max - r.shape[-1])) for r in rows], dim=0)[:, None, :]
         out = self._enhance(mix, n_steps, epsilon, None, None, None, use_aux_signal, keep_rms, None, "median",
-                            warm_start, noise)
+                            warm_start, noise, **extra)
         res, r0 = [], 0
         for r, nd, n in zip(rows, dims, lens):
             o = out[r0:r0 + r.shape[0], 0, :n]
             r0 += r.shape[0]
             res.append(o[0] if nd == 1 else o)
         return res
+
+    @staticmethod
+    def _counter_plan(rngs, channels):
+        """`rngs` of enhance_many -> None (generators) or (seed, [stream id per row]) for CounterNoise sources: one per entry, or
+        one shared (entry i = utterance stream + i); `channels[i]`: rows of entry i."""
+        per_entry = isinstance(rngs, (list, tuple))
+        srcs = list(rngs) if per_entry else [rngs]
+        if not any(is_counter(g) for g in srcs):
+            return None
+        if not all(is_counter(g) for g in srcs):
+            raise ValueError("enhance_many: CounterNoise sources and generators do not mix in one call")
+        if per_entry:
+            if len(srcs) != len(channels):
+                raise ValueError("enhance_many: one CounterNoise per input (or one shared)")
+            if len({g.seed for g in srcs}) != 1:
+                raise ValueError("enhance_many: the CounterNoise sources of one call must share their seed")
+        else:
+            srcs = [rngs.at(i) for i in range(len(channels))]
+        ids = [v for g, c in zip(srcs, channels) for v in g.stream_ids(c)]
+        if len(set(ids)) != len(ids):
+            raise ValueError("enhance_many: two rows of the call would draw the same noise (equal stream ids)")
+        return srcs[0].seed, ids
 
     def advance_generator_like_enhance(self, rng, channels, length, n_steps=None, warm_start=None, use_aux_signal=False):
         """Advance `rng` by exactly the draws `enhance` makes for a (channels, length) input -- x0, then one z per noisy step
@@ -761,8 +859,10 @@ class Universe:
         signals, as channels are everywhere else.  The signal is cut into windows of `segment_s` seconds that overlap by
         `overlap_s` seconds and run `max_batch` at a time through the walk of `enhance`; normalisation, mel scale, noise,
         keep_rms and the peak guard stay those of the whole file (include/ouniverse.h, ou_enhance_segments).  The noise is
-        drawn exactly as `enhance` draws it for this input, so a shared generator advances identically.  A file that fits into
-        one window gets the `enhance` result.  Workspace: ou_segments_workspace_bytes -- set by max_batch and segment_s."""
+        drawn exactly as `enhance` draws it for this input, so a shared generator advances identically -- as ONE (n_steps, C,
+        T_pad) tensor, n_steps times the recording.  `rng=noise.CounterNoise(seed, u)` removes that tensor: every window's noise
+        is computed at its offset from the counter-based function (row c: stream id (u << 16) | c), and the memory of the call is
+        the workspace plus input and output.  A file that fits into one window gets the `enhance` result.  Workspace: ou_segments_workspace_bytes -- set by max_batch and segment_s."""
         for k in ("target", "ensemble", "fake_score_snr", "warm_start"):
             if other.get(k) is not None:
                 raise ValueError(f"enhance_long does not take `{k}`")
@@ -787,7 +887,8 @@ class Universe:
         need, B, L = c_size_t(), c_int32(), c_int32()
         _lib.check(self._L.ou_segments_workspace_bytes(self._handle, C, T_raw, segment, overlap, int(max_batch), byref(need),
                                                         byref(B), byref(L)), self._handle)
-        noise = self.draw_noise_like_enhance(rng, C, T_raw, n_steps)
+        counter = is_counter(rng)
+        noise = None if counter else self.draw_noise_like_enhance(rng, C, T_raw, n_steps)
         skey = (int(n_steps), float(self.diff_kwargs.sigma_min), float(self.diff_kwargs.sigma_max))
         sigma = self._sigma_cache.get(skey)
         if sigma is None:
@@ -796,9 +897,11 @@ class Universe:
         ws = self._segments_workspace(B.value, L.value, need.value)
         out = torch.empty(C, T_raw, dtype=torch.float32, device=self.device)
         flags = _lib.OU_ENH_KEEP_RMS if keep_rms else 0
-        with torch.cuda.device(self.device):
+        source = self._counter_source(rng.seed, rng.stream_ids(C)) if counter else contextlib.nullcontext()
+        with torch.cuda.device(self.device), source:
             _lib.check(self._L.ou_enhance_segments(
-                self._handle, c_void_p(x.data_ptr()), c_void_p(out.data_ptr()), c_void_p(noise.data_ptr()), C, T_raw,
+                self._handle, c_void_p(x.data_ptr()), c_void_p(out.data_ptr()),
+                None if counter else c_void_p(noise.data_ptr()), C, T_raw,
                 segment, overlap, int(max_batch), n_steps, float(epsilon), ctypes.cast(sigma.data_ptr(), ctypes.POINTER(c_float)),
                 -1, flags, c_void_p(ws.data_ptr()), c_size_t(ws.numel()), self._stream()), self._handle)
         self._status()
