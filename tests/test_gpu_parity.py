@@ -266,6 +266,20 @@ def test_other_baseline_configs_full_width(name, T, n_steps):
     record(f"oracle.full_width.{name}", O.si_sdr(ref, out))
 
 
+def test_whole_file_call_at_a_real_length_vs_oracle():
+    """UNIVERSE++ 16 kHz, 30 s in ONE call (3 001 GRU frames per pass), 3 steps, B = 1, against the oracle on shared noise: a
+    whole-file call longer than a few seconds against something that is not HIP output."""
+    model, spec, sd = get_model("PP16")
+    T = 30 * spec.fs
+    mix = synth_mix(spec, 1, T)
+    Tp = T + (spec.tot_ds - T % spec.tot_ds)
+    nz = noise_list(13, 3, 1, Tp)
+    ref = O.enhance(sd, spec.to_dict(), mix, n_steps=3, noise=nz)
+    out = run_enhance(model, mix, nz, n_steps=3)
+    model.reset_workspace()
+    record("oracle.whole_file_30s.PP16", O.si_sdr(ref, out))
+
+
 def test_variable_length_batch_is_padded_batch_semantics():
     """configs[4]: a variable-length batch is right-zero-padded to its longest member (datasets/datamodule.py:24-42);
     the reference has no mask, so parity is defined on the padded batch.  Also checks that every utterance of the
