@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define OU_ABI_VERSION 6 /* 6: counter-based sampler noise (ou_set_noise_source, ou_noise_scratch_bytes, ou_noise_fill); existing entry points unchanged; 5: ou_enhance_var (batches whose rows have lengths of their own), workspace header carries the per-row geometry; ou_set_option / ou_get_option replace every OU_* environment switch (the library reads no environment variable), ou_config.fir_fold; 4: the packed blob carries a bf16-split weight copy (conv_split_kernel); 3: a Winograd-domain copy (round 5), ou_set_lane_batch, ou_lane_capacity */
+#define OU_ABI_VERSION 7 /* 7: ensembles in the library (ou_enhance_ensemble, ou_ensemble_workspace_bytes, ou_ensemble_reduce, ou_ensemble_reduce_scratch_bytes; option ens_share); existing entry points unchanged; 6: counter-based sampler noise (ou_set_noise_source, ou_noise_scratch_bytes, ou_noise_fill); existing entry points unchanged; 5: ou_enhance_var (batches whose rows have lengths of their own), workspace header carries the per-row geometry; ou_set_option / ou_get_option replace every OU_* environment switch (the library reads no environment variable), ou_config.fir_fold; 4: the packed blob carries a bf16-split weight copy (conv_split_kernel); 3: a Winograd-domain copy (round 5), ou_set_lane_batch, ou_lane_capacity */
 
 enum {
   OU_OK = 0,
@@ -155,7 +155,8 @@ int ou_aux_to_wav(ou_handle* h, float* wav_out, int32_t B, int32_t T, void* ws, 
  * OU_EINVAL before anything is launched -- ou_enhance_segments takes it:
  * pad (:219-223) -> normalize (utils/norm.py:47-87) -> conditioner -> x0 = sigma_0 * noise[0] ->
  * N-1 x { score; x += sigma_n^2*eta*score + beta*sigma_{n+1}*noise[n+1] } -> last clean step ->
- * unpad -> [keep_rms] -> peak guard.  Ensemble replication / reduction stays with the caller.
+ * unpad -> [keep_rms] -> peak guard.  Ensemble replication / reduction stays with the caller of THIS entry point
+ * (ou_enhance_ensemble below does both inside the library).
  *   mix, out : (B, T_raw) device
  *   noise    : (n_steps - warm_start, B, T_pad) standard-normal, device, in the reference's draw order
  *              (x0, z_0 .. z_{N-2}); T_pad = T_raw + (tot_ds - T_raw % tot_ds).  NULL when a noise source is set
@@ -183,6 +184,53 @@ int ou_enhance(ou_handle* h, const float* mix, float* out, const float* noise, i
 int ou_enhance_var(ou_handle* h, const float* mix, float* out, const float* noise, int32_t B, int32_t T_raw_max,
                    const int32_t* t_raw, int32_t n_steps, double epsilon, const float* sigma_host, int32_t warm_start,
                    uint32_t flags, void* ws, size_t ws_bytes, ou_stream_t stream);
+
+/* ---- ensembles (universe.py:261-264, 359-368: `ensemble=E` runs E samples of every input and returns their mean, median or
+ * "signal median", utils/stats.py:22-66) -------------------------------------------------------------------------------------
+ * Members are MEMBER-MAJOR everywhere: row e * B + b is member e of input b -- the order torch.stack([mix] * E) produces
+ * (universe.py:261-264) and the order of the stream ids of the counter-based noise (member e: the input's id + (e << 48)).
+ *
+ * ou_enhance_ensemble = ou_enhance / ou_enhance_var (t_raw given) of the E * B member rows, with
+ *   - the conditioner -- whose result depends on the input, not on the noise -- run ONCE over the B inputs and its results
+ *     replicated to the rows of the other members (option `ens_share`, default 1; 0: the conditioner runs over all E * B rows,
+ *     the arithmetic of the call on the replicated batch).  A B-row conditioner pass may select other kernels than an
+ *     (E * B)-row one: the members agree with those of `ens_share` = 0 to fp32 round-off (tests: >= 100 dB), not bit for bit;
+ *   - the sampler loop at E * B rows, as one chain on the caller's stream (no side streams inside the call);
+ *   - unpad, keep_rms and the peak guard per member row, as the reference applies them before the reduce; keep_rms restores
+ *     the RMS of the member's own input b (for B = 1 the reference's result; for B > 1 the reference fails to broadcast,
+ *     universe.py:354, and this per-input definition is the extension);
+ *   - the reduce over e into `out`.
+ *   mix, out    : (B, T_raw_max) device, the row conventions of ou_enhance_var (t_raw NULL: every row has T_raw_max samples)
+ *   members_out : NULL, or (E * B, T_raw_max) device: the post-processed members (rows of a ragged batch 0 behind their end)
+ *   noise       : (n_steps - max(warm_start, 0), E * B, T_pad_max) device; NULL when a noise source is set -- its n_streams
+ *                 must then equal E * B and its scratch hold two (E * B, T_pad_max) planes
+ *   stat        : OU_ENS_MEAN     fp32 sum over e = 0 .. E - 1 in that order, then one division by E
+ *                 OU_ENS_MEDIAN   the value of stable rank (E - 1) / 2: torch.median's lower median
+ *                 OU_ENS_SIGNAL_MEDIAN  per input ONE member: per sample the rank position of the member whose index is nearest
+ *                   E / 2 (both neighbours for odd E, the smaller position wins), histogram of the positions over the input's
+ *                   own samples, first maximum -> that member's row.  rank(c) = #{x_j < x_c} + #{j < c : x_j == x_c}
+ *   flags       : OU_ENH_KEEP_RMS, OU_ENH_NO_PEAK_GUARD; OU_ENH_USE_AUX_SIGNAL is refused (OU_EINVAL: without noise all members
+ *                 are equal); OU_ENH_SERIAL is implied
+ *   workspace   : ou_ensemble_workspace_bytes(h, B, T_pad_max, E) bytes -- the walk's workspace for E * B rows plus the member
+ *                 planes, a B x E histogram and B picks -- prepared with ou_workspace_init(h, E * B, T_pad_max, ..); a buffer
+ *                 prepared for another batch size is refused (OU_EINVAL)
+ * OU_EINVAL for E < 1, E > OU_MAX_ENSEMBLE, an unknown stat; the length guard of ou_enhance applies unchanged (per-row planes
+ * do not grow with E).  Inputs are assumed finite.  No float atomics: results do not depend on scheduling. */
+#define OU_MAX_ENSEMBLE 32
+enum { OU_ENS_MEAN = 0, OU_ENS_MEDIAN = 1, OU_ENS_SIGNAL_MEDIAN = 2 };
+int ou_ensemble_workspace_bytes(const ou_handle* h, int32_t B, int32_t T_pad_max, int32_t E, size_t* nbytes);
+int ou_enhance_ensemble(ou_handle* h, const float* mix, float* out, float* members_out, const float* noise, int32_t B,
+                        int32_t T_raw_max, const int32_t* t_raw, int32_t E, int32_t stat, int32_t n_steps, double epsilon,
+                        const float* sigma_host, int32_t warm_start, uint32_t flags, void* ws, size_t ws_bytes,
+                        ou_stream_t stream);
+/* The reduce alone (stateless: no handle), for bindings that keep their own sampler loop:
+ *   members: (E * B, row_stride) device, member-major; out: (B, row_stride) device; only the first `cols` columns of a row are
+ *   touched; len_host: NULL, or B valid lengths on the HOST (0 <= len[b] <= cols) -- nothing is read past len[b], and
+ *   out[b][len[b] .. cols) = 0.  scratch (OU_ENS_SIGNAL_MEDIAN only; device, >= ou_ensemble_reduce_scratch_bytes): the
+ *   histogram, int32 [B][E], then the picked member of every input, int32 [B].  Enqueued on `stream`. */
+size_t ou_ensemble_reduce_scratch_bytes(int32_t E, int32_t B);
+int ou_ensemble_reduce(const float* members, float* out, int32_t E, int32_t B, int64_t row_stride, int64_t cols,
+                       const int64_t* len_host, int32_t stat, void* scratch, size_t scratch_bytes, ou_stream_t stream);
 
 /* ---- segmented enhance: recordings of any length in bounded memory (extension; the reference runs a whole file per call)
  * A long row is cut into overlapping windows that run as one batch through the walk of ou_enhance; whatever the reference

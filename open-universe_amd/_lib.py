@@ -10,11 +10,14 @@ from ctypes import (POINTER, Structure, byref, c_char_p, c_double, c_float, c_in
                     c_void_p)
 
 OU_MAX_RATES = 8
-OU_ABI_VERSION = 6
+OU_ABI_VERSION = 7
 OU_OK, OU_EINVAL, OU_ENOTIMPL, OU_EMISSING, OU_ESHAPE, OU_EHIP, OU_ENOMEM, OU_ESYNC = 0, -1, -2, -3, -4, -5, -6, -7
 OU_KIND_UNIVERSE, OU_KIND_UNIVERSE_GAN = 0, 1
 OU_ACT_NONE, OU_ACT_PRELU, OU_ACT_SNAKE = 0, 1, 2
 OU_ENH_KEEP_RMS, OU_ENH_USE_AUX_SIGNAL, OU_ENH_NO_PEAK_GUARD, OU_ENH_SERIAL = 1, 2, 4, 8
+OU_MAX_ENSEMBLE = 32
+OU_ENS_MEAN, OU_ENS_MEDIAN, OU_ENS_SIGNAL_MEDIAN = 0, 1, 2
+ENSEMBLE_STATS = {"mean": OU_ENS_MEAN, "median": OU_ENS_MEDIAN, "signal_median": OU_ENS_SIGNAL_MEDIAN}
 
 
 class NetConfig(Structure):
@@ -109,6 +112,11 @@ def load():
         "ou_aux_to_wav": (i32, [vp, vp, i32, i32, vp, sz, vp]),
         "ou_enhance": (i32, [vp, vp, vp, vp, i32, i32, i32, c_double, POINTER(c_float), i32, c_uint32, vp, sz, vp]),
         "ou_enhance_var": (i32, [vp, vp, vp, vp, i32, i32, POINTER(i32), i32, c_double, POINTER(c_float), i32, c_uint32, vp, sz, vp]),
+        "ou_ensemble_workspace_bytes": (i32, [vp, i32, i32, i32, POINTER(sz)]),
+        "ou_enhance_ensemble": (i32, [vp, vp, vp, vp, vp, i32, i32, POINTER(i32), i32, i32, i32, c_double, POINTER(c_float), i32,
+                                      c_uint32, vp, sz, vp]),
+        "ou_ensemble_reduce_scratch_bytes": (sz, [i32, i32]),
+        "ou_ensemble_reduce": (i32, [vp, vp, i32, i32, c_int64, c_int64, POINTER(c_int64), i32, vp, sz, vp]),
         "ou_segment_plan": (i32, [i32, c_int64, i32, i32, i32, POINTER(c_int64), POINTER(i32), POINTER(c_int64),
                                   POINTER(c_int64), POINTER(i32), POINTER(i32), POINTER(c_int64)]),
         "ou_segments_workspace_bytes": (i32, [vp, i32, c_int64, i32, i32, i32, POINTER(sz), POINTER(i32), POINTER(i32)]),
@@ -162,6 +170,7 @@ EXPORTED_SYMBOLS = [
     "ou_packer_destroy", "ou_packed_bytes", "ou_create", "ou_destroy", "ou_workspace_bytes", "ou_schedule",
     "ou_condition", "ou_score", "ou_aux_to_wav", "ou_enhance", "ou_enhance_var", "ou_check_device_status",
     "ou_segment_plan", "ou_segments_workspace_bytes", "ou_enhance_segments",
+    "ou_ensemble_workspace_bytes", "ou_enhance_ensemble", "ou_ensemble_reduce_scratch_bytes", "ou_ensemble_reduce",
     "ou_set_noise_source", "ou_noise_scratch_bytes", "ou_noise_fill",
     "ou_set_option", "ou_get_option", "ou_reset_options", "ou_option_count", "ou_option_name", "ou_option_doc", "ou_option_default", "ou_plan_json",
     "ou_packer_plan_json", "ou_tensor", "ou_launch_stats", "ou_workspace_init", "ou_sampler_step",

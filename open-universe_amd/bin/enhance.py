@@ -226,6 +226,8 @@ def main(argv=None, model=None):
 
     check_segment_args(args, enhance_kwargs)
     check_noise_args(args, enhance_kwargs)
+    if args.pad_batch and enhance_kwargs.get("ensemble") is not None:
+        raise ValueError("--pad-batch cannot be combined with --ensemble (ensembles are batched exactly)")
     counter = args.noise == "counter"
     files, rel_path, dir_proc = find_files(args.input)
     # (counter mode: the file index is part of the noise function -- nothing to force for sharded runs, nothing to re-draw)
@@ -313,10 +315,13 @@ def main(argv=None, model=None):
 
     # --batch-size: files are read in processing order into a window (one sample rate, --batch-window files), sorted by length
     # inside it and enhanced batch_size at a time
-    if any(enhance_kwargs.get(key) is not None for key in ("ensemble", "target")):
-        raise ValueError("--batch-size cannot be combined with --ensemble (one call per file needed)")
-    kw = {key: v for key, v in enhance_kwargs.items() if key not in ("rng", "ensemble", "ensemble_stat", "target",
-                                                                    "fake_score_snr")}
+    if enhance_kwargs.get("target") is not None:
+        raise ValueError("--batch-size cannot be combined with --target (one call per file needed)")
+    # --ensemble E --batch-size K: every group is one enhance_many(ensemble=E) call (exact batching; the members are reduced
+    # inside the library)
+    ensemble = enhance_kwargs.get("ensemble")
+    drop = ("rng", "target", "fake_score_snr") + (("ensemble", "ensemble_stat") if ensemble is None else ())
+    kw = {key: v for key, v in enhance_kwargs.items() if key not in drop}
 
     window_size = max(1, args.batch_window if args.batch_window > 0 else 4 * args.batch_size)
     # Sorting a window by length needs a generator per file that starts where the serial loop's shared generator would stand
@@ -343,7 +348,9 @@ def main(argv=None, model=None):
                 elif can_sort:
                     g = torch.Generator(device=device)
                     g.set_state(rng.get_state())
-                    model.advance_generator_like_enhance(rng, sig.shape[0] if sig.ndim == 2 else 1, sig.shape[-1],
+                    # (with --ensemble E a file draws for its E * channels member rows)
+                    model.advance_generator_like_enhance(rng, (sig.shape[0] if sig.ndim == 2 else 1) * int(ensemble or 1),
+                                                         sig.shape[-1],
                                                          n_steps=kw.get("n_steps"), warm_start=kw.get("warm_start"),
                                                          use_aux_signal=bool(kw.get("use_aux_signal")))
                 else:

@@ -37,6 +37,7 @@ struct Options {
   int dbg_dec0_under_gru = 0;  // measurement only, INVALID results (see run_score); experiments library only
   int tile_prefetch = 1;
   int trace = 0, no_overlap = 0, ts = 0, deep_factor = 8, mask_fused = 1, split_wino = 1, d2_tile_rule = 1;
+  int ens_share = 1;           // ou_enhance_ensemble: conditioner once over the B inputs (1) or over all E * B rows (0)
   double tile_min = -1.0;      // < 0: the launcher's default
   std::string chain_ts;        // ou_set_stamp_layer (tuning)
 };
@@ -172,6 +173,7 @@ const OptDesc kOptions[] = {
     {"ts", &Options::ts, nullptr, false, "1: per-wave phase stamps in ou_bench_conv (tuning)"},
     {"trace", &Options::trace, nullptr, false, "1: one line per conv launch on stderr"},
     {"no_overlap", &Options::no_overlap, nullptr, false, "1: no side streams inside a call (every kernel alone on the device)"},
+    {"ens_share", &Options::ens_share, nullptr, false, "ou_enhance_ensemble: 1 = conditioner once over the B inputs, its results replicated; 0 = over all E * B rows"},
     {"dbg", &Options::dbg, nullptr, true, "phase ablation switches of the conv kernels: WRONG results by design"},
     {"dbg_dec0", &Options::dbg_dec0_under_gru, nullptr, true, "first decoder block under the GRU: upper-bound measurement, WRONG results"},
 };
@@ -305,6 +307,8 @@ struct Runner {
   std::vector<ConvArgs>* collect = nullptr;
   unsigned* status_words = nullptr;        // workspace header (layout_persist)
   unsigned long long* block3_bar = nullptr;
+  int gru_area_rows = 0;    // rows the GRU exchange areas were laid out for when that is more than B (ou_enhance_ensemble: the
+                            // conditioner runs B rows on the areas of an E * B-row workspace, as a sub-launch of a chunked batch does)
   bool gru_shared = false;  // GRU launches enqueued now may run beside another GRU layer (overlapped conditioner / score pass)
   hipEvent_t pre_gru = nullptr;  // OU_DBG_DEC0: recorded right before the score net's GRU launch
   bool want_pre_gru = false;
@@ -644,6 +648,7 @@ struct Runner {
     GruArgs a;
     a.gx = gx.p; a.whh = W(G.whh_off); a.bhn = W(G.bhn_off); a.out = out.p; a.res = res; a.res_scale = res_scale;
     a.xchg = xchg; a.err = errw; a.epoch = epoch; a.B = B; a.T = in.T; a.H = G.H;
+    if (gru_area_rows > B) a.xchg_granules = gru_granules(gru_area_rows, G.H);
     // kernel generation: the ring kernel (every wave gathers h straight from L2, no polling wave, no workgroup barrier)
     // for every batch size; OU_GRU_V=1 selects the polling-wave kernel of round 1.  Its publishes: see below.
     a.version = env.gru_v;
@@ -1513,6 +1518,300 @@ int ou_enhance_var(ou_handle* h, const float* mix, float* out, const float* nois
   if (!t_raw) return fail(h, OU_EINVAL, "ou_enhance_var: t_raw must be given (ou_enhance takes batches of equal lengths)");
   return enhance_impl(h, mix, out, noise, B, T_raw_max, t_raw, n_steps, epsilon, sigma_host, warm_start, flags, ws, ws_bytes,
                       stream);
+}
+
+}  // extern "C"
+
+namespace {
+// bytes of the ensemble call's own area, right behind the persistent block of the (E * B)-row workspace
+struct EnsArea {
+  size_t lens_b, members, hist, total;
+};
+EnsArea ens_area(int B, int E, long long cols) {
+  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+  EnsArea a;
+  size_t off = 0;
+  a.lens_b = off; off += al((size_t)B * kMaxLenLevels * 4);      // the conditioner's own [level][B] length table (ragged, shared)
+  a.members = off; off += al((size_t)E * B * (size_t)cols * 4);  // post-processed member planes (members_out == NULL)
+  a.hist = off; off += al(((size_t)B * E + B) * 4);              // signal median: histogram [B][E] + picks [B]
+  a.total = off;
+  return a;
+}
+
+// ou_enhance_ensemble: the walk of enhance_impl as ONE chain on the caller's stream for the E * B member rows, with the
+// conditioner (and, for a warm start, the decoupling layer) run once over the B inputs and replicated -- ens_share = 0: run
+// over all E * B rows --, the post step per member row and the reduce over the members.
+int ensemble_impl(ou_handle* h, const float* mix, float* out, float* members_out, const float* noise, int32_t B, int32_t T_raw,
+                  const int32_t* t_raw, int32_t E, int32_t stat, int32_t n_steps, double epsilon, const float* sigma_host,
+                  int32_t warm_start, uint32_t flags, void* ws, size_t ws_bytes, ou_stream_t stream) {
+  if (!h || !mix || !out || !ws || B < 1 || T_raw < 1) return fail(h, OU_EINVAL, "bad argument");
+  if (E < 1 || E > OU_MAX_ENSEMBLE)
+    return fail(h, OU_EINVAL, "ou_enhance_ensemble: 1 <= E <= " + std::to_string(OU_MAX_ENSEMBLE));
+  if (stat != OU_ENS_MEAN && stat != OU_ENS_MEDIAN && stat != OU_ENS_SIGNAL_MEDIAN)
+    return fail(h, OU_EINVAL, "ou_enhance_ensemble: stat must be OU_ENS_MEAN, OU_ENS_MEDIAN or OU_ENS_SIGNAL_MEDIAN");
+  if (flags & OU_ENH_USE_AUX_SIGNAL)
+    return fail(h, OU_EINVAL, "ou_enhance_ensemble: OU_ENH_USE_AUX_SIGNAL is refused (without noise all members are equal)");
+  if ((long long)E * B > 0x7fffffffll / 64) return fail(h, OU_EINVAL, "ou_enhance_ensemble: too many rows");
+  if (t_raw) {
+    int mx = 0;
+    bool all_whole = true;
+    for (int b = 0; b < B; b++) {
+      if (t_raw[b] < 1 || t_raw[b] > T_raw) return fail(h, OU_EINVAL, "ou_enhance_ensemble: 1 <= t_raw[b] <= T_raw_max");
+      mx = t_raw[b] > mx ? t_raw[b] : mx;
+      all_whole = all_whole && t_raw[b] == T_raw;
+    }
+    if (mx != T_raw) return fail(h, OU_EINVAL, "ou_enhance_ensemble: T_raw_max must be the length of the longest row");
+    if (all_whole) t_raw = nullptr;  // nothing ragged about this batch: the plain path (and its fused kernels)
+  }
+  const int EB = E * B;
+  const bool counter = h->noise_src.on;
+  if (counter && noise)
+    return fail(h, OU_EINVAL, "a noise source is set on this handle (ou_set_noise_source): `noise` must be NULL");
+  if (counter && (int)h->noise_src.streams.size() != EB)
+    return fail(h, OU_EINVAL, "noise source: n_streams (" + std::to_string(h->noise_src.streams.size()) +
+                                  ") must equal the member rows of the call (E * B = " + std::to_string(EB) + ")");
+  if (!noise && !counter) return fail(h, OU_EINVAL, "noise must be given");
+  if (n_steps < 2 || n_steps > kMaxSteps) return fail(h, OU_EINVAL, "n_steps must be in [2, 256]");
+  if (warm_start >= n_steps) return fail(h, OU_EINVAL, "warm_start must be < n_steps");
+  const Model& m = h->m;
+  const int tot = m.tot_ds;
+  const int pad = tot - T_raw % tot;  // universe.py:219-223 (a full block when already a multiple)
+  const int pad_left = pad / 2;
+  const int T = T_raw + pad;
+  const bool need_wav = warm_start >= 0;
+  {
+    const long long t_max = max_walk_length(h, need_wav);  // (per-row planes do not grow with E)
+    if (T > t_max)
+      return fail(h, OU_EINVAL, "input too long for one pass: " + std::to_string(T_raw) + " samples padded to " +
+                                    std::to_string(T) + " make a plane of the walk reach 2^32 bytes (at most " +
+                                    std::to_string(t_max) + " padded samples)");
+  }
+  if (!h->ws_ok(ws, ws_bytes, EB, T))
+    return fail(h, OU_EINVAL, "workspace was not prepared by ou_workspace_init for this (E * B, T_raw + pad)");
+  if (counter && (!h->noise_src.scratch || h->noise_src.scratch_bytes < (size_t)2 * EB * T * sizeof(float)))
+    return fail(h, OU_ENOMEM, "noise source: scratch too small: need " + std::to_string((size_t)2 * EB * T * sizeof(float)) +
+                                  " bytes (ou_noise_scratch_bytes for E * B rows)");
+  if (need_wav && (!m.dec.present || m.dec.act != OU_ACT_SNAKE))
+    return fail(h, OU_ENOTIMPL, "aux_to_wav needs the snake signal-decoupling layer (UNIVERSE++)");
+  const bool saved_overlap = h->overlap;
+  struct OverlapGuard { ou_handle* h; bool v; ~OverlapGuard() { h->overlap = v; } } overlap_guard{h, saved_overlap};
+  h->overlap = false;  // one chain on the caller's stream (the conditioner || first-encoder overlap of ou_enhance is dropped)
+  h->tensors.clear();
+  h->n_launch = h->n_conv = 0;
+  h->ev_used = 0;
+  hipStream_t st = (hipStream_t)stream;
+  const bool share = h->opt.ens_share != 0 && E > 1;
+  const int Bc = share ? B : EB;  // rows of the conditioner pass
+
+  // ---- layout: the persistent block for E * B rows (what ou_workspace_init prepared), the ensemble's own area, then the
+  // conditioner's scratch (Bc rows) and the per-step score scratch (E * B rows)
+  Runner r(h, ws, ws_bytes, false, st, EB);
+  Persist P = layout_persist(r, T);
+  const EnsArea A = ens_area(B, E, T_raw);
+  char* area = (char*)r.alloc_raw(A.total / 4);
+  if (r.oom) return finish(h, r);
+  int* lens_b = (int*)(area + A.lens_b);
+  float* members = members_out ? members_out : (float*)(area + A.members);
+  int* hist = (int*)(area + A.hist);
+
+  std::vector<float> sigma(n_steps);
+  double eta, beta;
+  schedule(m.cfg, n_steps, epsilon, sigma.data(), &eta, &beta);
+  if (sigma_host) std::memcpy(sigma.data(), sigma_host, sizeof(float) * n_steps);
+  std::vector<StepCoef> rows;
+  for (int n = 0; n < n_steps; n++)
+    rows.push_back(make_coef(m.cfg, sigma[n], n == n_steps - 1, eta, beta, n + 1 < n_steps ? sigma[n + 1] : 0.f));
+  upload_coefs(r, P.coef, rows);
+
+  Runner rc(h, ws, ws_bytes, false, st, Bc);  // the conditioner's runner: Bc rows on the prefix of the persistent tensors
+  rc.status_words = r.status_words;
+  rc.block3_bar = r.block3_bar;
+  rc.gru_area_rows = EB;
+  std::vector<int32_t> t_rep;  // member-major lengths: row e * B + b has t_raw[b]
+  if (t_raw) {
+    t_rep.resize(EB);
+    for (int e = 0; e < E; e++)
+      for (int b = 0; b < B; b++) t_rep[(size_t)e * B + b] = t_raw[b];
+    LevelSpec& lv = r.lv;
+    lv.n = 0;
+    auto add_level = [&](int num, int den) {
+      lv.num[lv.n] = num; lv.den[lv.n] = den; r.level_T[lv.n] = (int)((long long)T * num / den); lv.n++;
+    };
+    add_level(1, 1);
+    add_level(2, 1);
+    int cum = 1;
+    for (int i = 0; i < m.cfg.score.n_rates && lv.n < kMaxLenLevels; i++) { cum *= m.cfg.score.rate_factors[i]; add_level(1, cum); }
+    if (cum != tot) return fail(h, OU_EINVAL, "internal: rate factors do not multiply to the total down-sampling factor");
+    // E copies of the per-row geometry for the sampler loop; the length table is [level][rows], so the conditioner's B-row pass
+    // gets a table of its own ([level][B]; the RowInfo entries of rows 0 .. B - 1 serve both)
+    auto upload = [&](RowInfo* rows_dst, int* lens_dst, const int32_t* tr, int nrows) {
+      for (int off = 0; off < nrows; off += 64) {
+        RowBlock blk;
+        const int n = nrows - off < 64 ? nrows - off : 64;
+        for (int i = 0; i < 64; i++) blk.t_raw[i] = i < n ? tr[off + i] : 1;
+        r.chk(launch_upload_rows(rows_dst, lens_dst, blk, n, off, nrows, tot, lv, st), "upload rows");
+      }
+    };
+    upload(P.rows, P.lens, t_rep.data(), EB);
+    r.ragged = true;
+    r.lens_dev = P.lens;
+    r.rows_dev = P.rows;
+    rc.ragged = true;
+    rc.rows_dev = P.rows;
+    rc.lv = lv;
+    for (int l = 0; l < kMaxLenLevels; l++) rc.level_T[l] = r.level_T[l];
+    if (share) {
+      // (its RowInfo output goes to rows 0 .. B - 1 of P.rows once more: the same values)
+      upload(P.rows, lens_b, t_raw, B);
+      rc.lens_dev = lens_b;
+    } else {
+      rc.lens_dev = P.lens;
+    }
+  }
+  r.chk(launch_sigma_embed(P.coef, n_steps, r.W(m.sigma.p_off), m.sigma.simple, m.sigma.n_rff, m.film.D, P.g, st), "sigma");
+  r.chk(launch_film(P.g, r.W(m.film.w_off), r.W(m.film.b_off), P.film, n_steps, m.film.rows, m.film.D, st), "film");
+
+  // ---- pad + normalise the B inputs (one workgroup per row: what the replicated batch would give, bit for bit)
+  const float level = (float)std::pow(10.0, (double)m.cfg.level_db / 20.0);
+  if (r.ragged) r.chk(launch_pad_normalize_var(mix, P.mixn.p, P.stats, P.rows, B, T_raw, T, level, st), "normalize");
+  else r.chk(launch_pad_normalize(mix, P.mixn.p, P.stats, B, T_raw, T, pad_left, level, st), "normalize");
+  // Replication: rows [0, B) of a tensor laid out for E * B rows -> rows [e B, (e + 1) B), up to 16 tensors per launch
+  ReplicateTable tab;
+  int n_tab = 0;
+  auto flush_tab = [&]() {
+    if (n_tab && r.ok()) r.chk(launch_replicate_rows(tab, n_tab, E, st), "replicate rows");
+    n_tab = 0;
+  };
+  auto replicate = [&](void* p, size_t words_per_b_rows) {
+    if (E == 1) return;
+    if (n_tab == kReplicateEntries) flush_tab();
+    tab.p[n_tab] = (unsigned*)p;
+    tab.n[n_tab] = (long long)words_per_b_rows;
+    n_tab++;
+  };
+  auto replicate_t = [&](const Tensor& t) { replicate(t.p, (size_t)B * t.C * t.T); };
+  if (!share) {  // the conditioner runs over all member rows: only its input is replicated
+    replicate_t(P.mixn);
+    replicate(P.stats, (size_t)B * 4);
+    flush_tab();
+  }
+
+  // ---- conditioner (+ decoupling layer for a warm start) over Bc rows
+  rc.off = r.off;
+  run_condition(rc, P, P.mixn.p, T);
+  h->cond_B = 0;  // (the operator seams ou_score / ou_aux_to_wav do not take this layout)
+  h->cond_T = T;
+  if (need_wav) {
+    float* tmp = rc.alloc_raw((size_t)Bc * m.C0 * 2 * T);
+    if (rc.ok())
+      rc.chk(launch_decoupling(P.aux.p, rc.W(m.dec.alpha_off), rc.W(m.dec.up_off), rc.W(m.dec.down_off),
+                               rc.W(m.dec.conv.w_off), rc.W(m.dec.conv.b_off), tmp, P.wav.p, Bc, m.C0, T, st, rc.lens_of(T),
+                               rc.lens_of(2 * T)), "decoupling");
+  }
+  if (!rc.ok()) return finish(h, rc);
+  if (share) {
+    for (size_t j = 0; j < P.cond.size(); j++) { replicate_t(P.cond[j]); replicate_t(P.sc[j]); }
+    replicate_t(P.aux);
+    replicate_t(P.latent);
+    replicate_t(P.mixn);
+    replicate(P.stats, (size_t)B * 4);
+    replicate(P.mel_scale, (size_t)B);
+    if (need_wav) replicate_t(P.wav);
+    flush_tab();
+  }
+
+  // ---- the sampler loop at E * B rows, as enhance_impl runs it without the first-encoder overlap
+  r.off = rc.off;
+  const size_t nBT = (size_t)EB * T;
+  const int n_start = warm_start >= 0 ? warm_start : 0;
+  auto noise_plane = [&](int draw) -> const float* {
+    float* dst = h->noise_src.scratch + (size_t)(draw & 1) * nBT;
+    fill_noise_plane(r, dst, T, EB, h->noise_src.seed, draw, [&](int row, unsigned long long& sid, long long& t0, long long& len) {
+      sid = h->noise_src.streams[row];
+      t0 = 0;
+      len = t_raw ? t_rep[row] + (tot - t_rep[row] % tot) : T;
+    });
+    return dst;
+  };
+  r.chk(launch_init_x(counter ? noise_plane(0) : noise, warm_start >= 0 ? P.wav.p : nullptr, sigma[n_start], P.x.p, nBT, st),
+        "init x");  // universe.py:325-331
+  r.mask(P.x);
+  const size_t step_mark = r.off;
+  for (int n = n_start; n < n_steps; n++) {
+    const bool last = n == n_steps - 1;
+    const float* z = last ? nullptr : counter ? noise_plane(n + 1) : noise + (size_t)(n - n_start + 1) * nBT;
+    r.off = step_mark;  // every step re-uses the same scratch
+    run_score(r, P, P.x.p, z, P.x.p, OUT_UPDATE, P.coef + n, 0, P.film + (size_t)n * m.film.rows, 0, T);
+    if (!r.ok()) break;
+  }
+  if (!r.ok()) return finish(h, r);
+
+  // ---- per member row: unpad, keep_rms (the mix RMS of the member's own input: stats row e B + b = row b), peak guard
+  const int keep_rms = (flags & OU_ENH_KEEP_RMS) ? 1 : 0;
+  const int peak = (flags & OU_ENH_NO_PEAK_GUARD) ? 0 : 1;
+  if (r.ragged) r.chk(launch_post_var(P.x.p, P.stats, members, P.rows, EB, T_raw, T, keep_rms, peak, st), "post");
+  else r.chk(launch_post(P.x.p, P.stats, members, EB, T_raw, T, pad_left, keep_rms, peak, st), "post");
+  // ---- reduce over the members
+  std::vector<long long> len64;
+  if (t_raw) len64.assign(t_raw, t_raw + B);
+  if (r.ok()) {
+    r.chk(launch_ensemble_reduce(members, out, E, B, T_raw, T_raw, t_raw ? len64.data() : nullptr, stat, hist, hist + (size_t)B * E,
+                                 st), "ensemble reduce");
+  }
+  return finish(h, r);
+}
+}  // namespace
+
+extern "C" {
+
+int ou_ensemble_workspace_bytes(const ou_handle* hc, int32_t B, int32_t T_pad_max, int32_t E, size_t* nbytes) {
+  ou_handle* h = const_cast<ou_handle*>(hc);
+  if (!h || !nbytes || B < 1 || T_pad_max < 1) return fail(h, OU_EINVAL, "bad argument");
+  if (E < 1 || E > OU_MAX_ENSEMBLE || (long long)E * B > 0x7fffffffll / 64)
+    return fail(h, OU_EINVAL, "ou_ensemble_workspace_bytes: 1 <= E <= " + std::to_string(OU_MAX_ENSEMBLE));
+  size_t walk = 0;
+  const int rc = ou_workspace_bytes(h, E * B, T_pad_max, &walk);
+  if (rc != OU_OK) return rc;
+  // (T_pad_max bounds T_raw_max: the member planes are (E * B, T_raw_max))
+  *nbytes = ((walk + 255) & ~size_t(255)) + ens_area(B, E, T_pad_max).total;
+  return OU_OK;
+}
+
+int ou_enhance_ensemble(ou_handle* h, const float* mix, float* out, float* members_out, const float* noise, int32_t B,
+                        int32_t T_raw_max, const int32_t* t_raw, int32_t E, int32_t stat, int32_t n_steps, double epsilon,
+                        const float* sigma_host, int32_t warm_start, uint32_t flags, void* ws, size_t ws_bytes,
+                        ou_stream_t stream) {
+  return ensemble_impl(h, mix, out, members_out, noise, B, T_raw_max, t_raw, E, stat, n_steps, epsilon, sigma_host, warm_start,
+                       flags, ws, ws_bytes, stream);
+}
+
+size_t ou_ensemble_reduce_scratch_bytes(int32_t E, int32_t B) {
+  if (E < 1 || B < 1) return 0;
+  return (((size_t)B * E + B) * sizeof(int) + 255) & ~size_t(255);
+}
+
+int ou_ensemble_reduce(const float* members, float* out, int32_t E, int32_t B, int64_t row_stride, int64_t cols,
+                       const int64_t* len_host, int32_t stat, void* scratch, size_t scratch_bytes, ou_stream_t stream) {
+  if (!members || !out || B < 1 || cols < 1 || row_stride < cols) return fail(nullptr, OU_EINVAL, "ou_ensemble_reduce: bad argument");
+  if (E < 1 || E > OU_MAX_ENSEMBLE)
+    return fail(nullptr, OU_EINVAL, "ou_ensemble_reduce: 1 <= E <= " + std::to_string(OU_MAX_ENSEMBLE));
+  if (stat != OU_ENS_MEAN && stat != OU_ENS_MEDIAN && stat != OU_ENS_SIGNAL_MEDIAN)
+    return fail(nullptr, OU_EINVAL, "ou_ensemble_reduce: stat must be OU_ENS_MEAN, OU_ENS_MEDIAN or OU_ENS_SIGNAL_MEDIAN");
+  if (len_host)
+    for (int b = 0; b < B; b++)
+      if (len_host[b] < 0 || len_host[b] > cols) return fail(nullptr, OU_EINVAL, "ou_ensemble_reduce: 0 <= len[b] <= cols");
+  int* hist = nullptr;
+  if (stat == OU_ENS_SIGNAL_MEDIAN) {
+    if (!scratch || scratch_bytes < ou_ensemble_reduce_scratch_bytes(E, B) || reinterpret_cast<uintptr_t>(scratch) % 4 != 0)
+      return fail(nullptr, OU_ENOMEM, "ou_ensemble_reduce: the signal median needs ou_ensemble_reduce_scratch_bytes of scratch");
+    hist = (int*)scratch;
+  }
+  std::vector<long long> len64;
+  if (len_host) len64.assign(len_host, len_host + B);
+  const hipError_t e = launch_ensemble_reduce(members, out, E, B, row_stride, cols, len_host ? len64.data() : nullptr, stat, hist,
+                                              hist ? hist + (size_t)B * E : nullptr, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(nullptr, OU_EHIP, std::string("HIP error at ensemble reduce: ") + hipGetErrorString(e));
+  return OU_OK;
 }
 
 }  // extern "C"

@@ -986,7 +986,8 @@ hipError_t launch_gru(const GruArgs& a, int num_cu, hipStream_t st) {
     if (a.version == 2) {
       if (!a.epoch) return hipErrorInvalidValue;
       c.xchg_base = a.xchg;
-      c.xchg_granules = gru_granules(a.B, a.H);
+      // (the whole area: this batch's, or the larger one the caller laid it out for -- an epoch restart must clear it all)
+      c.xchg_granules = a.xchg_granules ? a.xchg_granules : gru_granules(a.B, a.H);
       hipError_t e;
       switch (HB) {
         case 1: e = launch_gru_ring<1>(c, upw, 2 * c.B, st); break;

@@ -221,6 +221,22 @@ struct NoiseRows {
 hipError_t launch_noise_fill(float* out, long long row_stride, long long cols, const NoiseRows& rows, int n_rows,
                              unsigned long long seed, int draw, hipStream_t st);
 
+// Ensemble reduce and row replication (ou_ensemble.hip; ou_enhance_ensemble / ou_ensemble_reduce in include/ouniverse.h).
+// members: (E * B, row_stride), member-major (row e * B + b = member e of input b); out: (B, row_stride).
+//   stat 0 mean (sequential fp32 sum over e, one division), 1 median (stable rank (E - 1) / 2), 2 signal median (utils/stats.py:
+//   22-66: per input the member whose rank position is most often that of the middle member; needs hist [B][E] and pick [B],
+//   device ints -- hist is cleared by the call).  len_host: B valid lengths on the host or null (= cols); out is 0 from there on.
+// Per-row values travel as kernel arguments, 16 inputs per launch: capturable, no host memory involved.
+constexpr int kMaxEnsemble = 32;
+constexpr int kEnsRowsPerLaunch = 16;
+struct EnsLens { long long len[kEnsRowsPerLaunch]; };
+hipError_t launch_ensemble_reduce(const float* members, float* out, int E, int B, long long row_stride, long long cols,
+                                  const long long* len_host, int stat, int* hist, int* pick, hipStream_t st);
+// entry k: the 4-byte words [0, n[k]) at p[k] are copied to [e n[k], (e + 1) n[k]) for e = 1 .. E - 1
+constexpr int kReplicateEntries = 16;
+struct ReplicateTable { unsigned* p[kReplicateEntries]; long long n[kReplicateEntries]; };
+hipError_t launch_replicate_rows(const ReplicateTable& tab, int n_entries, int E, hipStream_t st);
+
 // space-to-depth + PReLU for the conditioner's strided "st" convs: y[b][ci*R + k][q] = prelu(x[b][ci][q*R + k])
 hipError_t launch_s2d(const float* x, const float* alpha, float* y, int B, int C, int T, int R, hipStream_t st);
 // (`lens` of launch_in_conv / launch_out_conv / launch_fir: per-row valid lengths of a ragged batch or null, see ConvArgs::lens)

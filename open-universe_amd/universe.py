@@ -25,7 +25,7 @@ import torch
 
 from . import _lib
 from .config import ModelSpec
-from .noise import CounterNoise, is_counter
+from .noise import ENSEMBLE_SHIFT, CounterNoise, is_counter
 
 
 def randn(x, sigma, rng=None):
@@ -225,11 +225,13 @@ class Universe:
                 self._ws_need.clear()
         return n
 
-    def _workspace(self, B, T):
+    def _workspace(self, B, T, need=None):
+        """`need`: bytes when the call wants more than the walk's own workspace for (B, T) (enhance_ensemble)."""
         key = (B, T)
-        if self._ws_key == key:
+        if self._ws_key == key and (need is None or self._ws.numel() >= need):
             return self._ws
-        need = self._workspace_bytes(B, T)
+        if need is None:
+            need = self._workspace_bytes(B, T)
         cache = self._ws_cache
         ws = cache.get(B)
         if ws is None or ws.numel() < need:
@@ -711,7 +713,7 @@ class Universe:
 
     @torch.no_grad()
     def enhance_many(self, signals, rngs=None, pad_batch=False, n_steps=None, epsilon=None, use_aux_signal=False,
-                     keep_rms=False, warm_start=None, **other):
+                     keep_rms=False, warm_start=None, ensemble=None, ensemble_stat="median", return_members=False, **other):
         """Several independent inputs in ONE `enhance` call (extension; the reference's CLI loops over files one by one,
         bin/enhance.py:173-192).  `signals`: list of (L,) or (C, L) tensors -- a (C, L) entry is a file whose channels
         are rows of the batch, as in the reference.  `rngs`: one generator per entry, ONE shared generator, or None -- or
@@ -726,11 +728,17 @@ class Universe:
         (C_i, 1, L_i + pad_i).  Agrees with the one-by-one loop to fp32 round-off (the kernels a batch selects differ).
         pad_batch=True: right-zero-padded to the longest entry like `max_collator` (datasets/datamodule.py:24-42);
         the reference has no mask, the padding takes part in the normalisation / mel norm / GRU; outputs are cropped.
+        `ensemble=E` (with `ensemble_stat`): every entry is enhanced E times and reduced as `enhance(entry, ensemble=E)` does,
+        all entries in one ou_enhance_ensemble call (exact batching only: refused with pad_batch=True).  With generators the
+        noise of entry i is what `enhance(entry_i, ensemble=E, rng=..)` would draw alone ((E * C_i, 1, T_i) per step,
+        member-major), in serial-loop order; with CounterNoise member e of a row draws from the row's id + (e << 48)
+        (`stream_ids(C_i, E)`).  return_members=True (with `ensemble`): -> (results, members), members[i] of shape (E,) + the
+        shape of entry i.
         Returns the list of enhanced signals, each with the shape of its input."""
-        for k in ("target", "ensemble", "fake_score_snr"):
+        for k in ("target", "fake_score_snr"):
             if other.get(k) is not None:
                 raise ValueError(f"enhance_many does not take `{k}` (call enhance per input)")
-        unknown = set(other) - {"target", "ensemble", "fake_score_snr", "ensemble_stat", "rng"}
+        unknown = set(other) - {"target", "fake_score_snr", "rng"}
         if unknown:  # (a typo must not change behaviour on the batched path only)
             raise TypeError(f"enhance_many() got unexpected keyword argument(s): {sorted(unknown)}")
         if other.get("rng") is not None:
@@ -755,6 +763,11 @@ class Universe:
         n_noise = 0 if use_aux_signal else n_steps - n_start
         counter = self._counter_plan(rngs, [r.shape[0] for r in rows])
         extra = {} if counter is None else {"counter": counter}
+        if ensemble is not None:
+            return self._enhance_many_ensemble(rows, dims, lens, rngs, counter, int(ensemble), ensemble_stat, pad_batch,
+                                               n_steps, epsilon, use_aux_signal, keep_rms, warm_start, n_noise, return_members)
+        if return_members:
+            raise ValueError("enhance_many: return_members needs `ensemble`")
         if not pad_batch and any(n != l_max for n in lens):
             # exact batching of different lengths: per-row geometry through the whole path
             B = sum(r.shape[0] for r in rows)
@@ -802,6 +815,132 @@ class Universe:
             r0 += r.shape[0]
             res.append(o[0] if nd == 1 else o)
         return res
+
+    # ---- ensembles inside the library (ou_enhance_ensemble) ---------------------------------------------------------------
+    def _ensemble_call(self, mix, E, stat, n_steps, epsilon, keep_rms, warm_start, noise_t, t_raw, counter, return_members):
+        """mix: (B, 1, L) prepared; noise_t: (n, E * B, 1, T) or None (counter: (seed, E * B member-major stream ids)).
+        -> (out (B, 1, L), members (E, B, 1, L) or None)."""
+        if stat not in _lib.ENSEMBLE_STATS:
+            raise NotImplementedError()  # universe.py:368
+        B, _, mix_len = mix.shape
+        T = mix_len + (self.tot_ds - mix_len % self.tot_ds)
+        EB = E * B
+        skey = (int(n_steps), float(self.diff_kwargs.sigma_min), float(self.diff_kwargs.sigma_max))
+        sigma = self._sigma_cache.get(skey)
+        if sigma is None:
+            time = torch.linspace(0, 1, n_steps).to(torch.float32).flip(dims=[0])
+            sigma = self.get_std_dev(time).to(torch.float32).contiguous()
+            if len(self._sigma_cache) > 64:
+                self._sigma_cache.clear()
+            self._sigma_cache[skey] = sigma
+        out = torch.empty(B, 1, mix_len, dtype=torch.float32, device=self.device)
+        members = torch.empty(E, B, 1, mix_len, dtype=torch.float32, device=self.device) if return_members else None
+        need = c_size_t()
+        _lib.check(self._L.ou_ensemble_workspace_bytes(self._handle, B, T, E, byref(need)), self._handle)
+        ws = self._workspace(EB, T, need=need.value)
+        flags = _lib.OU_ENH_KEEP_RMS if keep_rms else 0
+        source = self._counter_source(counter[0], counter[1], EB, T) if counter is not None else contextlib.nullcontext()
+        rows_len = None if t_raw is None else (c_int32 * B)(*[int(v) for v in t_raw])
+        with torch.cuda.device(self.device), source:
+            _lib.check(self._L.ou_enhance_ensemble(
+                self._handle, c_void_p(mix.data_ptr()), c_void_p(out.data_ptr()),
+                c_void_p(members.data_ptr()) if members is not None else None,
+                c_void_p(noise_t.data_ptr()) if noise_t is not None else None, B, mix_len, rows_len, E,
+                _lib.ENSEMBLE_STATS[stat], int(n_steps), float(epsilon),
+                ctypes.cast(sigma.data_ptr(), ctypes.POINTER(c_float)), -1 if warm_start is None else int(warm_start), flags,
+                c_void_p(ws.data_ptr()), c_size_t(ws.numel()), self._stream()), self._handle)
+        self._cond_key = None
+        self._status()
+        return out, members
+
+    @torch.no_grad()
+    def enhance_ensemble(self, mix, ensemble: int, ensemble_stat: str = "median", n_steps: Optional[int] = None,
+                         epsilon: Optional[float] = None, rng=None, keep_rms: bool = False,
+                         warm_start: Optional[int] = None, return_members: bool = False):
+        """`enhance(mix, ensemble=E, ensemble_stat=..)` inside the library (extension, ou_enhance_ensemble): the conditioner runs
+        once over the inputs instead of E times (option `ens_share`), the members are reduced on the device.  Input shapes and
+        return convention of `enhance`; `rng`: a generator -- the draws are the (E * B, 1, T) shapes and order of
+        `enhance(ensemble=E)`, so one seed gives both paths the same noise -- or a `CounterNoise` (member e of row b draws from
+        the row's id + (e << 48)).  keep_rms restores every member to the RMS of its own input (for one input: the reference's
+        result; the reference fails for more).  return_members=True: -> (result, members), members (E,) + the result's shape.
+        Members agree with those of `enhance(ensemble=E)` to fp32 round-off (the conditioner's B-row pass may select other
+        kernels); with `set_option("ens_share", 0)` bit for bit."""
+        self._sync_env()
+        self._poll_deferred_status()
+        E = int(ensemble)
+        if not 1 <= E <= _lib.OU_MAX_ENSEMBLE:
+            raise ValueError(f"enhance_ensemble: 1 <= ensemble <= {_lib.OU_MAX_ENSEMBLE}")
+        epsilon = self.diff_kwargs.epsilon if epsilon is None else epsilon
+        n_steps = self.diff_kwargs.n_steps if n_steps is None else int(n_steps)
+        x_ndim = mix.ndim
+        if x_ndim == 1:
+            mix = mix[None, None, :]
+        elif x_ndim == 2:
+            mix = mix[:, None, :]
+        elif x_ndim > 3:
+            raise ValueError("The input should have at most 3 dimensions")
+        if mix.shape[1] != 1:
+            raise ValueError("enhance expects single-channel signals: (T,), (B,T) or (B,1,T)")
+        mix = self._prep(mix)
+        B, _, mix_len = mix.shape
+        T = mix_len + (self.tot_ds - mix_len % self.tot_ds)
+        n_noise = n_steps - (0 if warm_start is None else int(warm_start))
+        counter, noise_t = None, None
+        if is_counter(rng):
+            counter = (rng.seed, rng.stream_ids(B, E))
+        elif n_noise > 0:  # (n_noise <= 0: the C ABI refuses the call)
+            noise_t = torch.empty((n_noise, E * B, 1, T), dtype=torch.float32, device=self.device)
+            for k in range(n_noise):
+                torch.randn((E * B, 1, T), generator=rng, out=noise_t[k])
+        out, members = self._ensemble_call(mix, E, ensemble_stat, n_steps, epsilon, keep_rms, warm_start, noise_t, None,
+                                           counter, return_members)
+        if x_ndim == 1:
+            out, members = out[0, 0], (members[:, 0, 0] if members is not None else None)
+        elif x_ndim == 2:
+            out, members = out[:, 0, :], (members[:, :, 0, :] if members is not None else None)
+        return (out, members) if return_members else out
+
+    def _enhance_many_ensemble(self, rows, dims, lens, rngs, counter, E, stat, pad_batch, n_steps, epsilon, use_aux_signal,
+                               keep_rms, warm_start, n_noise, return_members=False):
+        """enhance_many(ensemble=E): all entries in one ou_enhance_ensemble call with per-row lengths."""
+        if pad_batch:
+            raise ValueError("enhance_many: `ensemble` runs with exact batching only (pad_batch=True is refused)")
+        if use_aux_signal:
+            raise ValueError("enhance_many: `ensemble` with use_aux_signal is refused (without noise all members are equal)")
+        if not 1 <= E <= _lib.OU_MAX_ENSEMBLE:
+            raise ValueError(f"enhance_many: 1 <= ensemble <= {_lib.OU_MAX_ENSEMBLE}")
+        self._sync_env()
+        self._poll_deferred_status()
+        epsilon = self.diff_kwargs.epsilon if epsilon is None else epsilon
+        l_max = max(lens)
+        T = l_max + (self.tot_ds - l_max % self.tot_ds)
+        B = sum(r.shape[0] for r in rows)
+        noise_t = None
+        if counter is not None:
+            counter = (counter[0], [s + (e << ENSEMBLE_SHIFT) for e in range(E) for s in counter[1]])
+        else:
+            noise_t = torch.zeros((n_noise, E * B, 1, T), dtype=torch.float32, device=self.device)
+            r0 = 0
+            for i, (r, n) in enumerate(zip(rows, lens)):
+                g = rngs[i] if isinstance(rngs, (list, tuple)) else rngs
+                C, Ti = r.shape[0], n + (self.tot_ds - n % self.tot_ds)
+                for k in range(n_noise):  # the draws of enhance(entry, ensemble=E) alone: (E * C, 1, Ti), member-major
+                    d = torch.randn((E * C, 1, Ti), dtype=torch.float32, device=self.device, generator=g)
+                    noise_t[k].view(E, B, 1, T)[:, r0:r0 + C, :, :Ti] = d.view(E, C, 1, Ti)
+                r0 += C
+        t_raw = [n for r, n in zip(rows, lens) for _ in range(r.shape[0])]
+        mix = torch.cat([torch.nn.functional.pad(r, (0, l_max - r.shape[-1])) for r in rows], dim=0)[:, None, :].contiguous()
+        out, mem = self._ensemble_call(mix, E, stat, n_steps, epsilon, keep_rms, warm_start, noise_t, t_raw, counter,
+                                       return_members)
+        res, mems, r0 = [], [], 0
+        for r, nd, n in zip(rows, dims, lens):
+            o = out[r0:r0 + r.shape[0], 0, :n]
+            res.append(o[0] if nd == 1 else o)
+            if mem is not None:
+                mm = mem[:, r0:r0 + r.shape[0], 0, :n]
+                mems.append(mm[:, 0] if nd == 1 else mm)
+            r0 += r.shape[0]
+        return (res, mems) if return_members else res
 
     @staticmethod
     def _counter_plan(rngs, channels):
@@ -1041,6 +1180,35 @@ class Universe:
 
 class UniverseGAN(Universe):
     """UNIVERSE++ (universe_gan.py:60): same inference surface; aux_to_wav goes through the decoupling layer."""
+
+
+def ensemble_reduce(members, stat="median", lens=None, return_pick=False, out=None):
+    """The library's ensemble reduce on its own (ou_ensemble_reduce; extension): members (E, B, S) float32 on a HIP device,
+    member-major, unit stride along S and rows one common stride apart (a view into a wider (E * B, row_stride) buffer is
+    fine) -> (B, S) mean / median / signal median over the members; `lens`: valid samples per input (the rest of `out` is 0).
+    return_pick=True (signal_median): -> (out, picked member per input).  `out`: a (B, S) view with the members' row stride."""
+    E, B, S = members.shape
+    rs = members.stride(1)
+    if members.dtype != torch.float32 or not members.is_cuda or members.stride(2) != 1 or members.stride(0) != B * rs:
+        raise ValueError("ensemble_reduce: members must be a float32 device tensor (E, B, S) with rows one stride apart")
+    if stat not in _lib.ENSEMBLE_STATS:
+        raise NotImplementedError()
+    L = _lib.load()
+    if out is None:
+        out = torch.empty((B, rs), dtype=torch.float32, device=members.device)[:, :S]
+    if out.shape != (B, S) or out.stride(0) != rs or out.stride(1) != 1:
+        raise ValueError("ensemble_reduce: out must be a (B, S) view with the members' row stride")
+    nb = L.ou_ensemble_reduce_scratch_bytes(E, B)
+    scratch = torch.empty(nb, dtype=torch.uint8, device=members.device)
+    len_arr = None if lens is None else (ctypes.c_int64 * B)(*[int(v) for v in lens])
+    with torch.cuda.device(members.device):
+        _lib.check(L.ou_ensemble_reduce(c_void_p(members.data_ptr()), c_void_p(out.data_ptr()), E, B, rs, S, len_arr,
+                                        _lib.ENSEMBLE_STATS[stat], c_void_p(scratch.data_ptr()), c_size_t(nb),
+                                        c_void_p(torch.cuda.current_stream(members.device).cuda_stream)))
+    if return_pick:
+        pick = scratch[B * E * 4:(B * E + B) * 4].view(torch.int32).to(torch.int64) if stat == "signal_median" else None
+        return out, pick
+    return out
 
 
 def signal_median(signal):
