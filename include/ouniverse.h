@@ -319,6 +319,47 @@ int ou_noise_scratch_bytes(const ou_handle* h, int32_t B, int32_t T_pad, size_t*
 int ou_noise_fill(float* out, int64_t row_stride, int64_t cols, int32_t rows, const uint64_t* streams_host,
                   const int64_t* t0_host, const int64_t* len_host, uint64_t seed, int32_t draw, ou_stream_t stream);
 
+/* ---- resampling (the two steps around enhance in the reference's CLI: torchaudio.functional.resample to the model rate and
+ * back, bin/enhance.py:77-80,186-190, with its defaults sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99) ------------
+ * Stateless: no handle.  The definition (torchaudio's documented algorithm restated; open_universe_amd/audio.py restates the
+ * same one as a dense conv1d).  With g = gcd(fs_in, fs_out):
+ *     orig = fs_in / g    new = fs_out / g    base = min(orig, new) * 0.99    width = ceil(6 * orig / base)
+ * and for a row x[0 .. n) (zero outside), output j = f * new + p (0 <= p < new) for 0 <= j < ceil(new * n / orig):
+ *     y[j] = sum_i k[p][i] * x[f * orig - width + i]                 0 <= i < 2 * width + orig
+ *     k[p][i] = sinc(pi t) cos^2(pi t / 12) base / orig,   t = clamp((-p / new + (i - width) / orig) * base, -6, 6)
+ * k is evaluated in double and rounded once to fp32.  The SUPPORT of phase p is the run of i whose unclamped t lies strictly
+ * inside (-6, 6); outside it k holds cos^2(pi / 2)-sized values (< 1e-30), which this path treats as zero.  So an output costs
+ * `taps` (the longest support) multiply-adds instead of 2 * width + orig: 34 of 475 at 44 100 -> 16 000, 13 of 174 back.
+ *
+ * Coefficient table (host functions; the caller uploads it once per rate pair and owns the device copy):
+ *     int32 first[new]        first input of phase p relative to f * orig (= first i of its support - width)
+ *     float coef[taps][new]   coef[t][p] = k[p][first[p] + width + t], 0 behind the phase's own support
+ * i.e. table_bytes = (taps + 1) * new * 4.  The values are computed in double, in the operation order of the definition, and
+ * rounded once: they ARE the dense kernel's entries.  OU_EINVAL: non-positive rates, a table_bytes that is not the plan's, or
+ * a reduced ratio so extreme that the table would not fit 32-bit indices (width > 2^28 or more than 2^29 words). */
+int ou_resample_plan(int32_t fs_in, int32_t fs_out, int32_t* orig, int32_t* new_, int32_t* width, int32_t* taps,
+                     size_t* table_bytes);
+int ou_resample_table(int32_t fs_in, int32_t fs_out, void* table, size_t table_bytes);
+/* ceil(new * n / orig): the outputs of a row of n samples (n itself for equal rates); -1 for a bad argument */
+int64_t ou_resample_length(int32_t fs_in, int32_t fs_out, int64_t n);
+/* Consecutive outputs of one row that one workgroup of ou_resample owns for this rate pair (tests choose lengths around it;
+ * results do not depend on it: every output is one sum in ascending tap order).  -1 for a bad rate pair. */
+int32_t ou_resample_tile(int32_t fs_in, int32_t fs_out);
+/* Resample `rows` rows of lengths of their own, one launch per 64 rows:
+ *   x        : (rows, x_stride) device; row b holds len[b] samples, nothing is read behind them
+ *   len_host : `rows` entries on the HOST, 0 <= len[b] <= x_stride
+ *   y        : (rows, y_stride) device; row b receives its ou_resample_length(fs_in, fs_out, len[b]) outputs, the columns from
+ *              there up to `cols` are zeroed, nothing behind `cols` is touched (cols <= y_stride)
+ *   table    : DEVICE copy of ou_resample_table's output, table_bytes = the plan's (anything else: OU_EINVAL).  A small table
+ *              is kept in LDS, a large one (813 KB of coefficients at 16 000 -> 16 001) is read through the caches.
+ * fs_in == fs_out: a plain copy with the same zeroing; the table is not read and may be NULL.
+ * OU_EINVAL, nothing launched: non-positive rates, rows < 1, an output row that does not fit cols or y_stride, lengths or
+ * strides whose products overflow the kernel's 64-bit offsets (rows * stride, new * len[b] <= 2^60).  All of that is decided
+ * on the host before the first HIP call.  Enqueued on `stream`: no allocation, no host synchronisation, capturable.  The
+ * accumulation is fp32 FMA in ascending tap order whatever the tiling, so a row's result does not depend on the batch it is in. */
+int ou_resample(const float* x, int64_t x_stride, const int64_t* len_host, float* y, int64_t y_stride, int64_t cols,
+                int32_t rows, int32_t fs_in, int32_t fs_out, const void* table, size_t table_bytes, ou_stream_t stream);
+
 /* One sampler update on caller-owned buffers, for bindings that keep the reference's Python loop
  * (universe.py:339 `x = x + s_now^2 * eta * score + beta * z`, :343 `x = x + s_last^2 * score`):
  *   x[i] += c1 * score[i] + c2 * z[i]     over n = B*T elements; z may be NULL (last step).

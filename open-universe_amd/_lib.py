@@ -126,6 +126,11 @@ def load():
         "ou_noise_scratch_bytes": (i32, [vp, i32, i32, POINTER(sz)]),
         "ou_noise_fill": (i32, [vp, c_int64, c_int64, i32, POINTER(c_uint64), POINTER(c_int64), POINTER(c_int64), c_uint64,
                                 i32, vp]),
+        "ou_resample_plan": (i32, [i32, i32, POINTER(i32), POINTER(i32), POINTER(i32), POINTER(i32), POINTER(sz)]),
+        "ou_resample_table": (i32, [i32, i32, vp, sz]),
+        "ou_resample_length": (c_int64, [i32, i32, c_int64]),
+        "ou_resample_tile": (i32, [i32, i32]),
+        "ou_resample": (i32, [vp, c_int64, POINTER(c_int64), vp, c_int64, c_int64, i32, i32, i32, vp, sz, vp]),
         "ou_check_device_status": (i32, [vp, vp]),
         "ou_set_option": (i32, [vp, c_char_p, c_double]),
         "ou_get_option": (i32, [vp, c_char_p, POINTER(c_double)]),
@@ -172,6 +177,7 @@ EXPORTED_SYMBOLS = [
     "ou_segment_plan", "ou_segments_workspace_bytes", "ou_enhance_segments",
     "ou_ensemble_workspace_bytes", "ou_enhance_ensemble", "ou_ensemble_reduce_scratch_bytes", "ou_ensemble_reduce",
     "ou_set_noise_source", "ou_noise_scratch_bytes", "ou_noise_fill",
+    "ou_resample_plan", "ou_resample_table", "ou_resample_length", "ou_resample_tile", "ou_resample",
     "ou_set_option", "ou_get_option", "ou_reset_options", "ou_option_count", "ou_option_name", "ou_option_doc", "ou_option_default", "ou_plan_json",
     "ou_packer_plan_json", "ou_tensor", "ou_launch_stats", "ou_workspace_init", "ou_sampler_step",
     "ou_set_gru_publish_mode", "ou_get_gru_publish_mode", "ou_set_lanes", "ou_set_lane_batch", "ou_lane_capacity",
@@ -251,6 +257,26 @@ def segment_weights(plan, k):
         m = u >= w1
         w[m] = np.float32(1.0) - ramp(u[m] - w1)
     return w
+
+
+def resample_plan(fs_in, fs_out):
+    """ou_resample_plan: dict of the ints `orig`, `new`, `width`, `taps`, `table_bytes` of a rate pair.  Pure host code."""
+    L = load()
+    o, n, w, t, nb = c_int32(), c_int32(), c_int32(), c_int32(), c_size_t()
+    check(L.ou_resample_plan(int(fs_in), int(fs_out), byref(o), byref(n), byref(w), byref(t), byref(nb)))
+    return {"orig": o.value, "new": n.value, "width": w.value, "taps": t.value, "table_bytes": nb.value}
+
+
+def resample_table(fs_in, fs_out):
+    """ou_resample_table as numpy arrays: (first (new,) int32, coef (taps, new) float32, the raw table as uint8).  Pure host code."""
+    import numpy as np
+
+    L = load()
+    plan = resample_plan(fs_in, fs_out)
+    raw = np.zeros(plan["table_bytes"], dtype=np.uint8)
+    check(L.ou_resample_table(int(fs_in), int(fs_out), raw.ctypes.data_as(c_void_p), c_size_t(raw.nbytes)))
+    n = plan["new"]
+    return raw[:4 * n].view(np.int32), raw[4 * n:].view(np.float32).reshape(plan["taps"], n), raw
 
 
 def make_config(spec, fir_fold=0, split_copy=True):

@@ -225,10 +225,11 @@ def _sinc_kernel(orig, new, device, lowpass_filter_width=6, rolloff=0.99):
     return _kernel_cache[key]
 
 
-def resample(audio, fs, target_fs):
-    """torchaudio.functional.resample(audio, fs, target_fs) with its default arguments (bin/enhance.py:77-80):
-    polyphase windowed-sinc FIR, evaluated as one strided conv1d on the tensor's device."""
-    fs, target_fs = int(fs), int(target_fs)
+_RESAMPLE_BACKENDS = ("torch", "library")
+_table_cache = {}
+
+
+def _resample_torch(audio, fs, target_fs):
     if fs == target_fs:
         return audio
     g = math.gcd(fs, target_fs)
@@ -242,6 +243,104 @@ def resample(audio, fs, target_fs):
     y = y.transpose(1, 2).reshape(n, -1)
     target_length = int(math.ceil(new * length / orig))
     return y[..., :target_length].reshape(shape[:-1] + (target_length,))
+
+
+def _device_table(L, fs, target_fs, device):
+    """The coefficient table of ou_resample on `device` (uploaded once per reduced rate pair and device) and its byte size."""
+    from . import _lib
+
+    g = math.gcd(fs, target_fs)
+    key = (fs // g, target_fs // g, str(device))
+    if key not in _table_cache:
+        raw = _lib.resample_table(fs, target_fs)[2]
+        _table_cache[key] = torch.from_numpy(raw).to(device)
+    return _table_cache[key]
+
+
+def _resample_rows(x, lens, fs, target_fs):
+    """ONE ou_resample call: x (rows, stride) float32 on a HIP device, row b holding lens[b] samples -> ((rows, cols) tensor,
+    output lengths); the columns behind a row's own output are zero."""
+    from . import _lib
+
+    L = _lib.load()
+    rows = x.shape[0]
+    out_lens = [int(L.ou_resample_length(fs, target_fs, int(n))) for n in lens]
+    cols = max(out_lens)
+    y = torch.empty((rows, cols), dtype=torch.float32, device=x.device)
+    if cols == 0:
+        return y, out_lens
+    if fs == target_fs:
+        tab_ptr, tab_bytes = None, 0
+    else:
+        tab = _device_table(L, fs, target_fs, x.device)
+        tab_ptr, tab_bytes = ctypes.c_void_p(tab.data_ptr()), tab.numel()
+    with torch.cuda.device(x.device):
+        _lib.check(L.ou_resample(ctypes.c_void_p(x.data_ptr()), x.stride(0), (ctypes.c_int64 * rows)(*[int(n) for n in lens]),
+                                 ctypes.c_void_p(y.data_ptr()), y.stride(0), cols, rows, fs, target_fs, tab_ptr,
+                                 ctypes.c_size_t(tab_bytes),
+                                 ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
+    return y, out_lens
+
+
+def _check_backend(backend):
+    if backend not in _RESAMPLE_BACKENDS:
+        raise ValueError(f"resample: backend must be one of {_RESAMPLE_BACKENDS}, not {backend!r}")
+
+
+def resample(audio, fs, target_fs, backend="torch"):
+    """torchaudio.functional.resample(audio, fs, target_fs) with its default arguments (bin/enhance.py:77-80):
+    polyphase windowed-sinc FIR.  backend "torch" (default): one strided conv1d over the dense kernel on the tensor's device.
+    backend "library" (extension): the library's own kernel (ou_resample), which evaluates only the taps inside the window's
+    support; the tensor must live on a HIP device (ValueError otherwise: there is no CPU path and no fallback)."""
+    _check_backend(backend)
+    fs, target_fs = int(fs), int(target_fs)
+    if backend == "torch":
+        return _resample_torch(audio, fs, target_fs)
+    if audio.device.type != "cuda":
+        raise ValueError("resample(backend='library') runs on a HIP device only: move the tensor there or use backend='torch'")
+    if fs == target_fs:
+        return audio
+    shape = audio.shape
+    x = audio.reshape(-1, shape[-1]).to(torch.float32).contiguous()
+    y, out_lens = _resample_rows(x, [shape[-1]] * x.shape[0], fs, target_fs)
+    return y.reshape(shape[:-1] + (out_lens[0] if out_lens else 0,))
+
+
+def resample_many(signals, fs, target_fs, backend="torch"):
+    """`resample` of a list of (T_i,) or (C_i, T_i) tensors of one rate -> list of the same shapes at the new rate.
+    backend "library": ONE ou_resample call over all channel rows of all signals (gathered into one padded buffer on the
+    device; the lengths travel as a host array), every row bit-identical to `resample(row, backend="library")`.
+    backend "torch": the loop over `resample`."""
+    _check_backend(backend)
+    fs, target_fs = int(fs), int(target_fs)
+    signals = list(signals)
+    if backend == "torch":
+        return [_resample_torch(s, fs, target_fs) for s in signals]
+    if not signals:
+        return []
+    for s in signals:
+        if s.device.type != "cuda":
+            raise ValueError("resample_many(backend='library') runs on a HIP device only")
+        if s.ndim not in (1, 2):
+            raise ValueError("resample_many: signals are (T,) or (C, T) tensors")
+    if fs == target_fs:
+        return signals
+    device = signals[0].device
+    counts = [1 if s.ndim == 1 else s.shape[0] for s in signals]
+    lens = [int(s.shape[-1]) for s, c in zip(signals, counts) for _ in range(c)]
+    stride = (max(lens) + 3) // 4 * 4  # 16-byte aligned rows: the kernel then stages with 16-byte loads
+    x = torch.empty((sum(counts), max(stride, 4)), dtype=torch.float32, device=device)
+    r = 0
+    for s, c in zip(signals, counts):
+        x[r:r + c, :s.shape[-1]] = s.to(device=device, dtype=torch.float32).reshape(c, -1)
+        r += c
+    y, out_lens = _resample_rows(x, lens, fs, target_fs)
+    out, r = [], 0
+    for s, c in zip(signals, counts):
+        o = y[r:r + c, :out_lens[r] if c else 0].clone()
+        out.append(o[0] if s.ndim == 1 else o)
+        r += c
+    return out
 
 
 # ---- FLAC encoder (the output side of a .flac input: the reference writes the enhanced file under the input's name with

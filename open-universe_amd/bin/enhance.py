@@ -33,7 +33,7 @@ from pathlib import Path
 import torch
 
 from .. import inference_utils
-from ..audio import AUDIO_SUFFIXES, can_decode, channels, load, resample, save
+from ..audio import AUDIO_SUFFIXES, can_decode, channels, load, resample, resample_many, save
 
 
 def handle_help(argv):
@@ -89,6 +89,11 @@ def build_parser():
                              "list, channel, step, sample) evaluated on the device (an extension; the reference has no such "
                              "mode): a file's result then does not depend on batching, lanes, segmenting or sharding, and no "
                              "noise tensor is held in memory")
+    parser.add_argument("--resampler", choices=("torch", "library"), default="torch",
+                        help="What resamples a file to the model rate and back.  torch (default): a strided conv1d over the "
+                             "dense windowed-sinc kernel.  library: the library's own kernel (ou_resample; an extension), the "
+                             "same filter evaluated over the window's support only -- with --batch-size one launch per "
+                             "window of files and per enhanced group instead of one chain of torch calls per file")
     parser.add_argument("--batch-size", type=int, default=1,
                         help="Enhance up to this many consecutive files of equal sample rate (any lengths) in one call; "
                              "every file gets the result it would get alone")
@@ -290,8 +295,9 @@ def main(argv=None, model=None):
 
                 def work(m, audio=audio, fs=fs, file_rng=file_rng):
                     with torch.no_grad():
-                        x = resample(audio, fs, m.fs)
-                        return resample(m.enhance(x, **dict(enhance_kwargs, rng=file_rng)), m.fs, fs)
+                        x = resample(audio, fs, m.fs, backend=args.resampler)
+                        return resample(m.enhance(x, **dict(enhance_kwargs, rng=file_rng)), m.fs, fs,
+                                        backend=args.resampler)
 
                 lane, enh = pool.submit(work, audio)
                 pending.append((lane, output_path, enh, fs))
@@ -306,9 +312,9 @@ def main(argv=None, model=None):
             if per_file_seed:
                 rng.manual_seed(args.seed + k)
             with torch.no_grad():
-                audio = resample(audio, fs, model.fs)
+                audio = resample(audio, fs, model.fs, backend=args.resampler)
                 enh = enhance_file(model, audio, args, enhance_kwargs, file_noise(args, k) if counter else rng)
-                enh = resample(enh, model.fs, fs)
+                enh = resample(enh, model.fs, fs, backend=args.resampler)
             save(output_path, enh.cpu(), fs)
             done.append(output_path)
         return done
@@ -338,8 +344,9 @@ def main(argv=None, model=None):
         fs = window[0][3]
         with torch.no_grad():
             items = []
-            for k, path, a, _ in window:
-                sig = resample(a.to(device), fs, model.fs)
+            # (library resampler: the whole window in one launch; torch: file by file, as before)
+            sigs = resample_many([a.to(device) for _, _, a, _ in window], fs, model.fs, backend=args.resampler)
+            for (k, path, _, _), sig in zip(window, sigs):
                 if counter:
                     g = file_noise(args, k)
                 elif per_file_seed:
@@ -362,8 +369,9 @@ def main(argv=None, model=None):
                 grp = [items[i] for i in order[b0:b0 + args.batch_size]]
                 rngs = [g for _, _, _, g in grp] if can_sort else rng
                 enhs = model.enhance_many([sig for _, _, sig, _ in grp], rngs, pad_batch=args.pad_batch, **kw)
-                for (k, _, _, _), e in zip(grp, enhs):
-                    results[k] = resample(e, model.fs, fs)
+                outs = resample_many(list(enhs), model.fs, fs, backend=args.resampler)
+                for (k, _, _, _), e in zip(grp, outs):
+                    results[k] = e
         for k, path, _, _ in window:  # written in processing order
             output_path = out_path(path)
             save(output_path, results[k].cpu(), fs)

@@ -237,6 +237,21 @@ constexpr int kReplicateEntries = 16;
 struct ReplicateTable { unsigned* p[kReplicateEntries]; long long n[kReplicateEntries]; };
 hipError_t launch_replicate_rows(const ReplicateTable& tab, int n_entries, int E, hipStream_t st);
 
+// Polyphase windowed-sinc resampler over ragged rows (ou_resample.hip; ou_resample in include/ouniverse.h).
+//   y[b][j] = sum_t coef[t][p] * x[b][f * orig + first[p] + t]   (j = f * nw + p, x zero outside [0, len[b]), t ascending, fp32 FMA)
+// for j < ylen[b]; 0 for ylen[b] <= j < cols.  table (device): int first[nw], then float coef[taps][nw].  orig == nw == 1 and
+// table == null: plain copy with the same zeroing.  Per-row values travel as kernel arguments, 64 rows per launch.
+constexpr int kResampleRowsPerLaunch = 64;
+struct ResampleRows {
+  long long len[kResampleRowsPerLaunch];
+  long long ylen[kResampleRowsPerLaunch];
+};
+// consecutive outputs of one row that a workgroup owns for this rate pair (a pure host function: tests pick lengths from it)
+int resample_tile(int orig, int nw, int taps);
+hipError_t launch_resample(const float* x, long long x_stride, float* y, long long y_stride, long long cols,
+                           const ResampleRows& rows, int n_rows, int orig, int nw, int taps, const void* table,
+                           hipStream_t st);
+
 // space-to-depth + PReLU for the conditioner's strided "st" convs: y[b][ci*R + k][q] = prelu(x[b][ci][q*R + k])
 hipError_t launch_s2d(const float* x, const float* alpha, float* y, int B, int C, int T, int R, hipStream_t st);
 // (`lens` of launch_in_conv / launch_out_conv / launch_fir: per-row valid lengths of a ragged batch or null, see ConvArgs::lens)
