@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define OU_ABI_VERSION 7 /* 7: ensembles in the library (ou_enhance_ensemble, ou_ensemble_workspace_bytes, ou_ensemble_reduce, ou_ensemble_reduce_scratch_bytes; option ens_share); existing entry points unchanged; 6: counter-based sampler noise (ou_set_noise_source, ou_noise_scratch_bytes, ou_noise_fill); existing entry points unchanged; 5: ou_enhance_var (batches whose rows have lengths of their own), workspace header carries the per-row geometry; ou_set_option / ou_get_option replace every OU_* environment switch (the library reads no environment variable), ou_config.fir_fold; 4: the packed blob carries a bf16-split weight copy (conv_split_kernel); 3: a Winograd-domain copy (round 5), ou_set_lane_batch, ou_lane_capacity */
+#define OU_ABI_VERSION 7 /* 7: segmented enhance of rows with lengths of their own (ou_segment_groups, ou_segments_var_workspace_bytes, ou_enhance_segments_var: additive, the number stays); ensembles in the library (ou_enhance_ensemble, ou_ensemble_workspace_bytes, ou_ensemble_reduce, ou_ensemble_reduce_scratch_bytes; option ens_share); existing entry points unchanged; 6: counter-based sampler noise (ou_set_noise_source, ou_noise_scratch_bytes, ou_noise_fill); existing entry points unchanged; 5: ou_enhance_var (batches whose rows have lengths of their own), workspace header carries the per-row geometry; ou_set_option / ou_get_option replace every OU_* environment switch (the library reads no environment variable), ou_config.fir_fold; 4: the packed blob carries a bf16-split weight copy (conv_split_kernel); 3: a Winograd-domain copy (round 5), ou_set_lane_batch, ou_lane_capacity */
 
 enum {
   OU_OK = 0,
@@ -268,6 +268,49 @@ int ou_enhance_segments(ou_handle* h, const float* mix, float* out, const float*
                         int32_t segment, int32_t overlap, int32_t max_batch, int32_t n_steps, double epsilon,
                         const float* sigma_host, int32_t warm_start, uint32_t flags, void* ws, size_t ws_bytes,
                         ou_stream_t stream);
+
+/* ---- segmented enhance of rows with lengths of their own (extension): ou_enhance_segments for a batch in which every row has
+ * its own length, as ou_enhance_var is to ou_enhance.  Row c is, by definition, ou_enhance_segments(C = 1, T_raw = t_raw[c]) on
+ * its own noise: its own pad split, whole-row mean / gain / mix_rms (bit-identical: the row's reductions use the block partition
+ * of the call on that row alone), its own mel scale, crossfades only between its own consecutive windows, keep_rms and the peak
+ * guard over its own samples.  What changes is the grouping: the windows of ALL rows share the window groups.
+ *
+ * Groups (pure host function).  Row c's windows are those of ou_segment_plan(tot_ds, t_raw[c], segment, overlap).  With S =
+ * segment rounded down to a multiple of tot_ds:
+ *   class FULL : every window (length S) of the rows with T_pad_c > S, in row-major order;
+ *   class SHORT: the single window (length T_pad_c <= S) of every other row, in input order.
+ * The entry list is FULL, then SHORT.  A group is up to `batch` consecutive entries of ONE class; batch = the larger of the two
+ * classes' even spread, ceil(n / ceil(n / max_batch)) for a class of n entries, so batch <= max_batch and a class of n entries
+ * makes ceil(n / batch) groups.  The walk always runs `batch` rows: a last partial group is filled by repeating its last real
+ * entry (as ou_enhance_segments does).  A group is `ragged` when its entries differ in length -- SHORT groups only; it runs
+ * through the ragged walk of ou_enhance_var at the length of its longest entry (entries are already padded windows: they are
+ * zero from their own length on, on every level), every other group through the plain walk at its entries' length.  length =
+ * the longest entry = min(S, max T_pad_c).  When all rows have one length, batch, length and the entry order are those of
+ * ou_enhance_segments for (C, T_raw).
+ * entry_row / entry_window / entry_length: `capacity` >= n_entries values; group_first / group_ragged: one per group (group g
+ * holds the entries from group_first[g] up to group_first[g] + batch, the next group's first entry or the end of its class,
+ * whichever comes first; `capacity` covers them too, n_groups <= n_entries).  All five may be NULL: only the counts are returned. */
+int ou_segment_groups(int32_t tot_ds, int32_t C, const int64_t* t_raw, int32_t segment, int32_t overlap, int32_t max_batch,
+                      int32_t capacity, int32_t* entry_row, int32_t* entry_window, int32_t* entry_length, int32_t* group_first,
+                      int32_t* group_ragged, int32_t* n_entries, int32_t* n_groups, int32_t* batch, int32_t* length);
+/* Workspace of ou_enhance_segments_var: the walk's workspace for (batch, length) plus the segment area -- the C rows'
+ * statistics, scales and partials (24 KiB per row), a per-row geometry table, one step of gathered noise (batch x length floats)
+ * and one carried window.  It depends on C, max_batch and segment, and on the lengths only through `length` (and through
+ * `batch` where fewer than max_batch entries exist).  Prepare the buffer with ou_workspace_init(h, batch, length, ..). */
+int ou_segments_var_workspace_bytes(const ou_handle* h, int32_t C, const int64_t* t_raw, int32_t segment, int32_t overlap,
+                                    int32_t max_batch, size_t* nbytes, int32_t* batch, int32_t* length);
+/*   mix, out : (C, T_raw_max) device; row c holds t_raw[c] samples, the rest of a mix row is ignored and the rest of an out row
+ *              is zeroed (the ou_enhance_var convention; out also serves as scratch for the mel frame energies)
+ *   t_raw    : HOST, C lengths, 1 <= t_raw[c] <= T_raw_max = the longest (OU_EINVAL otherwise, before anything is launched)
+ *   noise    : (n_steps, C, T_pad_max) device; row c uses its first T_pad_c columns (what the call on row c alone would draw).
+ *              With a noise source: NULL, n_streams == C, window k of row c draws at t = s_k + i from the stream of row c.
+ *   flags, warm_start: as ou_enhance_segments.
+ * Everything is enqueued on `stream`: no allocation, no host synchronisation, no side streams; the per-row geometry and every
+ * group's entries reach the device as kernel arguments (capturable). */
+int ou_enhance_segments_var(ou_handle* h, const float* mix, float* out, const float* noise, int32_t C, int64_t T_raw_max,
+                            const int64_t* t_raw, int32_t segment, int32_t overlap, int32_t max_batch, int32_t n_steps,
+                            double epsilon, const float* sigma_host, int32_t warm_start, uint32_t flags, void* ws,
+                            size_t ws_bytes, ou_stream_t stream);
 
 /* ---- counter-based sampler noise (extension; the reference draws its noise with torch.randn on the model's device) --------
  * By default every enhance entry point reads its noise from a tensor the caller has drawn.  With a noise SOURCE set on the

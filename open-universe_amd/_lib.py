@@ -122,6 +122,12 @@ def load():
         "ou_segments_workspace_bytes": (i32, [vp, i32, c_int64, i32, i32, i32, POINTER(sz), POINTER(i32), POINTER(i32)]),
         "ou_enhance_segments": (i32, [vp, vp, vp, vp, i32, c_int64, i32, i32, i32, i32, c_double, POINTER(c_float), i32,
                                       c_uint32, vp, sz, vp]),
+        "ou_segment_groups": (i32, [i32, i32, POINTER(c_int64), i32, i32, i32, i32, POINTER(i32), POINTER(i32), POINTER(i32),
+                                    POINTER(i32), POINTER(i32), POINTER(i32), POINTER(i32), POINTER(i32), POINTER(i32)]),
+        "ou_segments_var_workspace_bytes": (i32, [vp, i32, POINTER(c_int64), i32, i32, i32, POINTER(sz), POINTER(i32),
+                                                  POINTER(i32)]),
+        "ou_enhance_segments_var": (i32, [vp, vp, vp, vp, i32, c_int64, POINTER(c_int64), i32, i32, i32, i32, c_double,
+                                          POINTER(c_float), i32, c_uint32, vp, sz, vp]),
         "ou_set_noise_source": (i32, [vp, POINTER(NoiseSpec)]),
         "ou_noise_scratch_bytes": (i32, [vp, i32, i32, POINTER(sz)]),
         "ou_noise_fill": (i32, [vp, c_int64, c_int64, i32, POINTER(c_uint64), POINTER(c_int64), POINTER(c_int64), c_uint64,
@@ -175,6 +181,7 @@ EXPORTED_SYMBOLS = [
     "ou_packer_destroy", "ou_packed_bytes", "ou_create", "ou_destroy", "ou_workspace_bytes", "ou_schedule",
     "ou_condition", "ou_score", "ou_aux_to_wav", "ou_enhance", "ou_enhance_var", "ou_check_device_status",
     "ou_segment_plan", "ou_segments_workspace_bytes", "ou_enhance_segments",
+    "ou_segment_groups", "ou_segments_var_workspace_bytes", "ou_enhance_segments_var",
     "ou_ensemble_workspace_bytes", "ou_enhance_ensemble", "ou_ensemble_reduce_scratch_bytes", "ou_ensemble_reduce",
     "ou_set_noise_source", "ou_noise_scratch_bytes", "ou_noise_fill",
     "ou_resample_plan", "ou_resample_table", "ou_resample_length", "ou_resample_tile", "ou_resample",
@@ -232,6 +239,27 @@ def segment_plan(tot_ds, T_raw, segment, overlap):
     return {"starts": np.ctypeslib.as_array(starts).copy(), "lengths": np.ctypeslib.as_array(lens).copy(),
             "core_begin": np.ctypeslib.as_array(ce0).copy(), "core_end": np.ctypeslib.as_array(ce1).copy(),
             "overlap": ov.value, "T_pad": tp.value}
+
+
+def segment_groups(tot_ds, t_raw, segment, overlap, max_batch):
+    """The library's window groups for rows of lengths `t_raw` (ou_segment_groups): dict of numpy arrays `row`, `window`,
+    `length` (one entry per window: class FULL row-major, then class SHORT), `group_first`, `group_ragged` (one per group) and the
+    ints `batch` and `length_max`.  Pure host code."""
+    import numpy as np
+
+    L = load()
+    C = len(t_raw)
+    tr = (c_int64 * max(C, 1))(*[int(v) for v in t_raw])
+    ne, ng, b, ln = c_int32(), c_int32(), c_int32(), c_int32()
+    args = (int(tot_ds), C, tr, int(segment), int(overlap), int(max_batch))
+    check(L.ou_segment_groups(*args, 0, None, None, None, None, None, byref(ne), byref(ng), byref(b), byref(ln)))
+    n = ne.value
+    row, win, length, first, ragged = ((c_int32 * n)() for _ in range(5))
+    check(L.ou_segment_groups(*args, n, row, win, length, first, ragged, byref(ne), byref(ng), byref(b), byref(ln)))
+    as_np = lambda a, k: np.ctypeslib.as_array(a)[:k].copy()  # noqa: E731
+    return {"row": as_np(row, n), "window": as_np(win, n), "length": as_np(length, n),
+            "group_first": as_np(first, ng.value), "group_ragged": as_np(ragged, ng.value),
+            "batch": b.value, "length_max": ln.value}
 
 
 def segment_weights(plan, k):

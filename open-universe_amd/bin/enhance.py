@@ -111,6 +111,11 @@ def build_parser():
                              "noise and output level stay those of the whole file).  Off by default")
     parser.add_argument("--segment-overlap", type=float, default=None,
                         help="With --segment-seconds: overlap of consecutive windows in seconds (default 1.0)")
+    parser.add_argument("--segment-files", type=int, default=1,
+                        help="With --segment-seconds: enhance this many consecutive files of the sorted list in one call "
+                             "(Universe.enhance_long_many: files of any lengths, long ones in windows, short ones as one "
+                             "window each, the windows of all files share the window groups; every file gets the result "
+                             "it would get alone).  Default 1: one file per call")
     parser.add_argument("--pad-batch", action="store_true",
                         help="With --batch-size: files of different lengths are zero-padded to the longest WITHOUT a mask "
                              "(the reference's batch semantics: the padding changes every result)")
@@ -141,7 +146,11 @@ def check_segment_args(args, enhance_kwargs):
     if args.segment_seconds is None:
         if args.segment_overlap is not None:
             raise ValueError("--segment-overlap needs --segment-seconds")
+        if getattr(args, "segment_files", 1) != 1:
+            raise ValueError("--segment-files needs --segment-seconds")
         return
+    if getattr(args, "segment_files", 1) < 1:
+        raise ValueError("--segment-files must be at least 1")
     if not args.segment_seconds > 0:
         raise ValueError("--segment-seconds must be positive")
     ov = 1.0 if args.segment_overlap is None else args.segment_overlap
@@ -150,7 +159,8 @@ def check_segment_args(args, enhance_kwargs):
     if args.pad_batch:
         raise ValueError("--segment-seconds cannot be combined with --pad-batch")
     if args.batch_size > 1 or args.in_flight > 1:
-        raise ValueError("--segment-seconds runs one file per call: it cannot be combined with --batch-size or --in-flight")
+        raise ValueError("--segment-seconds cannot be combined with --batch-size or --in-flight (--segment-files N puts N "
+                         "files into one segmented call)")
     for key in ("ensemble", "target", "warm_start"):
         if enhance_kwargs.get(key) is not None:
             raise ValueError(f"--segment-seconds cannot be combined with --{key}")
@@ -303,6 +313,32 @@ def main(argv=None, model=None):
                 pending.append((lane, output_path, enh, fs))
             for item in pending:
                 finish(item)
+        return done
+    if args.segment_seconds is not None and args.segment_files > 1:
+        # --segment-files N: N consecutive files per enhance_long_many call.  Every file gets the generator or counter source
+        # the serial loop below would hand it (the shared generator advances file by file inside the call, in input order).
+        ov = 1.0 if args.segment_overlap is None else args.segment_overlap
+        kw = {key: v for key, v in enhance_kwargs.items() if key in ("n_steps", "epsilon", "keep_rms")}
+        for g0 in range(0, len(todo), args.segment_files):
+            grp = todo[g0:g0 + args.segment_files]
+            with torch.no_grad():
+                sigs, rates, rngs = [], [], []
+                for k, path in grp:
+                    audio, fs = load(path)
+                    sigs.append(resample(audio.to(device), fs, model.fs, backend=args.resampler))
+                    rates.append(fs)
+                    if counter:
+                        rngs.append(file_noise(args, k))
+                    elif per_file_seed:
+                        file_rng = torch.Generator(device=device)
+                        file_rng.manual_seed(args.seed + k)
+                        rngs.append(file_rng)
+                enhs = model.enhance_long_many(sigs, rngs if rngs else rng, segment_s=args.segment_seconds, overlap_s=ov, **kw)
+                outs = [resample(e, model.fs, fs, backend=args.resampler) for e, fs in zip(enhs, rates)]
+            for (k, path), enh, fs in zip(grp, outs, rates):
+                output_path = out_path(path)
+                save(output_path, enh.cpu(), fs)
+                done.append(output_path)
         return done
     if args.batch_size <= 1:
         for k, path in todo:

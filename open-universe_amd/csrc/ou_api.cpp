@@ -1863,6 +1863,76 @@ SegArea seg_area(int C, int B, long long L) {
   a.total = off;
   return a;
 }
+
+// Window groups of rows with lengths of their own (include/ouniverse.h, ou_segment_groups): a pure host function.
+struct SegEntry { int row, win, len; };
+struct SegGroups {
+  std::vector<SegGeom> rows;        // the plan of every row (seg_plan)
+  std::vector<long long> first;     // the row's first entry
+  std::vector<SegEntry> entries;    // class FULL (row-major), then class SHORT (input order)
+  std::vector<int> group_first;     // first entry of every group
+  std::vector<char> group_ragged;
+  long long n_full = 0;             // entries of class FULL
+  long long S = 0, hop = 0, O = 0;  // window length, hop and crossfade of the long rows
+  int batch = 0;
+  long long length = 0;             // the longest entry = min(S, max T_pad)
+  std::string err;
+};
+bool seg_groups(int tot, int C, const int64_t* t_raw, long long segment, long long overlap, int max_batch, SegGroups& G) {
+  if (C < 1 || !t_raw || max_batch < 1) { G.err = "segment groups: C >= 1, t_raw given and max_batch >= 1"; return false; }
+  G.rows.resize(C);
+  G.first.assign(C, 0);
+  long long n_full = 0, n_short = 0;
+  for (int c = 0; c < C; c++) {
+    SegPlan p;
+    if (!seg_plan(tot, t_raw[c], segment, overlap, p)) { G.err = p.err; return false; }
+    G.rows[c] = p.g;
+    if (p.g.L > 0x7fffffffll) { G.err = "segment too long"; return false; }
+    if (p.g.n_win > 1) n_full += p.g.n_win; else n_short++;
+    G.length = std::max(G.length, p.g.L);
+  }
+  if (n_full + n_short > 0x7fffffffll) { G.err = "segment groups: too many windows"; return false; }
+  G.S = segment - segment % tot;
+  G.O = overlap - overlap % tot;
+  G.hop = G.S - G.O;
+  G.n_full = n_full;
+  G.batch = std::max(n_full ? seg_batch(n_full, max_batch) : 0, n_short ? seg_batch(n_short, max_batch) : 0);
+  G.entries.reserve((size_t)(n_full + n_short));
+  for (int c = 0; c < C; c++)
+    if (G.rows[c].n_win > 1) {
+      G.first[c] = (long long)G.entries.size();
+      for (long long k = 0; k < G.rows[c].n_win; k++) G.entries.push_back(SegEntry{c, (int)k, (int)G.rows[c].L});
+    }
+  for (int c = 0; c < C; c++)
+    if (G.rows[c].n_win == 1) {
+      G.first[c] = (long long)G.entries.size();
+      G.entries.push_back(SegEntry{c, 0, (int)G.rows[c].L});
+    }
+  auto add_groups = [&](long long e0, long long e1) {
+    for (long long e = e0; e < e1; e += G.batch) {
+      const long long end = std::min<long long>(e + G.batch, e1);
+      bool ragged = false;
+      for (long long i = e + 1; i < end; i++) ragged = ragged || G.entries[i].len != G.entries[e].len;
+      G.group_first.push_back((int)e);
+      G.group_ragged.push_back(ragged ? 1 : 0);
+    }
+  };
+  add_groups(0, n_full);
+  add_groups(n_full, n_full + n_short);
+  return true;
+}
+// the var call's own area: seg_area plus the geometry table
+struct SegVarArea {
+  SegArea a;
+  size_t geom, total;
+};
+SegVarArea seg_var_area(int C, int B, long long L) {
+  SegVarArea v;
+  v.a = seg_area(C, B, L);
+  v.geom = v.a.total;
+  v.total = v.geom + (((size_t)C * sizeof(SegRow) + 255) & ~size_t(255));
+  return v;
+}
 }  // namespace
 
 extern "C" {
@@ -2039,6 +2109,255 @@ int ou_enhance_segments(ou_handle* h, const float* mix, float* out, const float*
   const int keep_rms = (flags & OU_ENH_KEEP_RMS) ? 1 : 0;
   const int peak = (flags & OU_ENH_NO_PEAK_GUARD) ? 0 : 1;
   if (!chk(launch_seg_post(out, part, stats, C, g.T_raw, keep_rms, peak, st), "segment post")) return OU_EHIP;
+  return OU_OK;
+}
+
+int ou_segment_groups(int32_t tot_ds, int32_t C, const int64_t* t_raw, int32_t segment, int32_t overlap, int32_t max_batch,
+                      int32_t capacity, int32_t* entry_row, int32_t* entry_window, int32_t* entry_length, int32_t* group_first,
+                      int32_t* group_ragged, int32_t* n_entries, int32_t* n_groups, int32_t* batch, int32_t* length) {
+  SegGroups G;
+  if (!seg_groups(tot_ds, C, t_raw, segment, overlap, max_batch, G)) return fail(nullptr, OU_EINVAL, G.err);
+  const int ne = (int)G.entries.size(), ng = (int)G.group_first.size();
+  if (n_entries) *n_entries = ne;
+  if (n_groups) *n_groups = ng;
+  if (batch) *batch = G.batch;
+  if (length) *length = (int32_t)G.length;
+  if (!entry_row && !entry_window && !entry_length && !group_first && !group_ragged) return OU_OK;
+  if (capacity < ne) return fail(nullptr, OU_EINVAL, "segment groups: capacity smaller than the number of entries");
+  for (int e = 0; e < ne; e++) {
+    if (entry_row) entry_row[e] = G.entries[e].row;
+    if (entry_window) entry_window[e] = G.entries[e].win;
+    if (entry_length) entry_length[e] = G.entries[e].len;
+  }
+  for (int g = 0; g < ng; g++) {
+    if (group_first) group_first[g] = G.group_first[g];
+    if (group_ragged) group_ragged[g] = G.group_ragged[g];
+  }
+  return OU_OK;
+}
+
+int ou_segments_var_workspace_bytes(const ou_handle* hc, int32_t C, const int64_t* t_raw, int32_t segment, int32_t overlap,
+                                    int32_t max_batch, size_t* nbytes, int32_t* batch, int32_t* length) {
+  ou_handle* h = const_cast<ou_handle*>(hc);
+  if (!h || !nbytes || !t_raw || C < 1 || max_batch < 1) return fail(h, OU_EINVAL, "bad argument");
+  SegGroups G;
+  if (!seg_groups(h->m.tot_ds, C, t_raw, segment, overlap, max_batch, G)) return fail(h, OU_EINVAL, G.err);
+  size_t walk = 0;
+  const int rc = ou_workspace_bytes(h, G.batch, (int32_t)G.length, &walk);
+  if (rc != OU_OK) return rc;
+  walk = (walk + 255) & ~size_t(255);
+  *nbytes = walk + seg_var_area(C, G.batch, G.length).total;
+  if (batch) *batch = G.batch;
+  if (length) *length = (int32_t)G.length;
+  return OU_OK;
+}
+
+int ou_enhance_segments_var(ou_handle* h, const float* mix, float* out, const float* noise, int32_t C, int64_t T_raw_max,
+                            const int64_t* t_raw, int32_t segment, int32_t overlap, int32_t max_batch, int32_t n_steps,
+                            double epsilon, const float* sigma_host, int32_t warm_start, uint32_t flags, void* ws,
+                            size_t ws_bytes, ou_stream_t stream) {
+  // (the lengths first: what they decide needs neither the handle nor a device)
+  if (!t_raw || C < 1 || C > 65535 || T_raw_max < 1) return fail(h, OU_EINVAL, "bad argument");
+  if (max_batch < 1) return fail(h, OU_EINVAL, "ou_enhance_segments_var: max_batch must be at least 1");
+  {
+    long long mx = 0;
+    for (int c = 0; c < C; c++) {
+      if (t_raw[c] < 1 || t_raw[c] > T_raw_max) return fail(h, OU_EINVAL, "ou_enhance_segments_var: 1 <= t_raw[c] <= T_raw_max");
+      mx = std::max<long long>(mx, t_raw[c]);
+    }
+    if (mx != T_raw_max) return fail(h, OU_EINVAL, "ou_enhance_segments_var: T_raw_max must be the length of the longest row");
+  }
+  if (!h || !mix || !out || !ws) return fail(h, OU_EINVAL, "bad argument");
+  const bool counter = h->noise_src.on;
+  if (counter && noise)
+    return fail(h, OU_EINVAL, "a noise source is set on this handle (ou_set_noise_source): `noise` must be NULL");
+  if (counter && (int)h->noise_src.streams.size() != C)
+    return fail(h, OU_EINVAL, "noise source: n_streams (" + std::to_string(h->noise_src.streams.size()) +
+                                  ") must equal the rows of the call (" + std::to_string(C) + ")");
+  if (!counter && !noise) return fail(h, OU_EINVAL, "noise must be given");
+  if (warm_start >= 0 || (flags & OU_ENH_USE_AUX_SIGNAL))
+    return fail(h, OU_EINVAL, "ou_enhance_segments_var: warm_start and use_aux_signal are not supported");
+  if (n_steps < 2 || n_steps > kMaxSteps) return fail(h, OU_EINVAL, "n_steps must be in [2, 256]");
+  const Model& m = h->m;
+  const int tot = m.tot_ds;
+  SegGroups G;
+  if (!seg_groups(tot, C, t_raw, segment, overlap, max_batch, G)) return fail(h, OU_EINVAL, G.err);
+  if (G.length > max_walk_length(h, false))
+    return fail(h, OU_EINVAL, "ou_enhance_segments_var: segment too long for one pass of the walk");
+  const int B = G.batch;
+  size_t walk = 0;
+  {
+    const int rc = ou_workspace_bytes(h, B, (int32_t)G.length, &walk);
+    if (rc != OU_OK) return rc;
+    walk = (walk + 255) & ~size_t(255);
+  }
+  const SegVarArea A = seg_var_area(C, B, G.length);
+  if (ws_bytes < walk + A.total) return fail(h, OU_ENOMEM, "workspace too small: need " + std::to_string(walk + A.total) +
+                                                               " bytes (ou_segments_var_workspace_bytes)");
+  if (!h->ws_ok(ws, ws_bytes, B, (int)G.length))
+    return fail(h, OU_EINVAL,
+                "workspace was not prepared by ou_workspace_init for (batch, length) of ou_segments_var_workspace_bytes");
+  char* seg = (char*)ws + walk;
+  float* stats = (float*)(seg + A.a.stats);
+  float* row_scale = (float*)(seg + A.a.row_scale);
+  double* part = (double*)(seg + A.a.part);
+  float* zbuf = (float*)(seg + A.a.zbuf);
+  float* carry = (float*)(seg + A.a.carry);
+  SegRow* geom = (SegRow*)(seg + A.geom);
+
+  const bool saved_overlap = h->overlap;
+  struct OverlapGuard { ou_handle* h; bool v; ~OverlapGuard() { h->overlap = v; } } overlap_guard{h, saved_overlap};
+  h->overlap = false;  // one chain on the caller's stream
+  h->tensors.clear();
+  h->n_launch = h->n_conv = 0;
+  h->ev_used = 0;
+  hipStream_t st = (hipStream_t)stream;
+  auto chk = [&](hipError_t e, const char* w) -> bool {
+    h->n_launch++;
+    if (e != hipSuccess) { fail(h, OU_EHIP, std::string("HIP error at ") + w + ": " + hipGetErrorString(e)); return false; }
+    return true;
+  };
+
+  // ---- the geometry table, then every row's statistics and mel scale in one set of launches (the output rows hold the frame
+  // energies until the first stitch)
+  long long T_pad_max = 0, frames_max = 0;
+  for (int c = 0; c < C; c++) {
+    T_pad_max = std::max(T_pad_max, G.rows[c].T_pad);
+    const long long Lf = G.rows[c].T_pad / tot;  // mel frames of the whole row (run_condition)
+    if (Lf > G.rows[c].T_raw) return fail(h, OU_EINVAL, "internal: mel frames do not fit into the output row");
+    frames_max = std::max(frames_max, Lf);
+  }
+  if (frames_max > 0x7fffffffll) return fail(h, OU_EINVAL, "input too long");
+  SegVar v;
+  v.S = G.S; v.hop = G.hop; v.overlap = G.O;
+  v.row_stride = T_raw_max; v.noise_stride = T_pad_max;
+  v.tot_ds = tot;
+  for (int off = 0; off < C; off += kSegRowsPerLaunch) {
+    SegRowBlock blk;
+    const int n = std::min(C - off, kSegRowsPerLaunch);
+    for (int i = 0; i < kSegRowsPerLaunch; i++) {
+      blk.t_raw[i] = i < n ? t_raw[off + i] : 1;
+      blk.first[i] = i < n ? G.first[off + i] : 0;
+    }
+    if (!chk(launch_seg_upload_rows(geom, blk, n, off, v, st), "segment rows")) return OU_EHIP;
+  }
+  const float level = (float)std::pow(10.0, (double)m.cfg.level_db / 20.0);
+  if (!chk(launch_seg_stats_var(mix, part, stats, geom, C, T_raw_max, level, st), "segment stats")) return OU_EHIP;
+  if (!chk(launch_seg_mel_energy_var(mix, stats, h->W + m.mel.win_off, h->W + m.mel.tw_off, h->W + m.mel.fb_off, out, geom, C,
+                                     T_raw_max, m.mel.n_fft, m.mel.hop, m.mel.pad_left, m.mel.n_freq, m.mel.n_mels, frames_max,
+                                     st), "segment mel energy"))
+    return OU_EHIP;
+  if (!chk(launch_seg_mel_scale_var(out, row_scale, geom, C, T_raw_max, st), "segment mel scale")) return OU_EHIP;
+
+  // ---- sampler constants (as ou_enhance)
+  std::vector<float> sigma(n_steps);
+  double eta, beta;
+  schedule(m.cfg, n_steps, epsilon, sigma.data(), &eta, &beta);
+  if (sigma_host) std::memcpy(sigma.data(), sigma_host, sizeof(float) * n_steps);
+  std::vector<StepCoef> coefs;
+  for (int n = 0; n < n_steps; n++)
+    coefs.push_back(make_coef(m.cfg, sigma[n], n == n_steps - 1, eta, beta, n + 1 < n_steps ? sigma[n + 1] : 0.f));
+
+  // ---- the groups: B entries at a time through the walk -- the plain one, or the ragged one where the entries differ in length
+  const size_t step_noise = (size_t)C * T_pad_max;  // one step of the callers' noise
+  const long long n_entries = (long long)G.entries.size();
+  bool coefs_up = false;
+  for (size_t gi = 0; gi < G.group_first.size(); gi++) {
+    const long long e0 = G.group_first[gi];
+    const bool full = e0 < G.n_full;
+    const long long e_end = std::min<long long>(e0 + B, full ? G.n_full : n_entries);
+    const int n_real = (int)(e_end - e0);
+    const bool ragged = G.group_ragged[gi] != 0;
+    // entry j of the group (the filler rows of a short last group repeat the last real one) and the length of the walk
+    auto entry = [&](int j) -> const SegEntry& { return G.entries[(size_t)(e0 + std::min(j, n_real - 1))]; };
+    int T = 0;
+    for (int j = 0; j < n_real; j++) T = std::max(T, entry(j).len);
+    auto start_of = [&](const SegEntry& e) { return e.win < G.rows[e.row].n_win - 1 ? e.win * G.hop : G.rows[e.row].T_pad - e.len; };
+    // fn(block, n, j0) for the entries [0, count) of the group, kSegEntriesPerLaunch at a time
+    auto for_blocks = [&](int count, auto fn) {
+      for (int j0 = 0; j0 < count; j0 += kSegEntriesPerLaunch) {
+        SegEntryBlock blk;
+        const int n = std::min(count - j0, kSegEntriesPerLaunch);
+        for (int i = 0; i < kSegEntriesPerLaunch; i++) {
+          const SegEntry& e = entry(j0 + std::min(i, n - 1));
+          blk.row[i] = e.row; blk.win[i] = e.win; blk.len[i] = e.len;
+        }
+        fn(blk, n, j0);
+      }
+    };
+    Runner r(h, ws, walk, false, st, B);
+    r.mel_scale_preset = true;
+    Persist P = layout_persist(r, T);
+    if (r.oom) return finish(h, r);
+    if (!coefs_up) {  // (the persistent area of the workspace keeps them from group to group: its layout depends on B alone)
+      upload_coefs(r, P.coef, coefs);
+      r.chk(launch_sigma_embed(P.coef, n_steps, r.W(m.sigma.p_off), m.sigma.simple, m.sigma.n_rff, m.film.D, P.g, st), "sigma");
+      r.chk(launch_film(P.g, r.W(m.film.w_off), r.W(m.film.b_off), P.film, n_steps, m.film.rows, m.film.D, st), "film");
+      coefs_up = true;
+    }
+    if (ragged) {
+      // the entries' lengths on every level of the network: T, 2 T and T / (r_0 .. r_i) (as ou_enhance_var; an entry is an
+      // already padded window, so its length is the level-0 length itself)
+      LevelSpec& lv = r.lv;
+      lv.n = 0;
+      auto add_level = [&](int num, int den) {
+        lv.num[lv.n] = num; lv.den[lv.n] = den; r.level_T[lv.n] = (int)((long long)T * num / den); lv.n++;
+      };
+      add_level(1, 1);
+      add_level(2, 1);
+      int cum = 1;
+      for (int i = 0; i < m.cfg.score.n_rates && lv.n < kMaxLenLevels; i++) { cum *= m.cfg.score.rate_factors[i]; add_level(1, cum); }
+      if (cum != tot) return fail(h, OU_EINVAL, "internal: rate factors do not multiply to the total down-sampling factor");
+      for_blocks(B, [&](const SegEntryBlock& blk, int n, int j0) {
+        r.chk(launch_seg_upload_lens(P.lens, blk, n, j0, B, lv, st), "segment lens");
+      });
+      r.ragged = true;
+      r.lens_dev = P.lens;
+    }
+    for_blocks(B, [&](const SegEntryBlock& blk, int n, int j0) {
+      r.chk(launch_seg_gather_input_var(mix, stats, row_scale, geom, P.mixn.p, P.mel_scale, blk, n, j0, T, v, st),
+            "segment gather");
+    });
+    run_condition(r, P, P.mixn.p, T);
+    // one step's noise of the group's entries (0 behind an entry's own length): a slice of the caller's rows, or -- counter
+    // mode -- the same positions (window k of row c: t = s_k + i, stream of row c) straight from the function
+    auto step_noise_plane = [&](int draw) {
+      if (!counter) {
+        for_blocks(B, [&](const SegEntryBlock& blk, int n, int j0) {
+          r.chk(launch_seg_gather_noise_var(noise + (size_t)draw * step_noise, geom, zbuf, blk, n, j0, T, v, st), "segment noise");
+        });
+        return;
+      }
+      fill_noise_plane(r, zbuf, T, B, h->noise_src.seed, draw, [&](int j, unsigned long long& sid, long long& t0, long long& len) {
+        const SegEntry& e = entry(j);
+        sid = h->noise_src.streams[e.row];
+        t0 = start_of(e);
+        len = e.len;
+      });
+    };
+    step_noise_plane(0);
+    r.chk(launch_init_x(zbuf, nullptr, sigma[0], P.x.p, (size_t)B * T, st), "init x");  // universe.py:325-327
+    const size_t step_mark = r.off;
+    for (int n = 0; n < n_steps && r.ok(); n++) {
+      const bool last = n == n_steps - 1;
+      if (!last) step_noise_plane(n + 1);
+      r.off = step_mark;
+      run_score(r, P, P.x.p, last ? nullptr : zbuf, P.x.p, OUT_UPDATE, P.coef + n, 0, P.film + (size_t)n * m.film.rows, 0, T);
+    }
+    if (r.ok())
+      for_blocks(n_real, [&](const SegEntryBlock& blk, int n, int j0) {
+        r.chk(launch_seg_stitch_var(P.x.p, carry, out, geom, blk, n, j0, T, v, st), "segment stitch");
+      });
+    if (r.ok() && full && e_end < G.n_full)  // the window in front of the next group
+      r.chk(hipMemcpyAsync(carry, P.x.p + (size_t)(n_real - 1) * T, (size_t)T * 4, hipMemcpyDeviceToDevice, st), "carry");
+    const int rc = finish(h, r);
+    if (rc != OU_OK) return rc;
+  }
+  h->cond_B = 0;  // (the operator seams see a whole-file batch only)
+  h->cond_T = (int)G.length;
+  const int keep_rms = (flags & OU_ENH_KEEP_RMS) ? 1 : 0;
+  const int peak = (flags & OU_ENH_NO_PEAK_GUARD) ? 0 : 1;
+  if (!chk(launch_seg_post_var(out, part, stats, geom, C, T_raw_max, keep_rms, peak, st), "segment post")) return OU_EHIP;
   return OU_OK;
 }
 

@@ -209,6 +209,48 @@ hipError_t launch_seg_stitch(const float* y, const float* carry, float* out, con
 hipError_t launch_seg_post(float* out, double* part, const float* stats, int C, long long T_raw, int keep_rms, int peak_guard,
                            hipStream_t st);
 
+// ---- ... with rows of lengths of their own (ou_enhance_segments_var) ---------------------------------------------------------
+// Row c has its own SegRow in a device table (written by launch_seg_upload_rows, 64 rows per launch, by value: capturable, no
+// host memory involved); mix / out are (C, row_stride), one step of noise is (C, noise_stride).  A group's entries (row, window,
+// length) travel as kernel arguments, 64 per launch.  Entries of a long row have length S and start at k * hop (the last one
+// at T_pad - S); the single entry of a row with T_pad <= S has length T_pad and starts at 0.
+struct SegRow { long long t_raw, T_pad, pad_left, n_win, first, frames; };  // first: the row's first entry; frames: mel frames
+struct SegVar {
+  long long S, hop, overlap;           // window length, hop and crossfade of the long rows
+  long long row_stride, noise_stride;  // T_raw_max, T_pad_max
+  int tot_ds;
+};
+constexpr int kSegRowsPerLaunch = 64;
+struct SegRowBlock { long long t_raw[kSegRowsPerLaunch]; long long first[kSegRowsPerLaunch]; };
+constexpr int kSegEntriesPerLaunch = 64;
+struct SegEntryBlock { int row[kSegEntriesPerLaunch]; int win[kSegEntriesPerLaunch]; int len[kSegEntriesPerLaunch]; };
+hipError_t launch_seg_upload_rows(SegRow* rows, const SegRowBlock& blk, int n, int off, const SegVar& v, hipStream_t st);
+// lens[l * B + j0 + i] <- len[i] * num_l / den_l: the per-level lengths of a ragged group, from the entry lengths directly (an
+// entry is an already padded window: no pad split as in launch_upload_rows)
+hipError_t launch_seg_upload_lens(int* lens, const SegEntryBlock& blk, int n, int j0, int B, const LevelSpec& lv, hipStream_t st);
+// Row c's reductions run over seg_reduce_blocks(t_raw[c]) blocks whatever the other rows are: its statistics have the bits of
+// the call on that row alone.  Grids are sized by the longest row (T_raw_max); part: [C][nb_max][3] doubles.
+hipError_t launch_seg_stats_var(const float* mix, double* part, float* stats, const SegRow* rows, int C, long long T_raw_max,
+                                float level, hipStream_t st);
+// esum[c * row_stride + f] for f < frames_c; scale[c] = the mel scale over those frames (mel_scale_kernel's arithmetic)
+hipError_t launch_seg_mel_energy_var(const float* mix, const float* stats, const float* win, const float* tw, const float* fb,
+                                     float* esum, const SegRow* rows, int C, long long row_stride, int n_fft, int hop, int mel_pad,
+                                     int n_freq, int n_mels, long long frames_max, hipStream_t st);
+hipError_t launch_seg_mel_scale_var(const float* esum, float* scale, const SegRow* rows, int C, long long row_stride,
+                                    hipStream_t st);
+// entries j0 .. j0 + n - 1 of a group whose walk runs at length T: mixn / z (B, T), 0 from the entry's own length on
+hipError_t launch_seg_gather_input_var(const float* mix, const float* stats, const float* row_mel_scale, const SegRow* rows,
+                                       float* mixn, float* mel_scale, const SegEntryBlock& blk, int n, int j0, long long T,
+                                       const SegVar& v, hipStream_t st);
+hipError_t launch_seg_gather_noise_var(const float* noise, const SegRow* rows, float* z, const SegEntryBlock& blk, int n, int j0,
+                                       long long T, const SegVar& v, hipStream_t st);
+// (y: (B, T); entry j > 0 with a window in front crossfades with row j - 1 of y, entry 0 with `carry`)
+hipError_t launch_seg_stitch_var(const float* y, const float* carry, float* out, const SegRow* rows, const SegEntryBlock& blk,
+                                 int n, int j0, long long T, const SegVar& v, hipStream_t st);
+// keep_rms + peak guard per row over its own samples, and out[c][t_raw_c ..) <- 0; part: [C][nb_max][2] doubles
+hipError_t launch_seg_post_var(float* out, double* part, const float* stats, const SegRow* rows, int C, long long T_raw_max,
+                               int keep_rms, int peak_guard, hipStream_t st);
+
 // Counter-based sampler noise (ou_noise.hip; the function z(seed, stream, draw, t) is defined in include/ouniverse.h).
 // One launch fills up to 64 rows: out[j][col] = col < len[j] ? z(seed, stream[j], draw, t0[j] + col) : 0 for col < cols.
 // The per-row values travel as kernel arguments (capturable, no host memory involved).

@@ -3,6 +3,9 @@
 // per row.  Reductions run in a fixed order (per-block partials in double, summed in block order by whoever needs the
 // total): two runs give the same bits.  With one block per row the order is exactly that of pad_normalize_kernel /
 // post_kernel, so a file that fits into one window gets the whole-file call's statistics bit for bit.
+// The *_var forms (ou_enhance_segments_var) do the same for rows of lengths of their own: the geometry of a row comes from a
+// device table, a group's entries (row, window, length) from the kernel arguments, and every row reduces over the block
+// partition of the call on that row alone.
 #include "ou_internal.h"
 
 namespace ou {
@@ -260,6 +263,282 @@ __global__ __launch_bounds__(256) void seg_post_scale_kernel(float* __restrict__
   }
 }
 
+// ==== rows of lengths of their own (ou_enhance_segments_var) ===============================================================
+// The same arithmetic in the same order as the kernels above, with the row's geometry read from the SegRow table instead of the
+// kernel arguments.  Grids are sized by the longest row; a block beyond the row's own share returns before it touches memory.
+// Row c reduces over seg_nb(t_raw[c]) blocks -- the partition of the call on that row alone -- so its mean, gain, mix_rms and
+// mel scale have that call's bits.
+
+// blocks of a whole-row reduction (= seg_reduce_blocks)
+__device__ __forceinline__ int seg_nb(long long T_raw) {
+  const long long nb = (T_raw + (1ll << 18) - 1) >> 18;
+  return (int)(nb < 1 ? 1 : nb > 1024 ? 1024 : nb);
+}
+// start of window k of row r, whose entries are `len` long (one window: T_pad - len = 0)
+__device__ __forceinline__ long long seg_start_var(const SegRow& r, long long k, long long len, long long hop) {
+  return k < r.n_win - 1 ? k * hop : r.T_pad - len;
+}
+
+__global__ void seg_upload_rows_kernel(SegRow* rows, SegRowBlock blk, int n, int off, SegVar v) {
+  const int i = threadIdx.x;
+  if (i >= n) return;
+  const long long t = blk.t_raw[i];
+  const long long pad = v.tot_ds - t % v.tot_ds;  // universe.py:219-223
+  SegRow r;
+  r.t_raw = t;
+  r.T_pad = t + pad;
+  r.pad_left = pad / 2;
+  r.n_win = r.T_pad <= v.S ? 1 : (r.T_pad - v.S + v.hop - 1) / v.hop + 1;
+  r.first = blk.first[i];
+  r.frames = r.T_pad / v.tot_ds;
+  rows[off + i] = r;
+}
+__global__ void seg_upload_lens_kernel(int* lens, SegEntryBlock blk, int n, int j0, int B, LevelSpec lv) {
+  const int i = threadIdx.x;
+  if (i >= n) return;
+  for (int l = 0; l < lv.n; l++) lens[l * B + j0 + i] = (int)((long long)blk.len[i] * lv.num[l] / lv.den[l]);
+}
+
+// grid (nb_max, C); part: [C][nb_max][3]
+__global__ __launch_bounds__(1024) void seg_stats1_var_kernel(const float* __restrict__ mix, double* __restrict__ part,
+                                                              const SegRow* __restrict__ rows, long long row_stride, int nb_max) {
+  __shared__ double shd[16];
+  const int j = blockIdx.x, c = blockIdx.y;
+  const long long T_raw = rows[c].t_raw;
+  const int nb = seg_nb(T_raw);
+  if (j >= nb) return;
+  const float* xb = mix + (size_t)c * row_stride;
+  double s = 0, sq = 0;
+  for (long long t = (long long)j * 1024 + threadIdx.x; t < T_raw; t += (long long)nb * 1024) {
+    const double d = xb[t];
+    s += d; sq += d * d;
+  }
+  s = seg_block_sum(s, shd);
+  sq = seg_block_sum(sq, shd);
+  if (threadIdx.x == 0) { part[((size_t)c * nb_max + j) * 3 + 0] = s; part[((size_t)c * nb_max + j) * 3 + 1] = sq; }
+}
+__global__ __launch_bounds__(1024) void seg_stats2_var_kernel(const float* __restrict__ mix, double* __restrict__ part,
+                                                              const SegRow* __restrict__ rows, long long row_stride, int nb_max) {
+  __shared__ double shd[16];
+  const int j = blockIdx.x, c = blockIdx.y;
+  const long long T_raw = rows[c].t_raw, T_pad = rows[c].T_pad;
+  const int nb = seg_nb(T_raw);
+  if (j >= nb) return;
+  const double* pc = part + (size_t)c * nb_max * 3;
+  double s = pc[0];
+  for (int i = 1; i < nb; i++) s += pc[i * 3];
+  const float mean = (float)(s / (double)T_pad);
+  const float* xb = mix + (size_t)c * row_stride;
+  double ss = 0;
+  for (long long t = (long long)j * 1024 + threadIdx.x; t < T_raw; t += (long long)nb * 1024) {
+    const double d = (double)(xb[t] - mean);
+    ss += d * d;
+  }
+  ss = seg_block_sum(ss, shd);
+  if (threadIdx.x == 0) part[((size_t)c * nb_max + j) * 3 + 2] = ss;
+}
+__global__ void seg_stats_finish_var_kernel(const double* __restrict__ part, float* __restrict__ stats,
+                                            const SegRow* __restrict__ rows, int nb_max, float level) {
+  const int c = blockIdx.x;
+  if (threadIdx.x != 0) return;
+  const long long T_raw = rows[c].t_raw, T_pad = rows[c].T_pad;
+  const int nb = seg_nb(T_raw);
+  const double* pc = part + (size_t)c * nb_max * 3;
+  double s = pc[0], sq = pc[1], ss = pc[2];
+  for (int i = 1; i < nb; i++) { s += pc[i * 3]; sq += pc[i * 3 + 1]; ss += pc[i * 3 + 2]; }
+  const float mean = (float)(s / (double)T_pad);
+  ss += (double)(T_pad - T_raw) * (double)(0.f - mean) * (double)(0.f - mean);
+  float sd = (float)sqrt(ss / (double)(T_pad - 1));
+  sd = fmaxf(sd, 1e-5f);
+  stats[c * 4 + 0] = mean;
+  stats[c * 4 + 1] = level / sd;
+  stats[c * 4 + 2] = (float)sqrt(sq / (double)T_raw);
+  stats[c * 4 + 3] = 0.f;
+}
+
+// grid (frames_max, C); esum[c * row_stride + f] for the row's own frames
+__global__ __launch_bounds__(512) void seg_mel_energy_var_kernel(const float* __restrict__ mix, const float* __restrict__ stats,
+                                                                 const float* __restrict__ win, const float* __restrict__ tw,
+                                                                 const float* __restrict__ fb, float* __restrict__ esum,
+                                                                 const SegRow* __restrict__ rows, long long row_stride, int n_fft,
+                                                                 int hop, int mel_pad, int n_freq, int n_mels) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  float* sx = sm;
+  float* tc = sx + n_fft;
+  float* ts = tc + n_fft;
+  float* pw = ts + n_fft;
+  __shared__ float shf[8];
+  const long long f = blockIdx.x;
+  const int c = blockIdx.y, tid = threadIdx.x;
+  const SegRow r = rows[c];
+  if (f >= r.frames) return;
+  const float mean = stats[c * 4 + 0], gain = stats[c * 4 + 1];
+  const float* xb = mix + (size_t)c * row_stride;
+  for (int n = tid; n < n_fft; n += 512) {
+    const long long t = f * hop + n - mel_pad;
+    float v = 0.f;
+    if (t >= 0 && t < r.T_pad) {
+      const long long tr = t - r.pad_left;
+      v = ((tr >= 0 && tr < r.t_raw) ? xb[tr] : 0.f);
+      v = (v - mean) * gain;
+    }
+    sx[n] = v * win[n];
+    tc[n] = tw[n];
+    ts[n] = tw[n_fft + n];
+  }
+  __syncthreads();
+  for (int k = tid; k < n_freq; k += 512) {
+    float re = 0.f, im = 0.f;
+    int idx = 0;
+    for (int n = 0; n < n_fft; n++) {
+      float v = sx[n];
+      re = fmaf(v, tc[idx], re);
+      im = fmaf(-v, ts[idx], im);
+      idx += k;
+      if (idx >= n_fft) idx -= n_fft;
+    }
+    pw[k] = re * re + im * im;
+  }
+  __syncthreads();
+  float e = 0.f;
+  for (int m = tid; m < n_mels; m += 512) {
+    float acc = 0.f;
+    for (int k = 0; k < n_freq; k++) acc = fmaf(pw[k], fb[(size_t)k * n_mels + m], acc);
+    e += acc * acc;
+  }
+  e = seg_block_sum(e, shf);
+  if (tid == 0) esum[(size_t)c * row_stride + f] = e;
+}
+// scale[c] = 1 / max(sqrt(mean of the row's frame energies), 1e-5): mel_scale_kernel (ou_small.hip) over the row's own frames
+__global__ __launch_bounds__(256) void seg_mel_scale_var_kernel(const float* __restrict__ esum, float* __restrict__ scale,
+                                                                const SegRow* __restrict__ rows, long long row_stride) {
+  __shared__ double shd[4];
+  const int c = blockIdx.x;
+  const long long Lb = rows[c].frames;
+  double s = 0;
+  for (long long f = threadIdx.x; f < Lb; f += 256) s += esum[(size_t)c * row_stride + f];
+  s = seg_block_sum(s, shd);
+  if (threadIdx.x == 0) scale[c] = 1.0f / fmaxf((float)sqrt(s / Lb), 1e-5f);
+}
+
+// grid (ceil(T / 1024), n): entry i of the block is row j0 + i of mixn (B, T); columns from the entry's length on are 0
+__global__ __launch_bounds__(256) void seg_gather_input_var_kernel(const float* __restrict__ mix, const float* __restrict__ stats,
+                                                                   const float* __restrict__ row_mel_scale,
+                                                                   const SegRow* __restrict__ rows, float* __restrict__ mixn,
+                                                                   float* __restrict__ mel_scale, SegEntryBlock blk, int j0,
+                                                                   long long T, SegVar v) {
+  const int i = blockIdx.y, j = j0 + i;
+  const int c = blk.row[i];
+  const long long k = blk.win[i], len = blk.len[i];
+  const SegRow r = rows[c];
+  const long long s = seg_start_var(r, k, len, v.hop);
+  const float mean = stats[c * 4 + 0], gain = stats[c * 4 + 1];
+  const float* xb = mix + (size_t)c * v.row_stride;
+  float* yb = mixn + (size_t)j * T;
+  for (long long t = (long long)blockIdx.x * 1024 + threadIdx.x; t < (long long)(blockIdx.x + 1) * 1024 && t < T; t += 256) {
+    float y = 0.f;
+    if (t < len) {
+      const long long tr = s + t - r.pad_left;
+      const float x = (tr >= 0 && tr < r.t_raw) ? xb[tr] : 0.f;
+      y = (x - mean) * gain;
+    }
+    yb[t] = y;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) mel_scale[j] = row_mel_scale[c];
+}
+__global__ __launch_bounds__(256) void seg_gather_noise_var_kernel(const float* __restrict__ noise, const SegRow* __restrict__ rows,
+                                                                   float* __restrict__ z, SegEntryBlock blk, int j0, long long T,
+                                                                   SegVar v) {
+  const int i = blockIdx.y, j = j0 + i;
+  const int c = blk.row[i];
+  const long long k = blk.win[i], len = blk.len[i];
+  const SegRow r = rows[c];
+  const float* src = noise + (size_t)c * v.noise_stride + seg_start_var(r, k, len, v.hop);
+  float* dst = z + (size_t)j * T;
+  for (long long t = (long long)blockIdx.x * 1024 + threadIdx.x; t < (long long)(blockIdx.x + 1) * 1024 && t < T; t += 256)
+    dst[t] = t < len ? src[t] : 0.f;
+}
+
+// grid (ceil(T / 1024), n): seg_stitch_kernel with the row's own geometry (a one-window row: w0 = 0, w1 = T_pad, no crossfade)
+__global__ __launch_bounds__(256) void seg_stitch_var_kernel(const float* __restrict__ y, const float* __restrict__ carry,
+                                                             float* __restrict__ out, const SegRow* __restrict__ rows,
+                                                             SegEntryBlock blk, int j0, long long T, SegVar v) {
+  const int i = blockIdx.y, j = j0 + i;
+  const int c = blk.row[i];
+  const long long k = blk.win[i], len = blk.len[i];
+  const SegRow r = rows[c];
+  const long long s = seg_start_var(r, k, len, v.hop);
+  const long long s_prev = k == 0 ? 0 : seg_start_var(r, k - 1, len, v.hop);
+  const long long w0 = k == 0 ? 0 : s_prev + len - v.overlap;
+  const long long w1 = k == r.n_win - 1 ? r.T_pad : s + len - v.overlap;
+  const long long e_prev = k == 0 ? 0 : s_prev + len;
+  const float* yk = y + (size_t)j * T;
+  const float* yp = j > 0 ? y + (size_t)(j - 1) * T : carry;
+  float* ob = out + (size_t)c * v.row_stride;
+  for (long long t = (long long)blockIdx.x * 1024 + threadIdx.x; t < (long long)(blockIdx.x + 1) * 1024 && t < len; t += 256) {
+    const long long u = s + t;
+    if (u < w0 || u >= w1) continue;
+    const long long tr = u - r.pad_left;
+    if (tr < 0 || tr >= r.t_raw) continue;
+    float val = yk[t];
+    if (u < e_prev) {
+      const float a = 0.5f - 0.5f * cosf(3.14159265358979f * ((float)(u - w0) + 0.5f) / (float)v.overlap);
+      val = (1.f - a) * yp[u - s_prev] + a * val;
+    }
+    ob[tr] = val;
+  }
+}
+
+// grid (nb_max, C); part: [C][nb_max][2].  Every block of the row's grid line also zeroes its share of out[c][t_raw_c ..).
+__global__ __launch_bounds__(1024) void seg_post_reduce_var_kernel(float* __restrict__ out, double* __restrict__ part,
+                                                                   const SegRow* __restrict__ rows, long long row_stride,
+                                                                   int nb_max) {
+  __shared__ double shd[16];
+  __shared__ float shf[16];
+  const int j = blockIdx.x, c = blockIdx.y;
+  const long long T_raw = rows[c].t_raw;
+  float* xb = out + (size_t)c * row_stride;
+  for (long long t = T_raw + (long long)j * 1024 + threadIdx.x; t < row_stride; t += (long long)nb_max * 1024) xb[t] = 0.f;
+  const int nb = seg_nb(T_raw);
+  if (j >= nb) return;
+  double sq = 0;
+  float mx = 0.f;
+  for (long long t = (long long)j * 1024 + threadIdx.x; t < T_raw; t += (long long)nb * 1024) {
+    const float x = xb[t];
+    const double d = x;
+    sq += d * d;
+    mx = fmaxf(mx, fabsf(x));
+  }
+  sq = seg_block_sum(sq, shd);
+  mx = seg_block_max(mx, shf);
+  if (threadIdx.x == 0) { part[((size_t)c * nb_max + j) * 2 + 0] = sq; part[((size_t)c * nb_max + j) * 2 + 1] = (double)mx; }
+}
+__global__ __launch_bounds__(256) void seg_post_scale_var_kernel(float* __restrict__ out, const double* __restrict__ part,
+                                                                 const float* __restrict__ stats, const SegRow* __restrict__ rows,
+                                                                 long long row_stride, int nb_max, int keep_rms, int peak_guard) {
+  const int c = blockIdx.y;
+  const long long T_raw = rows[c].t_raw;
+  const int nb = seg_nb(T_raw);
+  const double* pc = part + (size_t)c * nb_max * 2;
+  double sq = pc[0];
+  float mxa = (float)pc[1];
+  for (int i = 1; i < nb; i++) { sq += pc[i * 2]; mxa = fmaxf(mxa, (float)pc[i * 2 + 1]); }
+  float g = 1.f;
+  if (keep_rms) {
+    const float x_rms = fmaxf((float)sqrt(sq / (double)T_raw), 1e-5f);
+    g = stats[c * 4 + 2] / x_rms;
+  }
+  const float mx = mxa * g;
+  const bool div = peak_guard && mx > 1.0f;
+  if (!keep_rms && !div) return;
+  float* xb = out + (size_t)c * row_stride;
+  for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < T_raw; t += (long long)gridDim.x * 256) {
+    float x = xb[t] * g;
+    if (div) x = x / mx;
+    xb[t] = x;
+  }
+}
+
 }  // namespace
 
 int seg_reduce_blocks(long long T_raw) {
@@ -307,6 +586,72 @@ hipError_t launch_seg_post(float* out, double* part, const float* stats, int C, 
   if (nsb > 8192) nsb = 8192;
   hipLaunchKernelGGL(seg_post_scale_kernel, dim3((unsigned)nsb, C), dim3(256), 0, st, out, part, stats, T_raw, nb, keep_rms,
                      peak_guard);
+  return hipGetLastError();
+}
+
+// ---- rows of lengths of their own ----------------------------------------------------------------------------------------------
+hipError_t launch_seg_upload_rows(SegRow* rows, const SegRowBlock& blk, int n, int off, const SegVar& v, hipStream_t st) {
+  if (n < 1 || n > kSegRowsPerLaunch) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(seg_upload_rows_kernel, dim3(1), dim3(64), 0, st, rows, blk, n, off, v);
+  return hipGetLastError();
+}
+hipError_t launch_seg_upload_lens(int* lens, const SegEntryBlock& blk, int n, int j0, int B, const LevelSpec& lv, hipStream_t st) {
+  if (n < 1 || n > kSegEntriesPerLaunch || j0 < 0 || j0 + n > B) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(seg_upload_lens_kernel, dim3(1), dim3(64), 0, st, lens, blk, n, j0, B, lv);
+  return hipGetLastError();
+}
+hipError_t launch_seg_stats_var(const float* mix, double* part, float* stats, const SegRow* rows, int C, long long T_raw_max,
+                                float level, hipStream_t st) {
+  const int nb = seg_reduce_blocks(T_raw_max);
+  hipLaunchKernelGGL(seg_stats1_var_kernel, dim3(nb, C), dim3(1024), 0, st, mix, part, rows, T_raw_max, nb);
+  hipLaunchKernelGGL(seg_stats2_var_kernel, dim3(nb, C), dim3(1024), 0, st, mix, part, rows, T_raw_max, nb);
+  hipLaunchKernelGGL(seg_stats_finish_var_kernel, dim3(C), dim3(64), 0, st, part, stats, rows, nb, level);
+  return hipGetLastError();
+}
+hipError_t launch_seg_mel_energy_var(const float* mix, const float* stats, const float* win, const float* tw, const float* fb,
+                                     float* esum, const SegRow* rows, int C, long long row_stride, int n_fft, int hop, int mel_pad,
+                                     int n_freq, int n_mels, long long frames_max, hipStream_t st) {
+  if (frames_max < 1 || frames_max > 0x7fffffffll) return hipErrorInvalidValue;
+  const size_t smem = (size_t)(3 * n_fft + n_freq) * 4;
+  hipLaunchKernelGGL(seg_mel_energy_var_kernel, dim3((unsigned)frames_max, C), dim3(512), smem, st, mix, stats, win, tw, fb, esum,
+                     rows, row_stride, n_fft, hop, mel_pad, n_freq, n_mels);
+  return hipGetLastError();
+}
+hipError_t launch_seg_mel_scale_var(const float* esum, float* scale, const SegRow* rows, int C, long long row_stride,
+                                    hipStream_t st) {
+  hipLaunchKernelGGL(seg_mel_scale_var_kernel, dim3(C), dim3(256), 0, st, esum, scale, rows, row_stride);
+  return hipGetLastError();
+}
+hipError_t launch_seg_gather_input_var(const float* mix, const float* stats, const float* row_mel_scale, const SegRow* rows,
+                                       float* mixn, float* mel_scale, const SegEntryBlock& blk, int n, int j0, long long T,
+                                       const SegVar& v, hipStream_t st) {
+  if (n < 1 || n > kSegEntriesPerLaunch || T < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(seg_gather_input_var_kernel, dim3((unsigned)((T + 1023) / 1024), n), dim3(256), 0, st, mix, stats,
+                     row_mel_scale, rows, mixn, mel_scale, blk, j0, T, v);
+  return hipGetLastError();
+}
+hipError_t launch_seg_gather_noise_var(const float* noise, const SegRow* rows, float* z, const SegEntryBlock& blk, int n, int j0,
+                                       long long T, const SegVar& v, hipStream_t st) {
+  if (n < 1 || n > kSegEntriesPerLaunch || T < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(seg_gather_noise_var_kernel, dim3((unsigned)((T + 1023) / 1024), n), dim3(256), 0, st, noise, rows, z, blk,
+                     j0, T, v);
+  return hipGetLastError();
+}
+hipError_t launch_seg_stitch_var(const float* y, const float* carry, float* out, const SegRow* rows, const SegEntryBlock& blk,
+                                 int n, int j0, long long T, const SegVar& v, hipStream_t st) {
+  if (n < 1 || n > kSegEntriesPerLaunch || T < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(seg_stitch_var_kernel, dim3((unsigned)((T + 1023) / 1024), n), dim3(256), 0, st, y, carry, out, rows, blk, j0,
+                     T, v);
+  return hipGetLastError();
+}
+hipError_t launch_seg_post_var(float* out, double* part, const float* stats, const SegRow* rows, int C, long long T_raw_max,
+                               int keep_rms, int peak_guard, hipStream_t st) {
+  const int nb = seg_reduce_blocks(T_raw_max);
+  hipLaunchKernelGGL(seg_post_reduce_var_kernel, dim3(nb, C), dim3(1024), 0, st, out, part, rows, T_raw_max, nb);
+  long long nsb = (T_raw_max + 256 * 64 - 1) / (256 * 64);
+  if (nsb > 8192) nsb = 8192;
+  hipLaunchKernelGGL(seg_post_scale_var_kernel, dim3((unsigned)nsb, C), dim3(256), 0, st, out, part, stats, rows, T_raw_max, nb,
+                     keep_rms, peak_guard);
   return hipGetLastError();
 }
 

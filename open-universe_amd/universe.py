@@ -1046,6 +1046,88 @@ class Universe:
         self._status()
         return out if mix.ndim == 2 else out[0]
 
+    @torch.no_grad()
+    def enhance_long_many(self, signals, rngs=None, segment_s: float = SEGMENT_S, overlap_s: float = OVERLAP_S,
+                          max_batch: int = 32, n_steps: Optional[int] = None, epsilon: Optional[float] = None,
+                          keep_rms: Optional[bool] = False, **other):
+        """`enhance_long` of several independent inputs of ANY lengths in ONE call (extension; ou_enhance_segments_var).
+        `signals`: list of (L,) or (C, L) tensors, channels are rows as in `enhance_many`.  Inputs longer than a window are cut
+        into windows, shorter ones are one window each, and the windows of all rows share the window groups of `max_batch`;
+        every row still gets what `enhance_long` gives it alone (whole-row normalisation, mel scale, noise, keep_rms and peak
+        guard of its own; to fp32 round-off, since the kernels a group selects differ).  `rngs`: one generator per input, ONE
+        shared generator (it advances input by input, as `enhance_long` draws for each), or None -- or `noise.CounterNoise`
+        objects as in `enhance_many` (one per input with one seed, or one shared: input i is utterance `stream + i`).
+        Returns the list of enhanced signals, each with the shape of its input."""
+        for k in ("target", "ensemble", "fake_score_snr", "warm_start"):
+            if other.get(k) is not None:
+                raise ValueError(f"enhance_long_many does not take `{k}`")
+        if other.get("use_aux_signal"):
+            raise ValueError("enhance_long_many does not take `use_aux_signal`")
+        unknown = set(other) - {"target", "ensemble", "fake_score_snr", "warm_start", "use_aux_signal", "ensemble_stat"}
+        if unknown:
+            raise TypeError(f"enhance_long_many() got unexpected keyword argument(s): {sorted(unknown)}")
+        if not signals:
+            return []
+        self._sync_env()
+        self._poll_deferred_status()
+        rows, dims = [], []
+        for s in signals:
+            if s.ndim not in (1, 2):
+                raise ValueError("enhance_long_many takes (L,) or (C, L) signals")
+            dims.append(s.ndim)
+            rows.append(self._prep(s if s.ndim == 2 else s[None, :]))
+        lens = [int(r.shape[-1]) for r in rows]
+        if min(lens) < 1:
+            raise ValueError("enhance_long_many: empty input signal")
+        chans = [int(r.shape[0]) for r in rows]
+        C, l_max = sum(chans), max(lens)
+        n_steps = self.diff_kwargs.n_steps if n_steps is None else int(n_steps)
+        if epsilon is None:
+            epsilon = self.diff_kwargs.epsilon
+        segment = int(round(float(segment_s) * self.fs))
+        overlap = int(round(float(overlap_s) * self.fs))
+        t_raw = (ctypes.c_int64 * C)(*[n for n, c in zip(lens, chans) for _ in range(c)])
+        need, B, L = c_size_t(), c_int32(), c_int32()
+        _lib.check(self._L.ou_segments_var_workspace_bytes(self._handle, C, t_raw, segment, overlap, int(max_batch), byref(need),
+                                                            byref(B), byref(L)), self._handle)
+        counter = self._counter_plan(rngs, chans)
+        noise = None
+        if counter is None:
+            # the draws of `enhance_long` on every input alone, input by input: (C_i, 1, T_i) per step, x0 first
+            T_max = l_max + (self.tot_ds - l_max % self.tot_ds)
+            noise = torch.zeros((n_steps, C, T_max), dtype=torch.float32, device=self.device)
+            r0 = 0
+            for i, (c, n) in enumerate(zip(chans, lens)):
+                g = rngs[i] if isinstance(rngs, (list, tuple)) else rngs
+                Ti = n + (self.tot_ds - n % self.tot_ds)
+                for k in range(n_steps):
+                    noise[k, r0:r0 + c, :Ti] = torch.randn((c, 1, Ti), dtype=torch.float32, device=self.device,
+                                                           generator=g)[:, 0]
+                r0 += c
+        skey = (int(n_steps), float(self.diff_kwargs.sigma_min), float(self.diff_kwargs.sigma_max))
+        sigma = self._sigma_cache.get(skey)
+        if sigma is None:
+            time = torch.linspace(0, 1, n_steps).to(torch.float32).flip(dims=[0])
+            sigma = self._sigma_cache[skey] = self.get_std_dev(time).to(torch.float32).contiguous()
+        ws = self._segments_workspace(B.value, L.value, need.value)
+        mix = torch.cat([torch.nn.functional.pad(r, (0, l_max - r.shape[-1])) for r in rows], dim=0).contiguous()
+        out = torch.empty(C, l_max, dtype=torch.float32, device=self.device)
+        flags = _lib.OU_ENH_KEEP_RMS if keep_rms else 0
+        source = self._counter_source(*counter) if counter is not None else contextlib.nullcontext()
+        with torch.cuda.device(self.device), source:
+            _lib.check(self._L.ou_enhance_segments_var(
+                self._handle, c_void_p(mix.data_ptr()), c_void_p(out.data_ptr()),
+                None if noise is None else c_void_p(noise.data_ptr()), C, l_max, t_raw,
+                segment, overlap, int(max_batch), n_steps, float(epsilon), ctypes.cast(sigma.data_ptr(), ctypes.POINTER(c_float)),
+                -1, flags, c_void_p(ws.data_ptr()), c_size_t(ws.numel()), self._stream()), self._handle)
+        self._status()
+        res, r0 = [], 0
+        for c, nd, n in zip(chans, dims, lens):
+            o = out[r0:r0 + c, :n]
+            r0 += c
+            res.append(o[0] if nd == 1 else o)
+        return res
+
     def _segments_workspace(self, B, L, need):
         """The workspace of enhance_long: one buffer kept for re-use (outside the per-batch-size cache of `enhance`)."""
         cur = getattr(self, "_seg_ws", None)
