@@ -23,6 +23,7 @@ thread_local std::string g_last_error;
 constexpr int kMaxSteps = 256;
 constexpr size_t kProfSlots = 32768;
 constexpr float kInvSqrt2 = 0.70710678118654752440f;
+constexpr size_t align256(size_t bytes) { return (bytes + 255) & ~size_t(255); }  // granularity of every workspace area
 
 struct TensorRef {
   size_t off;  // bytes into the workspace
@@ -208,7 +209,7 @@ struct Runner {
   }
 
   float* alloc_raw(size_t floats) {
-    size_t bytes = (floats * 4 + 255) & ~size_t(255);
+    size_t bytes = align256(floats * 4);
     size_t o = off;
     off += bytes;
     if (!dry && off > cap) { oom = true; return (float*)base; }
@@ -1292,124 +1293,259 @@ void fill_noise_plane(Runner& r, float* dst, long long cols, int n_rows, unsigne
   }
 }
 
-// ou_enhance / ou_enhance_var.  `t_raw`: host array of B row lengths (max = T_raw) or null (every row T_raw samples long).
-int enhance_impl(ou_handle* h, const float* mix, float* out, const float* noise, int32_t B, int32_t T_raw,
-                 const int32_t* t_raw, int32_t n_steps, double epsilon, const float* sigma_host, int32_t warm_start,
-                 uint32_t flags, void* ws, size_t ws_bytes, ou_stream_t stream) {
-  if (!h || !mix || !out || !ws || B < 1 || T_raw < 1) return fail(h, OU_EINVAL, "bad argument");
-  if (t_raw) {
-    int mx = 0;
-    bool all_whole = true;
-    for (int b = 0; b < B; b++) {
-      if (t_raw[b] < 1 || t_raw[b] > T_raw) return fail(h, OU_EINVAL, "ou_enhance_var: 1 <= t_raw[b] <= T_raw_max");
-      mx = t_raw[b] > mx ? t_raw[b] : mx;
-      all_whole = all_whole && t_raw[b] == T_raw;
-    }
-    if (mx != T_raw) return fail(h, OU_EINVAL, "ou_enhance_var: T_raw_max must be the length of the longest row");
-    if (all_whole) t_raw = nullptr;  // nothing ragged about this batch: the plain path (and its fused kernels)
+// ---- the pieces the enhance entry points share.  ou_enhance / ou_enhance_var, ou_enhance_ensemble,
+// ou_enhance_segments and ou_enhance_segments_var are these pieces plus what each adds of its own.
+
+// Per-row lengths of a ragged call: every one in [1, T_max] and the longest equal to T_max.  `collapse`: when no row is shorter,
+// `t_raw` becomes null -- nothing ragged about the batch: the plain path (and its fused kernels).
+template <typename Len>
+int check_rows(ou_handle* h, const char* who, char idx, const Len*& t_raw, int n, long long T_max, bool collapse) {
+  long long mx = 0;
+  bool all_whole = true;
+  for (int i = 0; i < n; i++) {
+    if (t_raw[i] < 1 || t_raw[i] > T_max) return fail(h, OU_EINVAL, std::string(who) + ": 1 <= t_raw[" + idx + "] <= T_raw_max");
+    mx = std::max<long long>(mx, t_raw[i]);
+    all_whole = all_whole && t_raw[i] == T_max;
   }
-  const bool use_aux = (flags & OU_ENH_USE_AUX_SIGNAL) != 0;
-  const bool saved_overlap = h->overlap;
-  struct OverlapGuard { ou_handle* h; bool v; ~OverlapGuard() { h->overlap = v; } } overlap_guard{h, saved_overlap};
-  // Side streams inside the call only when this is the one call on the device.  With several lanes (ou_set_lanes) every lane
-  // is ONE chain on its caller's stream: HIP multiplexes its streams onto a handful of hardware queues, and four lanes with
-  // four streams each alias there -- measured: 4 lanes 122 utt/s with side streams (87 % of the time ONE kernel on the
-  // device), 209 utt/s as four chains (serial loop: 132).
-  if ((flags & OU_ENH_SERIAL) || h->lanes > 1) h->overlap = false;
+  if (mx != T_max) return fail(h, OU_EINVAL, std::string(who) + ": T_raw_max must be the length of the longest row");
+  if (collapse && all_whole) t_raw = nullptr;
+  return OU_OK;
+}
+
+// The caller's noise tensor against the handle's noise source (ou_set_noise_source): exactly one of them, and one stream id
+// per row (`rows_wording`: how the message names the rows).  `need_noise`: the call draws noise at all.
+int check_noise_source(ou_handle* h, const float* noise, int rows, const char* rows_wording, bool need_noise) {
   const bool counter = h->noise_src.on;
   if (counter && noise)
     return fail(h, OU_EINVAL, "a noise source is set on this handle (ou_set_noise_source): `noise` must be NULL");
-  if (counter && (int)h->noise_src.streams.size() != B)
-    return fail(h, OU_EINVAL, "noise source: n_streams (" + std::to_string(h->noise_src.streams.size()) +
-                                  ") must equal the rows of the call (" + std::to_string(B) + ")");
-  if (!use_aux && !noise && !counter) return fail(h, OU_EINVAL, "noise must be given");
+  if (counter && (int)h->noise_src.streams.size() != rows)
+    return fail(h, OU_EINVAL, "noise source: n_streams (" + std::to_string(h->noise_src.streams.size()) + ") must equal " +
+                                  rows_wording + std::to_string(rows) + ")");
+  if (need_noise && !noise && !counter) return fail(h, OU_EINVAL, "noise must be given");
+  return OU_OK;
+}
+int check_steps(ou_handle* h, int n_steps, int warm_start) {
   if (n_steps < 2 || n_steps > kMaxSteps) return fail(h, OU_EINVAL, "n_steps must be in [2, 256]");
   if (warm_start >= n_steps) return fail(h, OU_EINVAL, "warm_start must be < n_steps");
-  const Model& m = h->m;
-  const int tot = m.tot_ds;
-  const int pad = tot - T_raw % tot;  // universe.py:219-223 (a full block when already a multiple)
-  const int pad_left = pad / 2;
-  const int T = T_raw + pad;
-  {
-    const long long t_max = max_walk_length(h, use_aux || warm_start >= 0);
-    if (T > t_max)
-      return fail(h, OU_EINVAL, "input too long for one pass: " + std::to_string(T_raw) + " samples padded to " +
-                                    std::to_string(T) + " make a plane of the walk reach 2^32 bytes (at most " +
-                                    std::to_string(t_max) + " padded samples); ou_enhance_segments enhances it in windows");
-  }
-  if (!h->ws_ok(ws, ws_bytes, B, T))
-    return fail(h, OU_EINVAL, "workspace was not prepared by ou_workspace_init for this (B, T_raw + pad)");
-  if (counter && !use_aux && (!h->noise_src.scratch || h->noise_src.scratch_bytes < (size_t)2 * B * T * sizeof(float)))
-    return fail(h, OU_ENOMEM, "noise source: scratch too small: need " + std::to_string((size_t)2 * B * T * sizeof(float)) +
-                                  " bytes (ou_noise_scratch_bytes)");
-  h->tensors.clear();
-  h->n_launch = h->n_conv = 0;
-  h->ev_used = 0;
-  hipStream_t st = (hipStream_t)stream;
-  Runner r(h, ws, ws_bytes, false, st, B);
-  Persist P = layout_persist(r, T);
-  if (r.oom) return finish(h, r);
+  return OU_OK;
+}
+// counter mode: the two (rows, T) planes of the caller's scratch (`hint`: what the message says about its size)
+int check_noise_scratch(ou_handle* h, int rows, int T, const char* hint) {
+  const size_t need = (size_t)2 * rows * T * sizeof(float);
+  if (!h->noise_src.scratch || h->noise_src.scratch_bytes < need)
+    return fail(h, OU_ENOMEM, "noise source: scratch too small: need " + std::to_string(need) + " bytes (" + hint + ")");
+  return OU_OK;
+}
+// the length guard (max_walk_length) of the calls that take whole rows in one pass
+int check_walk_length(ou_handle* h, int T_raw, int T, bool need_wav, const char* advice) {
+  const long long t_max = max_walk_length(h, need_wav);
+  if (T > t_max)
+    return fail(h, OU_EINVAL, "input too long for one pass: " + std::to_string(T_raw) + " samples padded to " +
+                                  std::to_string(T) + " make a plane of the walk reach 2^32 bytes (at most " +
+                                  std::to_string(t_max) + " padded samples)" + advice);
+  return OU_OK;
+}
 
-  std::vector<float> sigma(n_steps);
-  double eta, beta;
-  schedule(m.cfg, n_steps, epsilon, sigma.data(), &eta, &beta);
-  if (sigma_host) std::memcpy(sigma.data(), sigma_host, sizeof(float) * n_steps);
-  std::vector<StepCoef> rows;
-  for (int n = 0; n < n_steps; n++)
-    rows.push_back(make_coef(m.cfg, sigma[n], n == n_steps - 1, eta, beta, n + 1 < n_steps ? sigma[n + 1] : 0.f));
-  upload_coefs(r, P.coef, rows);
-
-  if (t_raw) {
-    // per-row geometry and the rows' lengths on every level of the network: T, 2 T (the decoupling layer's up-sampled grid)
-    // and T / (r_0 .. r_i).  By value through kernel arguments: capturable, no host memory involved.
-    LevelSpec& lv = r.lv;
-    lv.n = 0;
-    auto add_level = [&](int num, int den) {
-      lv.num[lv.n] = num; lv.den[lv.n] = den; r.level_T[lv.n] = (int)((long long)T * num / den); lv.n++;
-    };
-    add_level(1, 1);
-    add_level(2, 1);
-    int cum = 1;
-    for (int i = 0; i < m.cfg.score.n_rates && lv.n < kMaxLenLevels; i++) { cum *= m.cfg.score.rate_factors[i]; add_level(1, cum); }
-    if (cum != tot) return fail(h, OU_EINVAL, "internal: rate factors do not multiply to the total down-sampling factor");
-    for (int off = 0; off < B; off += 64) {
-      RowBlock blk;
-      const int n = B - off < 64 ? B - off : 64;
-      for (int i = 0; i < 64; i++) blk.t_raw[i] = i < n ? t_raw[off + i] : 1;
-      r.chk(launch_upload_rows(P.rows, P.lens, blk, n, off, B, tot, lv, st), "upload rows");
-    }
-    r.ragged = true;
-    r.lens_dev = P.lens;
-    r.rows_dev = P.rows;
+// What a forward call does to the handle while it runs: the records of the previous call are dropped, and `serial` switches the
+// side streams off until the call returns.
+struct CallScope {
+  ou_handle* h;
+  bool saved_overlap;
+  CallScope(ou_handle* h_, bool serial) : h(h_), saved_overlap(h_->overlap) {
+    if (serial) h->overlap = false;
+    h->tensors.clear();
+    h->n_launch = h->n_conv = 0;
+    h->ev_used = 0;
   }
-  const float level = (float)std::pow(10.0, (double)m.cfg.level_db / 20.0);
-  // (launched behind the fork of the first score-encoder pass when there is one: the side stream's first kernel starts an event
-  // latency -- ~10 us -- after the fork, and this launch is what the device has to do in the meantime)
-  auto normalize = [&]() {
-    if (r.ragged) r.chk(launch_pad_normalize_var(mix, P.mixn.p, P.stats, P.rows, B, T_raw, T, level, st), "normalize");
-    else r.chk(launch_pad_normalize(mix, P.mixn.p, P.stats, B, T_raw, T, pad_left, level, st), "normalize");
+  ~CallScope() { h->overlap = saved_overlap; }
+  CallScope(const CallScope&) = delete;
+  CallScope& operator=(const CallScope&) = delete;
+};
+
+// A launch outside any walk, counted and reported as Runner::chk + finish do; false: it failed, enqueue nothing more.
+bool launched(ou_handle* h, hipError_t e, const char* w) {
+  h->n_launch++;
+  if (e == hipSuccess) return true;
+  fail(h, OU_EHIP, std::string("HIP error at ") + w + ": " + hipGetErrorString(e));
+  return false;
+}
+
+// The sampler's constants: the sigma schedule (the caller's table where given) and one StepCoef row per step.
+struct SamplerTables {
+  std::vector<float> sigma;
+  std::vector<StepCoef> coef;
+  SamplerTables(const ou_config& cfg, int n_steps, double epsilon, const float* sigma_host) : sigma(n_steps) {
+    double eta, beta;
+    schedule(cfg, n_steps, epsilon, sigma.data(), &eta, &beta);
+    if (sigma_host) std::memcpy(sigma.data(), sigma_host, sizeof(float) * n_steps);
+    for (int n = 0; n < n_steps; n++)
+      coef.push_back(make_coef(cfg, sigma[n], n == n_steps - 1, eta, beta, n + 1 < n_steps ? sigma[n + 1] : 0.f));
+  }
+  int n_steps() const { return (int)sigma.size(); }
+  void upload_coef(Runner& r, Persist& P) const { upload_coefs(r, P.coef, coef); }
+  // the FiLM rows of every step, from the uploaded coefficients (only a call that runs the score net needs them)
+  void upload_film(Runner& r, Persist& P) const {
+    const Model& m = r.h->m;
+    r.chk(launch_sigma_embed(P.coef, n_steps(), r.W(m.sigma.p_off), m.sigma.simple, m.sigma.n_rff, m.film.D, P.g, r.st), "sigma");
+    r.chk(launch_film(P.g, r.W(m.film.w_off), r.W(m.film.b_off), P.film, n_steps(), m.film.rows, m.film.D, r.st), "film");
+  }
+  void upload(Runner& r, Persist& P) const { upload_coef(r, P); upload_film(r, P); }
+};
+
+// Ragged walk: the levels on which rows have lengths of their own -- T, 2 T (the decoupling layer's up-sampled grid) and
+// T / (r_0 .. r_i).
+int set_levels(Runner& r, int T) {
+  const Model& m = r.h->m;
+  LevelSpec& lv = r.lv;
+  lv.n = 0;
+  auto add_level = [&](int num, int den) {
+    lv.num[lv.n] = num; lv.den[lv.n] = den; r.level_T[lv.n] = (int)((long long)T * num / den); lv.n++;
   };
-  bool normalized = false;
-  const size_t nBT = (size_t)B * T;
-  const int keep_rms = (flags & OU_ENH_KEEP_RMS) ? 1 : 0;
-  const int peak = (flags & OU_ENH_NO_PEAK_GUARD) ? 0 : 1;
-  const bool need_wav = use_aux || warm_start >= 0;
-  if (need_wav && (!m.dec.present || m.dec.act != OU_ACT_SNAKE))
-    return fail(h, OU_ENOTIMPL, "aux_to_wav needs the snake signal-decoupling layer (UNIVERSE++)");
-  const int n_start = warm_start >= 0 ? warm_start : 0;
-  // Counter mode: draw d (0: the initial draw, n + 1: z_n of the absolute step n) is filled into plane d & 1 of the scratch right
-  // in front of the launch that reads it, on the caller's stream -- the simplest place: the launches that read a plane are
-  // untouched, and at step n_start the fill runs beside the first score-encoder pass on its side stream.  Row b's positions are
-  // the columns of its own padded signal, the tail of a shorter row is 0.
-  auto noise_plane = [&](int draw) -> const float* {
-    float* dst = h->noise_src.scratch + (size_t)(draw & 1) * nBT;
-    fill_noise_plane(r, dst, T, B, h->noise_src.seed, draw, [&](int b, unsigned long long& sid, long long& t0, long long& len) {
-      sid = h->noise_src.streams[b];
+  add_level(1, 1);
+  add_level(2, 1);
+  int cum = 1;
+  for (int i = 0; i < m.cfg.score.n_rates && lv.n < kMaxLenLevels; i++) { cum *= m.cfg.score.rate_factors[i]; add_level(1, cum); }
+  if (cum != m.tot_ds) return fail(r.h, OU_EINVAL, "internal: rate factors do not multiply to the total down-sampling factor");
+  return OU_OK;
+}
+// Per-row geometry and the rows' lengths on the levels of set_levels for `n` rows of raw lengths `t_raw`.  By value through
+// kernel arguments: capturable, no host memory involved.
+void upload_row_lengths(Runner& r, RowInfo* rows_dst, int* lens_dst, const int32_t* t_raw, int n) {
+  for (int off = 0; off < n; off += 64) {
+    RowBlock blk;
+    const int k = n - off < 64 ? n - off : 64;
+    for (int i = 0; i < 64; i++) blk.t_raw[i] = i < k ? t_raw[off + i] : 1;
+    r.chk(launch_upload_rows(rows_dst, lens_dst, blk, k, off, n, r.h->m.tot_ds, r.lv, r.st), "upload rows");
+  }
+}
+
+// universe.py:219-223 + the level normalisation of `rows` inputs of T_raw samples (a ragged walk: of their own lengths) -> P.mixn
+void normalize(Runner& r, Persist& P, const float* mix, int rows, int T_raw, int T) {
+  const float level = (float)std::pow(10.0, (double)r.h->m.cfg.level_db / 20.0);
+  if (r.ragged) r.chk(launch_pad_normalize_var(mix, P.mixn.p, P.stats, P.rows, rows, T_raw, T, level, r.st), "normalize");
+  else r.chk(launch_pad_normalize(mix, P.mixn.p, P.stats, rows, T_raw, T, (T - T_raw) / 2, level, r.st), "normalize");
+}
+struct PostFlags {
+  int keep_rms, peak;
+  explicit PostFlags(uint32_t flags) : keep_rms((flags & OU_ENH_KEEP_RMS) ? 1 : 0), peak((flags & OU_ENH_NO_PEAK_GUARD) ? 0 : 1) {}
+};
+// unpad, de-normalise, keep_rms and the peak guard of `rows` rows of x -> out
+void post(Runner& r, Persist& P, const float* x, float* out, int rows, int T_raw, int T, PostFlags f) {
+  if (!r.ok()) return;
+  if (r.ragged) r.chk(launch_post_var(x, P.stats, out, P.rows, rows, T_raw, T, f.keep_rms, f.peak, r.st), "post");
+  else r.chk(launch_post(x, P.stats, out, rows, T_raw, T, (T - T_raw) / 2, f.keep_rms, f.peak, r.st), "post");
+}
+// the signal decoupling layer: P.aux -> P.wav for the rows of r (scratch from the walk's bump allocator)
+void decouple(Runner& r, Persist& P) {
+  const Model& m = r.h->m;
+  const int T = P.wav.T;
+  float* tmp = r.alloc_raw((size_t)r.B * m.C0 * 2 * T);
+  if (r.ok())
+    r.chk(launch_decoupling(P.aux.p, r.W(m.dec.alpha_off), r.W(m.dec.up_off), r.W(m.dec.down_off), r.W(m.dec.conv.w_off),
+                            r.W(m.dec.conv.b_off), tmp, P.wav.p, r.B, m.C0, T, r.st, r.lens_of(T), r.lens_of(2 * T)), "decoupling");
+}
+
+// Noise provider of the calls whose rows are whole signals: draw d is plane (d ? d - n_start : 0) of the caller's tensor, or --
+// counter mode -- filled into plane d & 1 of the scratch right in front of the launch that reads it, on the caller's stream (the
+// simplest place: the launches that read a plane are untouched, and at step n_start the fill runs beside the first score-encoder
+// pass on its side stream).  Row b's positions are the columns of its own padded signal, the tail of a shorter row is 0.
+// `t_raw`: raw length of every row of r, or null (all T).
+auto row_noise(Runner& r, const float* noise, int n_start, int T, const int32_t* t_raw) {
+  return [&r, noise, n_start, T, t_raw](int draw) -> const float* {
+    const ou_handle::NoiseSource& src = r.h->noise_src;
+    const size_t nBT = (size_t)r.B * T;
+    if (!src.on) return noise + (size_t)(draw ? draw - n_start : 0) * nBT;
+    float* dst = src.scratch + (size_t)(draw & 1) * nBT;
+    const int tot = r.h->m.tot_ds;
+    fill_noise_plane(r, dst, T, r.B, src.seed, draw, [&](int b, unsigned long long& sid, long long& t0, long long& len) {
+      sid = src.streams[b];
       t0 = 0;
       len = t_raw ? t_raw[b] + (tot - t_raw[b] % tot) : T;
     });
     return dst;
   };
+}
+
+// universe.py:325-327: x = sigma * z_0 (+ the warm start's signal).  `mask`: the plane may hold noise behind a row's own end.
+void init_x(Runner& r, Persist& P, const float* z0, const float* warm, float sigma, int T, bool mask) {
+  r.chk(launch_init_x(z0, warm, sigma, P.x.p, (size_t)r.B * T, r.st), "init x");
+  if (mask) r.mask(P.x);
+}
+// A first score-encoder pass that already ran on side stream 2 (ou_enhance's overlap with the conditioner): its results and
+// where its scratch ends.  Its init_x ran in front of it.
+struct FirstPass {
+  ScoreEnc E;
+  size_t off_after_enc = 0;
+};
+// The sampler loop (universe.py:325-343) over the rows of r, steps n_start .. N - 1, every step on the same scratch.  `z(draw)`
+// gives the noise plane of a draw -- 0: the initial noise, n + 1: z_n of step n -- and is called right in front of the launch
+// that reads the plane, so what it enqueues (a fill, a gather) keeps its place in the stream.
+template <typename NoiseFn>
+void sample(Runner& r, Persist& P, int T, const SamplerTables& tab, int n_start, const float* warm, bool mask_x0, NoiseFn z,
+            const FirstPass* first = nullptr) {
+  const Model& m = r.h->m;
+  const int n_steps = tab.n_steps();
+  if (!first) init_x(r, P, z(0), warm, tab.sigma[n_start], T, mask_x0);
+  const size_t step_mark = r.off;
+  for (int n = n_start; n < n_steps; n++) {
+    const float* zn = n == n_steps - 1 ? nullptr : z(n + 1);
+    const StepCoef* cf = P.coef + n;
+    const float* fr = P.film + (size_t)n * m.film.rows;
+    if (first && n == n_start) {
+      r.join(2, r.st);
+      r.off = first->off_after_enc;
+      run_score_dec(r, P, first->E, P.x.p, zn, P.x.p, OUT_UPDATE, cf, 0, fr, 0, T);
+    } else {
+      r.off = step_mark;
+      run_score(r, P, P.x.p, zn, P.x.p, OUT_UPDATE, cf, 0, fr, 0, T);
+    }
+    if (!r.ok()) break;
+  }
+}
+
+// ou_enhance / ou_enhance_var.  `t_raw`: host array of B row lengths (max = T_raw) or null (every row T_raw samples long).
+// Its own: the length guard, the dry walk for `mark`, the first score-encoder pass beside the conditioner, the use_aux exit.
+int enhance_impl(ou_handle* h, const float* mix, float* out, const float* noise, int32_t B, int32_t T_raw,
+                 const int32_t* t_raw, int32_t n_steps, double epsilon, const float* sigma_host, int32_t warm_start,
+                 uint32_t flags, void* ws, size_t ws_bytes, ou_stream_t stream) {
+  if (!h || !mix || !out || !ws || B < 1 || T_raw < 1) return fail(h, OU_EINVAL, "bad argument");
+  if (t_raw)
+    if (const int rc = check_rows(h, "ou_enhance_var", 'b', t_raw, B, T_raw, true)) return rc;
+  const bool use_aux = (flags & OU_ENH_USE_AUX_SIGNAL) != 0;
+  const bool counter = h->noise_src.on;
+  if (const int rc = check_noise_source(h, noise, B, "the rows of the call (", !use_aux)) return rc;
+  if (const int rc = check_steps(h, n_steps, warm_start)) return rc;
+  const Model& m = h->m;
+  const int T = T_raw + (m.tot_ds - T_raw % m.tot_ds);  // universe.py:219-223 (a full block when already a multiple)
+  const bool need_wav = use_aux || warm_start >= 0;
+  if (const int rc = check_walk_length(h, T_raw, T, need_wav, "; ou_enhance_segments enhances it in windows")) return rc;
+  if (!h->ws_ok(ws, ws_bytes, B, T))
+    return fail(h, OU_EINVAL, "workspace was not prepared by ou_workspace_init for this (B, T_raw + pad)");
+  if (counter && !use_aux)
+    if (const int rc = check_noise_scratch(h, B, T, "ou_noise_scratch_bytes")) return rc;
+  // Side streams inside the call only when this is the one call on the device.  With several lanes (ou_set_lanes) every lane
+  // is ONE chain on its caller's stream: HIP multiplexes its streams onto a handful of hardware queues, and four lanes with
+  // four streams each alias there -- measured: 4 lanes 122 utt/s with side streams (87 % of the time ONE kernel on the
+  // device), 209 utt/s as four chains (serial loop: 132).
+  CallScope scope(h, (flags & OU_ENH_SERIAL) || h->lanes > 1);
+  hipStream_t st = (hipStream_t)stream;
+  Runner r(h, ws, ws_bytes, false, st, B);
+  Persist P = layout_persist(r, T);
+  if (r.oom) return finish(h, r);
+
+  const SamplerTables tab(m.cfg, n_steps, epsilon, sigma_host);
+  tab.upload_coef(r, P);
+  if (t_raw) {
+    if (const int rc = set_levels(r, T)) return rc;
+    upload_row_lengths(r, P.rows, P.lens, t_raw, B);
+    r.ragged = true;
+    r.lens_dev = P.lens;
+    r.rows_dev = P.rows;
+  }
+  if (need_wav && (!m.dec.present || m.dec.act != OU_ACT_SNAKE))
+    return fail(h, OU_ENOTIMPL, "aux_to_wav needs the snake signal-decoupling layer (UNIVERSE++)");
+  const int n_start = warm_start >= 0 ? warm_start : 0;
+  auto z = row_noise(r, noise, n_start, T, t_raw);
 
   // Where the conditioner's scratch ends (= where the per-step score scratch starts): layout is a pure function of
   // (config, B, T), so a dry walk gives it before anything is launched.
@@ -1425,12 +1561,10 @@ int enhance_impl(ou_handle* h, const float* mix, float* out, const float* noise,
 
   // The first score-encoder pass (+ its GRU) does not depend on the conditioner: run it on side stream 2 while
   // the conditioner runs on the caller's stream (at batch 1 most CUs idle during the GRU passes of either).
-  ScoreEnc E0;
-  bool have_e0 = false;
-  size_t off_after_enc = 0;
+  FirstPass first;
+  bool have_first = false;
   if (!use_aux) {
-    r.chk(launch_sigma_embed(P.coef, n_steps, r.W(m.sigma.p_off), m.sigma.simple, m.sigma.n_rff, m.film.D, P.g, st), "sigma");
-    r.chk(launch_film(P.g, r.W(m.film.w_off), r.W(m.film.b_off), P.film, n_steps, m.film.rows, m.film.D, st), "film");
+    tab.upload_film(r, P);
     // (only when two GRU layers fit on the machine side by side: their clusters spin on each other's publishes and must
     // all be resident)
     const int share2 = Runner::gru_share_of(h->lanes, B, true);
@@ -1438,67 +1572,35 @@ int enhance_impl(ou_handle* h, const float* mix, float* out, const float* noise,
                          gru_ring_batch_cap(m.c_gru0.H, h->num_cu, share2, 0, B, h->lanes) >= 1;
     if (warm_start < 0 && h->overlap && gru_fit) {
       r.gru_shared = true;
-      r.chk(launch_init_x(counter ? noise_plane(0) : noise, nullptr, sigma[n_start], P.x.p, nBT, st), "init x");  // universe.py:325-327
-      r.mask(P.x);
+      init_x(r, P, z(0), nullptr, tab.sigma[n_start], T, true);
       const size_t save = r.off;
       r.fork(st, 2);
-      normalize();
-      normalized = true;
+      // (behind the fork: the side stream's first kernel starts an event latency -- ~10 us -- after the fork, and this launch is
+      // what the device has to do in the meantime)
+      normalize(r, P, mix, B, T_raw, T);
       r.st = h->aux[2];
       r.off = mark;
-      E0 = run_score_enc(r, P, P.x.p, P.coef + n_start, 0, P.film + (size_t)n_start * m.film.rows, 0, T);
-      off_after_enc = r.off;
+      first.E = run_score_enc(r, P, P.x.p, P.coef + n_start, 0, P.film + (size_t)n_start * m.film.rows, 0, T);
+      first.off_after_enc = r.off;
       r.st = st;
       r.off = save;
-      have_e0 = true;
+      have_first = true;
     }
   }
-  if (!normalized) normalize();
+  if (!have_first) normalize(r, P, mix, B, T_raw, T);
   run_condition(r, P, P.mixn.p, T);
   r.gru_shared = false;
   if (!r.dry && r.ok() && r.off != mark) return fail(h, OU_EINVAL, "internal: workspace layout mismatch");
   h->cond_B = r.ragged ? 0 : B;  // (the operator seams ou_score / ou_aux_to_wav take whole batches only)
   h->cond_T = T;
 
-  if (need_wav) {
-    float* tmp = r.alloc_raw((size_t)B * m.C0 * 2 * T);
-    if (r.ok())
-      r.chk(launch_decoupling(P.aux.p, r.W(m.dec.alpha_off), r.W(m.dec.up_off), r.W(m.dec.down_off),
-                              r.W(m.dec.conv.w_off), r.W(m.dec.conv.b_off), tmp, P.wav.p, B, m.C0, T, st, r.lens_of(T),
-                              r.lens_of(2 * T)), "decoupling");
-  }
-  auto post = [&](const float* x) {
-    if (!r.ok()) return;
-    if (r.ragged) r.chk(launch_post_var(x, P.stats, out, P.rows, B, T_raw, T, keep_rms, peak, st), "post");
-    else r.chk(launch_post(x, P.stats, out, B, T_raw, T, pad_left, keep_rms, peak, st), "post");
-  };
+  if (need_wav) decouple(r, P);
   if (use_aux) {
-    post(P.wav.p);
+    post(r, P, P.wav.p, out, B, T_raw, T, PostFlags(flags));
     return finish(h, r);
   }
-  // universe.py:325-331
-  if (!have_e0) {
-    r.chk(launch_init_x(counter ? noise_plane(0) : noise, warm_start >= 0 ? P.wav.p : nullptr, sigma[n_start], P.x.p, nBT, st),
-          "init x");
-    r.mask(P.x);
-  }
-  const size_t step_mark = r.off;
-  for (int n = n_start; n < n_steps; n++) {
-    const bool last = n == n_steps - 1;
-    const float* z = last ? nullptr : counter ? noise_plane(n + 1) : noise + (size_t)(n - n_start + 1) * nBT;
-    const StepCoef* cf = P.coef + n;
-    const float* fr = P.film + (size_t)n * m.film.rows;
-    if (n == n_start && have_e0) {
-      r.join(2, st);
-      r.off = off_after_enc;
-      run_score_dec(r, P, E0, P.x.p, z, P.x.p, OUT_UPDATE, cf, 0, fr, 0, T);
-    } else {
-      r.off = step_mark;  // every step re-uses the same scratch
-      run_score(r, P, P.x.p, z, P.x.p, OUT_UPDATE, cf, 0, fr, 0, T);
-    }
-    if (!r.ok()) break;
-  }
-  post(P.x.p);
+  sample(r, P, T, tab, n_start, warm_start >= 0 ? P.wav.p : nullptr, true, z, have_first ? &first : nullptr);
+  post(r, P, P.x.p, out, B, T_raw, T, PostFlags(flags));
   return finish(h, r);
 }
 }  // namespace
@@ -1528,19 +1630,18 @@ struct EnsArea {
   size_t lens_b, members, hist, total;
 };
 EnsArea ens_area(int B, int E, long long cols) {
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
   EnsArea a;
   size_t off = 0;
-  a.lens_b = off; off += al((size_t)B * kMaxLenLevels * 4);      // the conditioner's own [level][B] length table (ragged, shared)
-  a.members = off; off += al((size_t)E * B * (size_t)cols * 4);  // post-processed member planes (members_out == NULL)
-  a.hist = off; off += al(((size_t)B * E + B) * 4);              // signal median: histogram [B][E] + picks [B]
+  a.lens_b = off; off += align256((size_t)B * kMaxLenLevels * 4);      // the conditioner's own [level][B] length table (ragged, shared)
+  a.members = off; off += align256((size_t)E * B * (size_t)cols * 4);  // post-processed member planes (members_out == NULL)
+  a.hist = off; off += align256(((size_t)B * E + B) * 4);              // signal median: histogram [B][E] + picks [B]
   a.total = off;
   return a;
 }
 
-// ou_enhance_ensemble: the walk of enhance_impl as ONE chain on the caller's stream for the E * B member rows, with the
-// conditioner (and, for a warm start, the decoupling layer) run once over the B inputs and replicated -- ens_share = 0: run
-// over all E * B rows --, the post step per member row and the reduce over the members.
+// ou_enhance_ensemble: the shared pieces as ONE chain on the caller's stream for the E * B member rows.  Its own: the area
+// behind the persistent block, the conditioner (and, for a warm start, the decoupling layer) run once over the B inputs on a
+// second runner and replicated -- ens_share = 0: run over all E * B rows --, the post step per member row and the reduce.
 int ensemble_impl(ou_handle* h, const float* mix, float* out, float* members_out, const float* noise, int32_t B, int32_t T_raw,
                   const int32_t* t_raw, int32_t E, int32_t stat, int32_t n_steps, double epsilon, const float* sigma_host,
                   int32_t warm_start, uint32_t flags, void* ws, size_t ws_bytes, ou_stream_t stream) {
@@ -1552,53 +1653,22 @@ int ensemble_impl(ou_handle* h, const float* mix, float* out, float* members_out
   if (flags & OU_ENH_USE_AUX_SIGNAL)
     return fail(h, OU_EINVAL, "ou_enhance_ensemble: OU_ENH_USE_AUX_SIGNAL is refused (without noise all members are equal)");
   if ((long long)E * B > 0x7fffffffll / 64) return fail(h, OU_EINVAL, "ou_enhance_ensemble: too many rows");
-  if (t_raw) {
-    int mx = 0;
-    bool all_whole = true;
-    for (int b = 0; b < B; b++) {
-      if (t_raw[b] < 1 || t_raw[b] > T_raw) return fail(h, OU_EINVAL, "ou_enhance_ensemble: 1 <= t_raw[b] <= T_raw_max");
-      mx = t_raw[b] > mx ? t_raw[b] : mx;
-      all_whole = all_whole && t_raw[b] == T_raw;
-    }
-    if (mx != T_raw) return fail(h, OU_EINVAL, "ou_enhance_ensemble: T_raw_max must be the length of the longest row");
-    if (all_whole) t_raw = nullptr;  // nothing ragged about this batch: the plain path (and its fused kernels)
-  }
+  if (t_raw)
+    if (const int rc = check_rows(h, "ou_enhance_ensemble", 'b', t_raw, B, T_raw, true)) return rc;
   const int EB = E * B;
-  const bool counter = h->noise_src.on;
-  if (counter && noise)
-    return fail(h, OU_EINVAL, "a noise source is set on this handle (ou_set_noise_source): `noise` must be NULL");
-  if (counter && (int)h->noise_src.streams.size() != EB)
-    return fail(h, OU_EINVAL, "noise source: n_streams (" + std::to_string(h->noise_src.streams.size()) +
-                                  ") must equal the member rows of the call (E * B = " + std::to_string(EB) + ")");
-  if (!noise && !counter) return fail(h, OU_EINVAL, "noise must be given");
-  if (n_steps < 2 || n_steps > kMaxSteps) return fail(h, OU_EINVAL, "n_steps must be in [2, 256]");
-  if (warm_start >= n_steps) return fail(h, OU_EINVAL, "warm_start must be < n_steps");
+  if (const int rc = check_noise_source(h, noise, EB, "the member rows of the call (E * B = ", true)) return rc;
+  if (const int rc = check_steps(h, n_steps, warm_start)) return rc;
   const Model& m = h->m;
-  const int tot = m.tot_ds;
-  const int pad = tot - T_raw % tot;  // universe.py:219-223 (a full block when already a multiple)
-  const int pad_left = pad / 2;
-  const int T = T_raw + pad;
+  const int T = T_raw + (m.tot_ds - T_raw % m.tot_ds);  // universe.py:219-223 (a full block when already a multiple)
   const bool need_wav = warm_start >= 0;
-  {
-    const long long t_max = max_walk_length(h, need_wav);  // (per-row planes do not grow with E)
-    if (T > t_max)
-      return fail(h, OU_EINVAL, "input too long for one pass: " + std::to_string(T_raw) + " samples padded to " +
-                                    std::to_string(T) + " make a plane of the walk reach 2^32 bytes (at most " +
-                                    std::to_string(t_max) + " padded samples)");
-  }
+  if (const int rc = check_walk_length(h, T_raw, T, need_wav, "")) return rc;  // (per-row planes do not grow with E)
   if (!h->ws_ok(ws, ws_bytes, EB, T))
     return fail(h, OU_EINVAL, "workspace was not prepared by ou_workspace_init for this (E * B, T_raw + pad)");
-  if (counter && (!h->noise_src.scratch || h->noise_src.scratch_bytes < (size_t)2 * EB * T * sizeof(float)))
-    return fail(h, OU_ENOMEM, "noise source: scratch too small: need " + std::to_string((size_t)2 * EB * T * sizeof(float)) +
-                                  " bytes (ou_noise_scratch_bytes for E * B rows)");
+  if (h->noise_src.on)
+    if (const int rc = check_noise_scratch(h, EB, T, "ou_noise_scratch_bytes for E * B rows")) return rc;
   if (need_wav && (!m.dec.present || m.dec.act != OU_ACT_SNAKE))
     return fail(h, OU_ENOTIMPL, "aux_to_wav needs the snake signal-decoupling layer (UNIVERSE++)");
-  const bool saved_overlap = h->overlap;
-  struct OverlapGuard { ou_handle* h; bool v; ~OverlapGuard() { h->overlap = v; } } overlap_guard{h, saved_overlap};
-  h->overlap = false;  // one chain on the caller's stream (the conditioner || first-encoder overlap of ou_enhance is dropped)
-  h->tensors.clear();
-  h->n_launch = h->n_conv = 0;
-  h->ev_used = 0;
+  CallScope scope(h, true);  // one chain on the caller's stream (the conditioner || first-encoder overlap of ou_enhance is dropped)
   hipStream_t st = (hipStream_t)stream;
   const bool share = h->opt.ens_share != 0 && E > 1;
   const int Bc = share ? B : EB;  // rows of the conditioner pass
@@ -1614,14 +1684,8 @@ int ensemble_impl(ou_handle* h, const float* mix, float* out, float* members_out
   float* members = members_out ? members_out : (float*)(area + A.members);
   int* hist = (int*)(area + A.hist);
 
-  std::vector<float> sigma(n_steps);
-  double eta, beta;
-  schedule(m.cfg, n_steps, epsilon, sigma.data(), &eta, &beta);
-  if (sigma_host) std::memcpy(sigma.data(), sigma_host, sizeof(float) * n_steps);
-  std::vector<StepCoef> rows;
-  for (int n = 0; n < n_steps; n++)
-    rows.push_back(make_coef(m.cfg, sigma[n], n == n_steps - 1, eta, beta, n + 1 < n_steps ? sigma[n + 1] : 0.f));
-  upload_coefs(r, P.coef, rows);
+  const SamplerTables tab(m.cfg, n_steps, epsilon, sigma_host);
+  tab.upload_coef(r, P);
 
   Runner rc(h, ws, ws_bytes, false, st, Bc);  // the conditioner's runner: Bc rows on the prefix of the persistent tensors
   rc.status_words = r.status_words;
@@ -1632,61 +1696,37 @@ int ensemble_impl(ou_handle* h, const float* mix, float* out, float* members_out
     t_rep.resize(EB);
     for (int e = 0; e < E; e++)
       for (int b = 0; b < B; b++) t_rep[(size_t)e * B + b] = t_raw[b];
-    LevelSpec& lv = r.lv;
-    lv.n = 0;
-    auto add_level = [&](int num, int den) {
-      lv.num[lv.n] = num; lv.den[lv.n] = den; r.level_T[lv.n] = (int)((long long)T * num / den); lv.n++;
-    };
-    add_level(1, 1);
-    add_level(2, 1);
-    int cum = 1;
-    for (int i = 0; i < m.cfg.score.n_rates && lv.n < kMaxLenLevels; i++) { cum *= m.cfg.score.rate_factors[i]; add_level(1, cum); }
-    if (cum != tot) return fail(h, OU_EINVAL, "internal: rate factors do not multiply to the total down-sampling factor");
+    if (const int rc2 = set_levels(r, T)) return rc2;
     // E copies of the per-row geometry for the sampler loop; the length table is [level][rows], so the conditioner's B-row pass
     // gets a table of its own ([level][B]; the RowInfo entries of rows 0 .. B - 1 serve both)
-    auto upload = [&](RowInfo* rows_dst, int* lens_dst, const int32_t* tr, int nrows) {
-      for (int off = 0; off < nrows; off += 64) {
-        RowBlock blk;
-        const int n = nrows - off < 64 ? nrows - off : 64;
-        for (int i = 0; i < 64; i++) blk.t_raw[i] = i < n ? tr[off + i] : 1;
-        r.chk(launch_upload_rows(rows_dst, lens_dst, blk, n, off, nrows, tot, lv, st), "upload rows");
-      }
-    };
-    upload(P.rows, P.lens, t_rep.data(), EB);
+    upload_row_lengths(r, P.rows, P.lens, t_rep.data(), EB);
     r.ragged = true;
     r.lens_dev = P.lens;
     r.rows_dev = P.rows;
     rc.ragged = true;
     rc.rows_dev = P.rows;
-    rc.lv = lv;
+    rc.lv = r.lv;
     for (int l = 0; l < kMaxLenLevels; l++) rc.level_T[l] = r.level_T[l];
-    if (share) {
-      // (its RowInfo output goes to rows 0 .. B - 1 of P.rows once more: the same values)
-      upload(P.rows, lens_b, t_raw, B);
-      rc.lens_dev = lens_b;
-    } else {
-      rc.lens_dev = P.lens;
-    }
+    // (its RowInfo output goes to rows 0 .. B - 1 of P.rows once more: the same values)
+    if (share) upload_row_lengths(r, P.rows, lens_b, t_raw, B);
+    rc.lens_dev = share ? lens_b : P.lens;
   }
-  r.chk(launch_sigma_embed(P.coef, n_steps, r.W(m.sigma.p_off), m.sigma.simple, m.sigma.n_rff, m.film.D, P.g, st), "sigma");
-  r.chk(launch_film(P.g, r.W(m.film.w_off), r.W(m.film.b_off), P.film, n_steps, m.film.rows, m.film.D, st), "film");
+  tab.upload_film(r, P);
 
   // ---- pad + normalise the B inputs (one workgroup per row: what the replicated batch would give, bit for bit)
-  const float level = (float)std::pow(10.0, (double)m.cfg.level_db / 20.0);
-  if (r.ragged) r.chk(launch_pad_normalize_var(mix, P.mixn.p, P.stats, P.rows, B, T_raw, T, level, st), "normalize");
-  else r.chk(launch_pad_normalize(mix, P.mixn.p, P.stats, B, T_raw, T, pad_left, level, st), "normalize");
+  normalize(r, P, mix, B, T_raw, T);
   // Replication: rows [0, B) of a tensor laid out for E * B rows -> rows [e B, (e + 1) B), up to 16 tensors per launch
-  ReplicateTable tab;
+  ReplicateTable tab_rep;
   int n_tab = 0;
   auto flush_tab = [&]() {
-    if (n_tab && r.ok()) r.chk(launch_replicate_rows(tab, n_tab, E, st), "replicate rows");
+    if (n_tab && r.ok()) r.chk(launch_replicate_rows(tab_rep, n_tab, E, st), "replicate rows");
     n_tab = 0;
   };
   auto replicate = [&](void* p, size_t words_per_b_rows) {
     if (E == 1) return;
     if (n_tab == kReplicateEntries) flush_tab();
-    tab.p[n_tab] = (unsigned*)p;
-    tab.n[n_tab] = (long long)words_per_b_rows;
+    tab_rep.p[n_tab] = (unsigned*)p;
+    tab_rep.n[n_tab] = (long long)words_per_b_rows;
     n_tab++;
   };
   auto replicate_t = [&](const Tensor& t) { replicate(t.p, (size_t)B * t.C * t.T); };
@@ -1701,13 +1741,7 @@ int ensemble_impl(ou_handle* h, const float* mix, float* out, float* members_out
   run_condition(rc, P, P.mixn.p, T);
   h->cond_B = 0;  // (the operator seams ou_score / ou_aux_to_wav do not take this layout)
   h->cond_T = T;
-  if (need_wav) {
-    float* tmp = rc.alloc_raw((size_t)Bc * m.C0 * 2 * T);
-    if (rc.ok())
-      rc.chk(launch_decoupling(P.aux.p, rc.W(m.dec.alpha_off), rc.W(m.dec.up_off), rc.W(m.dec.down_off),
-                               rc.W(m.dec.conv.w_off), rc.W(m.dec.conv.b_off), tmp, P.wav.p, Bc, m.C0, T, st, rc.lens_of(T),
-                               rc.lens_of(2 * T)), "decoupling");
-  }
+  if (need_wav) decouple(rc, P);
   if (!rc.ok()) return finish(h, rc);
   if (share) {
     for (size_t j = 0; j < P.cond.size(); j++) { replicate_t(P.cond[j]); replicate_t(P.sc[j]); }
@@ -1720,37 +1754,14 @@ int ensemble_impl(ou_handle* h, const float* mix, float* out, float* members_out
     flush_tab();
   }
 
-  // ---- the sampler loop at E * B rows, as enhance_impl runs it without the first-encoder overlap
+  // ---- the sampler loop at E * B rows
   r.off = rc.off;
-  const size_t nBT = (size_t)EB * T;
-  const int n_start = warm_start >= 0 ? warm_start : 0;
-  auto noise_plane = [&](int draw) -> const float* {
-    float* dst = h->noise_src.scratch + (size_t)(draw & 1) * nBT;
-    fill_noise_plane(r, dst, T, EB, h->noise_src.seed, draw, [&](int row, unsigned long long& sid, long long& t0, long long& len) {
-      sid = h->noise_src.streams[row];
-      t0 = 0;
-      len = t_raw ? t_rep[row] + (tot - t_rep[row] % tot) : T;
-    });
-    return dst;
-  };
-  r.chk(launch_init_x(counter ? noise_plane(0) : noise, warm_start >= 0 ? P.wav.p : nullptr, sigma[n_start], P.x.p, nBT, st),
-        "init x");  // universe.py:325-331
-  r.mask(P.x);
-  const size_t step_mark = r.off;
-  for (int n = n_start; n < n_steps; n++) {
-    const bool last = n == n_steps - 1;
-    const float* z = last ? nullptr : counter ? noise_plane(n + 1) : noise + (size_t)(n - n_start + 1) * nBT;
-    r.off = step_mark;  // every step re-uses the same scratch
-    run_score(r, P, P.x.p, z, P.x.p, OUT_UPDATE, P.coef + n, 0, P.film + (size_t)n * m.film.rows, 0, T);
-    if (!r.ok()) break;
-  }
+  const int n_start = need_wav ? warm_start : 0;
+  sample(r, P, T, tab, n_start, need_wav ? P.wav.p : nullptr, true, row_noise(r, noise, n_start, T, t_raw ? t_rep.data() : nullptr));
   if (!r.ok()) return finish(h, r);
 
   // ---- per member row: unpad, keep_rms (the mix RMS of the member's own input: stats row e B + b = row b), peak guard
-  const int keep_rms = (flags & OU_ENH_KEEP_RMS) ? 1 : 0;
-  const int peak = (flags & OU_ENH_NO_PEAK_GUARD) ? 0 : 1;
-  if (r.ragged) r.chk(launch_post_var(P.x.p, P.stats, members, P.rows, EB, T_raw, T, keep_rms, peak, st), "post");
-  else r.chk(launch_post(P.x.p, P.stats, members, EB, T_raw, T, pad_left, keep_rms, peak, st), "post");
+  post(r, P, P.x.p, members, EB, T_raw, T, PostFlags(flags));
   // ---- reduce over the members
   std::vector<long long> len64;
   if (t_raw) len64.assign(t_raw, t_raw + B);
@@ -1773,7 +1784,7 @@ int ou_ensemble_workspace_bytes(const ou_handle* hc, int32_t B, int32_t T_pad_ma
   const int rc = ou_workspace_bytes(h, E * B, T_pad_max, &walk);
   if (rc != OU_OK) return rc;
   // (T_pad_max bounds T_raw_max: the member planes are (E * B, T_raw_max))
-  *nbytes = ((walk + 255) & ~size_t(255)) + ens_area(B, E, T_pad_max).total;
+  *nbytes = align256(walk) + ens_area(B, E, T_pad_max).total;
   return OU_OK;
 }
 
@@ -1787,7 +1798,7 @@ int ou_enhance_ensemble(ou_handle* h, const float* mix, float* out, float* membe
 
 size_t ou_ensemble_reduce_scratch_bytes(int32_t E, int32_t B) {
   if (E < 1 || B < 1) return 0;
-  return (((size_t)B * E + B) * sizeof(int) + 255) & ~size_t(255);
+  return align256(((size_t)B * E + B) * sizeof(int));
 }
 
 int ou_ensemble_reduce(const float* members, float* out, int32_t E, int32_t B, int64_t row_stride, int64_t cols,
@@ -1852,14 +1863,13 @@ struct SegArea {
   size_t stats, row_scale, part, zbuf, carry, total;
 };
 SegArea seg_area(int C, int B, long long L) {
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
   SegArea a;
   size_t off = 0;
-  a.stats = off; off += al((size_t)C * 4 * 4);
-  a.row_scale = off; off += al((size_t)C * 4);
-  a.part = off; off += al((size_t)C * 1024 * 3 * 8);
-  a.zbuf = off; off += al((size_t)B * L * 4);
-  a.carry = off; off += al((size_t)L * 4);
+  a.stats = off; off += align256((size_t)C * 4 * 4);
+  a.row_scale = off; off += align256((size_t)C * 4);
+  a.part = off; off += align256((size_t)C * 1024 * 3 * 8);
+  a.zbuf = off; off += align256((size_t)B * L * 4);
+  a.carry = off; off += align256((size_t)L * 4);
   a.total = off;
   return a;
 }
@@ -1930,7 +1940,7 @@ SegVarArea seg_var_area(int C, int B, long long L) {
   SegVarArea v;
   v.a = seg_area(C, B, L);
   v.geom = v.a.total;
-  v.total = v.geom + (((size_t)C * sizeof(SegRow) + 255) & ~size_t(255));
+  v.total = v.geom + align256((size_t)C * sizeof(SegRow));
   return v;
 }
 }  // namespace
@@ -1973,7 +1983,7 @@ int ou_segments_workspace_bytes(const ou_handle* hc, int32_t C, int64_t T_raw, i
   size_t walk = 0;
   const int rc = ou_workspace_bytes(h, B, (int32_t)p.g.L, &walk);
   if (rc != OU_OK) return rc;
-  walk = (walk + 255) & ~size_t(255);
+  walk = align256(walk);
   *nbytes = walk + seg_area(C, B, p.g.L).total;
   if (batch) *batch = B;
   if (length) *length = (int32_t)p.g.L;
@@ -1985,16 +1995,10 @@ int ou_enhance_segments(ou_handle* h, const float* mix, float* out, const float*
                         const float* sigma_host, int32_t warm_start, uint32_t flags, void* ws, size_t ws_bytes,
                         ou_stream_t stream) {
   if (!h || !mix || !out || !ws || C < 1 || T_raw < 1 || max_batch < 1) return fail(h, OU_EINVAL, "bad argument");
-  const bool counter = h->noise_src.on;
-  if (counter && noise)
-    return fail(h, OU_EINVAL, "a noise source is set on this handle (ou_set_noise_source): `noise` must be NULL");
-  if (counter && (int)h->noise_src.streams.size() != C)
-    return fail(h, OU_EINVAL, "noise source: n_streams (" + std::to_string(h->noise_src.streams.size()) +
-                                  ") must equal the rows of the call (" + std::to_string(C) + ")");
-  if (!counter && !noise) return fail(h, OU_EINVAL, "noise must be given");
+  if (const int rc = check_noise_source(h, noise, C, "the rows of the call (", true)) return rc;
   if (warm_start >= 0 || (flags & OU_ENH_USE_AUX_SIGNAL))
     return fail(h, OU_EINVAL, "ou_enhance_segments: warm_start and use_aux_signal are not supported");
-  if (n_steps < 2 || n_steps > kMaxSteps) return fail(h, OU_EINVAL, "n_steps must be in [2, 256]");
+  if (const int rc = check_steps(h, n_steps, warm_start)) return rc;
   SegPlan plan;
   if (!seg_plan(h->m.tot_ds, T_raw, segment, overlap, plan)) return fail(h, OU_EINVAL, plan.err);
   SegGeom g = plan.g;
@@ -2004,11 +2008,8 @@ int ou_enhance_segments(ou_handle* h, const float* mix, float* out, const float*
   const int B = seg_batch(g.n_entries, max_batch);
   const int L = (int)g.L;
   size_t walk = 0;
-  {
-    const int rc = ou_workspace_bytes(h, B, L, &walk);
-    if (rc != OU_OK) return rc;
-    walk = (walk + 255) & ~size_t(255);
-  }
+  if (const int rc = ou_workspace_bytes(h, B, L, &walk)) return rc;
+  walk = align256(walk);
   const SegArea A = seg_area(C, B, g.L);
   if (ws_bytes < walk + A.total) return fail(h, OU_ENOMEM, "workspace too small: need " + std::to_string(walk + A.total) +
                                                                " bytes (ou_segments_workspace_bytes)");
@@ -2021,12 +2022,7 @@ int ou_enhance_segments(ou_handle* h, const float* mix, float* out, const float*
   float* zbuf = (float*)(seg + A.zbuf);
   float* carry = (float*)(seg + A.carry);
 
-  const bool saved_overlap = h->overlap;
-  struct OverlapGuard { ou_handle* h; bool v; ~OverlapGuard() { h->overlap = v; } } overlap_guard{h, saved_overlap};
-  h->overlap = false;  // one chain on the caller's stream
-  h->tensors.clear();
-  h->n_launch = h->n_conv = 0;
-  h->ev_used = 0;
+  CallScope scope(h, true);  // one chain on the caller's stream
   hipStream_t st = (hipStream_t)stream;
   const Model& m = h->m;
 
@@ -2034,52 +2030,32 @@ int ou_enhance_segments(ou_handle* h, const float* mix, float* out, const float*
   const float level = (float)std::pow(10.0, (double)m.cfg.level_db / 20.0);
   const long long Lf = g.T_pad / m.tot_ds;  // mel frames of the whole file (run_condition)
   if (Lf > g.T_raw) return fail(h, OU_EINVAL, "internal: mel frames do not fit into the output row");
-  auto chk = [&](hipError_t e, const char* w) -> bool {
-    h->n_launch++;
-    if (e != hipSuccess) { fail(h, OU_EHIP, std::string("HIP error at ") + w + ": " + hipGetErrorString(e)); return false; }
-    return true;
-  };
-  if (!chk(launch_seg_stats(mix, part, stats, C, g.T_raw, g.T_pad, level, st), "segment stats")) return OU_EHIP;
-  if (!chk(launch_seg_mel_energy(mix, stats, h->W + m.mel.win_off, h->W + m.mel.tw_off, h->W + m.mel.fb_off, out, C, g.T_raw,
-                                 g.T_pad, g.pad_left, m.mel.n_fft, m.mel.hop, m.mel.pad_left, m.mel.n_freq, m.mel.n_mels, Lf,
-                                 st), "segment mel energy"))
+  if (!launched(h, launch_seg_stats(mix, part, stats, C, g.T_raw, g.T_pad, level, st), "segment stats")) return OU_EHIP;
+  if (!launched(h, launch_seg_mel_energy(mix, stats, h->W + m.mel.win_off, h->W + m.mel.tw_off, h->W + m.mel.fb_off, out, C,
+                                         g.T_raw, g.T_pad, g.pad_left, m.mel.n_fft, m.mel.hop, m.mel.pad_left, m.mel.n_freq,
+                                         m.mel.n_mels, Lf, st), "segment mel energy"))
     return OU_EHIP;
   if (Lf > 0x7fffffffll) return fail(h, OU_EINVAL, "input too long");
-  if (!chk(launch_mel_scale(out, row_scale, C, (int)Lf, st), "segment mel scale")) return OU_EHIP;
+  if (!launched(h, launch_mel_scale(out, row_scale, C, (int)Lf, st), "segment mel scale")) return OU_EHIP;
 
-  // ---- sampler constants (as ou_enhance)
-  std::vector<float> sigma(n_steps);
-  double eta, beta;
-  schedule(m.cfg, n_steps, epsilon, sigma.data(), &eta, &beta);
-  if (sigma_host) std::memcpy(sigma.data(), sigma_host, sizeof(float) * n_steps);
-  std::vector<StepCoef> rows;
-  for (int n = 0; n < n_steps; n++)
-    rows.push_back(make_coef(m.cfg, sigma[n], n == n_steps - 1, eta, beta, n + 1 < n_steps ? sigma[n + 1] : 0.f));
-
-  // ---- the windows, B at a time, through the plain walk of ou_enhance
-  const size_t nBL = (size_t)B * L;
+  // ---- the windows, B at a time, through the plain walk
+  const SamplerTables tab(m.cfg, n_steps, epsilon, sigma_host);
   const size_t step_noise = (size_t)C * g.T_pad;  // one step of the whole-file noise
-  bool coefs_up = false;
   for (long long e0 = 0; e0 < g.n_entries; e0 += B) {
     const int n_real = (int)std::min<long long>(B, g.n_entries - e0);
     Runner r(h, ws, walk, false, st, B);
     r.mel_scale_preset = true;
     Persist P = layout_persist(r, L);
     if (r.oom) return finish(h, r);
-    if (!coefs_up) {  // (the persistent area of the workspace keeps them from group to group)
-      upload_coefs(r, P.coef, rows);
-      r.chk(launch_sigma_embed(P.coef, n_steps, r.W(m.sigma.p_off), m.sigma.simple, m.sigma.n_rff, m.film.D, P.g, st), "sigma");
-      r.chk(launch_film(P.g, r.W(m.film.w_off), r.W(m.film.b_off), P.film, n_steps, m.film.rows, m.film.D, st), "film");
-      coefs_up = true;
-    }
+    if (e0 == 0) tab.upload(r, P);  // (the persistent area of the workspace keeps the tables from group to group)
     r.chk(launch_seg_gather_input(mix, stats, row_scale, P.mixn.p, P.mel_scale, g, e0, B, st), "segment gather");
     run_condition(r, P, P.mixn.p, L);
     // One step's noise of the group's windows: a slice of the caller's whole-row tensor, or -- counter mode -- the same
     // positions (window k of row c: t = s_k + i, stream of row c) straight from the function; no whole-row noise exists then.
-    auto step_noise_plane = [&](int draw) {
-      if (!counter) {
-        r.chk(launch_seg_gather_noise(noise + (size_t)draw * step_noise, zbuf, g, e0, B, st), "segment noise");
-        return;
+    auto z = [&](int draw) -> const float* {
+      if (noise) {
+        if (r.ok()) r.chk(launch_seg_gather_noise(noise + (size_t)draw * step_noise, zbuf, g, e0, B, st), "segment noise");
+        return zbuf;
       }
       fill_noise_plane(r, zbuf, L, B, h->noise_src.seed, draw, [&](int j, unsigned long long& sid, long long& t0, long long& len) {
         const long long e = std::min<long long>(e0 + j, g.n_entries - 1);  // (the filler rows of a short last group)
@@ -2088,27 +2064,18 @@ int ou_enhance_segments(ou_handle* h, const float* mix, float* out, const float*
         t0 = seg_start_host(g, e - c * g.n_win);
         len = L;
       });
+      return zbuf;
     };
-    step_noise_plane(0);
-    r.chk(launch_init_x(zbuf, nullptr, sigma[0], P.x.p, nBL, st), "init x");  // universe.py:325-327
-    const size_t step_mark = r.off;
-    for (int n = 0; n < n_steps && r.ok(); n++) {
-      const bool last = n == n_steps - 1;
-      if (!last) step_noise_plane(n + 1);
-      r.off = step_mark;
-      run_score(r, P, P.x.p, last ? nullptr : zbuf, P.x.p, OUT_UPDATE, P.coef + n, 0, P.film + (size_t)n * m.film.rows, 0, L);
-    }
+    sample(r, P, L, tab, 0, nullptr, false, z);
     if (r.ok()) r.chk(launch_seg_stitch(P.x.p, carry, out, g, e0, n_real, st), "segment stitch");
     if (r.ok() && e0 + B < g.n_entries)  // the window in front of the next group
       r.chk(hipMemcpyAsync(carry, P.x.p + (size_t)(n_real - 1) * L, (size_t)L * 4, hipMemcpyDeviceToDevice, st), "carry");
-    const int rc = finish(h, r);
-    if (rc != OU_OK) return rc;
+    if (const int rc = finish(h, r)) return rc;
   }
   h->cond_B = 0;  // (the operator seams see a whole-file batch only)
   h->cond_T = L;
-  const int keep_rms = (flags & OU_ENH_KEEP_RMS) ? 1 : 0;
-  const int peak = (flags & OU_ENH_NO_PEAK_GUARD) ? 0 : 1;
-  if (!chk(launch_seg_post(out, part, stats, C, g.T_raw, keep_rms, peak, st), "segment post")) return OU_EHIP;
+  const PostFlags pf(flags);
+  if (!launched(h, launch_seg_post(out, part, stats, C, g.T_raw, pf.keep_rms, pf.peak, st), "segment post")) return OU_EHIP;
   return OU_OK;
 }
 
@@ -2145,7 +2112,7 @@ int ou_segments_var_workspace_bytes(const ou_handle* hc, int32_t C, const int64_
   size_t walk = 0;
   const int rc = ou_workspace_bytes(h, G.batch, (int32_t)G.length, &walk);
   if (rc != OU_OK) return rc;
-  walk = (walk + 255) & ~size_t(255);
+  walk = align256(walk);
   *nbytes = walk + seg_var_area(C, G.batch, G.length).total;
   if (batch) *batch = G.batch;
   if (length) *length = (int32_t)G.length;
@@ -2159,25 +2126,12 @@ int ou_enhance_segments_var(ou_handle* h, const float* mix, float* out, const fl
   // (the lengths first: what they decide needs neither the handle nor a device)
   if (!t_raw || C < 1 || C > 65535 || T_raw_max < 1) return fail(h, OU_EINVAL, "bad argument");
   if (max_batch < 1) return fail(h, OU_EINVAL, "ou_enhance_segments_var: max_batch must be at least 1");
-  {
-    long long mx = 0;
-    for (int c = 0; c < C; c++) {
-      if (t_raw[c] < 1 || t_raw[c] > T_raw_max) return fail(h, OU_EINVAL, "ou_enhance_segments_var: 1 <= t_raw[c] <= T_raw_max");
-      mx = std::max<long long>(mx, t_raw[c]);
-    }
-    if (mx != T_raw_max) return fail(h, OU_EINVAL, "ou_enhance_segments_var: T_raw_max must be the length of the longest row");
-  }
+  if (const int rc = check_rows(h, "ou_enhance_segments_var", 'c', t_raw, C, T_raw_max, false)) return rc;
   if (!h || !mix || !out || !ws) return fail(h, OU_EINVAL, "bad argument");
-  const bool counter = h->noise_src.on;
-  if (counter && noise)
-    return fail(h, OU_EINVAL, "a noise source is set on this handle (ou_set_noise_source): `noise` must be NULL");
-  if (counter && (int)h->noise_src.streams.size() != C)
-    return fail(h, OU_EINVAL, "noise source: n_streams (" + std::to_string(h->noise_src.streams.size()) +
-                                  ") must equal the rows of the call (" + std::to_string(C) + ")");
-  if (!counter && !noise) return fail(h, OU_EINVAL, "noise must be given");
+  if (const int rc = check_noise_source(h, noise, C, "the rows of the call (", true)) return rc;
   if (warm_start >= 0 || (flags & OU_ENH_USE_AUX_SIGNAL))
     return fail(h, OU_EINVAL, "ou_enhance_segments_var: warm_start and use_aux_signal are not supported");
-  if (n_steps < 2 || n_steps > kMaxSteps) return fail(h, OU_EINVAL, "n_steps must be in [2, 256]");
+  if (const int rc = check_steps(h, n_steps, warm_start)) return rc;
   const Model& m = h->m;
   const int tot = m.tot_ds;
   SegGroups G;
@@ -2186,11 +2140,8 @@ int ou_enhance_segments_var(ou_handle* h, const float* mix, float* out, const fl
     return fail(h, OU_EINVAL, "ou_enhance_segments_var: segment too long for one pass of the walk");
   const int B = G.batch;
   size_t walk = 0;
-  {
-    const int rc = ou_workspace_bytes(h, B, (int32_t)G.length, &walk);
-    if (rc != OU_OK) return rc;
-    walk = (walk + 255) & ~size_t(255);
-  }
+  if (const int rc = ou_workspace_bytes(h, B, (int32_t)G.length, &walk)) return rc;
+  walk = align256(walk);
   const SegVarArea A = seg_var_area(C, B, G.length);
   if (ws_bytes < walk + A.total) return fail(h, OU_ENOMEM, "workspace too small: need " + std::to_string(walk + A.total) +
                                                                " bytes (ou_segments_var_workspace_bytes)");
@@ -2205,18 +2156,8 @@ int ou_enhance_segments_var(ou_handle* h, const float* mix, float* out, const fl
   float* carry = (float*)(seg + A.a.carry);
   SegRow* geom = (SegRow*)(seg + A.geom);
 
-  const bool saved_overlap = h->overlap;
-  struct OverlapGuard { ou_handle* h; bool v; ~OverlapGuard() { h->overlap = v; } } overlap_guard{h, saved_overlap};
-  h->overlap = false;  // one chain on the caller's stream
-  h->tensors.clear();
-  h->n_launch = h->n_conv = 0;
-  h->ev_used = 0;
+  CallScope scope(h, true);  // one chain on the caller's stream
   hipStream_t st = (hipStream_t)stream;
-  auto chk = [&](hipError_t e, const char* w) -> bool {
-    h->n_launch++;
-    if (e != hipSuccess) { fail(h, OU_EHIP, std::string("HIP error at ") + w + ": " + hipGetErrorString(e)); return false; }
-    return true;
-  };
 
   // ---- the geometry table, then every row's statistics and mel scale in one set of launches (the output rows hold the frame
   // energies until the first stitch)
@@ -2239,35 +2180,25 @@ int ou_enhance_segments_var(ou_handle* h, const float* mix, float* out, const fl
       blk.t_raw[i] = i < n ? t_raw[off + i] : 1;
       blk.first[i] = i < n ? G.first[off + i] : 0;
     }
-    if (!chk(launch_seg_upload_rows(geom, blk, n, off, v, st), "segment rows")) return OU_EHIP;
+    if (!launched(h, launch_seg_upload_rows(geom, blk, n, off, v, st), "segment rows")) return OU_EHIP;
   }
   const float level = (float)std::pow(10.0, (double)m.cfg.level_db / 20.0);
-  if (!chk(launch_seg_stats_var(mix, part, stats, geom, C, T_raw_max, level, st), "segment stats")) return OU_EHIP;
-  if (!chk(launch_seg_mel_energy_var(mix, stats, h->W + m.mel.win_off, h->W + m.mel.tw_off, h->W + m.mel.fb_off, out, geom, C,
-                                     T_raw_max, m.mel.n_fft, m.mel.hop, m.mel.pad_left, m.mel.n_freq, m.mel.n_mels, frames_max,
-                                     st), "segment mel energy"))
+  if (!launched(h, launch_seg_stats_var(mix, part, stats, geom, C, T_raw_max, level, st), "segment stats")) return OU_EHIP;
+  if (!launched(h, launch_seg_mel_energy_var(mix, stats, h->W + m.mel.win_off, h->W + m.mel.tw_off, h->W + m.mel.fb_off, out,
+                                             geom, C, T_raw_max, m.mel.n_fft, m.mel.hop, m.mel.pad_left, m.mel.n_freq,
+                                             m.mel.n_mels, frames_max, st), "segment mel energy"))
     return OU_EHIP;
-  if (!chk(launch_seg_mel_scale_var(out, row_scale, geom, C, T_raw_max, st), "segment mel scale")) return OU_EHIP;
-
-  // ---- sampler constants (as ou_enhance)
-  std::vector<float> sigma(n_steps);
-  double eta, beta;
-  schedule(m.cfg, n_steps, epsilon, sigma.data(), &eta, &beta);
-  if (sigma_host) std::memcpy(sigma.data(), sigma_host, sizeof(float) * n_steps);
-  std::vector<StepCoef> coefs;
-  for (int n = 0; n < n_steps; n++)
-    coefs.push_back(make_coef(m.cfg, sigma[n], n == n_steps - 1, eta, beta, n + 1 < n_steps ? sigma[n + 1] : 0.f));
+  if (!launched(h, launch_seg_mel_scale_var(out, row_scale, geom, C, T_raw_max, st), "segment mel scale")) return OU_EHIP;
 
   // ---- the groups: B entries at a time through the walk -- the plain one, or the ragged one where the entries differ in length
+  const SamplerTables tab(m.cfg, n_steps, epsilon, sigma_host);
   const size_t step_noise = (size_t)C * T_pad_max;  // one step of the callers' noise
   const long long n_entries = (long long)G.entries.size();
-  bool coefs_up = false;
   for (size_t gi = 0; gi < G.group_first.size(); gi++) {
     const long long e0 = G.group_first[gi];
     const bool full = e0 < G.n_full;
     const long long e_end = std::min<long long>(e0 + B, full ? G.n_full : n_entries);
     const int n_real = (int)(e_end - e0);
-    const bool ragged = G.group_ragged[gi] != 0;
     // entry j of the group (the filler rows of a short last group repeat the last real one) and the length of the walk
     auto entry = [&](int j) -> const SegEntry& { return G.entries[(size_t)(e0 + std::min(j, n_real - 1))]; };
     int T = 0;
@@ -2289,27 +2220,13 @@ int ou_enhance_segments_var(ou_handle* h, const float* mix, float* out, const fl
     r.mel_scale_preset = true;
     Persist P = layout_persist(r, T);
     if (r.oom) return finish(h, r);
-    if (!coefs_up) {  // (the persistent area of the workspace keeps them from group to group: its layout depends on B alone)
-      upload_coefs(r, P.coef, coefs);
-      r.chk(launch_sigma_embed(P.coef, n_steps, r.W(m.sigma.p_off), m.sigma.simple, m.sigma.n_rff, m.film.D, P.g, st), "sigma");
-      r.chk(launch_film(P.g, r.W(m.film.w_off), r.W(m.film.b_off), P.film, n_steps, m.film.rows, m.film.D, st), "film");
-      coefs_up = true;
-    }
-    if (ragged) {
-      // the entries' lengths on every level of the network: T, 2 T and T / (r_0 .. r_i) (as ou_enhance_var; an entry is an
-      // already padded window, so its length is the level-0 length itself)
-      LevelSpec& lv = r.lv;
-      lv.n = 0;
-      auto add_level = [&](int num, int den) {
-        lv.num[lv.n] = num; lv.den[lv.n] = den; r.level_T[lv.n] = (int)((long long)T * num / den); lv.n++;
-      };
-      add_level(1, 1);
-      add_level(2, 1);
-      int cum = 1;
-      for (int i = 0; i < m.cfg.score.n_rates && lv.n < kMaxLenLevels; i++) { cum *= m.cfg.score.rate_factors[i]; add_level(1, cum); }
-      if (cum != tot) return fail(h, OU_EINVAL, "internal: rate factors do not multiply to the total down-sampling factor");
+    if (gi == 0) tab.upload(r, P);  // (the persistent area keeps the tables from group to group: its layout depends on B alone)
+    if (G.group_ragged[gi]) {
+      // the entries' lengths on every level of the network (as ou_enhance_var; an entry is an already padded window, so its
+      // length is the level-0 length itself)
+      if (const int rc = set_levels(r, T)) return rc;
       for_blocks(B, [&](const SegEntryBlock& blk, int n, int j0) {
-        r.chk(launch_seg_upload_lens(P.lens, blk, n, j0, B, lv, st), "segment lens");
+        r.chk(launch_seg_upload_lens(P.lens, blk, n, j0, B, r.lv, st), "segment lens");
       });
       r.ragged = true;
       r.lens_dev = P.lens;
@@ -2319,14 +2236,15 @@ int ou_enhance_segments_var(ou_handle* h, const float* mix, float* out, const fl
             "segment gather");
     });
     run_condition(r, P, P.mixn.p, T);
-    // one step's noise of the group's entries (0 behind an entry's own length): a slice of the caller's rows, or -- counter
-    // mode -- the same positions (window k of row c: t = s_k + i, stream of row c) straight from the function
-    auto step_noise_plane = [&](int draw) {
-      if (!counter) {
+    // one step's noise of the group's entries (0 behind an entry's own length, so x needs no mask): a slice of the caller's
+    // rows, or -- counter mode -- the same positions (window k of row c: t = s_k + i, stream of row c) straight from the function
+    auto z = [&](int draw) -> const float* {
+      if (noise) {
         for_blocks(B, [&](const SegEntryBlock& blk, int n, int j0) {
-          r.chk(launch_seg_gather_noise_var(noise + (size_t)draw * step_noise, geom, zbuf, blk, n, j0, T, v, st), "segment noise");
+          if (r.ok())
+            r.chk(launch_seg_gather_noise_var(noise + (size_t)draw * step_noise, geom, zbuf, blk, n, j0, T, v, st), "segment noise");
         });
-        return;
+        return zbuf;
       }
       fill_noise_plane(r, zbuf, T, B, h->noise_src.seed, draw, [&](int j, unsigned long long& sid, long long& t0, long long& len) {
         const SegEntry& e = entry(j);
@@ -2334,30 +2252,22 @@ int ou_enhance_segments_var(ou_handle* h, const float* mix, float* out, const fl
         t0 = start_of(e);
         len = e.len;
       });
+      return zbuf;
     };
-    step_noise_plane(0);
-    r.chk(launch_init_x(zbuf, nullptr, sigma[0], P.x.p, (size_t)B * T, st), "init x");  // universe.py:325-327
-    const size_t step_mark = r.off;
-    for (int n = 0; n < n_steps && r.ok(); n++) {
-      const bool last = n == n_steps - 1;
-      if (!last) step_noise_plane(n + 1);
-      r.off = step_mark;
-      run_score(r, P, P.x.p, last ? nullptr : zbuf, P.x.p, OUT_UPDATE, P.coef + n, 0, P.film + (size_t)n * m.film.rows, 0, T);
-    }
+    sample(r, P, T, tab, 0, nullptr, false, z);
     if (r.ok())
       for_blocks(n_real, [&](const SegEntryBlock& blk, int n, int j0) {
         r.chk(launch_seg_stitch_var(P.x.p, carry, out, geom, blk, n, j0, T, v, st), "segment stitch");
       });
     if (r.ok() && full && e_end < G.n_full)  // the window in front of the next group
       r.chk(hipMemcpyAsync(carry, P.x.p + (size_t)(n_real - 1) * T, (size_t)T * 4, hipMemcpyDeviceToDevice, st), "carry");
-    const int rc = finish(h, r);
-    if (rc != OU_OK) return rc;
+    if (const int rc = finish(h, r)) return rc;
   }
   h->cond_B = 0;  // (the operator seams see a whole-file batch only)
   h->cond_T = (int)G.length;
-  const int keep_rms = (flags & OU_ENH_KEEP_RMS) ? 1 : 0;
-  const int peak = (flags & OU_ENH_NO_PEAK_GUARD) ? 0 : 1;
-  if (!chk(launch_seg_post_var(out, part, stats, geom, C, T_raw_max, keep_rms, peak, st), "segment post")) return OU_EHIP;
+  const PostFlags pf(flags);
+  if (!launched(h, launch_seg_post_var(out, part, stats, geom, C, T_raw_max, pf.keep_rms, pf.peak, st), "segment post"))
+    return OU_EHIP;
   return OU_OK;
 }
 

@@ -448,6 +448,31 @@ class Universe:
         return s_min * (s_max / s_min) ** time
 
     # ---- operator seams (universe.py:314-316, 286) --------------------------------------------------
+    def _sigma_table(self, n_steps):
+        """The discretised schedule exactly as the reference builds it (universe.py:308-311): host arithmetic, done once per
+        (n_steps, schedule)."""
+        skey = (int(n_steps), float(self.diff_kwargs.sigma_min), float(self.diff_kwargs.sigma_max))
+        sigma = self._sigma_cache.get(skey)
+        if sigma is None:
+            time = torch.linspace(0, 1, n_steps).to(torch.float32).flip(dims=[0])
+            sigma = self.get_std_dev(time).to(torch.float32).contiguous()
+            if len(self._sigma_cache) > 64:
+                self._sigma_cache.clear()
+            self._sigma_cache[skey] = sigma
+        return sigma
+
+    @staticmethod
+    def _refuse_long_options(method, other):
+        """enhance_long / enhance_long_many: the options of `enhance` that the segmented calls do not take, and typos."""
+        for k in ("target", "ensemble", "fake_score_snr", "warm_start"):
+            if other.get(k) is not None:
+                raise ValueError(f"{method} does not take `{k}`")
+        if other.get("use_aux_signal"):
+            raise ValueError(f"{method} does not take `use_aux_signal`")
+        unknown = set(other) - {"target", "ensemble", "fake_score_snr", "warm_start", "use_aux_signal", "ensemble_stat"}
+        if unknown:
+            raise TypeError(f"{method}() got unexpected keyword argument(s): {sorted(unknown)}")
+
     def _prep(self, x):
         if x.device != self.device:
             raise ValueError(f"input is on {x.device}, model on {self.device}")
@@ -651,16 +676,8 @@ class Universe:
                 noise_t = torch.stack([self._prep(z) for z in noise[:n_noise]], dim=0) if n_noise else None
                 if n_noise and noise_t.shape != (n_noise, B, 1, T):
                     raise ValueError(f"noise must be {n_noise} tensors of shape {(B, 1, T)}")
-            # discretised schedule exactly as the reference builds it (universe.py:308-311) -- host arithmetic, done once per
-            # (n_steps, schedule) and AFTER the draws are in the queue: the device is idle while the host prepares a call
-            skey = (int(n_steps), float(self.diff_kwargs.sigma_min), float(self.diff_kwargs.sigma_max))
-            sigma = self._sigma_cache.get(skey)
-            if sigma is None:
-                time = torch.linspace(0, 1, n_steps).to(torch.float32).flip(dims=[0])
-                sigma = self.get_std_dev(time).to(torch.float32).contiguous()
-                if len(self._sigma_cache) > 64:
-                    self._sigma_cache.clear()
-                self._sigma_cache[skey] = sigma
+            # (AFTER the draws are in the queue: the device is idle while the host prepares a call)
+            sigma = self._sigma_table(n_steps)
             out = torch.empty(B, 1, mix_len, dtype=torch.float32, device=self.device)
             ws = self._workspace(B, T)
             flags = (_lib.OU_ENH_KEEP_RMS if keep_rms else 0) | (_lib.OU_ENH_USE_AUX_SIGNAL if use_aux_signal else 0)
@@ -825,14 +842,7 @@ class Universe:
         B, _, mix_len = mix.shape
         T = mix_len + (self.tot_ds - mix_len % self.tot_ds)
         EB = E * B
-        skey = (int(n_steps), float(self.diff_kwargs.sigma_min), float(self.diff_kwargs.sigma_max))
-        sigma = self._sigma_cache.get(skey)
-        if sigma is None:
-            time = torch.linspace(0, 1, n_steps).to(torch.float32).flip(dims=[0])
-            sigma = self.get_std_dev(time).to(torch.float32).contiguous()
-            if len(self._sigma_cache) > 64:
-                self._sigma_cache.clear()
-            self._sigma_cache[skey] = sigma
+        sigma = self._sigma_table(n_steps)
         out = torch.empty(B, 1, mix_len, dtype=torch.float32, device=self.device)
         members = torch.empty(E, B, 1, mix_len, dtype=torch.float32, device=self.device) if return_members else None
         need = c_size_t()
@@ -1002,14 +1012,7 @@ class Universe:
         T_pad) tensor, n_steps times the recording.  `rng=noise.CounterNoise(seed, u)` removes that tensor: every window's noise
         is computed at its offset from the counter-based function (row c: stream id (u << 16) | c), and the memory of the call is
         the workspace plus input and output.  A file that fits into one window gets the `enhance` result.  Workspace: ou_segments_workspace_bytes -- set by max_batch and segment_s."""
-        for k in ("target", "ensemble", "fake_score_snr", "warm_start"):
-            if other.get(k) is not None:
-                raise ValueError(f"enhance_long does not take `{k}`")
-        if other.get("use_aux_signal"):
-            raise ValueError("enhance_long does not take `use_aux_signal`")
-        unknown = set(other) - {"target", "ensemble", "fake_score_snr", "warm_start", "use_aux_signal", "ensemble_stat"}
-        if unknown:
-            raise TypeError(f"enhance_long() got unexpected keyword argument(s): {sorted(unknown)}")
+        self._refuse_long_options("enhance_long", other)
         self._sync_env()
         self._poll_deferred_status()
         if mix.ndim not in (1, 2):
@@ -1028,11 +1031,7 @@ class Universe:
                                                         byref(B), byref(L)), self._handle)
         counter = is_counter(rng)
         noise = None if counter else self.draw_noise_like_enhance(rng, C, T_raw, n_steps)
-        skey = (int(n_steps), float(self.diff_kwargs.sigma_min), float(self.diff_kwargs.sigma_max))
-        sigma = self._sigma_cache.get(skey)
-        if sigma is None:
-            time = torch.linspace(0, 1, n_steps).to(torch.float32).flip(dims=[0])
-            sigma = self._sigma_cache[skey] = self.get_std_dev(time).to(torch.float32).contiguous()
+        sigma = self._sigma_table(n_steps)
         ws = self._segments_workspace(B.value, L.value, need.value)
         out = torch.empty(C, T_raw, dtype=torch.float32, device=self.device)
         flags = _lib.OU_ENH_KEEP_RMS if keep_rms else 0
@@ -1058,14 +1057,7 @@ class Universe:
         shared generator (it advances input by input, as `enhance_long` draws for each), or None -- or `noise.CounterNoise`
         objects as in `enhance_many` (one per input with one seed, or one shared: input i is utterance `stream + i`).
         Returns the list of enhanced signals, each with the shape of its input."""
-        for k in ("target", "ensemble", "fake_score_snr", "warm_start"):
-            if other.get(k) is not None:
-                raise ValueError(f"enhance_long_many does not take `{k}`")
-        if other.get("use_aux_signal"):
-            raise ValueError("enhance_long_many does not take `use_aux_signal`")
-        unknown = set(other) - {"target", "ensemble", "fake_score_snr", "warm_start", "use_aux_signal", "ensemble_stat"}
-        if unknown:
-            raise TypeError(f"enhance_long_many() got unexpected keyword argument(s): {sorted(unknown)}")
+        self._refuse_long_options("enhance_long_many", other)
         if not signals:
             return []
         self._sync_env()
@@ -1104,11 +1096,7 @@ class Universe:
                     noise[k, r0:r0 + c, :Ti] = torch.randn((c, 1, Ti), dtype=torch.float32, device=self.device,
                                                            generator=g)[:, 0]
                 r0 += c
-        skey = (int(n_steps), float(self.diff_kwargs.sigma_min), float(self.diff_kwargs.sigma_max))
-        sigma = self._sigma_cache.get(skey)
-        if sigma is None:
-            time = torch.linspace(0, 1, n_steps).to(torch.float32).flip(dims=[0])
-            sigma = self._sigma_cache[skey] = self.get_std_dev(time).to(torch.float32).contiguous()
+        sigma = self._sigma_table(n_steps)
         ws = self._segments_workspace(B.value, L.value, need.value)
         mix = torch.cat([torch.nn.functional.pad(r, (0, l_max - r.shape[-1])) for r in rows], dim=0).contiguous()
         out = torch.empty(C, l_max, dtype=torch.float32, device=self.device)
