@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define OU_ABI_VERSION 7 /* 7: segmented enhance of rows with lengths of their own (ou_segment_groups, ou_segments_var_workspace_bytes, ou_enhance_segments_var: additive, the number stays); ensembles in the library (ou_enhance_ensemble, ou_ensemble_workspace_bytes, ou_ensemble_reduce, ou_ensemble_reduce_scratch_bytes; option ens_share); existing entry points unchanged; 6: counter-based sampler noise (ou_set_noise_source, ou_noise_scratch_bytes, ou_noise_fill); existing entry points unchanged; 5: ou_enhance_var (batches whose rows have lengths of their own), workspace header carries the per-row geometry; ou_set_option / ou_get_option replace every OU_* environment switch (the library reads no environment variable), ou_config.fir_fold; 4: the packed blob carries a bf16-split weight copy (conv_split_kernel); 3: a Winograd-domain copy (round 5), ou_set_lane_batch, ou_lane_capacity */
+#define OU_ABI_VERSION 7 /* 7: ensembles of segmented rows (ou_segments_ensemble_workspace_bytes, ou_enhance_segments_ensemble: additive, the number stays); segmented enhance of rows with lengths of their own (ou_segment_groups, ou_segments_var_workspace_bytes, ou_enhance_segments_var: additive, the number stays); ensembles in the library (ou_enhance_ensemble, ou_ensemble_workspace_bytes, ou_ensemble_reduce, ou_ensemble_reduce_scratch_bytes; option ens_share); existing entry points unchanged; 6: counter-based sampler noise (ou_set_noise_source, ou_noise_scratch_bytes, ou_noise_fill); existing entry points unchanged; 5: ou_enhance_var (batches whose rows have lengths of their own), workspace header carries the per-row geometry; ou_set_option / ou_get_option replace every OU_* environment switch (the library reads no environment variable), ou_config.fir_fold; 4: the packed blob carries a bf16-split weight copy (conv_split_kernel); 3: a Winograd-domain copy (round 5), ou_set_lane_batch, ou_lane_capacity */
 
 enum {
   OU_OK = 0,
@@ -311,6 +311,44 @@ int ou_enhance_segments_var(ou_handle* h, const float* mix, float* out, const fl
                             const int64_t* t_raw, int32_t segment, int32_t overlap, int32_t max_batch, int32_t n_steps,
                             double epsilon, const float* sigma_host, int32_t warm_start, uint32_t flags, void* ws,
                             size_t ws_bytes, ou_stream_t stream);
+
+/* ---- ensembles of segmented rows (extension): ou_enhance_ensemble for rows of any length.  Member e of row c is, by definition,
+ * ou_enhance_segments(C = 1) of row c on that member's own noise -- whole-row statistics and mel scale of row c, crossfades only
+ * between consecutive windows of the row, keep_rms (the mix_rms of row c) and the peak guard over the member row's own samples --
+ * and out[c] is ou_ensemble_reduce over the E post-processed members of row c.  What changes is how the work is grouped.
+ *
+ * Everything is MEMBER-MAJOR: member row e * C + c.
+ *   mix, out : (C, T_raw) device (out also serves as scratch for the whole-row mel frame energies before the first window)
+ *   members  : (E * C, T_raw) device, caller-owned and REQUIRED: the post step runs over whole member rows before the reduce (as
+ *              in the reference, universe.py:352-368), so every member row has to exist whole.  THIS IS THE ONE PART OF THE CALL
+ *              THAT GROWS WITH THE RECORDING (E x the output); the workspace does not depend on T_raw, as for ou_enhance_segments.
+ *   noise    : (n_steps, E * C, T_pad) device; NULL when a noise source is set -- its n_streams must then equal E * C, and stream
+ *              e * C + c belongs to that member row.  Window k of a member row reads the positions s_k + i of that row's noise.
+ *   stat     : as ou_enhance_ensemble;  flags, warm_start: as ou_enhance_segments.
+ *
+ * Groups (pure host function).  The windows are those of ou_segment_plan, the entry list is row-major (c, k) as in
+ * ou_enhance_segments.  Bw = ceil(n / ceil(n / floor(max_batch / E))) entries per group for n = C * n_windows entries, and the
+ * walk runs batch = E * Bw <= max_batch rows: walk row e * Bw + j is member e of entry e0 + j.  A short last group repeats its
+ * last real entry per member (the filler of member e repeats member e's window and noise; fillers are never stitched).  The
+ * conditioner runs ONCE over the Bw inputs of a group and its results are replicated to the other members' rows (option
+ * `ens_share`, default 1, as in ou_enhance_ensemble; 0: the input is gathered E times and the conditioner runs over all E * Bw
+ * rows -- the arithmetic of ou_enhance_segments on E stacked copies of the rows).  A Bw-row conditioner pass, and a walk of
+ * another batch size, may select other kernels: members agree with the single-row calls to fp32 round-off, not bit for bit;
+ * E = 1 is ou_enhance_segments bit for bit.
+ *
+ * Workspace: ou_segments_ensemble_workspace_bytes returns batch = E * Bw and length; prepare the buffer with
+ * ou_workspace_init(h, batch, length, ..).  Behind the walk's workspace it holds C rows of statistics, E * C rows of post
+ * partials, E * Bw * length floats of step noise, E carried windows and the reduce scratch of ou_ensemble_reduce_scratch_bytes(E, C).
+ * OU_EINVAL, decided on the host before anything is launched: E < 1, E > OU_MAX_ENSEMBLE, E > max_batch, an unknown stat,
+ * members == NULL, warm_start >= 0, OU_ENH_USE_AUX_SIGNAL, a non-NULL `noise` while a source is set, n_streams != E * C (and E * C >
+ * 65535).  OU_ENOMEM and the unprepared-workspace refusal as in ou_enhance_segments.  Everything is enqueued on `stream`: no
+ * allocation, no host synchronisation, no side streams, no float atomics. */
+int ou_segments_ensemble_workspace_bytes(const ou_handle* h, int32_t C, int64_t T_raw, int32_t segment, int32_t overlap,
+                                         int32_t max_batch, int32_t E, size_t* nbytes, int32_t* batch, int32_t* length);
+int ou_enhance_segments_ensemble(ou_handle* h, const float* mix, float* out, float* members, const float* noise, int32_t C,
+                                 int64_t T_raw, int32_t E, int32_t stat, int32_t segment, int32_t overlap, int32_t max_batch,
+                                 int32_t n_steps, double epsilon, const float* sigma_host, int32_t warm_start, uint32_t flags,
+                                 void* ws, size_t ws_bytes, ou_stream_t stream);
 
 /* ---- counter-based sampler noise (extension; the reference draws its noise with torch.randn on the model's device) --------
  * By default every enhance entry point reads its noise from a tensor the caller has drawn.  With a noise SOURCE set on the

@@ -116,6 +116,10 @@ def build_parser():
                              "(Universe.enhance_long_many: files of any lengths, long ones in windows, short ones as one "
                              "window each, the windows of all files share the window groups; every file gets the result "
                              "it would get alone).  Default 1: one file per call")
+    parser.add_argument("--segment-ensemble", type=int, default=None,
+                        help="With --segment-seconds: enhance every file as an ensemble of this many samples, reduced with "
+                             "--ensemble_stat (Universe.enhance_long_ensemble: the windows of all members share the window "
+                             "groups and the conditioner runs once per window).  Not with --ensemble or --segment-files > 1")
     parser.add_argument("--pad-batch", action="store_true",
                         help="With --batch-size: files of different lengths are zero-padded to the longest WITHOUT a mask "
                              "(the reference's batch semantics: the padding changes every result)")
@@ -143,6 +147,17 @@ def group_files(todo, infos, batch_size, pad_batch=False):
 
 def check_segment_args(args, enhance_kwargs):
     """--segment-seconds / --segment-overlap: refused with what they cannot be combined with."""
+    seg_ens = getattr(args, "segment_ensemble", None)
+    if seg_ens is not None:
+        if enhance_kwargs.get("ensemble") is not None:
+            raise ValueError("--segment-ensemble cannot be combined with --ensemble (--segment-ensemble E is the ensemble of a "
+                             "segmented file)")
+        if args.segment_seconds is None:
+            raise ValueError("--segment-ensemble needs --segment-seconds")
+        if seg_ens < 1:
+            raise ValueError("--segment-ensemble must be at least 1")
+        if getattr(args, "segment_files", 1) > 1:
+            raise ValueError("--segment-ensemble cannot be combined with --segment-files > 1 (one file per call)")
     if args.segment_seconds is None:
         if args.segment_overlap is not None:
             raise ValueError("--segment-overlap needs --segment-seconds")
@@ -189,7 +204,13 @@ def file_noise(args, k):
 
 
 def enhance_file(model, audio, args, enhance_kwargs, rng):
-    """One file of the serial loop: `enhance`, or `enhance_long` when --segment-seconds is set and the file is longer."""
+    """One file of the serial loop: `enhance`, or `enhance_long` when --segment-seconds is set and the file is longer; with
+    --segment-ensemble E every file goes through `enhance_long_ensemble` (a short file is one window)."""
+    if args.segment_seconds is not None and getattr(args, "segment_ensemble", None) is not None:
+        ov = 1.0 if args.segment_overlap is None else args.segment_overlap
+        kw = {k: v for k, v in enhance_kwargs.items() if k in ("n_steps", "epsilon", "keep_rms") and v is not None}
+        return model.enhance_long_ensemble(audio, args.segment_ensemble, enhance_kwargs.get("ensemble_stat") or "median",
+                                           segment_s=args.segment_seconds, overlap_s=ov, rng=rng, **kw)
     if args.segment_seconds is not None and audio.shape[-1] > args.segment_seconds * model.fs:
         ov = 1.0 if args.segment_overlap is None else args.segment_overlap
         kw = {k: v for k, v in enhance_kwargs.items() if k in ("n_steps", "epsilon", "keep_rms")}

@@ -1874,6 +1874,39 @@ SegArea seg_area(int C, int B, long long L) {
   return a;
 }
 
+// ... and of ou_enhance_segments_ensemble: E member rows per input row, Bw entries (E * Bw walk rows) per group
+struct SegEnsArea {
+  size_t stats, row_scale, part, zbuf, carry, hist, total;
+};
+SegEnsArea seg_ens_area(int C, int E, int Bw, long long L) {
+  SegEnsArea a;
+  size_t off = 0;
+  a.stats = off; off += align256((size_t)C * 4 * 4);
+  a.row_scale = off; off += align256((size_t)C * 4);
+  // the statistics' partials of the C input rows ([C][nb][3]), then the post partials of the E * C member rows ([E * C][nb][2])
+  a.part = off; off += align256(std::max((size_t)C * 3, (size_t)E * C * 2) * 1024 * 8);
+  a.zbuf = off; off += align256((size_t)E * Bw * L * 4);
+  a.carry = off; off += align256((size_t)E * L * 4);
+  a.hist = off; off += ou_ensemble_reduce_scratch_bytes(E, C);
+  a.total = off;
+  return a;
+}
+// what both entry points of the segmented ensemble refuse, and the plan of the call.  Bw: entries per group
+int seg_ens_plan(ou_handle* h, const char* who, int C, long long T_raw, int segment, int overlap, int max_batch, int E, SegGeom& g,
+                 int& Bw) {
+  if (C < 1 || T_raw < 1 || max_batch < 1) return fail(h, OU_EINVAL, "bad argument");
+  if (E < 1 || E > OU_MAX_ENSEMBLE) return fail(h, OU_EINVAL, std::string(who) + ": 1 <= E <= " + std::to_string(OU_MAX_ENSEMBLE));
+  if (E > max_batch) return fail(h, OU_EINVAL, std::string(who) + ": E must not exceed max_batch (a group holds all E members of its entries)");
+  if ((long long)E * C > 65535) return fail(h, OU_EINVAL, std::string(who) + ": too many member rows (E * C <= 65535)");
+  SegPlan plan;
+  if (!seg_plan(h->m.tot_ds, T_raw, segment, overlap, plan)) return fail(h, OU_EINVAL, plan.err);
+  g = plan.g;
+  if (g.L > 0x7fffffffll) return fail(h, OU_EINVAL, "segment too long");
+  g.n_entries = (long long)C * g.n_win;
+  Bw = seg_batch(g.n_entries, max_batch / E);
+  return OU_OK;
+}
+
 // Window groups of rows with lengths of their own (include/ouniverse.h, ou_segment_groups): a pure host function.
 struct SegEntry { int row, win, len; };
 struct SegGroups {
@@ -2076,6 +2109,163 @@ int ou_enhance_segments(ou_handle* h, const float* mix, float* out, const float*
   h->cond_T = L;
   const PostFlags pf(flags);
   if (!launched(h, launch_seg_post(out, part, stats, C, g.T_raw, pf.keep_rms, pf.peak, st), "segment post")) return OU_EHIP;
+  return OU_OK;
+}
+
+int ou_segments_ensemble_workspace_bytes(const ou_handle* hc, int32_t C, int64_t T_raw, int32_t segment, int32_t overlap,
+                                         int32_t max_batch, int32_t E, size_t* nbytes, int32_t* batch, int32_t* length) {
+  ou_handle* h = const_cast<ou_handle*>(hc);
+  if (!h || !nbytes) return fail(h, OU_EINVAL, "bad argument");
+  SegGeom g;
+  int Bw = 0;
+  if (const int rc = seg_ens_plan(h, "ou_segments_ensemble_workspace_bytes", C, T_raw, segment, overlap, max_batch, E, g, Bw))
+    return rc;
+  size_t walk = 0;
+  if (const int rc = ou_workspace_bytes(h, E * Bw, (int32_t)g.L, &walk)) return rc;
+  *nbytes = align256(walk) + seg_ens_area(C, E, Bw, g.L).total;
+  if (batch) *batch = E * Bw;
+  if (length) *length = (int32_t)g.L;
+  return OU_OK;
+}
+
+// ou_enhance_segments with E members per row: the windows of ou_enhance_segments in groups of Bw entries, every group one walk
+// of E * Bw rows (member-major) whose conditioner runs once over the Bw inputs (ensemble_impl's arrangement); the members are
+// stitched into the caller's (E * C, T_raw) rows, post-processed there and reduced into `out`.
+int ou_enhance_segments_ensemble(ou_handle* h, const float* mix, float* out, float* members, const float* noise, int32_t C,
+                                 int64_t T_raw, int32_t E, int32_t stat, int32_t segment, int32_t overlap, int32_t max_batch,
+                                 int32_t n_steps, double epsilon, const float* sigma_host, int32_t warm_start, uint32_t flags,
+                                 void* ws, size_t ws_bytes, ou_stream_t stream) {
+  const char* who = "ou_enhance_segments_ensemble";
+  if (!h || !mix || !out || !ws) return fail(h, OU_EINVAL, "bad argument");
+  SegGeom g;
+  int Bw = 0;
+  if (const int rc = seg_ens_plan(h, who, C, T_raw, segment, overlap, max_batch, E, g, Bw)) return rc;
+  if (stat != OU_ENS_MEAN && stat != OU_ENS_MEDIAN && stat != OU_ENS_SIGNAL_MEDIAN)
+    return fail(h, OU_EINVAL, std::string(who) + ": stat must be OU_ENS_MEAN, OU_ENS_MEDIAN or OU_ENS_SIGNAL_MEDIAN");
+  if (!members)
+    return fail(h, OU_EINVAL, std::string(who) + ": `members` must be given ((E * C, T_raw): the post step runs over whole member rows)");
+  if (warm_start >= 0 || (flags & OU_ENH_USE_AUX_SIGNAL))
+    return fail(h, OU_EINVAL, std::string(who) + ": warm_start and use_aux_signal are not supported");
+  const int EC = E * C;
+  if (const int rc = check_noise_source(h, noise, EC, "the member rows of the call (E * C = ", true)) return rc;
+  if (const int rc = check_steps(h, n_steps, warm_start)) return rc;
+  if (g.L > max_walk_length(h, false)) return fail(h, OU_EINVAL, std::string(who) + ": segment too long for one pass of the walk");
+  const int B = E * Bw;  // rows of the walk
+  const int L = (int)g.L;
+  size_t walk = 0;
+  if (const int rc = ou_workspace_bytes(h, B, L, &walk)) return rc;
+  walk = align256(walk);
+  const SegEnsArea A = seg_ens_area(C, E, Bw, g.L);
+  if (ws_bytes < walk + A.total) return fail(h, OU_ENOMEM, "workspace too small: need " + std::to_string(walk + A.total) +
+                                                               " bytes (ou_segments_ensemble_workspace_bytes)");
+  if (!h->ws_ok(ws, ws_bytes, B, L))
+    return fail(h, OU_EINVAL,
+                "workspace was not prepared by ou_workspace_init for (batch, length) of ou_segments_ensemble_workspace_bytes");
+  char* seg = (char*)ws + walk;
+  float* stats = (float*)(seg + A.stats);
+  float* row_scale = (float*)(seg + A.row_scale);
+  double* part = (double*)(seg + A.part);
+  float* zbuf = (float*)(seg + A.zbuf);
+  float* carry = (float*)(seg + A.carry);
+  int* hist = (int*)(seg + A.hist);
+
+  CallScope scope(h, true);  // one chain on the caller's stream
+  hipStream_t st = (hipStream_t)stream;
+  const Model& m = h->m;
+  const bool share = h->opt.ens_share != 0 && E > 1;
+  const int Bc = share ? Bw : B;  // rows of the conditioner pass
+
+  // ---- whole-row statistics and mel scale of the C inputs, as ou_enhance_segments (`out` holds the frame energies meanwhile)
+  const float level = (float)std::pow(10.0, (double)m.cfg.level_db / 20.0);
+  const long long Lf = g.T_pad / m.tot_ds;
+  if (Lf > g.T_raw) return fail(h, OU_EINVAL, "internal: mel frames do not fit into the output row");
+  if (Lf > 0x7fffffffll) return fail(h, OU_EINVAL, "input too long");
+  if (!launched(h, launch_seg_stats(mix, part, stats, C, g.T_raw, g.T_pad, level, st), "segment stats")) return OU_EHIP;
+  if (!launched(h, launch_seg_mel_energy(mix, stats, h->W + m.mel.win_off, h->W + m.mel.tw_off, h->W + m.mel.fb_off, out, C,
+                                         g.T_raw, g.T_pad, g.pad_left, m.mel.n_fft, m.mel.hop, m.mel.pad_left, m.mel.n_freq,
+                                         m.mel.n_mels, Lf, st), "segment mel energy"))
+    return OU_EHIP;
+  if (!launched(h, launch_mel_scale(out, row_scale, C, (int)Lf, st), "segment mel scale")) return OU_EHIP;
+
+  // ---- the groups: Bw entries at a time, E * Bw rows through the walk
+  const SamplerTables tab(m.cfg, n_steps, epsilon, sigma_host);
+  const size_t step_noise = (size_t)EC * g.T_pad;  // one step of the members' whole-row noise
+  for (long long e0 = 0; e0 < g.n_entries; e0 += Bw) {
+    const int n_real = (int)std::min<long long>(Bw, g.n_entries - e0);
+    Runner r(h, ws, walk, false, st, B);
+    Persist P = layout_persist(r, L);
+    if (r.oom) return finish(h, r);
+    if (e0 == 0) tab.upload(r, P);  // (the persistent area of the workspace keeps the tables from group to group)
+    // the conditioner's runner: Bc rows on the prefix of the persistent tensors (ensemble_impl)
+    Runner rc(h, ws, walk, false, st, Bc);
+    rc.mel_scale_preset = true;
+    rc.status_words = r.status_words;
+    rc.block3_bar = r.block3_bar;
+    rc.gru_area_rows = B;
+    rc.off = r.off;
+    // the group's inputs: once into the prefix, or -- the conditioner over all rows -- once per member
+    for (int e = 0; e < (share ? 1 : E); e++)
+      rc.chk(launch_seg_gather_input(mix, stats, row_scale, P.mixn.p + (size_t)e * Bw * L, P.mel_scale + (size_t)e * Bw, g, e0, Bw,
+                                     st), "segment gather");
+    run_condition(rc, P, P.mixn.p, L);
+    if (share && rc.ok()) {  // what the score passes read per row: rows [0, Bw) -> the rows of the other members
+      ReplicateTable rep;
+      int n_rep = 0;
+      auto flush_rep = [&]() {
+        if (n_rep && rc.ok()) rc.chk(launch_replicate_rows(rep, n_rep, E, st), "replicate rows");
+        n_rep = 0;
+      };
+      auto replicate = [&](void* p, size_t words) {
+        if (n_rep == kReplicateEntries) flush_rep();
+        rep.p[n_rep] = (unsigned*)p;
+        rep.n[n_rep] = (long long)words;
+        n_rep++;
+      };
+      auto replicate_t = [&](const Tensor& t) { replicate(t.p, (size_t)Bw * t.C * t.T); };
+      for (size_t j = 0; j < P.cond.size(); j++) { replicate_t(P.cond[j]); replicate_t(P.sc[j]); }
+      replicate_t(P.aux);
+      replicate_t(P.latent);
+      replicate_t(P.mixn);
+      replicate(P.mel_scale, (size_t)Bw);
+      flush_rep();
+    }
+    if (const int rc2 = finish(h, rc)) return rc2;
+    r.off = rc.off;
+    // One step's noise of the E * Bw walk rows: window k of member row e * C + c reads the positions s_k + i of that row's
+    // noise -- gathered from the caller's tensor, or (counter mode) filled from the stream of that member row.  The filler
+    // rows of a short last group repeat their member's last real entry.
+    auto z = [&](int draw) -> const float* {
+      if (noise) {
+        if (r.ok())
+          r.chk(launch_seg_gather_noise_mm(noise + (size_t)draw * step_noise, zbuf, g, e0, Bw, E, C, st), "segment noise");
+        return zbuf;
+      }
+      fill_noise_plane(r, zbuf, L, B, h->noise_src.seed, draw, [&](int row, unsigned long long& sid, long long& t0, long long& len) {
+        const int e = row / Bw, j = row - e * Bw;
+        const long long en = std::min<long long>(e0 + j, g.n_entries - 1);
+        const long long c = en / g.n_win;
+        sid = h->noise_src.streams[(size_t)e * C + c];
+        t0 = seg_start_host(g, en - c * g.n_win);
+        len = L;
+      });
+      return zbuf;
+    };
+    sample(r, P, L, tab, 0, nullptr, false, z);
+    if (r.ok()) r.chk(launch_seg_stitch_mm(P.x.p, carry, members, g, e0, n_real, Bw, E, C, st), "segment stitch");
+    if (e0 + Bw < g.n_entries)  // every member's window in front of the next group
+      for (int e = 0; e < E && r.ok(); e++)
+        r.chk(hipMemcpyAsync(carry + (size_t)e * L, P.x.p + ((size_t)e * Bw + n_real - 1) * L, (size_t)L * 4,
+                             hipMemcpyDeviceToDevice, st), "carry");
+    if (const int rc2 = finish(h, r)) return rc2;
+  }
+  h->cond_B = 0;  // (the operator seams see a whole-file batch only)
+  h->cond_T = L;
+  // ---- the post step over every member row (keep_rms: the mix_rms of the member's own input row), then the reduce over e
+  const PostFlags pf(flags);
+  if (!launched(h, launch_seg_post_mm(members, part, stats, E, C, g.T_raw, pf.keep_rms, pf.peak, st), "segment post")) return OU_EHIP;
+  if (!launched(h, launch_ensemble_reduce(members, out, E, C, g.T_raw, g.T_raw, nullptr, stat, hist, hist + (size_t)C * E, st),
+                "ensemble reduce"))
+    return OU_EHIP;
   return OU_OK;
 }
 

@@ -251,6 +251,19 @@ hipError_t launch_seg_stitch_var(const float* y, const float* carry, float* out,
 hipError_t launch_seg_post_var(float* out, double* part, const float* stats, const SegRow* rows, int C, long long T_raw_max,
                                int keep_rms, int peak_guard, hipStream_t st);
 
+// ---- ... member-major (ou_enhance_segments_ensemble) ---------------------------------------------------------------------------
+// A group's walk runs E * Bw rows, row e * Bw + j = member e of entry e0 + j; the members' long rows are (E * C, T_raw), row
+// e * C + c.  One step's noise is (E * C, T_pad); `carry` is (E, L): member e's window in front of the group.  The per-sample
+// arithmetic is that of the kernels above (E = 1: their bits); rows move in 16-byte accesses from the destination row's first
+// 16-byte boundary on, word by word in front of it and behind the last whole quad.
+hipError_t launch_seg_gather_noise_mm(const float* noise, float* z, const SegGeom& g, long long e0, int Bw, int E, int C,
+                                      hipStream_t st);
+hipError_t launch_seg_stitch_mm(const float* y, const float* carry, float* members, const SegGeom& g, long long e0, int n_real,
+                                int Bw, int E, int C, hipStream_t st);
+// keep_rms + peak guard over the E * C member rows in place; row r takes mix_rms from statistics row r % C.  part: [E * C][nb][2]
+hipError_t launch_seg_post_mm(float* members, double* part, const float* stats, int E, int C, long long T_raw, int keep_rms,
+                              int peak_guard, hipStream_t st);
+
 // Counter-based sampler noise (ou_noise.hip; the function z(seed, stream, draw, t) is defined in include/ouniverse.h).
 // One launch fills up to 64 rows: out[j][col] = col < len[j] ? z(seed, stream[j], draw, t0[j] + col) : 0 for col < cols.
 // The per-row values travel as kernel arguments (capturable, no host memory involved).

@@ -539,6 +539,127 @@ __global__ __launch_bounds__(256) void seg_post_scale_var_kernel(float* __restri
   }
 }
 
+
+// ==== member-major forms (ou_enhance_segments_ensemble) =======================================================================
+// A group runs E * Bw walk rows: row e * Bw + j is member e of entry e0 + j (entries past the last real one repeat it), and the
+// long rows of the members are member-major too: row e * C + c.  grid.z = e.  The arithmetic per sample is that of the kernels
+// above, so E = 1 gives their bits.  Rows are moved in 16-byte accesses from the first 16-byte boundary of the DESTINATION row
+// on (the source side loads 16 bytes where it is aligned there as well, else four words); the up to 3 samples in front of it
+// and behind the last whole quad go word by word.
+
+__device__ __forceinline__ bool seg_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// words from p to the next 16-byte boundary (p is 4-byte aligned)
+__device__ __forceinline__ int seg_head_words(const void* p) { return (int)((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) >> 2; }
+__device__ __forceinline__ float4 seg_load4(const float* p) {
+  if (seg_aligned16(p)) return *reinterpret_cast<const float4*>(p);
+  return make_float4(p[0], p[1], p[2], p[3]);
+}
+
+// z[e * Bw + j][t] = noise[e * C + c_j][s_j + t]   (one step's (E * C, T_pad) slice).  grid (ceil(L / 1024), Bw, E)
+__global__ __launch_bounds__(256) void seg_gather_noise_mm_kernel(const float* __restrict__ noise, float* __restrict__ z,
+                                                                  SegGeom g, long long e0, int C) {
+  const int j = blockIdx.y, m = blockIdx.z, Bw = gridDim.y;
+  long long e = e0 + j;
+  if (e > g.n_entries - 1) e = g.n_entries - 1;
+  const long long c = e / g.n_win, k = e - c * g.n_win;
+  const float* src = noise + ((size_t)m * C + (size_t)c) * (size_t)g.T_pad + seg_start(g, k);
+  float* dst = z + ((size_t)m * Bw + j) * (size_t)g.L;
+  const long long head = seg_head_words(dst) < g.L ? seg_head_words(dst) : g.L;
+  const long long nq = (g.L - head) >> 2;
+  const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (q < nq) *reinterpret_cast<float4*>(dst + head + 4 * q) = seg_load4(src + head + 4 * q);
+  const long long rest = g.L - 4 * nq;  // head + tail: at most 6 words
+  if (blockIdx.x == 0 && threadIdx.x < rest) {
+    const long long t = threadIdx.x < head ? threadIdx.x : 4 * nq + threadIdx.x;
+    dst[t] = src[t];
+  }
+}
+
+// seg_stitch_kernel for walk row e * Bw + j with carry e (carry: (E, L)) into members row e * C + c_j.  Window-local columns
+// [t0, t1) are what the entry writes: [w_k, w_{k+1}) of the padded row, cut to the raw row.  grid (ceil(L / 1024), n_real, E)
+__global__ __launch_bounds__(256) void seg_stitch_mm_kernel(const float* __restrict__ y, const float* __restrict__ carry,
+                                                            float* __restrict__ members, SegGeom g, long long e0, int Bw, int C) {
+  const int j = blockIdx.y, m = blockIdx.z;
+  const long long e = e0 + j;
+  const long long c = e / g.n_win, k = e - c * g.n_win;
+  const long long s = seg_start(g, k);
+  const long long s_prev = k == 0 ? 0 : seg_start(g, k - 1);
+  const long long w0 = k == 0 ? 0 : s_prev + g.L - g.overlap;
+  const long long w1 = k == g.n_win - 1 ? g.T_pad : s + g.L - g.overlap;
+  const long long e_prev = k == 0 ? 0 : s_prev + g.L;
+  const float* yk = y + ((size_t)m * Bw + j) * (size_t)g.L;
+  const float* yp = j > 0 ? yk - g.L : carry + (size_t)m * (size_t)g.L;
+  float* ob = members + ((size_t)m * C + (size_t)c) * (size_t)g.T_raw;
+  long long u0 = w0 > g.pad_left ? w0 : g.pad_left;  // padded-row positions [u0, u1) -> ob[u - pad_left]
+  long long u1 = w1 < g.pad_left + g.T_raw ? w1 : g.pad_left + g.T_raw;
+  if (u0 < s) u0 = s;
+  if (u1 > s + g.L) u1 = s + g.L;
+  const long long n = u1 - u0;
+  if (n <= 0) return;
+  auto value = [&](long long u, float v) {
+    if (u < e_prev) {
+      const float a = 0.5f - 0.5f * cosf(3.14159265358979f * ((float)(u - w0) + 0.5f) / (float)g.overlap);
+      v = (1.f - a) * yp[u - s_prev] + a * v;
+    }
+    return v;
+  };
+  float* dst = ob + (u0 - g.pad_left);
+  const float* src = yk + (u0 - s);
+  const long long head = seg_head_words(dst) < n ? seg_head_words(dst) : n;
+  const long long nq = (n - head) >> 2;
+  const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (q < nq) {
+    const long long i = head + 4 * q;
+    float4 v = seg_load4(src + i);
+    v.x = value(u0 + i, v.x); v.y = value(u0 + i + 1, v.y); v.z = value(u0 + i + 2, v.z); v.w = value(u0 + i + 3, v.w);
+    *reinterpret_cast<float4*>(dst + i) = v;
+  }
+  const long long rest = n - 4 * nq;
+  if (blockIdx.x == 0 && threadIdx.x < rest) {
+    const long long i = threadIdx.x < head ? threadIdx.x : 4 * nq + threadIdx.x;
+    dst[i] = value(u0 + i, src[i]);
+  }
+}
+
+// seg_post_scale_kernel over the E * C member rows: row r restores the mix_rms of its own input, statistics row r % C.  (The
+// partials come from seg_post_reduce_kernel over E * C rows: it reads no statistics.)  grid (blocks, E * C)
+__global__ __launch_bounds__(256) void seg_post_scale_mm_kernel(float* __restrict__ members, const double* __restrict__ part,
+                                                                const float* __restrict__ stats, long long T_raw, int nb, int C,
+                                                                int keep_rms, int peak_guard) {
+  const int r = blockIdx.y;
+  const double* pc = part + (size_t)r * nb * 2;
+  double sq = pc[0];
+  float mxa = (float)pc[1];
+  for (int i = 1; i < nb; i++) { sq += pc[i * 2]; mxa = fmaxf(mxa, (float)pc[i * 2 + 1]); }
+  float g = 1.f;
+  if (keep_rms) {
+    const float x_rms = fmaxf((float)sqrt(sq / (double)T_raw), 1e-5f);
+    g = stats[(r % C) * 4 + 2] / x_rms;
+  }
+  const float mx = mxa * g;
+  const bool div = peak_guard && mx > 1.0f;
+  if (!keep_rms && !div) return;
+  auto scale = [&](float x) {
+    x = x * g;
+    if (div) x = x / mx;
+    return x;
+  };
+  float* xb = members + (size_t)r * (size_t)T_raw;
+  const long long head = seg_head_words(xb) < T_raw ? seg_head_words(xb) : T_raw;
+  const long long nq = (T_raw - head) >> 2;
+  float4* xq = reinterpret_cast<float4*>(xb + head);
+  for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long long)gridDim.x * 256) {
+    float4 v = xq[q];
+    v.x = scale(v.x); v.y = scale(v.y); v.z = scale(v.z); v.w = scale(v.w);
+    xq[q] = v;
+  }
+  const long long rest = T_raw - 4 * nq;
+  if (blockIdx.x == 0 && threadIdx.x < rest) {
+    const long long t = threadIdx.x < head ? threadIdx.x : 4 * nq + threadIdx.x;
+    xb[t] = scale(xb[t]);
+  }
+}
+
 }  // namespace
 
 int seg_reduce_blocks(long long T_raw) {
@@ -651,6 +772,36 @@ hipError_t launch_seg_post_var(float* out, double* part, const float* stats, con
   long long nsb = (T_raw_max + 256 * 64 - 1) / (256 * 64);
   if (nsb > 8192) nsb = 8192;
   hipLaunchKernelGGL(seg_post_scale_var_kernel, dim3((unsigned)nsb, C), dim3(256), 0, st, out, part, stats, rows, T_raw_max, nb,
+                     keep_rms, peak_guard);
+  return hipGetLastError();
+}
+
+// ---- member-major forms ----------------------------------------------------------------------------------------------------------
+static bool seg_mm_grid_ok(const SegGeom& g, int rows_y, int E) {
+  return g.L >= 1 && (g.L + 1023) / 1024 <= 0x7fffffffll && rows_y >= 1 && rows_y <= 65535 && E >= 1 && E <= 65535;
+}
+hipError_t launch_seg_gather_noise_mm(const float* noise, float* z, const SegGeom& g, long long e0, int Bw, int E, int C,
+                                      hipStream_t st) {
+  if (!seg_mm_grid_ok(g, Bw, E) || C < 1 || e0 < 0 || e0 >= g.n_entries) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(seg_gather_noise_mm_kernel, dim3((unsigned)((g.L + 1023) / 1024), Bw, E), dim3(256), 0, st, noise, z, g, e0,
+                     C);
+  return hipGetLastError();
+}
+hipError_t launch_seg_stitch_mm(const float* y, const float* carry, float* members, const SegGeom& g, long long e0, int n_real,
+                                int Bw, int E, int C, hipStream_t st) {
+  if (!seg_mm_grid_ok(g, n_real, E) || n_real > Bw || C < 1 || e0 < 0 || e0 + n_real > g.n_entries) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(seg_stitch_mm_kernel, dim3((unsigned)((g.L + 1023) / 1024), n_real, E), dim3(256), 0, st, y, carry, members,
+                     g, e0, Bw, C);
+  return hipGetLastError();
+}
+hipError_t launch_seg_post_mm(float* members, double* part, const float* stats, int E, int C, long long T_raw, int keep_rms,
+                              int peak_guard, hipStream_t st) {
+  if (E < 1 || C < 1 || (long long)E * C > 65535 || T_raw < 1) return hipErrorInvalidValue;
+  const int nb = seg_reduce_blocks(T_raw);
+  hipLaunchKernelGGL(seg_post_reduce_kernel, dim3(nb, E * C), dim3(1024), 0, st, members, part, T_raw, nb);
+  long long nsb = (T_raw + 256 * 64 - 1) / (256 * 64);  // ~64 samples per thread
+  if (nsb > 8192) nsb = 8192;
+  hipLaunchKernelGGL(seg_post_scale_mm_kernel, dim3((unsigned)nsb, E * C), dim3(256), 0, st, members, part, stats, T_raw, nb, C,
                      keep_rms, peak_guard);
   return hipGetLastError();
 }

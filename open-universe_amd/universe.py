@@ -466,7 +466,8 @@ class Universe:
         """enhance_long / enhance_long_many: the options of `enhance` that the segmented calls do not take, and typos."""
         for k in ("target", "ensemble", "fake_score_snr", "warm_start"):
             if other.get(k) is not None:
-                raise ValueError(f"{method} does not take `{k}`")
+                hint = " (enhance_long_ensemble runs ensembles of long recordings)" if k == "ensemble" else ""
+                raise ValueError(f"{method} does not take `{k}`{hint}")
         if other.get("use_aux_signal"):
             raise ValueError(f"{method} does not take `use_aux_signal`")
         unknown = set(other) - {"target", "ensemble", "fake_score_snr", "warm_start", "use_aux_signal", "ensemble_stat"}
@@ -1011,7 +1012,8 @@ class Universe:
         drawn exactly as `enhance` draws it for this input, so a shared generator advances identically -- as ONE (n_steps, C,
         T_pad) tensor, n_steps times the recording.  `rng=noise.CounterNoise(seed, u)` removes that tensor: every window's noise
         is computed at its offset from the counter-based function (row c: stream id (u << 16) | c), and the memory of the call is
-        the workspace plus input and output.  A file that fits into one window gets the `enhance` result.  Workspace: ou_segments_workspace_bytes -- set by max_batch and segment_s."""
+        the workspace plus input and output.  A file that fits into one window gets the `enhance` result.  Workspace: ou_segments_workspace_bytes -- set by max_batch and segment_s.
+        Ensembles of long recordings: `enhance_long_ensemble` (`ensemble=` is refused here)."""
         self._refuse_long_options("enhance_long", other)
         self._sync_env()
         self._poll_deferred_status()
@@ -1026,24 +1028,87 @@ class Universe:
             epsilon = self.diff_kwargs.epsilon
         segment = int(round(float(segment_s) * self.fs))
         overlap = int(round(float(overlap_s) * self.fs))
+        if is_counter(rng):
+            noise, counter = None, (rng.seed, rng.stream_ids(C))
+        else:
+            noise, counter = self.draw_noise_like_enhance(rng, C, T_raw, n_steps), None
+        out = self._segments_call(x, segment, overlap, max_batch, n_steps, epsilon, keep_rms, noise, counter)
+        return out if mix.ndim == 2 else out[0]
+
+    def _segments_call(self, x, segment, overlap, max_batch, n_steps, epsilon, keep_rms, noise, counter):
+        """ou_enhance_segments of the prepared (C, T_raw) rows `x` on `noise` ((n_steps, C, T_pad)) or, with noise None, on the
+        counter source `counter` = (seed, C stream ids).  (Also what the tests of enhance_long_ensemble run a single member row
+        through, on that member's own noise or stream id.)"""
+        C, T_raw = x.shape
         need, B, L = c_size_t(), c_int32(), c_int32()
         _lib.check(self._L.ou_segments_workspace_bytes(self._handle, C, T_raw, segment, overlap, int(max_batch), byref(need),
                                                         byref(B), byref(L)), self._handle)
-        counter = is_counter(rng)
-        noise = None if counter else self.draw_noise_like_enhance(rng, C, T_raw, n_steps)
         sigma = self._sigma_table(n_steps)
         ws = self._segments_workspace(B.value, L.value, need.value)
         out = torch.empty(C, T_raw, dtype=torch.float32, device=self.device)
         flags = _lib.OU_ENH_KEEP_RMS if keep_rms else 0
-        source = self._counter_source(rng.seed, rng.stream_ids(C)) if counter else contextlib.nullcontext()
+        source = self._counter_source(*counter) if noise is None else contextlib.nullcontext()
         with torch.cuda.device(self.device), source:
             _lib.check(self._L.ou_enhance_segments(
                 self._handle, c_void_p(x.data_ptr()), c_void_p(out.data_ptr()),
-                None if counter else c_void_p(noise.data_ptr()), C, T_raw,
+                None if noise is None else c_void_p(noise.data_ptr()), C, T_raw,
                 segment, overlap, int(max_batch), n_steps, float(epsilon), ctypes.cast(sigma.data_ptr(), ctypes.POINTER(c_float)),
                 -1, flags, c_void_p(ws.data_ptr()), c_size_t(ws.numel()), self._stream()), self._handle)
         self._status()
-        return out if mix.ndim == 2 else out[0]
+        return out
+
+    @torch.no_grad()
+    def enhance_long_ensemble(self, mix, ensemble: int, ensemble_stat: str = "median", segment_s: float = SEGMENT_S,
+                              overlap_s: float = OVERLAP_S, max_batch: int = 32, rng=None, n_steps: Optional[int] = None,
+                              epsilon: Optional[float] = None, keep_rms: bool = False, return_members: bool = False):
+        """`enhance_ensemble` of a recording of any length (extension; ou_enhance_segments_ensemble).  `mix`: (T,) or (C, T), rows
+        are independent signals.  Member e of row c is `enhance_long` of row c alone on that member's noise (to fp32 round-off:
+        the kernels a group selects differ), the result is `ensemble_reduce` over the post-processed members of every row.  The
+        windows of `enhance_long` run in groups of at most `max_batch` walk rows, all E members of a window in one group, and the
+        conditioner runs once per window, not once per member (option `ens_share`).  `rng`: a generator -- the draws are those of
+        `enhance(mix, ensemble=E)` for this input, n_steps draws of (E * C, 1, T_pad), so it ends where
+        `advance_generator_like_enhance(rng, E * C, T)` ends -- or a `CounterNoise` (member e of row c: `stream_ids(C, E)`; no
+        noise tensor exists then).  Memory: the workspace (set by max_batch and segment_s) plus the E member rows of every
+        input row -- the one part that grows with the recording.  return_members=True: -> (result, members (E,) + mix.shape)."""
+        self._sync_env()
+        self._poll_deferred_status()
+        E = int(ensemble)
+        if not 1 <= E <= _lib.OU_MAX_ENSEMBLE:
+            raise ValueError(f"enhance_long_ensemble: 1 <= ensemble <= {_lib.OU_MAX_ENSEMBLE}")
+        if ensemble_stat not in _lib.ENSEMBLE_STATS:
+            raise NotImplementedError()  # universe.py:368
+        if mix.ndim not in (1, 2):
+            raise ValueError("enhance_long_ensemble takes (T,) or (C, T) signals")
+        x = self._prep(mix if mix.ndim == 2 else mix[None, :])
+        C, T_raw = x.shape
+        if T_raw < 1:
+            raise ValueError("enhance_long_ensemble: empty input signal")
+        n_steps = self.diff_kwargs.n_steps if n_steps is None else int(n_steps)
+        if epsilon is None:
+            epsilon = self.diff_kwargs.epsilon
+        segment = int(round(float(segment_s) * self.fs))
+        overlap = int(round(float(overlap_s) * self.fs))
+        need, B, L = c_size_t(), c_int32(), c_int32()
+        _lib.check(self._L.ou_segments_ensemble_workspace_bytes(self._handle, C, T_raw, segment, overlap, int(max_batch), E,
+                                                                 byref(need), byref(B), byref(L)), self._handle)
+        counter = is_counter(rng)
+        noise = None if counter else self.draw_noise_like_enhance(rng, E * C, T_raw, n_steps)
+        sigma = self._sigma_table(n_steps)
+        ws = self._segments_workspace(B.value, L.value, need.value)
+        out = torch.empty(C, T_raw, dtype=torch.float32, device=self.device)
+        members = torch.empty(E, C, T_raw, dtype=torch.float32, device=self.device)
+        flags = _lib.OU_ENH_KEEP_RMS if keep_rms else 0
+        source = self._counter_source(rng.seed, rng.stream_ids(C, E)) if counter else contextlib.nullcontext()
+        with torch.cuda.device(self.device), source:
+            _lib.check(self._L.ou_enhance_segments_ensemble(
+                self._handle, c_void_p(x.data_ptr()), c_void_p(out.data_ptr()), c_void_p(members.data_ptr()),
+                None if counter else c_void_p(noise.data_ptr()), C, T_raw, E, _lib.ENSEMBLE_STATS[ensemble_stat],
+                segment, overlap, int(max_batch), n_steps, float(epsilon), ctypes.cast(sigma.data_ptr(), ctypes.POINTER(c_float)),
+                -1, flags, c_void_p(ws.data_ptr()), c_size_t(ws.numel()), self._stream()), self._handle)
+        self._status()
+        if mix.ndim == 1:
+            out, members = out[0], members[:, 0]
+        return (out, members) if return_members else out
 
     @torch.no_grad()
     def enhance_long_many(self, signals, rngs=None, segment_s: float = SEGMENT_S, overlap_s: float = OVERLAP_S,
