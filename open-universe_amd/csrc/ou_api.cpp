@@ -1858,38 +1858,58 @@ int seg_batch(long long entries, int max_batch) {
   const long long groups = (entries + max_batch - 1) / max_batch;
   return (int)((entries + groups - 1) / groups);
 }
-// bytes of the segmented call's own area behind the walk's workspace
+// The segmented call's own area behind the walk's workspace (offsets in bytes): E member rows per input row, Bw entries (E * Bw
+// walk rows of L samples) per group.  `with_hist`: the scratch of the ensemble reduce; `with_table`: the SegRow table.
 struct SegArea {
-  size_t stats, row_scale, part, zbuf, carry, total;
+  size_t stats, row_scale, part, zbuf, carry, hist, geom, total;
 };
-SegArea seg_area(int C, int B, long long L) {
+SegArea seg_area(int C, int E, int Bw, long long L, bool with_hist, bool with_table) {
   SegArea a;
   size_t off = 0;
   a.stats = off; off += align256((size_t)C * 4 * 4);
   a.row_scale = off; off += align256((size_t)C * 4);
-  a.part = off; off += align256((size_t)C * 1024 * 3 * 8);
-  a.zbuf = off; off += align256((size_t)B * L * 4);
-  a.carry = off; off += align256((size_t)L * 4);
-  a.total = off;
-  return a;
-}
-
-// ... and of ou_enhance_segments_ensemble: E member rows per input row, Bw entries (E * Bw walk rows) per group
-struct SegEnsArea {
-  size_t stats, row_scale, part, zbuf, carry, hist, total;
-};
-SegEnsArea seg_ens_area(int C, int E, int Bw, long long L) {
-  SegEnsArea a;
-  size_t off = 0;
-  a.stats = off; off += align256((size_t)C * 4 * 4);
-  a.row_scale = off; off += align256((size_t)C * 4);
-  // the statistics' partials of the C input rows ([C][nb][3]), then the post partials of the E * C member rows ([E * C][nb][2])
+  // the statistics' partials of the C input rows ([C][nb][3]), then the post partials of the E * C long rows ([E * C][nb][2])
   a.part = off; off += align256(std::max((size_t)C * 3, (size_t)E * C * 2) * 1024 * 8);
   a.zbuf = off; off += align256((size_t)E * Bw * L * 4);
   a.carry = off; off += align256((size_t)E * L * 4);
-  a.hist = off; off += ou_ensemble_reduce_scratch_bytes(E, C);
+  a.hist = off; off += with_hist ? ou_ensemble_reduce_scratch_bytes(E, C) : 0;
+  a.geom = off; off += with_table ? align256((size_t)C * sizeof(SegRow)) : 0;
   a.total = off;
   return a;
+}
+// what a *_workspace_bytes function answers: the walk of B rows of L samples plus the area
+int seg_workspace_bytes(ou_handle* h, int B, long long L, const SegArea& A, size_t* nbytes, int32_t* batch, int32_t* length) {
+  size_t walk = 0;
+  if (const int rc = ou_workspace_bytes(h, B, (int32_t)L, &walk)) return rc;
+  *nbytes = align256(walk) + A.total;
+  if (batch) *batch = B;
+  if (length) *length = (int32_t)L;
+  return OU_OK;
+}
+// The caller's workspace against that answer (`sizer`: the name of the function that gives it), and the area's pointers.
+struct SegWs {
+  size_t walk;  // bytes of the walk's part
+  float *stats, *row_scale, *zbuf, *carry;
+  double* part;
+  int* hist;
+  SegRow* geom;
+};
+int seg_workspace(ou_handle* h, void* ws, size_t ws_bytes, int B, int L, const SegArea& A, const char* sizer, SegWs& w) {
+  if (const int rc = ou_workspace_bytes(h, B, L, &w.walk)) return rc;
+  w.walk = align256(w.walk);
+  if (ws_bytes < w.walk + A.total)
+    return fail(h, OU_ENOMEM, "workspace too small: need " + std::to_string(w.walk + A.total) + " bytes (" + sizer + ")");
+  if (!h->ws_ok(ws, ws_bytes, B, L))
+    return fail(h, OU_EINVAL, std::string("workspace was not prepared by ou_workspace_init for (batch, length) of ") + sizer);
+  char* seg = (char*)ws + w.walk;
+  w.stats = (float*)(seg + A.stats);
+  w.row_scale = (float*)(seg + A.row_scale);
+  w.part = (double*)(seg + A.part);
+  w.zbuf = (float*)(seg + A.zbuf);
+  w.carry = (float*)(seg + A.carry);
+  w.hist = (int*)(seg + A.hist);
+  w.geom = (SegRow*)(seg + A.geom);
+  return OU_OK;
 }
 // what both entry points of the segmented ensemble refuse, and the plan of the call.  Bw: entries per group
 int seg_ens_plan(ou_handle* h, const char* who, int C, long long T_raw, int segment, int overlap, int max_batch, int E, SegGeom& g,
@@ -1964,17 +1984,152 @@ bool seg_groups(int tot, int C, const int64_t* t_raw, long long segment, long lo
   add_groups(n_full, n_full + n_short);
   return true;
 }
-// the var call's own area: seg_area plus the geometry table
-struct SegVarArea {
-  SegArea a;
-  size_t geom, total;
-};
-SegVarArea seg_var_area(int C, int B, long long L) {
-  SegVarArea v;
-  v.a = seg_area(C, B, L);
-  v.geom = v.a.total;
-  v.total = v.geom + align256((size_t)C * sizeof(SegRow));
-  return v;
+
+// ---- the pieces of the segmented calls ------------------------------------------------------------------------
+// Whole-row statistics and frame energies of the C input rows (`esum`: the output rows hold the energies until the first stitch);
+// the caller turns the energies into w.row_scale.  false: a launch failed.
+template <class Rows>
+bool seg_row_stats(ou_handle* h, const float* mix, float* esum, const SegWs& w, const Rows& rows, int C, long long frames_max,
+                   hipStream_t st) {
+  const Model& m = h->m;
+  const float level = (float)std::pow(10.0, (double)m.cfg.level_db / 20.0);
+  return launched(h, launch_seg_stats(mix, w.part, w.stats, rows, C, level, st), "segment stats") &&
+         launched(h, launch_seg_mel_energy(mix, w.stats, h->W + m.mel.win_off, h->W + m.mel.tw_off, h->W + m.mel.fb_off, esum, rows,
+                                           C, m.mel.n_fft, m.mel.hop, m.mel.pad_left, m.mel.n_freq, m.mel.n_mels, frames_max, st),
+                  "segment mel energy");
+}
+// One step's noise of a group's n_rows walk rows of T columns, in w.zbuf: `gather(slice)` enqueues the gather from one step's
+// slice of the caller's tensor (step_noise words), or -- counter mode -- the same positions come straight from the function, no
+// whole-row noise exists then: `entry(row, stream_row, t0, len)` names the long row whose stream walk row `row` reads, the first
+// position and the length (0 behind it, so x needs no mask).
+template <class Gather, class EntryFn>
+auto seg_noise(ou_handle* h, Runner& r, const float* noise, size_t step_noise, float* zbuf, int T, int n_rows, Gather gather,
+               EntryFn entry) {
+  return [=, &r](int draw) -> const float* {
+    if (noise) {
+      gather(noise + (size_t)draw * step_noise);
+      return zbuf;
+    }
+    fill_noise_plane(r, zbuf, T, n_rows, h->noise_src.seed, draw, [&](int row, unsigned long long& sid, long long& t0, long long& len) {
+      long long stream_row = 0;
+      entry(row, stream_row, t0, len);
+      sid = h->noise_src.streams[(size_t)stream_row];
+    });
+    return zbuf;
+  };
+}
+// every member's last real window of the group -> `carry` (E, T): the window in front of the next group
+void seg_carry(Runner& r, float* carry, const float* x, int T, int Bw, int E, int n_real) {
+  for (int e = 0; e < E && r.ok(); e++)
+    r.chk(hipMemcpyAsync(carry + (size_t)e * T, x + ((size_t)e * Bw + n_real - 1) * T, (size_t)T * 4, hipMemcpyDeviceToDevice, r.st),
+          "carry");
+}
+// after the last group: what the operator seams see, and the post step over the E * C long rows
+template <class Rows>
+int seg_epilogue(ou_handle* h, float* long_rows, const SegWs& w, const Rows& rows, int E, int C, int L, uint32_t flags,
+                 hipStream_t st) {
+  h->cond_B = 0;  // (the operator seams see a whole-file batch only)
+  h->cond_T = L;
+  const PostFlags pf(flags);
+  if (!launched(h, launch_seg_post(long_rows, w.part, w.stats, rows, E, C, pf.keep_rms, pf.peak, st), "segment post")) return OU_EHIP;
+  return OU_OK;
+}
+
+// ou_enhance_segments (E = 1, members = out, no reduce) and ou_enhance_segments_ensemble behind their own refusals: the windows
+// in groups of Bw entries, every group one walk of E * Bw rows (member-major) whose conditioner runs once over the Bw inputs
+// (ensemble_impl's arrangement) or -- not shared, E = 1 -- over all rows; the members are stitched into the (E * C, T_raw) rows
+// `members`, post-processed there and, `reduce`, reduced into `out`.
+int seg_enhance(ou_handle* h, const char* who, const char* sizer, const float* mix, float* out, float* members, const float* noise,
+                int C, int E, bool reduce, int stat, SegGeom g, int Bw, int n_steps, double epsilon, const float* sigma_host,
+                uint32_t flags, void* ws, size_t ws_bytes, ou_stream_t stream) {
+  if (g.L > max_walk_length(h, false)) return fail(h, OU_EINVAL, std::string(who) + ": segment too long for one pass of the walk");
+  const int B = E * Bw;  // rows of the walk
+  const int L = (int)g.L;
+  SegWs w;
+  if (const int rc = seg_workspace(h, ws, ws_bytes, B, L, seg_area(C, E, Bw, g.L, reduce, false), sizer, w)) return rc;
+
+  CallScope scope(h, true);  // one chain on the caller's stream
+  hipStream_t st = (hipStream_t)stream;
+  const Model& m = h->m;
+  const bool share = h->opt.ens_share != 0 && E > 1;
+  const int Bc = share ? Bw : B;  // rows of the conditioner pass
+
+  // ---- whole-row statistics and mel scale of the C inputs
+  const long long Lf = g.T_pad / m.tot_ds;  // mel frames of the whole row (run_condition)
+  if (Lf > g.T_raw) return fail(h, OU_EINVAL, "internal: mel frames do not fit into the output row");
+  if (Lf > 0x7fffffffll) return fail(h, OU_EINVAL, "input too long");
+  const SegRowsAlike rows{SegRow{g.T_raw, g.T_pad, g.pad_left, g.n_win, 0, Lf}};
+  if (!seg_row_stats(h, mix, out, w, rows, C, Lf, st)) return OU_EHIP;
+  if (!launched(h, launch_mel_scale(out, w.row_scale, C, (int)Lf, st), "segment mel scale")) return OU_EHIP;
+
+  // ---- the groups: Bw entries at a time, E * Bw rows through the walk
+  const SamplerTables tab(m.cfg, n_steps, epsilon, sigma_host);
+  for (long long e0 = 0; e0 < g.n_entries; e0 += Bw) {
+    const int n_real = (int)std::min<long long>(Bw, g.n_entries - e0);
+    const SegEntriesArith ents{e0, g.n_entries, g.n_win, g.L, g.hop, g.overlap};
+    Runner r(h, ws, w.walk, false, st, B);
+    Persist P = layout_persist(r, L);
+    if (r.oom) return finish(h, r);
+    if (e0 == 0) tab.upload(r, P);  // (the persistent area of the workspace keeps the tables from group to group)
+    // the conditioner's runner: Bc rows on the prefix of the persistent tensors (ensemble_impl)
+    Runner rc(h, ws, w.walk, false, st, Bc);
+    rc.mel_scale_preset = true;
+    rc.status_words = r.status_words;
+    rc.block3_bar = r.block3_bar;
+    rc.gru_area_rows = B;
+    rc.off = r.off;
+    // the group's inputs: once into the prefix, or -- the conditioner over all rows -- once per member
+    for (int e = 0; e < (share ? 1 : E); e++)
+      rc.chk(launch_seg_gather_input(mix, w.stats, w.row_scale, P.mixn.p + (size_t)e * Bw * L, P.mel_scale + (size_t)e * Bw, rows,
+                                     ents, Bw, L, st), "segment gather");
+    run_condition(rc, P, P.mixn.p, L);
+    if (share && rc.ok()) {  // what the score passes read per row: rows [0, Bw) -> the rows of the other members
+      ReplicateTable rep;
+      int n_rep = 0;
+      auto flush_rep = [&]() {
+        if (n_rep && rc.ok()) rc.chk(launch_replicate_rows(rep, n_rep, E, st), "replicate rows");
+        n_rep = 0;
+      };
+      auto replicate = [&](void* p, size_t words) {
+        if (n_rep == kReplicateEntries) flush_rep();
+        rep.p[n_rep] = (unsigned*)p;
+        rep.n[n_rep] = (long long)words;
+        n_rep++;
+      };
+      auto replicate_t = [&](const Tensor& t) { replicate(t.p, (size_t)Bw * t.C * t.T); };
+      for (size_t j = 0; j < P.cond.size(); j++) { replicate_t(P.cond[j]); replicate_t(P.sc[j]); }
+      replicate_t(P.aux);
+      replicate_t(P.latent);
+      replicate_t(P.mixn);
+      replicate(P.mel_scale, (size_t)Bw);
+      flush_rep();
+    }
+    if (const int rc2 = finish(h, rc)) return rc2;
+    r.off = rc.off;
+    // walk row e * Bw + j: window k of long row e * C + c, positions s_k + i of that row's noise.  The filler rows of a short
+    // last group repeat their member's last real entry.
+    auto z = seg_noise(h, r, noise, (size_t)E * C * g.T_pad, w.zbuf, L, B,
+                       [&](const float* slice) {
+                         if (r.ok()) r.chk(launch_seg_gather_noise(slice, w.zbuf, rows, ents, Bw, L, Bw, E, C, st), "segment noise");
+                       },
+                       [&](int row, long long& stream_row, long long& t0, long long& len) {
+                         const int e = row / Bw;
+                         const SegEnt en = ents.entry(row - e * Bw);
+                         stream_row = (long long)e * C + en.row;
+                         t0 = seg_start_host(g, en.win);
+                         len = L;
+                       });
+    sample(r, P, L, tab, 0, nullptr, false, z);
+    if (r.ok()) r.chk(launch_seg_stitch(P.x.p, w.carry, members, rows, ents, n_real, L, Bw, E, C, st), "segment stitch");
+    if (e0 + Bw < g.n_entries) seg_carry(r, w.carry, P.x.p, L, Bw, E, n_real);
+    if (const int rc2 = finish(h, r)) return rc2;
+  }
+  // ---- the post step over every long row (keep_rms: the mix_rms of the member's own input row), then the reduce over e
+  if (const int rc = seg_epilogue(h, members, w, rows, E, C, L, flags, st)) return rc;
+  if (reduce && !launched(h, launch_ensemble_reduce(members, out, E, C, g.T_raw, g.T_raw, nullptr, stat, w.hist,
+                                                    w.hist + (size_t)C * E, st), "ensemble reduce"))
+    return OU_EHIP;
+  return OU_OK;
 }
 }  // namespace
 
@@ -2013,14 +2168,7 @@ int ou_segments_workspace_bytes(const ou_handle* hc, int32_t C, int64_t T_raw, i
   if (!seg_plan(h->m.tot_ds, T_raw, segment, overlap, p)) return fail(h, OU_EINVAL, p.err);
   if (p.g.L > 0x7fffffffll) return fail(h, OU_EINVAL, "segment too long");
   const int B = seg_batch((long long)C * p.g.n_win, max_batch);
-  size_t walk = 0;
-  const int rc = ou_workspace_bytes(h, B, (int32_t)p.g.L, &walk);
-  if (rc != OU_OK) return rc;
-  walk = align256(walk);
-  *nbytes = walk + seg_area(C, B, p.g.L).total;
-  if (batch) *batch = B;
-  if (length) *length = (int32_t)p.g.L;
-  return OU_OK;
+  return seg_workspace_bytes(h, B, p.g.L, seg_area(C, 1, B, p.g.L, false, false), nbytes, batch, length);
 }
 
 int ou_enhance_segments(ou_handle* h, const float* mix, float* out, const float* noise, int32_t C, int64_t T_raw,
@@ -2036,80 +2184,8 @@ int ou_enhance_segments(ou_handle* h, const float* mix, float* out, const float*
   if (!seg_plan(h->m.tot_ds, T_raw, segment, overlap, plan)) return fail(h, OU_EINVAL, plan.err);
   SegGeom g = plan.g;
   g.n_entries = (long long)C * g.n_win;
-  if (g.L > max_walk_length(h, false))
-    return fail(h, OU_EINVAL, "ou_enhance_segments: segment too long for one pass of the walk");
-  const int B = seg_batch(g.n_entries, max_batch);
-  const int L = (int)g.L;
-  size_t walk = 0;
-  if (const int rc = ou_workspace_bytes(h, B, L, &walk)) return rc;
-  walk = align256(walk);
-  const SegArea A = seg_area(C, B, g.L);
-  if (ws_bytes < walk + A.total) return fail(h, OU_ENOMEM, "workspace too small: need " + std::to_string(walk + A.total) +
-                                                               " bytes (ou_segments_workspace_bytes)");
-  if (!h->ws_ok(ws, ws_bytes, B, L))
-    return fail(h, OU_EINVAL, "workspace was not prepared by ou_workspace_init for (batch, length) of ou_segments_workspace_bytes");
-  char* seg = (char*)ws + walk;
-  float* stats = (float*)(seg + A.stats);
-  float* row_scale = (float*)(seg + A.row_scale);
-  double* part = (double*)(seg + A.part);
-  float* zbuf = (float*)(seg + A.zbuf);
-  float* carry = (float*)(seg + A.carry);
-
-  CallScope scope(h, true);  // one chain on the caller's stream
-  hipStream_t st = (hipStream_t)stream;
-  const Model& m = h->m;
-
-  // ---- whole-file statistics and mel scale (the output buffer holds the frame energies until the first stitch)
-  const float level = (float)std::pow(10.0, (double)m.cfg.level_db / 20.0);
-  const long long Lf = g.T_pad / m.tot_ds;  // mel frames of the whole file (run_condition)
-  if (Lf > g.T_raw) return fail(h, OU_EINVAL, "internal: mel frames do not fit into the output row");
-  if (!launched(h, launch_seg_stats(mix, part, stats, C, g.T_raw, g.T_pad, level, st), "segment stats")) return OU_EHIP;
-  if (!launched(h, launch_seg_mel_energy(mix, stats, h->W + m.mel.win_off, h->W + m.mel.tw_off, h->W + m.mel.fb_off, out, C,
-                                         g.T_raw, g.T_pad, g.pad_left, m.mel.n_fft, m.mel.hop, m.mel.pad_left, m.mel.n_freq,
-                                         m.mel.n_mels, Lf, st), "segment mel energy"))
-    return OU_EHIP;
-  if (Lf > 0x7fffffffll) return fail(h, OU_EINVAL, "input too long");
-  if (!launched(h, launch_mel_scale(out, row_scale, C, (int)Lf, st), "segment mel scale")) return OU_EHIP;
-
-  // ---- the windows, B at a time, through the plain walk
-  const SamplerTables tab(m.cfg, n_steps, epsilon, sigma_host);
-  const size_t step_noise = (size_t)C * g.T_pad;  // one step of the whole-file noise
-  for (long long e0 = 0; e0 < g.n_entries; e0 += B) {
-    const int n_real = (int)std::min<long long>(B, g.n_entries - e0);
-    Runner r(h, ws, walk, false, st, B);
-    r.mel_scale_preset = true;
-    Persist P = layout_persist(r, L);
-    if (r.oom) return finish(h, r);
-    if (e0 == 0) tab.upload(r, P);  // (the persistent area of the workspace keeps the tables from group to group)
-    r.chk(launch_seg_gather_input(mix, stats, row_scale, P.mixn.p, P.mel_scale, g, e0, B, st), "segment gather");
-    run_condition(r, P, P.mixn.p, L);
-    // One step's noise of the group's windows: a slice of the caller's whole-row tensor, or -- counter mode -- the same
-    // positions (window k of row c: t = s_k + i, stream of row c) straight from the function; no whole-row noise exists then.
-    auto z = [&](int draw) -> const float* {
-      if (noise) {
-        if (r.ok()) r.chk(launch_seg_gather_noise(noise + (size_t)draw * step_noise, zbuf, g, e0, B, st), "segment noise");
-        return zbuf;
-      }
-      fill_noise_plane(r, zbuf, L, B, h->noise_src.seed, draw, [&](int j, unsigned long long& sid, long long& t0, long long& len) {
-        const long long e = std::min<long long>(e0 + j, g.n_entries - 1);  // (the filler rows of a short last group)
-        const long long c = e / g.n_win;
-        sid = h->noise_src.streams[c];
-        t0 = seg_start_host(g, e - c * g.n_win);
-        len = L;
-      });
-      return zbuf;
-    };
-    sample(r, P, L, tab, 0, nullptr, false, z);
-    if (r.ok()) r.chk(launch_seg_stitch(P.x.p, carry, out, g, e0, n_real, st), "segment stitch");
-    if (r.ok() && e0 + B < g.n_entries)  // the window in front of the next group
-      r.chk(hipMemcpyAsync(carry, P.x.p + (size_t)(n_real - 1) * L, (size_t)L * 4, hipMemcpyDeviceToDevice, st), "carry");
-    if (const int rc = finish(h, r)) return rc;
-  }
-  h->cond_B = 0;  // (the operator seams see a whole-file batch only)
-  h->cond_T = L;
-  const PostFlags pf(flags);
-  if (!launched(h, launch_seg_post(out, part, stats, C, g.T_raw, pf.keep_rms, pf.peak, st), "segment post")) return OU_EHIP;
-  return OU_OK;
+  return seg_enhance(h, "ou_enhance_segments", "ou_segments_workspace_bytes", mix, out, out, noise, C, 1, false, 0, g,
+                     seg_batch(g.n_entries, max_batch), n_steps, epsilon, sigma_host, flags, ws, ws_bytes, stream);
 }
 
 int ou_segments_ensemble_workspace_bytes(const ou_handle* hc, int32_t C, int64_t T_raw, int32_t segment, int32_t overlap,
@@ -2120,17 +2196,9 @@ int ou_segments_ensemble_workspace_bytes(const ou_handle* hc, int32_t C, int64_t
   int Bw = 0;
   if (const int rc = seg_ens_plan(h, "ou_segments_ensemble_workspace_bytes", C, T_raw, segment, overlap, max_batch, E, g, Bw))
     return rc;
-  size_t walk = 0;
-  if (const int rc = ou_workspace_bytes(h, E * Bw, (int32_t)g.L, &walk)) return rc;
-  *nbytes = align256(walk) + seg_ens_area(C, E, Bw, g.L).total;
-  if (batch) *batch = E * Bw;
-  if (length) *length = (int32_t)g.L;
-  return OU_OK;
+  return seg_workspace_bytes(h, E * Bw, g.L, seg_area(C, E, Bw, g.L, true, false), nbytes, batch, length);
 }
 
-// ou_enhance_segments with E members per row: the windows of ou_enhance_segments in groups of Bw entries, every group one walk
-// of E * Bw rows (member-major) whose conditioner runs once over the Bw inputs (ensemble_impl's arrangement); the members are
-// stitched into the caller's (E * C, T_raw) rows, post-processed there and reduced into `out`.
 int ou_enhance_segments_ensemble(ou_handle* h, const float* mix, float* out, float* members, const float* noise, int32_t C,
                                  int64_t T_raw, int32_t E, int32_t stat, int32_t segment, int32_t overlap, int32_t max_batch,
                                  int32_t n_steps, double epsilon, const float* sigma_host, int32_t warm_start, uint32_t flags,
@@ -2146,127 +2214,10 @@ int ou_enhance_segments_ensemble(ou_handle* h, const float* mix, float* out, flo
     return fail(h, OU_EINVAL, std::string(who) + ": `members` must be given ((E * C, T_raw): the post step runs over whole member rows)");
   if (warm_start >= 0 || (flags & OU_ENH_USE_AUX_SIGNAL))
     return fail(h, OU_EINVAL, std::string(who) + ": warm_start and use_aux_signal are not supported");
-  const int EC = E * C;
-  if (const int rc = check_noise_source(h, noise, EC, "the member rows of the call (E * C = ", true)) return rc;
+  if (const int rc = check_noise_source(h, noise, E * C, "the member rows of the call (E * C = ", true)) return rc;
   if (const int rc = check_steps(h, n_steps, warm_start)) return rc;
-  if (g.L > max_walk_length(h, false)) return fail(h, OU_EINVAL, std::string(who) + ": segment too long for one pass of the walk");
-  const int B = E * Bw;  // rows of the walk
-  const int L = (int)g.L;
-  size_t walk = 0;
-  if (const int rc = ou_workspace_bytes(h, B, L, &walk)) return rc;
-  walk = align256(walk);
-  const SegEnsArea A = seg_ens_area(C, E, Bw, g.L);
-  if (ws_bytes < walk + A.total) return fail(h, OU_ENOMEM, "workspace too small: need " + std::to_string(walk + A.total) +
-                                                               " bytes (ou_segments_ensemble_workspace_bytes)");
-  if (!h->ws_ok(ws, ws_bytes, B, L))
-    return fail(h, OU_EINVAL,
-                "workspace was not prepared by ou_workspace_init for (batch, length) of ou_segments_ensemble_workspace_bytes");
-  char* seg = (char*)ws + walk;
-  float* stats = (float*)(seg + A.stats);
-  float* row_scale = (float*)(seg + A.row_scale);
-  double* part = (double*)(seg + A.part);
-  float* zbuf = (float*)(seg + A.zbuf);
-  float* carry = (float*)(seg + A.carry);
-  int* hist = (int*)(seg + A.hist);
-
-  CallScope scope(h, true);  // one chain on the caller's stream
-  hipStream_t st = (hipStream_t)stream;
-  const Model& m = h->m;
-  const bool share = h->opt.ens_share != 0 && E > 1;
-  const int Bc = share ? Bw : B;  // rows of the conditioner pass
-
-  // ---- whole-row statistics and mel scale of the C inputs, as ou_enhance_segments (`out` holds the frame energies meanwhile)
-  const float level = (float)std::pow(10.0, (double)m.cfg.level_db / 20.0);
-  const long long Lf = g.T_pad / m.tot_ds;
-  if (Lf > g.T_raw) return fail(h, OU_EINVAL, "internal: mel frames do not fit into the output row");
-  if (Lf > 0x7fffffffll) return fail(h, OU_EINVAL, "input too long");
-  if (!launched(h, launch_seg_stats(mix, part, stats, C, g.T_raw, g.T_pad, level, st), "segment stats")) return OU_EHIP;
-  if (!launched(h, launch_seg_mel_energy(mix, stats, h->W + m.mel.win_off, h->W + m.mel.tw_off, h->W + m.mel.fb_off, out, C,
-                                         g.T_raw, g.T_pad, g.pad_left, m.mel.n_fft, m.mel.hop, m.mel.pad_left, m.mel.n_freq,
-                                         m.mel.n_mels, Lf, st), "segment mel energy"))
-    return OU_EHIP;
-  if (!launched(h, launch_mel_scale(out, row_scale, C, (int)Lf, st), "segment mel scale")) return OU_EHIP;
-
-  // ---- the groups: Bw entries at a time, E * Bw rows through the walk
-  const SamplerTables tab(m.cfg, n_steps, epsilon, sigma_host);
-  const size_t step_noise = (size_t)EC * g.T_pad;  // one step of the members' whole-row noise
-  for (long long e0 = 0; e0 < g.n_entries; e0 += Bw) {
-    const int n_real = (int)std::min<long long>(Bw, g.n_entries - e0);
-    Runner r(h, ws, walk, false, st, B);
-    Persist P = layout_persist(r, L);
-    if (r.oom) return finish(h, r);
-    if (e0 == 0) tab.upload(r, P);  // (the persistent area of the workspace keeps the tables from group to group)
-    // the conditioner's runner: Bc rows on the prefix of the persistent tensors (ensemble_impl)
-    Runner rc(h, ws, walk, false, st, Bc);
-    rc.mel_scale_preset = true;
-    rc.status_words = r.status_words;
-    rc.block3_bar = r.block3_bar;
-    rc.gru_area_rows = B;
-    rc.off = r.off;
-    // the group's inputs: once into the prefix, or -- the conditioner over all rows -- once per member
-    for (int e = 0; e < (share ? 1 : E); e++)
-      rc.chk(launch_seg_gather_input(mix, stats, row_scale, P.mixn.p + (size_t)e * Bw * L, P.mel_scale + (size_t)e * Bw, g, e0, Bw,
-                                     st), "segment gather");
-    run_condition(rc, P, P.mixn.p, L);
-    if (share && rc.ok()) {  // what the score passes read per row: rows [0, Bw) -> the rows of the other members
-      ReplicateTable rep;
-      int n_rep = 0;
-      auto flush_rep = [&]() {
-        if (n_rep && rc.ok()) rc.chk(launch_replicate_rows(rep, n_rep, E, st), "replicate rows");
-        n_rep = 0;
-      };
-      auto replicate = [&](void* p, size_t words) {
-        if (n_rep == kReplicateEntries) flush_rep();
-        rep.p[n_rep] = (unsigned*)p;
-        rep.n[n_rep] = (long long)words;
-        n_rep++;
-      };
-      auto replicate_t = [&](const Tensor& t) { replicate(t.p, (size_t)Bw * t.C * t.T); };
-      for (size_t j = 0; j < P.cond.size(); j++) { replicate_t(P.cond[j]); replicate_t(P.sc[j]); }
-      replicate_t(P.aux);
-      replicate_t(P.latent);
-      replicate_t(P.mixn);
-      replicate(P.mel_scale, (size_t)Bw);
-      flush_rep();
-    }
-    if (const int rc2 = finish(h, rc)) return rc2;
-    r.off = rc.off;
-    // One step's noise of the E * Bw walk rows: window k of member row e * C + c reads the positions s_k + i of that row's
-    // noise -- gathered from the caller's tensor, or (counter mode) filled from the stream of that member row.  The filler
-    // rows of a short last group repeat their member's last real entry.
-    auto z = [&](int draw) -> const float* {
-      if (noise) {
-        if (r.ok())
-          r.chk(launch_seg_gather_noise_mm(noise + (size_t)draw * step_noise, zbuf, g, e0, Bw, E, C, st), "segment noise");
-        return zbuf;
-      }
-      fill_noise_plane(r, zbuf, L, B, h->noise_src.seed, draw, [&](int row, unsigned long long& sid, long long& t0, long long& len) {
-        const int e = row / Bw, j = row - e * Bw;
-        const long long en = std::min<long long>(e0 + j, g.n_entries - 1);
-        const long long c = en / g.n_win;
-        sid = h->noise_src.streams[(size_t)e * C + c];
-        t0 = seg_start_host(g, en - c * g.n_win);
-        len = L;
-      });
-      return zbuf;
-    };
-    sample(r, P, L, tab, 0, nullptr, false, z);
-    if (r.ok()) r.chk(launch_seg_stitch_mm(P.x.p, carry, members, g, e0, n_real, Bw, E, C, st), "segment stitch");
-    if (e0 + Bw < g.n_entries)  // every member's window in front of the next group
-      for (int e = 0; e < E && r.ok(); e++)
-        r.chk(hipMemcpyAsync(carry + (size_t)e * L, P.x.p + ((size_t)e * Bw + n_real - 1) * L, (size_t)L * 4,
-                             hipMemcpyDeviceToDevice, st), "carry");
-    if (const int rc2 = finish(h, r)) return rc2;
-  }
-  h->cond_B = 0;  // (the operator seams see a whole-file batch only)
-  h->cond_T = L;
-  // ---- the post step over every member row (keep_rms: the mix_rms of the member's own input row), then the reduce over e
-  const PostFlags pf(flags);
-  if (!launched(h, launch_seg_post_mm(members, part, stats, E, C, g.T_raw, pf.keep_rms, pf.peak, st), "segment post")) return OU_EHIP;
-  if (!launched(h, launch_ensemble_reduce(members, out, E, C, g.T_raw, g.T_raw, nullptr, stat, hist, hist + (size_t)C * E, st),
-                "ensemble reduce"))
-    return OU_EHIP;
-  return OU_OK;
+  return seg_enhance(h, who, "ou_segments_ensemble_workspace_bytes", mix, out, members, noise, C, E, true, stat, g, Bw, n_steps,
+                     epsilon, sigma_host, flags, ws, ws_bytes, stream);
 }
 
 int ou_segment_groups(int32_t tot_ds, int32_t C, const int64_t* t_raw, int32_t segment, int32_t overlap, int32_t max_batch,
@@ -2299,14 +2250,7 @@ int ou_segments_var_workspace_bytes(const ou_handle* hc, int32_t C, const int64_
   if (!h || !nbytes || !t_raw || C < 1 || max_batch < 1) return fail(h, OU_EINVAL, "bad argument");
   SegGroups G;
   if (!seg_groups(h->m.tot_ds, C, t_raw, segment, overlap, max_batch, G)) return fail(h, OU_EINVAL, G.err);
-  size_t walk = 0;
-  const int rc = ou_workspace_bytes(h, G.batch, (int32_t)G.length, &walk);
-  if (rc != OU_OK) return rc;
-  walk = align256(walk);
-  *nbytes = walk + seg_var_area(C, G.batch, G.length).total;
-  if (batch) *batch = G.batch;
-  if (length) *length = (int32_t)G.length;
-  return OU_OK;
+  return seg_workspace_bytes(h, G.batch, G.length, seg_area(C, 1, G.batch, G.length, false, true), nbytes, batch, length);
 }
 
 int ou_enhance_segments_var(ou_handle* h, const float* mix, float* out, const float* noise, int32_t C, int64_t T_raw_max,
@@ -2329,22 +2273,10 @@ int ou_enhance_segments_var(ou_handle* h, const float* mix, float* out, const fl
   if (G.length > max_walk_length(h, false))
     return fail(h, OU_EINVAL, "ou_enhance_segments_var: segment too long for one pass of the walk");
   const int B = G.batch;
-  size_t walk = 0;
-  if (const int rc = ou_workspace_bytes(h, B, (int32_t)G.length, &walk)) return rc;
-  walk = align256(walk);
-  const SegVarArea A = seg_var_area(C, B, G.length);
-  if (ws_bytes < walk + A.total) return fail(h, OU_ENOMEM, "workspace too small: need " + std::to_string(walk + A.total) +
-                                                               " bytes (ou_segments_var_workspace_bytes)");
-  if (!h->ws_ok(ws, ws_bytes, B, (int)G.length))
-    return fail(h, OU_EINVAL,
-                "workspace was not prepared by ou_workspace_init for (batch, length) of ou_segments_var_workspace_bytes");
-  char* seg = (char*)ws + walk;
-  float* stats = (float*)(seg + A.a.stats);
-  float* row_scale = (float*)(seg + A.a.row_scale);
-  double* part = (double*)(seg + A.a.part);
-  float* zbuf = (float*)(seg + A.a.zbuf);
-  float* carry = (float*)(seg + A.a.carry);
-  SegRow* geom = (SegRow*)(seg + A.geom);
+  SegWs w;
+  if (const int rc = seg_workspace(h, ws, ws_bytes, B, (int)G.length, seg_area(C, 1, B, G.length, false, true),
+                                   "ou_segments_var_workspace_bytes", w))
+    return rc;
 
   CallScope scope(h, true);  // one chain on the caller's stream
   hipStream_t st = (hipStream_t)stream;
@@ -2359,10 +2291,7 @@ int ou_enhance_segments_var(ou_handle* h, const float* mix, float* out, const fl
     frames_max = std::max(frames_max, Lf);
   }
   if (frames_max > 0x7fffffffll) return fail(h, OU_EINVAL, "input too long");
-  SegVar v;
-  v.S = G.S; v.hop = G.hop; v.overlap = G.O;
-  v.row_stride = T_raw_max; v.noise_stride = T_pad_max;
-  v.tot_ds = tot;
+  const SegVar v{G.S, G.hop, tot};
   for (int off = 0; off < C; off += kSegRowsPerLaunch) {
     SegRowBlock blk;
     const int n = std::min(C - off, kSegRowsPerLaunch);
@@ -2370,19 +2299,14 @@ int ou_enhance_segments_var(ou_handle* h, const float* mix, float* out, const fl
       blk.t_raw[i] = i < n ? t_raw[off + i] : 1;
       blk.first[i] = i < n ? G.first[off + i] : 0;
     }
-    if (!launched(h, launch_seg_upload_rows(geom, blk, n, off, v, st), "segment rows")) return OU_EHIP;
+    if (!launched(h, launch_seg_upload_rows(w.geom, blk, n, off, v, st), "segment rows")) return OU_EHIP;
   }
-  const float level = (float)std::pow(10.0, (double)m.cfg.level_db / 20.0);
-  if (!launched(h, launch_seg_stats_var(mix, part, stats, geom, C, T_raw_max, level, st), "segment stats")) return OU_EHIP;
-  if (!launched(h, launch_seg_mel_energy_var(mix, stats, h->W + m.mel.win_off, h->W + m.mel.tw_off, h->W + m.mel.fb_off, out,
-                                             geom, C, T_raw_max, m.mel.n_fft, m.mel.hop, m.mel.pad_left, m.mel.n_freq,
-                                             m.mel.n_mels, frames_max, st), "segment mel energy"))
-    return OU_EHIP;
-  if (!launched(h, launch_seg_mel_scale_var(out, row_scale, geom, C, T_raw_max, st), "segment mel scale")) return OU_EHIP;
+  const SegRowsTable rows{w.geom, T_raw_max, T_pad_max};
+  if (!seg_row_stats(h, mix, out, w, rows, C, frames_max, st)) return OU_EHIP;
+  if (!launched(h, launch_seg_mel_scale_var(out, w.row_scale, w.geom, C, T_raw_max, st), "segment mel scale")) return OU_EHIP;
 
   // ---- the groups: B entries at a time through the walk -- the plain one, or the ragged one where the entries differ in length
   const SamplerTables tab(m.cfg, n_steps, epsilon, sigma_host);
-  const size_t step_noise = (size_t)C * T_pad_max;  // one step of the callers' noise
   const long long n_entries = (long long)G.entries.size();
   for (size_t gi = 0; gi < G.group_first.size(); gi++) {
     const long long e0 = G.group_first[gi];
@@ -2393,20 +2317,20 @@ int ou_enhance_segments_var(ou_handle* h, const float* mix, float* out, const fl
     auto entry = [&](int j) -> const SegEntry& { return G.entries[(size_t)(e0 + std::min(j, n_real - 1))]; };
     int T = 0;
     for (int j = 0; j < n_real; j++) T = std::max(T, entry(j).len);
-    auto start_of = [&](const SegEntry& e) { return e.win < G.rows[e.row].n_win - 1 ? e.win * G.hop : G.rows[e.row].T_pad - e.len; };
-    // fn(block, n, j0) for the entries [0, count) of the group, kSegEntriesPerLaunch at a time
+    // fn(entries, n) for the entries [0, count) of the group, kSegEntriesPerLaunch at a time
     auto for_blocks = [&](int count, auto fn) {
       for (int j0 = 0; j0 < count; j0 += kSegEntriesPerLaunch) {
-        SegEntryBlock blk;
+        SegEntriesList ents;
+        ents.j0 = j0; ents.hop = G.hop; ents.overlap = G.O;
         const int n = std::min(count - j0, kSegEntriesPerLaunch);
         for (int i = 0; i < kSegEntriesPerLaunch; i++) {
           const SegEntry& e = entry(j0 + std::min(i, n - 1));
-          blk.row[i] = e.row; blk.win[i] = e.win; blk.len[i] = e.len;
+          ents.blk.row[i] = e.row; ents.blk.win[i] = e.win; ents.blk.len[i] = e.len;
         }
-        fn(blk, n, j0);
+        fn(ents, n);
       }
     };
-    Runner r(h, ws, walk, false, st, B);
+    Runner r(h, ws, w.walk, false, st, B);
     r.mel_scale_preset = true;
     Persist P = layout_persist(r, T);
     if (r.oom) return finish(h, r);
@@ -2415,50 +2339,38 @@ int ou_enhance_segments_var(ou_handle* h, const float* mix, float* out, const fl
       // the entries' lengths on every level of the network (as ou_enhance_var; an entry is an already padded window, so its
       // length is the level-0 length itself)
       if (const int rc = set_levels(r, T)) return rc;
-      for_blocks(B, [&](const SegEntryBlock& blk, int n, int j0) {
-        r.chk(launch_seg_upload_lens(P.lens, blk, n, j0, B, r.lv, st), "segment lens");
+      for_blocks(B, [&](const SegEntriesList& ents, int n) {
+        r.chk(launch_seg_upload_lens(P.lens, ents.blk, n, ents.j0, B, r.lv, st), "segment lens");
       });
       r.ragged = true;
       r.lens_dev = P.lens;
     }
-    for_blocks(B, [&](const SegEntryBlock& blk, int n, int j0) {
-      r.chk(launch_seg_gather_input_var(mix, stats, row_scale, geom, P.mixn.p, P.mel_scale, blk, n, j0, T, v, st),
-            "segment gather");
+    for_blocks(B, [&](const SegEntriesList& ents, int n) {
+      r.chk(launch_seg_gather_input(mix, w.stats, w.row_scale, P.mixn.p, P.mel_scale, rows, ents, n, T, st), "segment gather");
     });
     run_condition(r, P, P.mixn.p, T);
-    // one step's noise of the group's entries (0 behind an entry's own length, so x needs no mask): a slice of the caller's
-    // rows, or -- counter mode -- the same positions (window k of row c: t = s_k + i, stream of row c) straight from the function
-    auto z = [&](int draw) -> const float* {
-      if (noise) {
-        for_blocks(B, [&](const SegEntryBlock& blk, int n, int j0) {
-          if (r.ok())
-            r.chk(launch_seg_gather_noise_var(noise + (size_t)draw * step_noise, geom, zbuf, blk, n, j0, T, v, st), "segment noise");
-        });
-        return zbuf;
-      }
-      fill_noise_plane(r, zbuf, T, B, h->noise_src.seed, draw, [&](int j, unsigned long long& sid, long long& t0, long long& len) {
-        const SegEntry& e = entry(j);
-        sid = h->noise_src.streams[e.row];
-        t0 = start_of(e);
-        len = e.len;
-      });
-      return zbuf;
-    };
+    // walk row j: window k of row c, positions s_k + i of that row's noise
+    auto z = seg_noise(h, r, noise, (size_t)C * T_pad_max, w.zbuf, T, B,
+                       [&](const float* slice) {
+                         for_blocks(B, [&](const SegEntriesList& ents, int n) {
+                           if (r.ok()) r.chk(launch_seg_gather_noise(slice, w.zbuf, rows, ents, n, T, B, 1, C, st), "segment noise");
+                         });
+                       },
+                       [&](int j, long long& stream_row, long long& t0, long long& len) {
+                         const SegEntry& e = entry(j);
+                         stream_row = e.row;
+                         t0 = e.win < G.rows[e.row].n_win - 1 ? e.win * G.hop : G.rows[e.row].T_pad - e.len;
+                         len = e.len;
+                       });
     sample(r, P, T, tab, 0, nullptr, false, z);
     if (r.ok())
-      for_blocks(n_real, [&](const SegEntryBlock& blk, int n, int j0) {
-        r.chk(launch_seg_stitch_var(P.x.p, carry, out, geom, blk, n, j0, T, v, st), "segment stitch");
+      for_blocks(n_real, [&](const SegEntriesList& ents, int n) {
+        r.chk(launch_seg_stitch(P.x.p, w.carry, out, rows, ents, n, T, B, 1, C, st), "segment stitch");
       });
-    if (r.ok() && full && e_end < G.n_full)  // the window in front of the next group
-      r.chk(hipMemcpyAsync(carry, P.x.p + (size_t)(n_real - 1) * T, (size_t)T * 4, hipMemcpyDeviceToDevice, st), "carry");
+    if (full && e_end < G.n_full) seg_carry(r, w.carry, P.x.p, T, B, 1, n_real);  // the window in front of the next group
     if (const int rc = finish(h, r)) return rc;
   }
-  h->cond_B = 0;  // (the operator seams see a whole-file batch only)
-  h->cond_T = (int)G.length;
-  const PostFlags pf(flags);
-  if (!launched(h, launch_seg_post_var(out, part, stats, geom, C, T_raw_max, pf.keep_rms, pf.peak, st), "segment post"))
-    return OU_EHIP;
-  return OU_OK;
+  return seg_epilogue(h, out, w, rows, 1, C, (int)G.length, flags, st);
 }
 
 int ou_transform_frames(int32_t T, int32_t n_fft, int32_t hop) {

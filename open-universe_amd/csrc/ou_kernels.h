@@ -182,87 +182,127 @@ hipError_t launch_mel(const float* x, const float* win, const float* tw, const f
 hipError_t launch_mel_scale(const float* esum, float* scale, int B, int L, hipStream_t st, const int* lens = nullptr);
 
 // ---- segmented enhance (ou_segment.hip): long rows cut into overlapping windows of L samples --------------------------------
-// Window k of a row starts at k * hop (the last one at T_pad - L); the entries of a call are (row, window) pairs in row-major
-// order, e = row * n_win + k.  Every offset into a long row is 64-bit.
-struct SegGeom {
+// Window k of a row starts at k * hop (the last one at T_pad - L); the entries of a call are (row, window) pairs.  Every offset
+// into a long row is 64-bit.  Each operation is ONE kernel body, a template over two small by-value descriptions (DESIGN.md
+// 4.6.2): "the rows of the call" (SegRowsAlike | SegRowsTable) and "the entries of a group" (SegEntriesArith | SegEntriesList).
+struct SegGeom {  // the plan of a row (host side, seg_plan)
   long long T_raw, T_pad, pad_left;
   long long L, hop, overlap;
   long long n_win, n_entries;
 };
-// blocks per row of the whole-row reductions (their partials: [C][nb][3] doubles for the statistics, [C][nb][2] for the post)
-int seg_reduce_blocks(long long T_raw);
-// stats[c] = {mean, gain, mix_rms, 0} of the padded whole row (pad_normalize_kernel's layout and arithmetic)
-hipError_t launch_seg_stats(const float* mix, double* part, float* stats, int C, long long T_raw, long long T_pad, float level,
-                            hipStream_t st);
-// esum[c][f] = frame energies of the mel front-end over the whole normalised row (mel_kernel without the mel output)
-hipError_t launch_seg_mel_energy(const float* mix, const float* stats, const float* win, const float* tw, const float* fb,
-                                 float* esum, int C, long long T_raw, long long T_pad, long long pad_left, int n_fft, int hop,
-                                 int mel_pad, int n_freq, int n_mels, long long L, hipStream_t st);
-// the B windows e0 .. e0 + B - 1 of a group: normalised input (B, L) and each entry's row mel scale; one step's noise (B, L)
-hipError_t launch_seg_gather_input(const float* mix, const float* stats, const float* row_mel_scale, float* mixn,
-                                   float* mel_scale, const SegGeom& g, long long e0, int B, hipStream_t st);
-hipError_t launch_seg_gather_noise(const float* noise, float* z, const SegGeom& g, long long e0, int B, hipStream_t st);
-// crossfade the group's n_real window outputs (and `carry`, the window in front of the group) into the unpadded long output
-hipError_t launch_seg_stitch(const float* y, const float* carry, float* out, const SegGeom& g, long long e0, int n_real,
-                             hipStream_t st);
-// keep_rms + peak guard over whole long rows, in place (universe.py:349-357)
-hipError_t launch_seg_post(float* out, double* part, const float* stats, int C, long long T_raw, int keep_rms, int peak_guard,
-                           hipStream_t st);
-
-// ---- ... with rows of lengths of their own (ou_enhance_segments_var) ---------------------------------------------------------
-// Row c has its own SegRow in a device table (written by launch_seg_upload_rows, 64 rows per launch, by value: capturable, no
-// host memory involved); mix / out are (C, row_stride), one step of noise is (C, noise_stride).  A group's entries (row, window,
-// length) travel as kernel arguments, 64 per launch.  Entries of a long row have length S and start at k * hop (the last one
-// at T_pad - S); the single entry of a row with T_pad <= S has length T_pad and starts at 0.
 struct SegRow { long long t_raw, T_pad, pad_left, n_win, first, frames; };  // first: the row's first entry; frames: mel frames
+// blocks of a whole-row reduction: one per 256 Ki samples (one block per row up to 16 s at 16 kHz), 1024 at the most
+__host__ __device__ inline int seg_nb(long long T_raw) {
+  const long long nb = (T_raw + (1ll << 18) - 1) >> 18;
+  return (int)(nb < 1 ? 1 : nb > 1024 ? 1024 : nb);
+}
+// Rows of the call.  Both answer: row(c); stride() of the mix / out rows; noise_stride() of one step's noise rows;
+// frame_stride() of the frame-energy rows; blocks(row), the row's own reduce blocks; part_stride(), the blocks the partials of a
+// row are laid out for (= the grid of the reductions); zero_tail, whether out[c][t_raw_c, stride) exists and is to be zeroed.
+// All rows alike (ou_enhance_segments, ou_enhance_segments_ensemble): the numbers by value; the frame energies are packed (C,
+// frames), which is what launch_mel_scale reads.
+struct SegRowsAlike {
+  SegRow r;
+  static constexpr bool zero_tail = false;
+  __host__ __device__ SegRow row(long long) const { return r; }
+  __host__ __device__ long long stride() const { return r.t_raw; }
+  __host__ __device__ long long noise_stride() const { return r.T_pad; }
+  __host__ __device__ long long frame_stride() const { return r.frames; }
+  __host__ __device__ int blocks(const SegRow&) const { return seg_nb(r.t_raw); }
+  __host__ __device__ int part_stride() const { return seg_nb(r.t_raw); }
+};
+// Rows of lengths of their own (ou_enhance_segments_var): row c has its SegRow in a device table (written by
+// launch_seg_upload_rows, 64 rows per launch, by value: capturable, no host memory involved); mix / out and the frame energies
+// are (C, row_stride), one step of noise is (C, noise_row_stride).  Grids are sized by the longest row; row c reduces over
+// seg_nb(t_raw[c]) blocks whatever the other rows are, so its statistics have the bits of the call on that row alone.
+struct SegRowsTable {
+  const SegRow* rows;
+  long long row_stride, noise_row_stride;  // T_raw_max, T_pad_max
+  static constexpr bool zero_tail = true;
+  __device__ SegRow row(long long c) const { return rows[c]; }
+  __host__ __device__ long long stride() const { return row_stride; }
+  __host__ __device__ long long noise_stride() const { return noise_row_stride; }
+  __host__ __device__ long long frame_stride() const { return row_stride; }
+  __host__ __device__ int blocks(const SegRow& r) const { return seg_nb(r.t_raw); }
+  __host__ __device__ int part_stride() const { return seg_nb(row_stride); }
+};
+// Entries of a group.  Both answer entry(i) = (row, window, length) of the i-th entry of the launch, slot(i), its row in the
+// walk's (Bw, T) planes, and hop / overlap of the long rows.
+struct SegEnt { long long row, win, len; };
+// Arithmetic: entry i is (c, k) = divmod(min(e0 + i, n_entries - 1), n_win) -- row-major over rows alike, the entries past the
+// last real one repeating it -- and every entry is L long.
+struct SegEntriesArith {
+  long long e0, n_entries, n_win, L;
+  long long hop, overlap;
+  __host__ __device__ SegEnt entry(int i) const {
+    long long e = e0 + i;
+    if (e > n_entries - 1) e = n_entries - 1;
+    const long long c = e / n_win;
+    return SegEnt{c, e - c * n_win, L};
+  }
+  __host__ __device__ int slot(int i) const { return i; }
+};
+// A list: up to 64 (row, window, length) triples as kernel arguments; entry i is row j0 + i of the walk.  Entries of a long row
+// have length S and start at k * hop (the last one at T_pad - S); the single entry of a row with T_pad <= S has length T_pad.
+constexpr int kSegEntriesPerLaunch = 64;
+struct SegEntryBlock { int row[kSegEntriesPerLaunch]; int win[kSegEntriesPerLaunch]; int len[kSegEntriesPerLaunch]; };
+struct SegEntriesList {
+  SegEntryBlock blk;
+  int j0;
+  long long hop, overlap;
+  __host__ __device__ SegEnt entry(int i) const { return SegEnt{blk.row[i], blk.win[i], blk.len[i]}; }
+  __host__ __device__ int slot(int i) const { return j0 + i; }
+};
+
+// stats[c] = {mean, gain, mix_rms, 0} of the padded whole row (pad_normalize_kernel's layout and arithmetic); part: [C]
+// [part_stride][3] doubles
+template <class Rows>
+hipError_t launch_seg_stats(const float* mix, double* part, float* stats, const Rows& rows, int C, float level, hipStream_t st);
+// esum[c * frame_stride + f] = frame energies of the mel front-end over the whole normalised row (mel_kernel without the mel
+// output), f < frames_c <= frames_max
+template <class Rows>
+hipError_t launch_seg_mel_energy(const float* mix, const float* stats, const float* win, const float* tw, const float* fb,
+                                 float* esum, const Rows& rows, int C, int n_fft, int hop, int mel_pad, int n_freq, int n_mels,
+                                 long long frames_max, hipStream_t st);
+// scale[c] = the mel scale over the row's own frames of esum (C, row_stride): mel_scale_kernel's arithmetic (the rows alike go
+// through launch_mel_scale itself)
+hipError_t launch_seg_mel_scale_var(const float* esum, float* scale, const SegRow* rows, int C, long long row_stride,
+                                    hipStream_t st);
+// the first n entries of `ents`: normalised input into rows slot(i) of mixn (.., T), 0 from the entry's own length on, and each
+// entry's row mel scale
+template <class Rows, class Entries>
+hipError_t launch_seg_gather_input(const float* mix, const float* stats, const float* row_mel_scale, float* mixn,
+                                   float* mel_scale, const Rows& rows, const Entries& ents, int n, long long T, hipStream_t st);
+// Members are a grid dimension of what follows: a group's walk runs E * Bw rows of T columns, row m * Bw + slot = member m of
+// the entry; the long rows are (E * C, stride), row m * C + c, one step's noise (E * C, noise_stride), `carry` (E, T): member
+// m's window in front of the group.  Rows move in 16-byte accesses from the destination row's first 16-byte boundary on, word by
+// word in front of it and behind the last whole quad.
+// one step's noise of the first n entries: z[m * Bw + slot][t] = noise[m * C + c][s + t], 0 from the entry's own length on
+template <class Rows, class Entries>
+hipError_t launch_seg_gather_noise(const float* noise, float* z, const Rows& rows, const Entries& ents, int n, long long T, int Bw,
+                                   int E, int C, hipStream_t st);
+// crossfade the window outputs y of the first n entries (entry with slot j > 0 and a window in front: with row j - 1 of y, slot
+// 0: with `carry`) into the unpadded long rows
+template <class Rows, class Entries>
+hipError_t launch_seg_stitch(const float* y, const float* carry, float* out, const Rows& rows, const Entries& ents, int n,
+                             long long T, int Bw, int E, int C, hipStream_t st);
+// keep_rms + peak guard over the E * C long rows in place (universe.py:349-357); row r takes its length and mix_rms from row
+// r % C.  part: [E * C][part_stride][2] doubles.  Rows of a table: out[r][t_raw, stride) <- 0 as well.
+template <class Rows>
+hipError_t launch_seg_post(float* out, double* part, const float* stats, const Rows& rows, int E, int C, int keep_rms,
+                           int peak_guard, hipStream_t st);
+
+// the SegRow table and the per-level lengths of a ragged group, from kernel arguments
 struct SegVar {
-  long long S, hop, overlap;           // window length, hop and crossfade of the long rows
-  long long row_stride, noise_stride;  // T_raw_max, T_pad_max
+  long long S, hop;  // window length and hop of the long rows
   int tot_ds;
 };
 constexpr int kSegRowsPerLaunch = 64;
 struct SegRowBlock { long long t_raw[kSegRowsPerLaunch]; long long first[kSegRowsPerLaunch]; };
-constexpr int kSegEntriesPerLaunch = 64;
-struct SegEntryBlock { int row[kSegEntriesPerLaunch]; int win[kSegEntriesPerLaunch]; int len[kSegEntriesPerLaunch]; };
 hipError_t launch_seg_upload_rows(SegRow* rows, const SegRowBlock& blk, int n, int off, const SegVar& v, hipStream_t st);
 // lens[l * B + j0 + i] <- len[i] * num_l / den_l: the per-level lengths of a ragged group, from the entry lengths directly (an
 // entry is an already padded window: no pad split as in launch_upload_rows)
 hipError_t launch_seg_upload_lens(int* lens, const SegEntryBlock& blk, int n, int j0, int B, const LevelSpec& lv, hipStream_t st);
-// Row c's reductions run over seg_reduce_blocks(t_raw[c]) blocks whatever the other rows are: its statistics have the bits of
-// the call on that row alone.  Grids are sized by the longest row (T_raw_max); part: [C][nb_max][3] doubles.
-hipError_t launch_seg_stats_var(const float* mix, double* part, float* stats, const SegRow* rows, int C, long long T_raw_max,
-                                float level, hipStream_t st);
-// esum[c * row_stride + f] for f < frames_c; scale[c] = the mel scale over those frames (mel_scale_kernel's arithmetic)
-hipError_t launch_seg_mel_energy_var(const float* mix, const float* stats, const float* win, const float* tw, const float* fb,
-                                     float* esum, const SegRow* rows, int C, long long row_stride, int n_fft, int hop, int mel_pad,
-                                     int n_freq, int n_mels, long long frames_max, hipStream_t st);
-hipError_t launch_seg_mel_scale_var(const float* esum, float* scale, const SegRow* rows, int C, long long row_stride,
-                                    hipStream_t st);
-// entries j0 .. j0 + n - 1 of a group whose walk runs at length T: mixn / z (B, T), 0 from the entry's own length on
-hipError_t launch_seg_gather_input_var(const float* mix, const float* stats, const float* row_mel_scale, const SegRow* rows,
-                                       float* mixn, float* mel_scale, const SegEntryBlock& blk, int n, int j0, long long T,
-                                       const SegVar& v, hipStream_t st);
-hipError_t launch_seg_gather_noise_var(const float* noise, const SegRow* rows, float* z, const SegEntryBlock& blk, int n, int j0,
-                                       long long T, const SegVar& v, hipStream_t st);
-// (y: (B, T); entry j > 0 with a window in front crossfades with row j - 1 of y, entry 0 with `carry`)
-hipError_t launch_seg_stitch_var(const float* y, const float* carry, float* out, const SegRow* rows, const SegEntryBlock& blk,
-                                 int n, int j0, long long T, const SegVar& v, hipStream_t st);
-// keep_rms + peak guard per row over its own samples, and out[c][t_raw_c ..) <- 0; part: [C][nb_max][2] doubles
-hipError_t launch_seg_post_var(float* out, double* part, const float* stats, const SegRow* rows, int C, long long T_raw_max,
-                               int keep_rms, int peak_guard, hipStream_t st);
-
-// ---- ... member-major (ou_enhance_segments_ensemble) ---------------------------------------------------------------------------
-// A group's walk runs E * Bw rows, row e * Bw + j = member e of entry e0 + j; the members' long rows are (E * C, T_raw), row
-// e * C + c.  One step's noise is (E * C, T_pad); `carry` is (E, L): member e's window in front of the group.  The per-sample
-// arithmetic is that of the kernels above (E = 1: their bits); rows move in 16-byte accesses from the destination row's first
-// 16-byte boundary on, word by word in front of it and behind the last whole quad.
-hipError_t launch_seg_gather_noise_mm(const float* noise, float* z, const SegGeom& g, long long e0, int Bw, int E, int C,
-                                      hipStream_t st);
-hipError_t launch_seg_stitch_mm(const float* y, const float* carry, float* members, const SegGeom& g, long long e0, int n_real,
-                                int Bw, int E, int C, hipStream_t st);
-// keep_rms + peak guard over the E * C member rows in place; row r takes mix_rms from statistics row r % C.  part: [E * C][nb][2]
-hipError_t launch_seg_post_mm(float* members, double* part, const float* stats, int E, int C, long long T_raw, int keep_rms,
-                              int peak_guard, hipStream_t st);
 
 // Counter-based sampler noise (ou_noise.hip; the function z(seed, stream, draw, t) is defined in include/ouniverse.h).
 // One launch fills up to 64 rows: out[j][col] = col < len[j] ? z(seed, stream[j], draw, t0[j] + col) : 0 for col < cols.

@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
 """A/B of the enhance entry points between two builds of the library: same bits, same launches.
 
-Every way into the sampler (ou_enhance, ou_enhance_var, ou_enhance_ensemble, ou_enhance_segments, ou_enhance_segments_var) is
-called once on the reduced-width models of the GPU tests, 3 steps, fixed seeds, and one JSON line per call is printed: the
-call's name, both counters of ou_launch_stats and the SHA-256 of the output bytes.  Run it once per library and compare the
-files byte for byte:
+Every way into the sampler -- the six entry points ou_enhance, ou_enhance_var, ou_enhance_ensemble, ou_enhance_segments,
+ou_enhance_segments_var and ou_enhance_segments_ensemble -- is called on the reduced-width models of the GPU tests, 3 steps,
+fixed seeds, and one JSON line per call is printed: the call's name, both counters of ou_launch_stats and the SHA-256 of the
+output bytes.  The segmented entry points are also called on edge shapes:
+rows of 1, 2, 3 and 5 samples, of tot_ds + 1, 16 tot_ds + 2 and 33 tot_ds + 3, so that the longest row is 1, 2 and 3 past a
+multiple of 4 -- the word-by-word head and tail of the 16-byte row moves and the guards of rows shorter than a quad.  Run it
+once per library and compare the files byte for byte:
 
     OU_LIBRARY=/path/to/parent/libouniverse.so timeout -k 10 600 python tools/driver_ab.py --out parent.json
     timeout -k 10 600 python tools/driver_ab.py --out branch.json && cmp parent.json branch.json
@@ -107,6 +110,32 @@ def calls(model, spec):
         yield f"enhance_long.c{C}.counter", lambda C=C: model.enhance_long(long3[:C], rng=CounterNoise(71, C), **seg)
     yield "enhance_long_many.six.tensor", lambda: model.enhance_long_many(six, [gen(80 + i) for i in range(6)], **seg)
     yield "enhance_long_many.six.counter", lambda: model.enhance_long_many(six, [CounterNoise(81, 5 + i) for i in range(6)], **seg)
+
+    ens = dict(seg, max_batch=12)
+    two_long = long3[:2]
+
+    def long_ensemble(share, mix, rng, stat, **kw):
+        model.set_option("ens_share", share)
+        try:
+            return model.enhance_long_ensemble(mix, 3, ensemble_stat=stat, rng=rng, return_members=True, **ens, **kw)
+        finally:
+            model.set_option("ens_share", 1)
+    yield "enhance_long_ensemble.share1.tensor.median", lambda: long_ensemble(1, two_long, gen(90), "median")
+    yield "enhance_long_ensemble.share0.tensor.median", lambda: long_ensemble(0, two_long, gen(90), "median")
+    yield "enhance_long_ensemble.share1.counter.mean", lambda: long_ensemble(1, two_long, CounterNoise(91, 4), "mean")
+
+    # edge shapes (keep_rms: the post scale moves every row)
+    edge = [1, 2, 3, 5, td + 1, 16 * td + 2, 33 * td + 3]
+    for T in edge:
+        mix = synth_mix(spec, 2, T, seed=2100).cuda()
+        yield f"edge.enhance_long.t{T}", lambda mix=mix: model.enhance_long(mix, rng=gen(100), keep_rms=True, **seg)
+        yield f"edge.enhance_long_ensemble.t{T}", lambda mix=mix: long_ensemble(1, mix, gen(101), "median", keep_rms=True)
+    for n in (5, 6, 7):  # the longest row: tot_ds + 1, 16 tot_ds + 2, 33 tot_ds + 3
+        rows = [synth_mix(spec, 1, T, seed=2200 + i)[0].cuda() for i, T in enumerate(edge[:n])]
+        yield f"edge.enhance_long_many.max{edge[n - 1]}.tensor", lambda rows=rows: model.enhance_long_many(
+            rows, [gen(110 + i) for i in range(len(rows))], keep_rms=True, **seg)
+    yield "edge.enhance_long_many.counter", lambda rows=rows: model.enhance_long_many(
+        rows, [CounterNoise(111, 9 + i) for i in range(len(rows))], keep_rms=True, **seg)
 
 
 def main():
