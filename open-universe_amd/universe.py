@@ -14,6 +14,7 @@ and draws nothing (extension, noise.py) --, owns the device buffers (PyTorch = d
 status codes to the reference's exception types.  No torch compute fallback exists: without the library or
 without a GPU construction fails.
 """
+import collections
 import contextlib
 import ctypes
 import math
@@ -32,6 +33,116 @@ def randn(x, sigma, rng=None):
     """universe.py:39-41 (kept for API parity; the product path passes raw normal draws to the C ABI)."""
     noise = torch.randn(x.shape, dtype=x.dtype, device=x.device, generator=rng)
     return noise * sigma[:, None, None]
+
+
+def padded(n, tot_ds):
+    """The length the network walks a signal of n samples at: the next multiple of tot_ds ABOVE n (`Universe.pad` gives a length
+    that already is a multiple one whole block more)."""
+    return n + (tot_ds - n % tot_ds)
+
+
+def as_rows(s, who, prep, t="L"):
+    """A (t,) or (C, t) signal as prepared (C, t) rows; `who`: the method named in the refusal."""
+    if s.ndim not in (1, 2):
+        raise ValueError(f"{who} takes ({t},) or (C, {t}) signals")
+    return prep(s if s.ndim == 2 else s[None, :])
+
+
+class Packed(collections.namedtuple("Packed", "dims chans lens batch")):
+    """A list of (L,) / (C, L) signals as ONE batch (pack_rows): per entry its rank, channels (= rows) and length, and `batch`,
+    the (sum C, longest L) tensor of all rows, right-padded with zeros."""
+    __slots__ = ()
+
+    @property
+    def row_lens(self):
+        """The length of every ROW of the batch (an entry's length, once per channel)."""
+        return [n for c, n in zip(self.chans, self.lens) for _ in range(c)]
+
+    def entries(self, rngs, own_length=True):
+        """-> [(channels, length, generator)] for draw_noise; `rngs`: one generator per entry, or ONE for all (or None).
+        own_length=False: every entry draws at the length of the longest (the rows of a plain batch)."""
+        per_entry = isinstance(rngs, (list, tuple))
+        return [(c, n if own_length else self.batch.shape[-1], rngs[i] if per_entry else rngs)
+                for i, (c, n) in enumerate(zip(self.chans, self.lens))]
+
+
+def pack_rows(signals, who, prep):
+    """List of (L,) or (C, L) signals -> Packed; `prep`: what makes a signal float32, contiguous and on the right device."""
+    rows = [as_rows(s, who, prep) for s in signals]
+    lens = [int(r.shape[-1]) for r in rows]
+    if min(lens) < 1:
+        raise ValueError(f"{who}: empty input signal")
+    batch = torch.cat([torch.nn.functional.pad(r, (0, max(lens) - n)) for r, n in zip(rows, lens)], dim=0)
+    return Packed([s.ndim for s in signals], [int(r.shape[0]) for r in rows], lens, batch)
+
+
+def unpack_rows(pk, out, members=None):
+    """The inverse of pack_rows on a result: out (rows, L max) or (rows, 1, L max), members (E, rows, ..) likewise or None ->
+    (list of per-entry outputs with the shape of their inputs, list of per-entry members (E,) + that shape -- empty without
+    members).  Views, nothing is copied."""
+    if out.ndim == 3:
+        out, members = out[:, 0], (None if members is None else members[:, :, 0])
+    res, mems, r0 = [], [], 0
+    for nd, c, n in zip(pk.dims, pk.chans, pk.lens):
+        o = out[r0:r0 + c, :n]
+        res.append(o[0] if nd == 1 else o)
+        if members is not None:
+            m = members[:, r0:r0 + c, :n]
+            mems.append(m[:, 0] if nd == 1 else m)
+        r0 += c
+    return res, mems
+
+
+def draw_noise(tot_ds, entries, n, members=1, planes=None, device=None, discard=False):
+    """Every `torch.randn` of the enhance methods.  `entries`: [(channels C_i, length L_i, generator g_i)], the inputs of one
+    call; `n`: noise planes of the call (x0 first); `members`: E of an ensemble.  Performs, entry by entry and inside an entry
+    plane by plane -- the order of the serial loop, so a generator shared by several entries ends where that loop leaves it --,
+    the draws of the call on that entry ALONE: n times randn((E * C_i, 1, T_i), generator=g_i), T_i = padded(L_i).  (On the
+    device the values of a draw depend on its shape: the shapes are part of the contract.)  Draw k of entry i lands member-major
+    in plane k, columns [0, T_i) of the entry's rows: planes.view(n, E, rows, 1, T)[k, :, r_i : r_i + C_i, :, :T_i], rows = sum C_i,
+    T = max T_i.  Where that block is contiguous -- one row, or ONE entry that is the whole plane: `enhance` at any batch size,
+    `enhance_ensemble`, `draw_noise_like_enhance` -- the draw goes `out=` straight to its place, no temporary and no copy kernel;
+    elsewhere it is drawn and copied.
+    `planes`: None -- a new (n, E * rows, 1, T) float32 tensor on `device` is made, zeros where some T_i < T (what no draw covers
+    stays 0), else uninitialised -- or any contiguous tensor of that many elements.  -> planes.
+    discard=True: draw and drop (advance the generators, nothing is kept) -> None."""
+    E = int(members)
+    if len(entries) == 1 and not discard:  # the whole-plane case, nothing but the draws on its way (the host path of `enhance`)
+        c, length, g = entries[0]
+        rows, T = E * int(c), padded(int(length), tot_ds)
+        slots = None
+        if planes is None:
+            planes = slots = torch.empty((n, rows, 1, T), dtype=torch.float32, device=device)
+        elif planes.shape[-1] == T and planes.numel() == n * rows * T:
+            slots = planes.view(n, rows, 1, T)
+        if slots is not None:
+            for k in range(n):
+                torch.randn((rows, 1, T), generator=g, out=slots[k])
+            return planes
+    chans = [int(c) for c, _, _ in entries]
+    Ts = [padded(int(length), tot_ds) for _, length, _ in entries]
+    if discard:
+        for (_, _, g), c, Ti in zip(entries, chans, Ts):
+            for _ in range(n):
+                torch.randn((E * c, 1, Ti), dtype=torch.float32, device=device, generator=g)
+        return None
+    if planes is None:
+        make = torch.zeros if min(Ts) < max(Ts) else torch.empty
+        planes = make((n, E * sum(chans), 1, max(Ts)), dtype=torch.float32, device=device)
+    slots = planes.view(n, E, sum(chans), 1, planes.shape[-1])
+    r0 = 0
+    for (_, _, g), c, Ti in zip(entries, chans, Ts):
+        for k in range(n):
+            dst = slots[k, :, r0:r0 + c, :, :Ti]
+            if dst.is_contiguous():
+                torch.randn((E * c, 1, Ti), generator=g, out=dst.view(E * c, 1, Ti))
+            else:
+                dst.copy_(torch.randn((E * c, 1, Ti), dtype=torch.float32, device=planes.device, generator=g).view(E, c, 1, Ti))
+        r0 += c
+    return planes
+
+
+_KEEP = object()  # (_forward: leave Universe._cond_key as it is)
 
 
 class Universe:
@@ -578,6 +689,73 @@ class Universe:
                                              self._stream()))
         return out
 
+    # ---- what the enhance methods are arranged from (the Python side) ---------------------------------
+    def _defaults(self, n_steps, epsilon):
+        return (self.diff_kwargs.n_steps if n_steps is None else int(n_steps),
+                self.diff_kwargs.epsilon if epsilon is None else epsilon)
+
+    def _begin(self, n_steps=None, epsilon=None, segment_s=None, overlap_s=None):
+        """What every enhance call starts with: environment steering (tools only), a look at the deferred status of an earlier
+        call, the per-call defaults.  -> (n_steps, epsilon), with a window also (.., segment, overlap) in samples."""
+        self._sync_env()
+        self._poll_deferred_status()
+        n_steps, epsilon = self._defaults(n_steps, epsilon)
+        if segment_s is None:
+            return n_steps, epsilon
+        return n_steps, epsilon, int(round(float(segment_s) * self.fs)), int(round(float(overlap_s) * self.fs))
+
+    @staticmethod
+    def _lift(mix):
+        """(T,) / (B, T) / (B, 1, T) -> ((B, 1, T), the rank to give back); `_lower` is the inverse."""
+        x_ndim = mix.ndim
+        if x_ndim == 1:
+            mix = mix[None, None, :]
+        elif x_ndim == 2:
+            mix = mix[:, None, :]
+        elif x_ndim > 3:
+            raise ValueError("The input should have at most 3 dimensions")
+        if mix.ndim == 3 and mix.shape[1] != 1:
+            raise ValueError("enhance expects single-channel signals: (T,), (B,T) or (B,1,T)")
+        return mix, x_ndim
+
+    @staticmethod
+    def _lower(x_ndim, x, members=None):
+        """(B, 1, L) and, if any, the members (E, B, 1, L) back at the rank of the input."""
+        if x_ndim == 1:
+            return x[0, 0], (None if members is None else members[:, 0, 0])
+        if x_ndim == 2:
+            return x[:, 0, :], (None if members is None else members[:, :, 0, :])
+        return x, members
+
+    def _long_rows(self, mix, who):
+        """The (T,) / (C, T) input of a segmented call as prepared (C, T) rows."""
+        x = as_rows(mix, who, self._prep, "T")
+        if x.shape[-1] < 1:
+            raise ValueError(f"{who}: empty input signal")
+        return x
+
+    def _forward(self, fn, bufs, dims, n_steps, epsilon, warm_start, flags, ws, counter=None, scratch=(), cond_key=_KEEP):
+        """The one call into a sampler entry point: fn(handle, *pointers of bufs (None: NULL), *dims, n_steps, epsilon, sigma table,
+        warm_start, flags, workspace, its bytes, stream) on this model's device, inside the counter source `counter` = (seed,
+        stream ids) if there is one -- `scratch` = (rows, T) where the call needs the two-plane noise scratch --, return code
+        mapped to the reference's exceptions, `cond_key` recorded, status word polled."""
+        sigma = self._sigma_table(n_steps)
+        source = self._counter_source(counter[0], counter[1], *scratch) if counter is not None else contextlib.nullcontext()
+        with torch.cuda.device(self.device), source:
+            _lib.check(fn(self._handle, *[None if b is None else c_void_p(b.data_ptr()) for b in bufs], *dims, int(n_steps),
+                          float(epsilon), ctypes.cast(sigma.data_ptr(), ctypes.POINTER(c_float)),
+                          -1 if warm_start is None else int(warm_start), flags, c_void_p(ws.data_ptr()), c_size_t(ws.numel()),
+                          self._stream()), self._handle)
+        if cond_key is not _KEEP:
+            self._cond_key = cond_key
+        self._status()
+
+    def _segments_sizer(self, sizer, *args):
+        """A segment workspace sizer (ou_segments*_workspace_bytes) and the buffer it asks for: -> (ws, walk rows B, walk length L)."""
+        need, B, L = c_size_t(), c_int32(), c_int32()
+        _lib.check(sizer(self._handle, *args, byref(need), byref(B), byref(L)), self._handle)
+        return self._segments_workspace(B.value, L.value, need.value), B.value, L.value
+
     # ---- the hot path ------------------------------------------------------------------------------
     def enhance(
         self,
@@ -609,21 +787,8 @@ class Universe:
         """`t_raw`: per-row lengths of a batch whose rows are utterances of different lengths (enhance_many, exact
         batching -> ou_enhance_var); `mix` is then (B, 1, max length) and `noise` a (n, B, 1, T) tensor.
         `counter`: (seed, [one stream id per row]) -- counter-based noise (noise.py) instead of `noise` / `rng`."""
-        self._sync_env()
-        self._poll_deferred_status()
-        if epsilon is None:
-            epsilon = self.diff_kwargs.epsilon
-        if n_steps is None:
-            n_steps = self.diff_kwargs.n_steps
-        x_ndim = mix.ndim
-        if x_ndim == 1:
-            mix = mix[None, None, :]
-        elif x_ndim == 2:
-            mix = mix[:, None, :]
-        elif x_ndim > 3:
-            raise ValueError("The input should have at most 3 dimensions")
-        if mix.ndim == 3 and mix.shape[1] != 1:
-            raise ValueError("enhance expects single-channel signals: (T,), (B,T) or (B,1,T)")
+        n_steps, epsilon = self._begin(n_steps, epsilon)
+        mix, x_ndim = self._lift(mix)
         if ensemble_stat not in ("mean", "median", "signal_median") and ensemble is not None:
             raise NotImplementedError()  # universe.py:368
         mix = self._prep(mix)
@@ -635,8 +800,8 @@ class Universe:
                 raise RuntimeError("keep_rms with ensemble is only defined for a single input signal (as in the reference)")
             mix = torch.stack([mix] * ensemble, dim=0).view((-1,) + mix_shape[1:])
         B, _, mix_len = mix.shape
-        pad = self.tot_ds - mix_len % self.tot_ds
-        T = mix_len + pad
+        T = padded(mix_len, self.tot_ds)
+        pad = T - mix_len
         if is_counter(rng):
             if target is not None:
                 raise ValueError("`target` (the oracle-score path) draws from a torch.Generator: it does not take a CounterNoise")
@@ -662,13 +827,11 @@ class Universe:
             elif counter is not None:
                 noise_t = None  # the library fills one step's plane at a time (ou_set_noise_source)
             elif noise is None:
-                # draw order of the reference: x0, then z_n for n = n_start .. N-2 (universe.py:326,330,338)
-                # (each draw lands in its slice of the tensor the C ABI takes: the same n separate (B, 1, T) draws -- generator
-                # state and values are those of the reference's loop -- without a stack copy per draw behind them)
+                # draw order of the reference: x0, then z_n for n = n_start .. N-2 (universe.py:326,330,338): the whole-plane case
+                # of draw_noise -- n separate (B, 1, T) draws, each `out=` into its slice of the tensor the C ABI takes, no
+                # temporaries, no copies -- queued BEFORE the host prepares the call (the device is idle meanwhile)
                 # (n_noise <= 0: warm_start >= n_steps -- the C ABI refuses the call below)
-                noise_t = torch.empty((n_noise, B, 1, T), dtype=torch.float32, device=self.device) if n_noise > 0 else None
-                for k in range(n_noise):
-                    torch.randn((B, 1, T), generator=rng, out=noise_t[k])
+                noise_t = draw_noise(self.tot_ds, [(B, mix_len, rng)], n_noise, device=self.device) if n_noise > 0 else None
             elif torch.is_tensor(noise):  # (all steps in one (n, B, 1, T) tensor: taken as it is)
                 noise_t = self._prep(noise[:n_noise]) if n_noise else None
                 if n_noise and tuple(noise_t.shape) != (n_noise, B, 1, T):
@@ -677,32 +840,16 @@ class Universe:
                 noise_t = torch.stack([self._prep(z) for z in noise[:n_noise]], dim=0) if n_noise else None
                 if n_noise and noise_t.shape != (n_noise, B, 1, T):
                     raise ValueError(f"noise must be {n_noise} tensors of shape {(B, 1, T)}")
-            # (AFTER the draws are in the queue: the device is idle while the host prepares a call)
-            sigma = self._sigma_table(n_steps)
             out = torch.empty(B, 1, mix_len, dtype=torch.float32, device=self.device)
             ws = self._workspace(B, T)
             flags = (_lib.OU_ENH_KEEP_RMS if keep_rms else 0) | (_lib.OU_ENH_USE_AUX_SIGNAL if use_aux_signal else 0)
-            source = self._counter_source(counter[0], counter[1], B, T) if counter is not None else contextlib.nullcontext()
-            with torch.cuda.device(self.device), source:
-                if t_raw is not None:
-                    if len(t_raw) != B:
-                        raise ValueError("t_raw must have one entry per row of the batch")
-                    rows_len = (c_int32 * B)(*[int(v) for v in t_raw])
-                    _lib.check(self._L.ou_enhance_var(
-                        self._handle, c_void_p(mix.data_ptr()), c_void_p(out.data_ptr()),
-                        c_void_p(noise_t.data_ptr()) if noise_t is not None else None, B, mix_len, rows_len, int(n_steps),
-                        float(epsilon), ctypes.cast(sigma.data_ptr(), ctypes.POINTER(c_float)),
-                        -1 if warm_start is None else int(warm_start), flags, c_void_p(ws.data_ptr()),
-                        c_size_t(ws.numel()), self._stream()), self._handle)
-                else:
-                    _lib.check(self._L.ou_enhance(
-                        self._handle, c_void_p(mix.data_ptr()), c_void_p(out.data_ptr()),
-                        c_void_p(noise_t.data_ptr()) if noise_t is not None else None, B, mix_len, int(n_steps),
-                        float(epsilon), ctypes.cast(sigma.data_ptr(), ctypes.POINTER(c_float)),
-                        -1 if warm_start is None else int(warm_start), flags, c_void_p(ws.data_ptr()),
-                        c_size_t(ws.numel()), self._stream()), self._handle)
-            self._cond_key = (B, T) if t_raw is None else None
-            self._status()
+            fn, dims = self._L.ou_enhance, (B, mix_len)
+            if t_raw is not None:
+                if len(t_raw) != B:
+                    raise ValueError("t_raw must have one entry per row of the batch")
+                fn, dims = self._L.ou_enhance_var, (B, mix_len, (c_int32 * B)(*[int(v) for v in t_raw]))
+            self._forward(fn, (mix, out, noise_t), dims, n_steps, epsilon, warm_start, flags, ws, counter, (B, T),
+                          cond_key=(B, T) if t_raw is None else None)
             x = out
 
         if target is not None:
@@ -723,11 +870,7 @@ class Universe:
                 x = signal_median(x)
             else:
                 raise NotImplementedError()
-        if x_ndim == 1:
-            x = x[0, 0]
-        elif x_ndim == 2:
-            x = x[:, 0, :]
-        return x
+        return self._lower(x_ndim, x)[0]
 
     @torch.no_grad()
     def enhance_many(self, signals, rngs=None, pad_batch=False, n_steps=None, epsilon=None, use_aux_signal=False,
@@ -763,76 +906,30 @@ class Universe:
             raise ValueError("enhance_many takes the generators as `rngs` (one per input, or one shared)")
         if not signals:
             return []
-        rows, dims = [], []
-        for s in signals:
-            if s.ndim not in (1, 2):
-                raise ValueError("enhance_many takes (L,) or (C, L) signals")
-            dims.append(s.ndim)
-            rows.append(self._prep(s if s.ndim == 2 else s[None, :]))
-        lens = [int(r.shape[-1]) for r in rows]
-        if min(lens) < 1:
-            raise ValueError("enhance_many: empty input signal")
-        l_max = max(lens)
-        n_steps = self.diff_kwargs.n_steps if n_steps is None else int(n_steps)
-        T = l_max + (self.tot_ds - l_max % self.tot_ds)
+        pk = pack_rows(signals, "enhance_many", self._prep)
+        n_steps = self._defaults(n_steps, None)[0]
         n_start = 0 if warm_start is None else int(warm_start)
         if n_start >= n_steps:
             raise ValueError("warm_start must be < n_steps")
         n_noise = 0 if use_aux_signal else n_steps - n_start
-        counter = self._counter_plan(rngs, [r.shape[0] for r in rows])
-        extra = {} if counter is None else {"counter": counter}
+        counter = self._counter_plan(rngs, pk.chans)
         if ensemble is not None:
-            return self._enhance_many_ensemble(rows, dims, lens, rngs, counter, int(ensemble), ensemble_stat, pad_batch,
-                                               n_steps, epsilon, use_aux_signal, keep_rms, warm_start, n_noise, return_members)
+            return self._enhance_many_ensemble(pk, rngs, counter, int(ensemble), ensemble_stat, pad_batch, n_steps, epsilon,
+                                               use_aux_signal, keep_rms, warm_start, n_noise, return_members)
         if return_members:
             raise ValueError("enhance_many: return_members needs `ensemble`")
-        if not pad_batch and any(n != l_max for n in lens):
-            # exact batching of different lengths: per-row geometry through the whole path
-            B = sum(r.shape[0] for r in rows)
-            noise_t = None
-            if n_noise and counter is None:
-                noise_t = torch.zeros((n_noise, B, 1, T), dtype=torch.float32, device=self.device)
-            t_raw, r0 = [], 0
-            for i, (r, n) in enumerate(zip(rows, lens)):
-                g = rngs[i] if isinstance(rngs, (list, tuple)) else rngs
-                Ti = n + (self.tot_ds - n % self.tot_ds)
-                for k in range(n_noise if counter is None else 0):  # the draws of the call on this entry alone (x0 first)
-                    dst = noise_t[k, r0:r0 + r.shape[0], :, :Ti]
-                    if dst.is_contiguous():  # (one row: the draw goes straight to its place)
-                        torch.randn((r.shape[0], 1, Ti), generator=g, out=dst)
-                    else:
-                        dst.copy_(torch.randn((r.shape[0], 1, Ti), dtype=torch.float32, device=self.device, generator=g))
-                t_raw += [n] * r.shape[0]
-                r0 += r.shape[0]
-            mix = torch.cat([torch.nn.functional.pad(r, (0, l_max - r.shape[-1])) for r in rows], dim=0)[:, None, :]
-            out = self._enhance(mix, n_steps, epsilon, None, None, None, use_aux_signal, keep_rms, None, "median",
-                                warm_start, noise_t, t_raw=t_raw, **extra)
-            res, r0 = [], 0
-            for r, nd, n in zip(rows, dims, lens):
-                o = out[r0:r0 + r.shape[0], 0, :n]
-                r0 += r.shape[0]
-                res.append(o[0] if nd == 1 else o)
-            return res
-        # entry by entry, step by step (the serial loop's draw order), every draw straight into its rows of the step's tensor
-        B = sum(r.shape[0] for r in rows)
+        # exact batching of different lengths: per-row geometry through the whole path (t_raw -> ou_enhance_var), every entry
+        # draws at its own padded length; otherwise one plain batch, every entry draws at the padded length of the longest
+        ragged = not pad_batch and any(n != max(pk.lens) for n in pk.lens)
+        extra = {} if counter is None else {"counter": counter}
+        if ragged:
+            extra["t_raw"] = pk.row_lens
         noise = None
-        if counter is None:
-            noise = torch.empty((n_noise, B, 1, T), dtype=torch.float32, device=self.device)
-            r0 = 0
-            for i, r in enumerate(rows):
-                g = rngs[i] if isinstance(rngs, (list, tuple)) else rngs
-                for k in range(n_noise):
-                    torch.randn((r.shape[0], 1, T), generator=g, out=noise[k, r0:r0 + r.shape[0]])
-                r0 += r.shape[0]
-        mix = torch.cat([torch.nn.functional.pad(r, (0, l_max - r.shape[-1])) for r in rows], dim=0)[:, None, :]
-        out = self._enhance(mix, n_steps, epsilon, None, None, None, use_aux_signal, keep_rms, None, "median",
+        if counter is None and n_noise:
+            noise = draw_noise(self.tot_ds, pk.entries(rngs, own_length=ragged), n_noise, device=self.device)
+        out = self._enhance(pk.batch[:, None, :], n_steps, epsilon, None, None, None, use_aux_signal, keep_rms, None, "median",
                             warm_start, noise, **extra)
-        res, r0 = [], 0
-        for r, nd, n in zip(rows, dims, lens):
-            o = out[r0:r0 + r.shape[0], 0, :n]
-            r0 += r.shape[0]
-            res.append(o[0] if nd == 1 else o)
-        return res
+        return unpack_rows(pk, out)[0]
 
     # ---- ensembles inside the library (ou_enhance_ensemble) ---------------------------------------------------------------
     def _ensemble_call(self, mix, E, stat, n_steps, epsilon, keep_rms, warm_start, noise_t, t_raw, counter, return_members):
@@ -841,27 +938,15 @@ class Universe:
         if stat not in _lib.ENSEMBLE_STATS:
             raise NotImplementedError()  # universe.py:368
         B, _, mix_len = mix.shape
-        T = mix_len + (self.tot_ds - mix_len % self.tot_ds)
-        EB = E * B
-        sigma = self._sigma_table(n_steps)
+        T = padded(mix_len, self.tot_ds)
         out = torch.empty(B, 1, mix_len, dtype=torch.float32, device=self.device)
         members = torch.empty(E, B, 1, mix_len, dtype=torch.float32, device=self.device) if return_members else None
         need = c_size_t()
         _lib.check(self._L.ou_ensemble_workspace_bytes(self._handle, B, T, E, byref(need)), self._handle)
-        ws = self._workspace(EB, T, need=need.value)
-        flags = _lib.OU_ENH_KEEP_RMS if keep_rms else 0
-        source = self._counter_source(counter[0], counter[1], EB, T) if counter is not None else contextlib.nullcontext()
+        ws = self._workspace(E * B, T, need=need.value)
         rows_len = None if t_raw is None else (c_int32 * B)(*[int(v) for v in t_raw])
-        with torch.cuda.device(self.device), source:
-            _lib.check(self._L.ou_enhance_ensemble(
-                self._handle, c_void_p(mix.data_ptr()), c_void_p(out.data_ptr()),
-                c_void_p(members.data_ptr()) if members is not None else None,
-                c_void_p(noise_t.data_ptr()) if noise_t is not None else None, B, mix_len, rows_len, E,
-                _lib.ENSEMBLE_STATS[stat], int(n_steps), float(epsilon),
-                ctypes.cast(sigma.data_ptr(), ctypes.POINTER(c_float)), -1 if warm_start is None else int(warm_start), flags,
-                c_void_p(ws.data_ptr()), c_size_t(ws.numel()), self._stream()), self._handle)
-        self._cond_key = None
-        self._status()
+        self._forward(self._L.ou_enhance_ensemble, (mix, out, members, noise_t), (B, mix_len, rows_len, E, _lib.ENSEMBLE_STATS[stat]),
+                      n_steps, epsilon, warm_start, _lib.OU_ENH_KEEP_RMS if keep_rms else 0, ws, counter, (E * B, T), cond_key=None)
         return out, members
 
     @torch.no_grad()
@@ -876,43 +961,25 @@ class Universe:
         result; the reference fails for more).  return_members=True: -> (result, members), members (E,) + the result's shape.
         Members agree with those of `enhance(ensemble=E)` to fp32 round-off (the conditioner's B-row pass may select other
         kernels); with `set_option("ens_share", 0)` bit for bit."""
-        self._sync_env()
-        self._poll_deferred_status()
+        n_steps, epsilon = self._begin(n_steps, epsilon)
         E = int(ensemble)
         if not 1 <= E <= _lib.OU_MAX_ENSEMBLE:
             raise ValueError(f"enhance_ensemble: 1 <= ensemble <= {_lib.OU_MAX_ENSEMBLE}")
-        epsilon = self.diff_kwargs.epsilon if epsilon is None else epsilon
-        n_steps = self.diff_kwargs.n_steps if n_steps is None else int(n_steps)
-        x_ndim = mix.ndim
-        if x_ndim == 1:
-            mix = mix[None, None, :]
-        elif x_ndim == 2:
-            mix = mix[:, None, :]
-        elif x_ndim > 3:
-            raise ValueError("The input should have at most 3 dimensions")
-        if mix.shape[1] != 1:
-            raise ValueError("enhance expects single-channel signals: (T,), (B,T) or (B,1,T)")
+        mix, x_ndim = self._lift(mix)
         mix = self._prep(mix)
         B, _, mix_len = mix.shape
-        T = mix_len + (self.tot_ds - mix_len % self.tot_ds)
         n_noise = n_steps - (0 if warm_start is None else int(warm_start))
         counter, noise_t = None, None
         if is_counter(rng):
             counter = (rng.seed, rng.stream_ids(B, E))
         elif n_noise > 0:  # (n_noise <= 0: the C ABI refuses the call)
-            noise_t = torch.empty((n_noise, E * B, 1, T), dtype=torch.float32, device=self.device)
-            for k in range(n_noise):
-                torch.randn((E * B, 1, T), generator=rng, out=noise_t[k])
-        out, members = self._ensemble_call(mix, E, ensemble_stat, n_steps, epsilon, keep_rms, warm_start, noise_t, None,
-                                           counter, return_members)
-        if x_ndim == 1:
-            out, members = out[0, 0], (members[:, 0, 0] if members is not None else None)
-        elif x_ndim == 2:
-            out, members = out[:, 0, :], (members[:, :, 0, :] if members is not None else None)
+            noise_t = draw_noise(self.tot_ds, [(B, mix_len, rng)], n_noise, E, device=self.device)
+        out, members = self._lower(x_ndim, *self._ensemble_call(mix, E, ensemble_stat, n_steps, epsilon, keep_rms, warm_start,
+                                                                noise_t, None, counter, return_members))
         return (out, members) if return_members else out
 
-    def _enhance_many_ensemble(self, rows, dims, lens, rngs, counter, E, stat, pad_batch, n_steps, epsilon, use_aux_signal,
-                               keep_rms, warm_start, n_noise, return_members=False):
+    def _enhance_many_ensemble(self, pk, rngs, counter, E, stat, pad_batch, n_steps, epsilon, use_aux_signal, keep_rms,
+                               warm_start, n_noise, return_members=False):
         """enhance_many(ensemble=E): all entries in one ou_enhance_ensemble call with per-row lengths."""
         if pad_batch:
             raise ValueError("enhance_many: `ensemble` runs with exact batching only (pad_batch=True is refused)")
@@ -920,37 +987,15 @@ class Universe:
             raise ValueError("enhance_many: `ensemble` with use_aux_signal is refused (without noise all members are equal)")
         if not 1 <= E <= _lib.OU_MAX_ENSEMBLE:
             raise ValueError(f"enhance_many: 1 <= ensemble <= {_lib.OU_MAX_ENSEMBLE}")
-        self._sync_env()
-        self._poll_deferred_status()
-        epsilon = self.diff_kwargs.epsilon if epsilon is None else epsilon
-        l_max = max(lens)
-        T = l_max + (self.tot_ds - l_max % self.tot_ds)
-        B = sum(r.shape[0] for r in rows)
+        n_steps, epsilon = self._begin(n_steps, epsilon)
         noise_t = None
         if counter is not None:
             counter = (counter[0], [s + (e << ENSEMBLE_SHIFT) for e in range(E) for s in counter[1]])
-        else:
-            noise_t = torch.zeros((n_noise, E * B, 1, T), dtype=torch.float32, device=self.device)
-            r0 = 0
-            for i, (r, n) in enumerate(zip(rows, lens)):
-                g = rngs[i] if isinstance(rngs, (list, tuple)) else rngs
-                C, Ti = r.shape[0], n + (self.tot_ds - n % self.tot_ds)
-                for k in range(n_noise):  # the draws of enhance(entry, ensemble=E) alone: (E * C, 1, Ti), member-major
-                    d = torch.randn((E * C, 1, Ti), dtype=torch.float32, device=self.device, generator=g)
-                    noise_t[k].view(E, B, 1, T)[:, r0:r0 + C, :, :Ti] = d.view(E, C, 1, Ti)
-                r0 += C
-        t_raw = [n for r, n in zip(rows, lens) for _ in range(r.shape[0])]
-        mix = torch.cat([torch.nn.functional.pad(r, (0, l_max - r.shape[-1])) for r in rows], dim=0)[:, None, :].contiguous()
-        out, mem = self._ensemble_call(mix, E, stat, n_steps, epsilon, keep_rms, warm_start, noise_t, t_raw, counter,
-                                       return_members)
-        res, mems, r0 = [], [], 0
-        for r, nd, n in zip(rows, dims, lens):
-            o = out[r0:r0 + r.shape[0], 0, :n]
-            res.append(o[0] if nd == 1 else o)
-            if mem is not None:
-                mm = mem[:, r0:r0 + r.shape[0], 0, :n]
-                mems.append(mm[:, 0] if nd == 1 else mm)
-            r0 += r.shape[0]
+        else:  # the draws of enhance(entry, ensemble=E) alone: (E * C_i, 1, T_i), member-major
+            noise_t = draw_noise(self.tot_ds, pk.entries(rngs), n_noise, E, device=self.device)
+        out, mem = self._ensemble_call(pk.batch[:, None, :], E, stat, n_steps, epsilon, keep_rms, warm_start, noise_t, pk.row_lens,
+                                       counter, return_members)
+        res, mems = unpack_rows(pk, out, mem)
         return (res, mems) if return_members else res
 
     @staticmethod
@@ -983,23 +1028,17 @@ class Universe:
         window, bin/enhance.py)."""
         n_steps = self.diff_kwargs.n_steps if n_steps is None else int(n_steps)
         n_noise = 0 if use_aux_signal else n_steps - (0 if warm_start is None else int(warm_start))
-        T = int(length) + (self.tot_ds - int(length) % self.tot_ds)
-        for _ in range(n_noise):
-            torch.randn((int(channels), 1, T), dtype=torch.float32, device=self.device, generator=rng)
-
-    # ---- recordings of any length: segmented enhance (ou_enhance_segments) ---------------------------------------------
-    SEGMENT_S = 8.0
-    OVERLAP_S = 1.0
+        draw_noise(self.tot_ds, [(int(channels), int(length), rng)], n_noise, device=self.device, discard=True)
 
     def draw_noise_like_enhance(self, rng, channels, length, n_steps=None):
         """The noise `enhance` draws for a (channels, length) input -- x0, then one z per noisy step, each (channels, 1, length
         + pad) -- in ONE (n_steps, channels, length + pad) tensor, drawn in that order from `rng`."""
         n_steps = self.diff_kwargs.n_steps if n_steps is None else int(n_steps)
-        T = int(length) + (self.tot_ds - int(length) % self.tot_ds)
-        noise = torch.empty((n_steps, int(channels), T), dtype=torch.float32, device=self.device)
-        for k in range(n_steps):
-            torch.randn((int(channels), 1, T), generator=rng, out=noise[k].view(int(channels), 1, T))
-        return noise
+        return draw_noise(self.tot_ds, [(int(channels), int(length), rng)], n_steps, device=self.device)[:, :, 0]
+
+    # ---- recordings of any length: segmented enhance (ou_enhance_segments) ---------------------------------------------
+    SEGMENT_S = 8.0
+    OVERLAP_S = 1.0
 
     @torch.no_grad()
     def enhance_long(self, mix, segment_s: float = SEGMENT_S, overlap_s: float = OVERLAP_S, max_batch: int = 32,
@@ -1015,19 +1054,9 @@ class Universe:
         the workspace plus input and output.  A file that fits into one window gets the `enhance` result.  Workspace: ou_segments_workspace_bytes -- set by max_batch and segment_s.
         Ensembles of long recordings: `enhance_long_ensemble` (`ensemble=` is refused here)."""
         self._refuse_long_options("enhance_long", other)
-        self._sync_env()
-        self._poll_deferred_status()
-        if mix.ndim not in (1, 2):
-            raise ValueError("enhance_long takes (T,) or (C, T) signals")
-        x = self._prep(mix if mix.ndim == 2 else mix[None, :])
+        n_steps, epsilon, segment, overlap = self._begin(n_steps, epsilon, segment_s, overlap_s)
+        x = self._long_rows(mix, "enhance_long")
         C, T_raw = x.shape
-        if T_raw < 1:
-            raise ValueError("enhance_long: empty input signal")
-        n_steps = self.diff_kwargs.n_steps if n_steps is None else int(n_steps)
-        if epsilon is None:
-            epsilon = self.diff_kwargs.epsilon
-        segment = int(round(float(segment_s) * self.fs))
-        overlap = int(round(float(overlap_s) * self.fs))
         if is_counter(rng):
             noise, counter = None, (rng.seed, rng.stream_ids(C))
         else:
@@ -1035,27 +1064,36 @@ class Universe:
         out = self._segments_call(x, segment, overlap, max_batch, n_steps, epsilon, keep_rms, noise, counter)
         return out if mix.ndim == 2 else out[0]
 
+    def _segments_plan(self, C, T, segment, overlap, max_batch, ensemble=None, t_raw=None):
+        """What tells the three segmented entry points apart -- plain, `ensemble` = (E, stat), `t_raw` = a length per row --, sized:
+        -> (library function, its arguments between the noise pointer and n_steps, workspace)."""
+        geo = (segment, overlap, int(max_batch))
+        if ensemble is not None:
+            fn, sizer = self._L.ou_enhance_segments_ensemble, self._L.ou_segments_ensemble_workspace_bytes
+            sized, dims = (C, T) + geo + (ensemble[0],), (C, T, ensemble[0], _lib.ENSEMBLE_STATS[ensemble[1]]) + geo
+        elif t_raw is not None:
+            fn, sizer = self._L.ou_enhance_segments_var, self._L.ou_segments_var_workspace_bytes
+            sized, dims = (C, t_raw) + geo, (C, T, t_raw) + geo
+        else:
+            fn, sizer = self._L.ou_enhance_segments, self._L.ou_segments_workspace_bytes
+            sized, dims = (C, T) + geo, (C, T) + geo
+        return fn, dims, self._segments_sizer(sizer, *sized)[0]
+
+    def _segments_run(self, plan, x, n_steps, epsilon, keep_rms, noise, counter, members=None):
+        """The call `plan` (_segments_plan) on the prepared (C, T) rows `x` -> out (C, T); `members`: the (E, C, T) tensor an
+        ensemble writes its members to.  Noise as in `_segments_call`; no noise scratch (the library fills window by window)."""
+        fn, dims, ws = plan
+        out = torch.empty(x.shape, dtype=torch.float32, device=self.device)
+        self._forward(fn, (x, out, noise) if members is None else (x, out, members, noise), dims, n_steps, epsilon, None,
+                      _lib.OU_ENH_KEEP_RMS if keep_rms else 0, ws, counter if noise is None else None)
+        return out
+
     def _segments_call(self, x, segment, overlap, max_batch, n_steps, epsilon, keep_rms, noise, counter):
         """ou_enhance_segments of the prepared (C, T_raw) rows `x` on `noise` ((n_steps, C, T_pad)) or, with noise None, on the
         counter source `counter` = (seed, C stream ids).  (Also what the tests of enhance_long_ensemble run a single member row
         through, on that member's own noise or stream id.)"""
-        C, T_raw = x.shape
-        need, B, L = c_size_t(), c_int32(), c_int32()
-        _lib.check(self._L.ou_segments_workspace_bytes(self._handle, C, T_raw, segment, overlap, int(max_batch), byref(need),
-                                                        byref(B), byref(L)), self._handle)
-        sigma = self._sigma_table(n_steps)
-        ws = self._segments_workspace(B.value, L.value, need.value)
-        out = torch.empty(C, T_raw, dtype=torch.float32, device=self.device)
-        flags = _lib.OU_ENH_KEEP_RMS if keep_rms else 0
-        source = self._counter_source(*counter) if noise is None else contextlib.nullcontext()
-        with torch.cuda.device(self.device), source:
-            _lib.check(self._L.ou_enhance_segments(
-                self._handle, c_void_p(x.data_ptr()), c_void_p(out.data_ptr()),
-                None if noise is None else c_void_p(noise.data_ptr()), C, T_raw,
-                segment, overlap, int(max_batch), n_steps, float(epsilon), ctypes.cast(sigma.data_ptr(), ctypes.POINTER(c_float)),
-                -1, flags, c_void_p(ws.data_ptr()), c_size_t(ws.numel()), self._stream()), self._handle)
-        self._status()
-        return out
+        return self._segments_run(self._segments_plan(*x.shape, segment, overlap, max_batch), x, n_steps, epsilon, keep_rms,
+                                  noise, counter)
 
     @torch.no_grad()
     def enhance_long_ensemble(self, mix, ensemble: int, ensemble_stat: str = "median", segment_s: float = SEGMENT_S,
@@ -1070,42 +1108,21 @@ class Universe:
         `advance_generator_like_enhance(rng, E * C, T)` ends -- or a `CounterNoise` (member e of row c: `stream_ids(C, E)`; no
         noise tensor exists then).  Memory: the workspace (set by max_batch and segment_s) plus the E member rows of every
         input row -- the one part that grows with the recording.  return_members=True: -> (result, members (E,) + mix.shape)."""
-        self._sync_env()
-        self._poll_deferred_status()
+        n_steps, epsilon, segment, overlap = self._begin(n_steps, epsilon, segment_s, overlap_s)
         E = int(ensemble)
         if not 1 <= E <= _lib.OU_MAX_ENSEMBLE:
             raise ValueError(f"enhance_long_ensemble: 1 <= ensemble <= {_lib.OU_MAX_ENSEMBLE}")
         if ensemble_stat not in _lib.ENSEMBLE_STATS:
             raise NotImplementedError()  # universe.py:368
-        if mix.ndim not in (1, 2):
-            raise ValueError("enhance_long_ensemble takes (T,) or (C, T) signals")
-        x = self._prep(mix if mix.ndim == 2 else mix[None, :])
+        x = self._long_rows(mix, "enhance_long_ensemble")
         C, T_raw = x.shape
-        if T_raw < 1:
-            raise ValueError("enhance_long_ensemble: empty input signal")
-        n_steps = self.diff_kwargs.n_steps if n_steps is None else int(n_steps)
-        if epsilon is None:
-            epsilon = self.diff_kwargs.epsilon
-        segment = int(round(float(segment_s) * self.fs))
-        overlap = int(round(float(overlap_s) * self.fs))
-        need, B, L = c_size_t(), c_int32(), c_int32()
-        _lib.check(self._L.ou_segments_ensemble_workspace_bytes(self._handle, C, T_raw, segment, overlap, int(max_batch), E,
-                                                                 byref(need), byref(B), byref(L)), self._handle)
-        counter = is_counter(rng)
-        noise = None if counter else self.draw_noise_like_enhance(rng, E * C, T_raw, n_steps)
-        sigma = self._sigma_table(n_steps)
-        ws = self._segments_workspace(B.value, L.value, need.value)
-        out = torch.empty(C, T_raw, dtype=torch.float32, device=self.device)
+        plan = self._segments_plan(C, T_raw, segment, overlap, max_batch, ensemble=(E, ensemble_stat))
+        if is_counter(rng):
+            noise, counter = None, (rng.seed, rng.stream_ids(C, E))
+        else:
+            noise, counter = self.draw_noise_like_enhance(rng, E * C, T_raw, n_steps), None
         members = torch.empty(E, C, T_raw, dtype=torch.float32, device=self.device)
-        flags = _lib.OU_ENH_KEEP_RMS if keep_rms else 0
-        source = self._counter_source(rng.seed, rng.stream_ids(C, E)) if counter else contextlib.nullcontext()
-        with torch.cuda.device(self.device), source:
-            _lib.check(self._L.ou_enhance_segments_ensemble(
-                self._handle, c_void_p(x.data_ptr()), c_void_p(out.data_ptr()), c_void_p(members.data_ptr()),
-                None if counter else c_void_p(noise.data_ptr()), C, T_raw, E, _lib.ENSEMBLE_STATS[ensemble_stat],
-                segment, overlap, int(max_batch), n_steps, float(epsilon), ctypes.cast(sigma.data_ptr(), ctypes.POINTER(c_float)),
-                -1, flags, c_void_p(ws.data_ptr()), c_size_t(ws.numel()), self._stream()), self._handle)
-        self._status()
+        out = self._segments_run(plan, x, n_steps, epsilon, keep_rms, noise, counter, members)
         if mix.ndim == 1:
             out, members = out[0], members[:, 0]
         return (out, members) if return_members else out
@@ -1125,61 +1142,15 @@ class Universe:
         self._refuse_long_options("enhance_long_many", other)
         if not signals:
             return []
-        self._sync_env()
-        self._poll_deferred_status()
-        rows, dims = [], []
-        for s in signals:
-            if s.ndim not in (1, 2):
-                raise ValueError("enhance_long_many takes (L,) or (C, L) signals")
-            dims.append(s.ndim)
-            rows.append(self._prep(s if s.ndim == 2 else s[None, :]))
-        lens = [int(r.shape[-1]) for r in rows]
-        if min(lens) < 1:
-            raise ValueError("enhance_long_many: empty input signal")
-        chans = [int(r.shape[0]) for r in rows]
-        C, l_max = sum(chans), max(lens)
-        n_steps = self.diff_kwargs.n_steps if n_steps is None else int(n_steps)
-        if epsilon is None:
-            epsilon = self.diff_kwargs.epsilon
-        segment = int(round(float(segment_s) * self.fs))
-        overlap = int(round(float(overlap_s) * self.fs))
-        t_raw = (ctypes.c_int64 * C)(*[n for n, c in zip(lens, chans) for _ in range(c)])
-        need, B, L = c_size_t(), c_int32(), c_int32()
-        _lib.check(self._L.ou_segments_var_workspace_bytes(self._handle, C, t_raw, segment, overlap, int(max_batch), byref(need),
-                                                            byref(B), byref(L)), self._handle)
-        counter = self._counter_plan(rngs, chans)
+        n_steps, epsilon, segment, overlap = self._begin(n_steps, epsilon, segment_s, overlap_s)
+        pk = pack_rows(signals, "enhance_long_many", self._prep)
+        C, l_max = pk.batch.shape
+        plan = self._segments_plan(C, l_max, segment, overlap, max_batch, t_raw=(ctypes.c_int64 * C)(*pk.row_lens))
+        counter = self._counter_plan(rngs, pk.chans)
         noise = None
-        if counter is None:
-            # the draws of `enhance_long` on every input alone, input by input: (C_i, 1, T_i) per step, x0 first
-            T_max = l_max + (self.tot_ds - l_max % self.tot_ds)
-            noise = torch.zeros((n_steps, C, T_max), dtype=torch.float32, device=self.device)
-            r0 = 0
-            for i, (c, n) in enumerate(zip(chans, lens)):
-                g = rngs[i] if isinstance(rngs, (list, tuple)) else rngs
-                Ti = n + (self.tot_ds - n % self.tot_ds)
-                for k in range(n_steps):
-                    noise[k, r0:r0 + c, :Ti] = torch.randn((c, 1, Ti), dtype=torch.float32, device=self.device,
-                                                           generator=g)[:, 0]
-                r0 += c
-        sigma = self._sigma_table(n_steps)
-        ws = self._segments_workspace(B.value, L.value, need.value)
-        mix = torch.cat([torch.nn.functional.pad(r, (0, l_max - r.shape[-1])) for r in rows], dim=0).contiguous()
-        out = torch.empty(C, l_max, dtype=torch.float32, device=self.device)
-        flags = _lib.OU_ENH_KEEP_RMS if keep_rms else 0
-        source = self._counter_source(*counter) if counter is not None else contextlib.nullcontext()
-        with torch.cuda.device(self.device), source:
-            _lib.check(self._L.ou_enhance_segments_var(
-                self._handle, c_void_p(mix.data_ptr()), c_void_p(out.data_ptr()),
-                None if noise is None else c_void_p(noise.data_ptr()), C, l_max, t_raw,
-                segment, overlap, int(max_batch), n_steps, float(epsilon), ctypes.cast(sigma.data_ptr(), ctypes.POINTER(c_float)),
-                -1, flags, c_void_p(ws.data_ptr()), c_size_t(ws.numel()), self._stream()), self._handle)
-        self._status()
-        res, r0 = [], 0
-        for c, nd, n in zip(chans, dims, lens):
-            o = out[r0:r0 + c, :n]
-            r0 += c
-            res.append(o[0] if nd == 1 else o)
-        return res
+        if counter is None:  # the draws of `enhance_long` on every input alone, input by input: (C_i, 1, T_i) per step, x0 first
+            noise = draw_noise(self.tot_ds, pk.entries(rngs), n_steps, device=self.device)
+        return unpack_rows(pk, self._segments_run(plan, pk.batch, n_steps, epsilon, keep_rms, noise, counter))[0]
 
     def _segments_workspace(self, B, L, need):
         """The workspace of enhance_long: one buffer kept for re-use (outside the per-batch-size cache of `enhance`)."""
@@ -1216,7 +1187,7 @@ class Universe:
                 raise RuntimeError(f"graphed_enhance(serial=False) captures four streams; GPU_MAX_HW_QUEUES={hwq} makes the HIP "
                                    "runtime crash when such a graph is replayed -- use serial=True (the default)")
         B, mix_len = int(batch), int(length)
-        T = mix_len + (self.tot_ds - mix_len % self.tot_ds)
+        T = padded(mix_len, self.tot_ds)
         dev = self.device
         s_mix = torch.zeros(B, 1, mix_len, dtype=torch.float32, device=dev)
         s_noise = torch.zeros(n_steps, B, 1, T, dtype=torch.float32, device=dev)

@@ -3,8 +3,12 @@
 
 Every way into the sampler -- the six entry points ou_enhance, ou_enhance_var, ou_enhance_ensemble, ou_enhance_segments,
 ou_enhance_segments_var and ou_enhance_segments_ensemble -- is called on the reduced-width models of the GPU tests, 3 steps,
-fixed seeds, and one JSON line per call is printed: the call's name, both counters of ou_launch_stats and the SHA-256 of the
-output bytes.  The segmented entry points are also called on edge shapes:
+fixed seeds, and one JSON line per call is printed: the call's name, both counters of ou_launch_stats, the SHA-256 of the
+output bytes and `rng`, the SHA-256 of the end states (`get_state()`, concatenated) of the generators handed to the call (empty
+for counter sources and calls without a generator).  The Python paths in front of the entry points are covered too: shared
+generators, `pad_batch`, the `ensemble=` glue of `enhance`, noise handed over as a list or a tensor, `return_members`.  So the
+tool also compares two versions of the Python front end on ONE library (the second use below).  The segmented entry points are
+also called on edge shapes:
 rows of 1, 2, 3 and 5 samples, of tot_ds + 1, 16 tot_ds + 2 and 33 tot_ds + 3, so that the longest row is 1, 2 and 3 past a
 multiple of 4 -- the word-by-word head and tail of the 16-byte row moves and the guards of rows shorter than a quad.  Run it
 once per library and compare the files byte for byte:
@@ -12,15 +16,15 @@ once per library and compare the files byte for byte:
     OU_LIBRARY=/path/to/parent/libouniverse.so timeout -k 10 600 python tools/driver_ab.py --out parent.json
     timeout -k 10 600 python tools/driver_ab.py --out branch.json && cmp parent.json branch.json
 
+    # two checkouts, one library:
+    OU_LIBRARY=/path/to/libouniverse.so timeout -k 10 600 python <parent checkout>/tools/driver_ab.py --out parent.json
+
 One process, all calls in a fixed order; needs a gfx950 device."""
 import argparse
-import ctypes
 import hashlib
 import json
 import os
 import sys
-from ctypes import c_float, c_size_t, c_void_p
-
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,6 +34,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from helpers import get_spec, synth_mix  # noqa: E402
 from open_universe_amd import Universe, UniverseGAN, _lib, state_dict as S  # noqa: E402
 from open_universe_amd.noise import CounterNoise  # noqa: E402
+from open_universe_amd.universe import draw_noise  # noqa: E402
 
 N = 3
 
@@ -57,24 +62,23 @@ def enhance_serial(model, mix, rng):
     """ou_enhance with OU_ENH_SERIAL (the flag has no keyword in Universe.enhance: graphed_enhance sets it)."""
     x = model._prep(mix)[None, None, :]
     L = x.shape[-1]
-    T = L + (model.tot_ds - L % model.tot_ds)
-    noise = torch.empty((N, 1, 1, T), dtype=torch.float32, device=model.device)
-    for k in range(N):
-        torch.randn((1, 1, T), generator=rng, out=noise[k])
-    sigma = model._sigma_table(N)
+    noise = draw_noise(model.tot_ds, [(1, L, rng)], N, device=model.device)
     out = torch.empty(1, 1, L, dtype=torch.float32, device=model.device)
-    ws = model._workspace(1, T)
-    with torch.cuda.device(model.device):
-        _lib.check(model._L.ou_enhance(
-            model._handle, c_void_p(x.data_ptr()), c_void_p(out.data_ptr()), c_void_p(noise.data_ptr()), 1, L, N,
-            float(model.diff_kwargs.epsilon), ctypes.cast(sigma.data_ptr(), ctypes.POINTER(c_float)), -1, _lib.OU_ENH_SERIAL,
-            c_void_p(ws.data_ptr()), c_size_t(ws.numel()), model._stream()), model._handle)
-    model._status()
+    ws = model._workspace(1, noise.shape[-1])
+    model._forward(model._L.ou_enhance, (x, out, noise), (1, L), N, model.diff_kwargs.epsilon, None, _lib.OU_ENH_SERIAL, ws)
     return out
 
 
+def rng_digest(gens):
+    h = hashlib.sha256()
+    for g in gens:
+        h.update(g.get_state().cpu().numpy().tobytes())
+    return h.hexdigest() if gens else ""
+
+
 def calls(model, spec):
-    """-> (name, thunk) for every call of the comparison."""
+    """-> (name, seeds, fn) for every call of the comparison: fn takes the generators made from `seeds` (none: a counter source,
+    or no noise at all)."""
     td = spec.tot_ds
     one = synth_mix(spec, 1, 23 * td + 5, seed=1500)[0].cuda()
     two = synth_mix(spec, 2, 19 * td + 11, seed=1600).cuda()
@@ -83,13 +87,14 @@ def calls(model, spec):
     six = [synth_mix(spec, 1, n, seed=2000 + i)[0].cuda()
            for i, n in enumerate([41 * td + 7, 9 * td, 57, 16 * td - 1, 16 * td, 70 * td + 3])]
     seg = dict(segment_s=16 * td / spec.fs, overlap_s=2 * td / spec.fs, max_batch=4, n_steps=N)
+    three, many6 = [20, 21, 22], [80 + i for i in range(6)]
 
-    yield "enhance.b1", lambda: model.enhance(one, n_steps=N, rng=gen(11))
-    yield "enhance.b1.serial", lambda: enhance_serial(model, one, gen(11))
-    yield "enhance.b1.warm_start", lambda: model.enhance(one, n_steps=N, rng=gen(12), warm_start=1)
-    yield "enhance.b2.use_aux_signal", lambda: model.enhance(two, n_steps=N, use_aux_signal=True)
-    yield "enhance_many.ragged.tensor", lambda: model.enhance_many(ragged, [gen(20 + i) for i in range(3)], n_steps=N)
-    yield "enhance_many.ragged.counter", lambda: model.enhance_many(ragged, CounterNoise(31, 2), n_steps=N)
+    yield "enhance.b1", [11], lambda g: model.enhance(one, n_steps=N, rng=g[0])
+    yield "enhance.b1.serial", [11], lambda g: enhance_serial(model, one, g[0])
+    yield "enhance.b1.warm_start", [12], lambda g: model.enhance(one, n_steps=N, rng=g[0], warm_start=1)
+    yield "enhance.b2.use_aux_signal", [], lambda g: model.enhance(two, n_steps=N, use_aux_signal=True)
+    yield "enhance_many.ragged.tensor", three, lambda g: model.enhance_many(ragged, g, n_steps=N)
+    yield "enhance_many.ragged.counter", [], lambda g: model.enhance_many(ragged, CounterNoise(31, 2), n_steps=N)
     for share in (1, 0):
         def with_share(fn, share=share):
             model.set_option("ens_share", share)
@@ -98,18 +103,18 @@ def calls(model, spec):
             finally:
                 model.set_option("ens_share", 1)
         tag = f"enhance_ensemble.share{share}"
-        yield tag + ".plain", lambda w=with_share: w(lambda: model.enhance_ensemble(two, 3, n_steps=N, rng=gen(40)))
-        yield tag + ".plain.counter", lambda w=with_share: w(
+        yield tag + ".plain", [40], lambda g, w=with_share: w(lambda: model.enhance_ensemble(two, 3, n_steps=N, rng=g[0]))
+        yield tag + ".plain.counter", [], lambda g, w=with_share: w(
             lambda: model.enhance_ensemble(two, 3, n_steps=N, rng=CounterNoise(41, 3)))
-        yield tag + ".ragged", lambda w=with_share: w(
-            lambda: model.enhance_many(ragged, [gen(50 + i) for i in range(3)], n_steps=N, ensemble=3))
-    yield "enhance_ensemble.share1.ragged.warm_start", lambda: model.enhance_many(
-        ragged, [gen(60 + i) for i in range(3)], n_steps=N, ensemble=3, ensemble_stat="mean", warm_start=1)
+        yield tag + ".ragged", [50, 51, 52], lambda g, w=with_share: w(
+            lambda: model.enhance_many(ragged, g, n_steps=N, ensemble=3))
+    yield "enhance_ensemble.share1.ragged.warm_start", [60, 61, 62], lambda g: model.enhance_many(
+        ragged, g, n_steps=N, ensemble=3, ensemble_stat="mean", warm_start=1)
     for C in (1, 3):
-        yield f"enhance_long.c{C}.tensor", lambda C=C: model.enhance_long(long3[:C], rng=gen(70 + C), **seg)
-        yield f"enhance_long.c{C}.counter", lambda C=C: model.enhance_long(long3[:C], rng=CounterNoise(71, C), **seg)
-    yield "enhance_long_many.six.tensor", lambda: model.enhance_long_many(six, [gen(80 + i) for i in range(6)], **seg)
-    yield "enhance_long_many.six.counter", lambda: model.enhance_long_many(six, [CounterNoise(81, 5 + i) for i in range(6)], **seg)
+        yield f"enhance_long.c{C}.tensor", [70 + C], lambda g, C=C: model.enhance_long(long3[:C], rng=g[0], **seg)
+        yield f"enhance_long.c{C}.counter", [], lambda g, C=C: model.enhance_long(long3[:C], rng=CounterNoise(71, C), **seg)
+    yield "enhance_long_many.six.tensor", many6, lambda g: model.enhance_long_many(six, g, **seg)
+    yield "enhance_long_many.six.counter", [], lambda g: model.enhance_long_many(six, [CounterNoise(81, 5 + i) for i in range(6)], **seg)
 
     ens = dict(seg, max_batch=12)
     two_long = long3[:2]
@@ -120,22 +125,38 @@ def calls(model, spec):
             return model.enhance_long_ensemble(mix, 3, ensemble_stat=stat, rng=rng, return_members=True, **ens, **kw)
         finally:
             model.set_option("ens_share", 1)
-    yield "enhance_long_ensemble.share1.tensor.median", lambda: long_ensemble(1, two_long, gen(90), "median")
-    yield "enhance_long_ensemble.share0.tensor.median", lambda: long_ensemble(0, two_long, gen(90), "median")
-    yield "enhance_long_ensemble.share1.counter.mean", lambda: long_ensemble(1, two_long, CounterNoise(91, 4), "mean")
+    yield "enhance_long_ensemble.share1.tensor.median", [90], lambda g: long_ensemble(1, two_long, g[0], "median")
+    yield "enhance_long_ensemble.share0.tensor.median", [90], lambda g: long_ensemble(0, two_long, g[0], "median")
+    yield "enhance_long_ensemble.share1.counter.mean", [], lambda g: long_ensemble(1, two_long, CounterNoise(91, 4), "mean")
 
     # edge shapes (keep_rms: the post scale moves every row)
     edge = [1, 2, 3, 5, td + 1, 16 * td + 2, 33 * td + 3]
     for T in edge:
         mix = synth_mix(spec, 2, T, seed=2100).cuda()
-        yield f"edge.enhance_long.t{T}", lambda mix=mix: model.enhance_long(mix, rng=gen(100), keep_rms=True, **seg)
-        yield f"edge.enhance_long_ensemble.t{T}", lambda mix=mix: long_ensemble(1, mix, gen(101), "median", keep_rms=True)
+        yield f"edge.enhance_long.t{T}", [100], lambda g, mix=mix: model.enhance_long(mix, rng=g[0], keep_rms=True, **seg)
+        yield f"edge.enhance_long_ensemble.t{T}", [101], lambda g, mix=mix: long_ensemble(1, mix, g[0], "median", keep_rms=True)
     for n in (5, 6, 7):  # the longest row: tot_ds + 1, 16 tot_ds + 2, 33 tot_ds + 3
         rows = [synth_mix(spec, 1, T, seed=2200 + i)[0].cuda() for i, T in enumerate(edge[:n])]
-        yield f"edge.enhance_long_many.max{edge[n - 1]}.tensor", lambda rows=rows: model.enhance_long_many(
-            rows, [gen(110 + i) for i in range(len(rows))], keep_rms=True, **seg)
-    yield "edge.enhance_long_many.counter", lambda rows=rows: model.enhance_long_many(
+        yield f"edge.enhance_long_many.max{edge[n - 1]}.tensor", [110 + i for i in range(n)], lambda g, rows=rows: (
+            model.enhance_long_many(rows, g, keep_rms=True, **seg))
+    yield "edge.enhance_long_many.counter", [], lambda g, rows=rows: model.enhance_long_many(
         rows, [CounterNoise(111, 9 + i) for i in range(len(rows))], keep_rms=True, **seg)
+
+    # the Python paths in front of the entry points that the calls above do not reach
+    yield "py.enhance_many.pad_batch.shared", [120], lambda g: model.enhance_many(ragged, g[0], pad_batch=True, n_steps=N)
+    yield "py.enhance_many.ragged.shared", [121], lambda g: model.enhance_many(ragged, g[0], n_steps=N)
+    for stat in ("mean", "median", "signal_median"):
+        yield f"py.enhance.ensemble3.{stat}", [122], lambda g, stat=stat: model.enhance(
+            two, n_steps=N, rng=g[0], ensemble=3, ensemble_stat=stat)
+    T2 = two.shape[-1] + (td - two.shape[-1] % td)
+    z = torch.randn((N, 2, 1, T2), generator=torch.Generator().manual_seed(123)).cuda()
+    for tag, noise in (("list", list(z)), ("tensor", z)):
+        yield f"py.enhance.noise_{tag}", [], lambda g, noise=noise: model._enhance(
+            two, N, None, None, None, None, False, False, None, "median", None, noise)
+    for tag, mix in (("t", one), ("bt", two)):
+        yield f"py.enhance_ensemble.members.{tag}", [124], lambda g, mix=mix: model.enhance_ensemble(
+            mix, 3, n_steps=N, rng=g[0], return_members=True)
+    yield "py.enhance_long_many.shared", [125], lambda g: model.enhance_long_many(six, g[0], **seg)
 
 
 def main():
@@ -146,11 +167,13 @@ def main():
     lines = []
     for name in args.models:
         model, spec = build(name)
-        for call, thunk in calls(model, spec):
-            out = thunk()
+        for call, seeds, fn in calls(model, spec):
+            gens = [gen(s) for s in seeds]
+            out = fn(gens)
             torch.cuda.synchronize()
             launches, convs = model.launch_stats()
-            lines.append(json.dumps({"call": f"{name}.{call}", "launches": launches, "convs": convs, "sha256": digest(out)}))
+            lines.append(json.dumps({"call": f"{name}.{call}", "launches": launches, "convs": convs, "sha256": digest(out),
+                                     "rng": rng_digest(gens)}))
             print(lines[-1], flush=True)
     if args.out:
         with open(args.out, "w") as f:
