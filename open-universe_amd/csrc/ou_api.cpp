@@ -80,8 +80,6 @@ struct ou_handle {
   std::vector<ProfRec> prof;
   size_t prof_used = 0;
   unsigned long long* prof_dev = nullptr;  // [kProfSlots][32] device-side {16 x min start, 16 x ~max end} ticks
-  int fuse_mode = -1;  // OU_FUSE: -1 auto (cost model), 0 never, 2 / 3 force that depth where the shape allows
-  int fuse_nc = 0;     // OU_FUSE_NC: force 128 / 256 columns per tile
   // workspaces that ou_workspace_init has prepared (cleared status word, GRU tag epochs and exchange areas) and the
   // shape each was prepared for: the forward calls refuse anything else -- an uninitialised buffer would feed the
   // recurrence kernels a garbage epoch and garbage tags
@@ -128,9 +126,6 @@ struct Tensor {
   int C = 0, T = 0;
 };
 
-// Bump allocator over the caller's workspace.  In `dry` mode nothing is launched and `base` may be null:
-// the same walk then only measures the footprint (ou_workspace_bytes) -> layout is a pure function of
-// (config, B, T).
 // Tuning / test switches.  Until ABI 4 these were ~35 OU_* environment variables read by the library; since ABI 5
 // the library reads NO environment variable: every switch is a typed option of the handle (ou_set_option / ou_get_option,
 // include/ouniverse.h), echoed by ou_plan_json, and a forward call works on a copy taken when it starts.
@@ -184,28 +179,69 @@ const OptDesc* find_option(const char* key) {
     if (std::strcmp(kOptions[i].key, key) == 0) return &kOptions[i];
   return nullptr;
 }
-using EnvCfg = Options;
 
+// The state of one walk over the network: a bump allocator over the caller's workspace and the one gate,
+// launch(), through which everything a forward call enqueues goes.  In `dry` mode nothing is launched and `base` may be null:
+// the same walk then only measures the footprint (ou_workspace_bytes) -> layout is a pure function of (config, B, T).
 struct Runner {
   ou_handle* h;
-  EnvCfg env;
+  Options env;  // the handle's options as the call found them
   char* base;
   size_t cap;
   size_t off = 0;
   bool dry;
-  hipStream_t st;
+  hipStream_t st;       // where the next launch goes (a side stream while a branch runs there)
+  hipStream_t main_st;  // the caller's stream
   int B;
   hipError_t herr = hipSuccess;
   bool oom = false;
   const char* where = "";
   size_t max_plane = 0;            // largest (C, T) plane of one batch row that alloc() handed out (length guard)
   bool mel_scale_preset = false;   // the caller wrote the per-row mel scale (segmented enhance: whole-file scale)
+  // ragged batch (ou_enhance_var): per-row lengths on every level, see ou_kernels.h
+  bool ragged = false;
+  const int* lens_dev = nullptr;  // [lv.n][B]
+  const RowInfo* rows_dev = nullptr;
+  LevelSpec lv;
+  int level_T[kMaxLenLevels] = {0};
+  unsigned* status_words = nullptr;        // workspace header (layout_persist)
+  unsigned long long* block3_bar = nullptr;
+  int gru_area_rows = 0;    // rows the GRU exchange areas were laid out for when that is more than B (ou_enhance_ensemble: the
+                            // conditioner runs B rows on the areas of an E * B-row workspace, as a sub-launch of a chunked batch does)
+  bool gru_shared = false;  // GRU launches enqueued now may run beside another GRU layer (overlapped conditioner / score pass)
 
   Runner(ou_handle* h_, void* ws, size_t cap_, bool dry_, hipStream_t st_, int B_)
-      : h(h_), env(h_->opt), base((char*)ws), cap(cap_), dry(dry_), st(st_), B(B_), main_st(st_) {
+      : h(h_), env(h_->opt), base((char*)ws), cap(cap_), dry(dry_), st(st_), main_st(st_), B(B_) {
 #ifndef OU_EXPERIMENTS
     env.dbg = 0; env.dbg_dec0_under_gru = 0;  // (switches with WRONG results by design: experiments library only)
 #endif
+  }
+  // The conditioner's runner of a call whose score passes run more rows than its conditioner (ou_enhance_ensemble, the segmented
+  // ensembles): the first Bc rows of r, on r's workspace from r's bump pointer on, with r's GRU exchange areas.
+  static Runner conditioner_of(const Runner& r, int Bc) {
+    Runner c(r.h, r.base, r.cap, false, r.st, Bc);
+    c.status_words = r.status_words;
+    c.block3_bar = r.block3_bar;
+    c.gru_area_rows = r.B;
+    c.off = r.off;
+    c.mel_scale_preset = r.mel_scale_preset;
+    c.lv = r.lv;
+    for (int l = 0; l < kMaxLenLevels; l++) c.level_T[l] = r.level_T[l];
+    return c;
+  }
+  // into ragged mode: `lens` = the rows' lengths on the levels of set_levels ([lv.n][B], device), `rows` = their geometry
+  void set_ragged(const int* lens, const RowInfo* rows) {
+    ragged = true;
+    lens_dev = lens;
+    rows_dev = rows;
+  }
+
+  bool ok() const { return herr == hipSuccess && !oom; }
+  // THE launch gate: nothing is enqueued in a dry walk or after the first failure; the first error wins (finish())
+  template <class F>
+  void launch(const char* w, F&& enqueue) {
+    if (dry || !ok()) return;
+    chk(enqueue(), w);
   }
 
   float* alloc_raw(size_t floats) {
@@ -225,7 +261,6 @@ struct Runner {
     if (!name.empty()) h->tensors[name] = TensorRef{o, C, T};
     return t;
   }
-  hipStream_t main_st = nullptr;
   hipEvent_t next_event() {
     if (h->ev_used == h->events.size()) {
       hipEvent_t e;
@@ -234,28 +269,16 @@ struct Runner {
     }
     return h->events[h->ev_used++];
   }
-  // make side stream k wait for everything enqueued so far on `from`
-  void fork(hipStream_t from, int k) {
-    if (dry) return;
+  // make stream `to` wait for everything enqueued so far on `from`
+  void wait_for(hipStream_t from, hipStream_t to, const char* w_record, const char* w_wait) {
+    if (dry || !ok()) return;
     hipEvent_t e = next_event();
     if (!e) { herr = hipErrorOutOfMemory; where = "event"; return; }
-    chk(hipEventRecord(e, from), "fork record");
-    chk(hipStreamWaitEvent(h->aux[k], e, 0), "fork wait");
+    launch(w_record, [&] { return hipEventRecord(e, from); });
+    launch(w_wait, [&] { return hipStreamWaitEvent(to, e, 0); });
   }
-  // make `to` wait for everything enqueued so far on side stream k
-  void join(int k, hipStream_t to) {
-    if (dry) return;
-    hipEvent_t e = next_event();
-    if (!e) { herr = hipErrorOutOfMemory; where = "event"; return; }
-    chk(hipEventRecord(e, h->aux[k]), "join record");
-    chk(hipStreamWaitEvent(to, e, 0), "join wait");
-  }
-  // ---- ragged batch (ou_enhance_var): per-row lengths on every level, see ou_kernels.h
-  bool ragged = false;
-  const int* lens_dev = nullptr;  // [lv.n][B]
-  const RowInfo* rows_dev = nullptr;
-  LevelSpec lv;
-  int level_T[kMaxLenLevels] = {0};
+  void fork(hipStream_t from, int k) { wait_for(from, h->aux[k], "fork record", "fork wait"); }  // side stream k behind `from`
+  void join(int k, hipStream_t to) { wait_for(h->aux[k], to, "join record", "join wait"); }      // `to` behind side stream k
   // per-row lengths of a (B, C, Tl) tensor (null when all rows are whole)
   const int* lens_of(int Tl) {
     if (!ragged) return nullptr;
@@ -268,15 +291,32 @@ struct Runner {
   void mask(float* p, int C, int T) {
     if (!ragged || dry || !ok()) return;
     const int* ln = lens_of(T);
-    if (ln) chk(launch_mask_tail(p, ln, B, C, T, st), "mask tail");
+    if (ln) launch("mask tail", [&] { return launch_mask_tail(p, ln, B, C, T, st); });
   }
   void mask(const Tensor& t) { mask(t.p, t.C, t.T); }
-  bool ok() const { return herr == hipSuccess && !oom; }
-  void chk(hipError_t e, const char* w) {
-    if (e != hipSuccess && herr == hipSuccess) { herr = e; where = w; }
-    h->n_launch++;
+  // A producer of a (B, C, T) tensor that can keep that invariant itself: `enqueue(lens)` launches it; handed the rows' lengths
+  // (mask_fused) it zeroes behind them in its own epilogue, handed null a mask_tail launch follows.
+  template <class F>
+  void launch_masked(const char* w, float* p, int C, int T, F&& enqueue) {
+    const int* ln = env.mask_fused ? lens_of(T) : nullptr;
+    launch(w, [&] { return enqueue(ln); });
+    if (!ln) mask(p, C, T);
   }
   const float* W(size_t off_floats) const { return h->W + off_floats; }
+
+  // ---- records of the per-launch profile (ou_profile_enable).  Open one: the slot the kernel stamps, or null (profiling off, or
+  // no slot left); close: the variant code the launcher chose; drop: the launch did not happen.
+  unsigned long long* prof_open(double flops, double bytes, int cfg) {
+    if (!h->profile || !h->prof_dev || h->prof_used >= kProfSlots) return nullptr;
+    h->prof.push_back(ou_handle::ProfRec{flops, bytes, cfg});
+    return h->prof_dev + 32 * h->prof_used++;
+  }
+  void prof_close(const unsigned long long* slot, int cfg) {
+    if (slot) h->prof.back().cfg = cfg;
+  }
+  void prof_drop(const unsigned long long* slot) {
+    if (slot) { h->prof.pop_back(); h->prof_used--; }
+  }
 
   struct Epi {
     const float* add = nullptr;
@@ -288,7 +328,7 @@ struct Runner {
     const float* in_scale = nullptr;
     bool act = true;  // apply the layer's PReLU prologue (if it has one)
     // up-path anti-alias FIR fused into the conv epilogue: taps, 2r + 1, the manual bias added after the FIR.  conv()
-    // sets `unsupported` instead of failing when no kernel with that epilogue fits the layer.
+    // answers `supported = false` instead of failing when no kernel with that epilogue fits the layer.
     const float* fir = nullptr;
     int fir_len = 0;
     const float* fir_bias = nullptr;
@@ -296,23 +336,11 @@ struct Runner {
     bool rate_down = false;
     bool rate_up = false;  // the last up conv on rate_up_kernel (`fir` = the filter AFTER the conv or null, fir_bias / res)
     // store prelu(y; out_alpha) instead of y (ConvArgs::out_act): for outputs whose only reader is the next PReLU_Conv.  conv()
-    // leaves in `stored_act` whether the kernel that took the layer did so (else y is stored and the reader keeps its PReLU).
+    // answers in `stored_act` whether the kernel that took the layer did so (else y is stored and the reader keeps its PReLU).
     bool out_act = false;
     float out_alpha = 1.f;
     bool no_mask = false;  // ragged batch: the caller fills the tail itself (GRU input projections)
   };
-  bool stored_act = false;
-  bool unsupported = false;
-  // conv() in collect mode: the launch arguments are appended here instead of being launched (block(): the three body convs
-  // of a deep-level ConvBlock in one launch, conv_block3_kernel)
-  std::vector<ConvArgs>* collect = nullptr;
-  unsigned* status_words = nullptr;        // workspace header (layout_persist)
-  unsigned long long* block3_bar = nullptr;
-  int gru_area_rows = 0;    // rows the GRU exchange areas were laid out for when that is more than B (ou_enhance_ensemble: the
-                            // conditioner runs B rows on the areas of an E * B-row workspace, as a sub-launch of a chunked batch does)
-  bool gru_shared = false;  // GRU launches enqueued now may run beside another GRU layer (overlapped conditioner / score pass)
-  hipEvent_t pre_gru = nullptr;  // OU_DBG_DEC0: recorded right before the score net's GRU launch
-  bool want_pre_gru = false;
   // GRU launches that can meet on one XCD: this call's own two layers when they overlap, times the lanes whose clusters are
   // dealt to the same XCDs (lane l deals its 2 B clusters from XCD 2 B l on)
   static int gru_share_of(int lanes, int B, bool overlap) {
@@ -321,12 +349,10 @@ struct Runner {
     return by_lanes * (overlap ? 2 : 1);
   }
 
-  Tensor conv(const ConvL& L, const Tensor& in, const std::string& name, const Epi& e, const Tensor* dst = nullptr) {
-    int Nq, Tout;
-    if (L.stride > 1) { Nq = in.T / L.stride; Tout = Nq; }
-    else { Nq = in.T; Tout = in.T * L.up; }
-    Tensor out = dst ? *dst : alloc(name, L.Cout, Tout);
-    if (dry || !ok()) return out;
+  static int conv_nq(const ConvL& L, int Tin) { return L.stride > 1 ? Tin / L.stride : Tin; }
+  static int conv_tout(const ConvL& L, int Tin) { return L.stride > 1 ? Tin / L.stride : Tin * L.up; }
+  // the launch arguments of layer L reading `in`, writing `out`, with epilogue e
+  ConvArgs conv_args(const ConvL& L, const Tensor& in, const Tensor& out, const Epi& e) {
     ConvArgs a;
     a.x = in.p; a.w = W(L.w_off); a.bias = W(L.b_off); a.y = out.p;
     if (L.KWP) { a.wd = W(L.wd_off); a.wu = W(L.wu_off); }
@@ -339,106 +365,160 @@ struct Runner {
     a.add = e.add; a.add_scale = e.add_scale;
     a.film = e.film; a.film_bstride = e.film_bstride;
     a.res = e.res; a.res_scale = e.res_scale;
-    if (e.out_act && !collect && !e.fir && !e.rate_down && !e.rate_up) { a.out_act = 1; a.out_alpha = e.out_alpha; }
-    stored_act = false;
+    if (e.out_act && !e.fir && !e.rate_down && !e.rate_up) { a.out_act = 1; a.out_alpha = e.out_alpha; }
     if (e.fir && !e.rate_down) { a.fir = e.fir; a.fir_len = e.fir_len; a.bias = e.fir_bias; }  // (also rate_up)
     if (e.rate_down) { a.fir = e.fir; a.fir_len = e.fir ? e.fir_len : 0; }
     a.B = B; a.Cin = L.Cin; a.Tin = in.T; a.Cout = L.Cout; a.M = L.M; a.Mp = L.Mp; a.KW = L.KW;
-    a.stride = L.stride; a.pad = L.pad; a.up = L.up; a.CK = L.CK; a.Nq = Nq; a.Tout = Tout;
+    a.stride = L.stride; a.pad = L.pad; a.up = L.up; a.CK = L.CK; a.Nq = conv_nq(L, in.T); a.Tout = conv_tout(L, in.T);
     a.force_cfg = h->force_cfg; a.force_sc = h->force_sc;
     a.dbg = env.dbg; a.force_xcd_map = env.xcd_map; a.direct = env.conv_direct; a.d4_fir_unfused = env.d4_fir; a.d4_force = env.d4_force; a.d4_short = env.d4_short; a.deep_factor = env.deep_factor; a.d2_tile_rule = env.d2_tile_rule; a.d2_wk = env.d2_wk; a.wino = env.wino; a.d2_map = env.d2_map;
     a.tile_min = env.tile_min; a.tile_prefetch = env.tile_prefetch;
     a.tstamps = h->tstamps;
     // ragged batch: the kernel keeps "zero behind the row's own end" in its epilogue where its family can (conv_masks_rows)
-    if (ragged && env.mask_fused && !e.no_mask) a.lens = lens_of(Tout);
-    if (collect) { collect->push_back(a); return out; }
+    if (ragged && env.mask_fused && !e.no_mask) a.lens = lens_of(a.Tout);
+    return a;
+  }
+
+  // What conv() decided: the output, whether it was stored activated (Epi::out_act), and -- Epi::fir on the generic kernels
+  // only -- whether a kernel with that epilogue took the layer (false: nothing was launched, the caller runs conv + launch_fir)
+  struct ConvOut {
+    Tensor out;
+    bool stored_act = false;
+    bool supported = true;
+  };
+  // one conv layer: allocate (unless `dst`), then profile, launch, mask, trace and count
+  ConvOut conv(const ConvL& L, const Tensor& in, const std::string& name, const Epi& e, const Tensor* dst = nullptr) {
+    ConvOut o;
+    o.out = dst ? *dst : alloc(name, L.Cout, conv_tout(L, in.T));
+    if (dry || !ok()) return o;
+    ConvArgs a = conv_args(L, in, o.out, e);
+    // algorithmic (reference, un-folded) work of this layer: dense FLOPs, activations once, weights once (the packed layers
+    // carry the reference's own kernel sizes)
+    a.prof = prof_open(2.0 * L.M * (double)a.Nq * L.Cin * L.KW * B,
+                       4.0 * ((double)B * ((double)L.Cin * in.T + (double)L.Cout * a.Tout) + (double)L.M * L.Cin * L.KW), -1);
     int cfg = -1;
-    if (h->profile && h->prof_dev && h->prof_used < kProfSlots) {
-      ou_handle::ProfRec rec;
-      // algorithmic (reference, un-folded) work of this layer: dense FLOPs, activations once, weights once
-      const int kref = L.KW;  // the packed layers carry the reference's own kernel sizes
-      rec.flops = 2.0 * L.M * (double)Nq * L.Cin * kref * B;
-      rec.bytes = 4.0 * ((double)B * ((double)L.Cin * in.T + (double)L.Cout * Tout) + (double)L.M * L.Cin * kref);
-      rec.cfg = -1;
-      a.prof = h->prof_dev + 32 * h->prof_used;
-      h->prof.push_back(rec);
-      h->prof_used++;
-    }
-    unsupported = false;
+    hipError_t le;
     if (e.rate_down) {
-      chk(launch_rate_down(a, st, &cfg), L.name.c_str());
+      le = launch_rate_down(a, st, &cfg);
     } else if (e.rate_up) {
-      chk(launch_rate_up(a, st, &cfg), L.name.c_str());
+      le = launch_rate_up(a, st, &cfg);
     } else {
-      hipError_t le = launch_conv(a, h->num_cu, st, &cfg);
+      le = launch_conv(a, h->num_cu, st, &cfg);
       if (le == hipErrorNotSupported && a.out_act) {  // the kernel for this layer has no activating epilogue: store y
         a.out_act = 0;
         le = launch_conv(a, h->num_cu, st, &cfg);
       }
-      stored_act = a.out_act != 0;
-      if (le == hipErrorNotSupported && e.fir) {  // the caller falls back to conv + launch_fir
-        if (a.prof) { h->prof.pop_back(); h->prof_used--; }
-        unsupported = true;
-        return out;
+      o.stored_act = a.out_act != 0;
+      if (le == hipErrorNotSupported && e.fir) {  // not a failure and not counted: the caller falls back to conv + launch_fir
+        prof_drop(a.prof);
+        o.supported = false;
+        return o;
       }
-      chk(le, L.name.c_str());
     }
-    if (a.prof) h->prof.back().cfg = cfg;
+    launch(L.name.c_str(), [le] { return le; });  // (the gate was passed above: this records the launcher's answer)
+    prof_close(a.prof, cfg);
     h->last_cfg = cfg;
-    if (!e.no_mask && !(a.lens && conv_masks_rows(cfg))) mask(out);
+    if (!e.no_mask && !(a.lens && conv_masks_rows(cfg))) mask(o.out);
     if (h->trace)
       std::fprintf(stderr, "OU_TRACE conv %-64s cfg=%d M=%d Nq=%d K=%d(Cin=%d KW=%d CK=%d) stride=%d up=%d B=%d MFLOP=%.1f\n",
-                   name.c_str(), cfg, L.M, Nq, L.Cin * L.KW, L.Cin, L.KW, L.CK, L.stride, L.up, B,
-                   2.0 * L.M * Nq * L.Cin * L.KW * B * 1e-6);
+                   name.c_str(), cfg, L.M, a.Nq, L.Cin * L.KW, L.Cin, L.KW, L.CK, L.stride, L.up, B,
+                   2.0 * L.M * a.Nq * L.Cin * L.KW * B * 1e-6);
     h->n_conv++;
-    return out;
+    return o;
   }
 
-  struct BlockOut { Tensor h_next, v, c1; };
-  // ConvBlock.forward  (blocks.py:327-412).  `res` for dir==0 blocks must already be folded into `hin`.
+  // ---- ConvBlock.forward  (blocks.py:327-412) in three parts: up_path, body, down_path; block() sequences them.
+
+  // What rate_up_supported / rate_down_supported ask about the rate-change conv of a block reading Tin frames: the shape and
+  // whether a FIR rides along (fir_mode 1: in front of the down conv, 2: behind the up conv).  Pure function of the layer shape.
+  ConvArgs rate_probe(const ConvL& rc, int Tin) {
+    ConvArgs a;
+    a.up = rc.up; a.stride = rc.stride; a.KW = rc.KW; a.pad = rc.pad; a.Tin = Tin;
+    a.Nq = conv_nq(rc, Tin); a.Tout = conv_tout(rc, Tin); a.M = rc.M; a.Cout = rc.Cout; a.Cin = rc.Cin;
+    a.fir = (rc.fir_mode == 1 || rc.fir_mode == 2) ? W(rc.fir_off) : nullptr; a.fir_len = rc.fir_len;
+    return a;
+  }
+
+  // blocks.py:366-376: the block's input brought to the block's rate, `res` (the skip connection) added.  `res` for dir == 0
+  // blocks must already be folded into `hin`.
+  Tensor up_path(const BlockL& Bk, const Tensor& hin, const std::string& nm, const float* res) {
+    if (Bk.dir != 2) return hin;
+    const ConvL& rc = Bk.rc;
+    Epi e;
+    e.res = res; e.res_scale = kInvSqrt2;  // blocks.py:374-376 fused into the up-conv epilogue
+    if (rc.fir_mode == 2) { e.fir = W(rc.fir_off); e.fir_len = rc.fir_len; e.fir_bias = W(rc.fbias_off); }
+    if ((rc.fir_mode == 0 || rc.fir_mode == 2) && env.rate_small != 0 && rate_up_supported(rate_probe(rc, hin.T))) {
+      e.rate_up = true;
+      return conv(rc, hin, nm + ".up", e).out;
+    }
+    // (fir_mode 4: FIR folded into 3-tap phase GEMMs by the packer, its manual bias = the conv bias)
+    if (rc.fir_mode != 2) return conv(rc, hin, nm + ".up", e).out;
+    // PReLU -> transposed conv (r phase GEMMs) -> FIR + bias + residual add: fused into the conv's epilogue where
+    // the direct kernel takes the layer, else as one bandwidth pass after it
+    const Tensor u = alloc(nm + ".upc", rc.Cout, hin.T * rc.up);
+    const Tensor hu = alloc(nm + ".up", u.C, u.T);
+    if (env.fuse_upfir != 0 && conv(rc, hin, nm + ".up", e, &hu).supported) return hu;
+    conv(rc, hin, nm + ".upc", Epi(), &u);
+    launch_masked("fir(up)", hu.p, hu.C, hu.T, [&](const int* ln) {
+      return launch_fir(u.p, W(rc.fir_off), rc.fir_len, 0.f, 0, W(rc.fbias_off), res, kInvSqrt2, hu.p, B, u.C, u.T, st, ln);
+    });
+    return hu;
+  }
+
+  // The launch arguments of the fused body of a ConvBlock at `depth` (3: conv1 .. conv3, 2: conv2, conv3): plan_chain prices
+  // them (chain_cost reads the shape, `wu` / `add` / `film` / `c1_out` as flags and `lens`), body launches them.  depth 0 in the
+  // result: the layers are not a body the fused kernels take.
+  ChainArgs chain_args(const BlockL& Bk, int depth, const Tensor& hu, const Tensor& c1, const Tensor& v, const Epi& e1,
+                       bool need_c1) {
+    ChainArgs ca;
+    ca.depth = depth; ca.B = B; ca.C = Bk.C; ca.T = hu.T; ca.Mp = Bk.c1.Mp;
+    ca.x = depth == 3 ? hu.p : c1.p;
+    ca.y = v.p; ca.res = hu.p; ca.res_scale = kInvSqrt2;
+    if (depth == 3) {
+      ca.add = e1.add; ca.add_scale = e1.add_scale; ca.film = e1.film; ca.film_bstride = e1.film_bstride;
+      ca.c1_out = need_c1 ? c1.p : nullptr;
+    }
+    const ConvL* ls[3] = {&Bk.c1, &Bk.c2, &Bk.c3};
+    for (int s2 = 0; s2 < depth; s2++) {
+      const ConvL& L = *ls[3 - depth + s2];
+      if (!L.act || L.stride != 1 || L.up != 1 || L.Cin != Bk.C || L.Cout != Bk.C || L.pad != (L.KW - 1) / 2 || L.Mp != Bk.c1.Mp)
+        ca.depth = 0;
+      ChainConv& c = ca.cv[s2];
+      c.w = W(L.w_off); c.bias = W(L.b_off); c.alpha = L.act ? h->alphas[L.a_off] : 0.f; c.KW = L.KW; c.CK = L.CK;
+      if (L.KWP) c.wu = W(L.wu_off);
+    }
+    ca.force_nc = env.fuse_nc;
+    ca.wino = env.wino && env.conv_direct >= 5;
+    ca.lens = lens_of(hu.T);
+    return ca;
+  }
   // How the three body convs of a ConvBlock run: 0 = three generic launches, 3 = one fused launch, 2 = conv1 generic +
-  // fused (conv2, conv3).  Pure function of (layer shapes, B, T, device, OU_FUSE*) -- estimated cycles, see
+  // fused (conv2, conv3).  Pure function of (layer shapes, B, T, device, options fuse / fuse_nc) -- estimated cycles, see
   // chain_cost(); the generic launches are priced at their measured ~45 TFLOP/s with a 12 us floor.
-  int plan_chain(const BlockL& Bk, int T) {
-    h->fuse_mode = env.fuse; h->fuse_nc = env.fuse_nc;
-    if (h->fuse_mode == 0) return 0;
+  int plan_chain(const BlockL& Bk, const Tensor& hu, const Tensor& c1, const Tensor& v, const Epi& e1, bool need_c1) {
+    const int T = hu.T;
+    if (env.fuse == 0) return 0;
     // (ragged batch: conv_chainw_kernel zeroes its LDS tiles and its output behind every row's own end -- ChainArgs::lens)
     if (ragged && !env.mask_fused) return 0;  // (the separate-mask form has no place to mask inside a fused body)
     // Throughput regime: with >= ~2 wave tiles per SIMD the three convs run unfused on conv_direct3_kernel at 70-100 TFLOP/s
     // each, ahead of the fused body's ~75 (measured end to end: PP16 B = 4 19.2 -> 18.4 ms, OR16 B = 16 57.7 -> 55.5 ms, B = 8
     // even); below that the fused launch wins (B = 1: 24 us for all three convs).
-    if (h->fuse_mode < 0 && Bk.C % 16 == 0 && Bk.c1.KWP && Bk.c2.KWP && Bk.c3.KWP) {
+    if (env.fuse < 0 && Bk.C % 16 == 0 && Bk.c1.KWP && Bk.c2.KWP && Bk.c3.KWP) {
       if (env.conv_direct >= 3 && direct3_tiles_per_simd(Bk.C, T, B, h->num_cu) >= 1.9 && T >= 1024) return 0;
       // Round 5, measured and left off: with minimal filtering the three split-K launches of a 64-channel body (17.0 + 11.7 +
       // 11.7 us at B = 1, back to back) look level with conv1 + the fused pair (17.0 + 24.8) -- end to end the unfused form is
       // 0.04-0.07 ms per enhance SLOWER (6.88-6.91 vs 6.83-6.85 ms, three alternating runs).  OU_UNFUSE64=1 selects it.
       if (env.unfuse64 && env.conv_direct >= 5 && env.wino && Bk.C % 64 == 0 && T >= 1024) return 0;
     }
-    auto shape = [&](int depth) {
-      ChainArgs ca;
-      ca.depth = depth; ca.B = B; ca.C = Bk.C; ca.T = T; ca.Mp = Bk.c1.Mp; ca.force_nc = h->fuse_nc;
-      const ConvL* ls[3] = {&Bk.c1, &Bk.c2, &Bk.c3};
-      for (int s2 = 0; s2 < depth; s2++) {
-        const ConvL& L = *ls[3 - depth + s2];
-        if (!L.act || L.stride != 1 || L.up != 1 || L.Cin != Bk.C || L.Cout != Bk.C || L.pad != (L.KW - 1) / 2 ||
-            L.Mp != Bk.c1.Mp)
-          ca.depth = 0;
-        ca.cv[s2].KW = L.KW; ca.cv[s2].CK = L.CK;
-        if (L.KWP) ca.cv[s2].wu = h->W;  // (a marker: the layer HAS the Winograd-domain copy -- what chain_cost's shape test asks)
-      }
-      ca.wino = env.wino && env.conv_direct >= 5;
-      ca.lens = ragged ? lens_of(T) : nullptr;
-      return ca;
-    };
     auto generic = [&](const ConvL& L) {
       const double cyc = 2.0 * L.M * (double)T * L.Cin * L.KW * B / 45e12 * 2.3e9;
       return cyc > 28000.0 ? cyc : 28000.0;
     };
-    const double c3 = chain_cost(shape(3), h->num_cu, nullptr);
-    double c2 = chain_cost(shape(2), h->num_cu, nullptr);
+    const double c3 = chain_cost(chain_args(Bk, 3, hu, c1, v, e1, need_c1), h->num_cu, nullptr);
+    double c2 = chain_cost(chain_args(Bk, 2, hu, c1, v, e1, need_c1), h->num_cu, nullptr);
     if (c2 >= 0) c2 += generic(Bk.c1);
-    if (h->fuse_mode == 3) return c3 >= 0 ? 3 : 0;
-    if (h->fuse_mode == 2) return c2 >= 0 ? 2 : 0;
+    if (env.fuse == 3) return c3 >= 0 ? 3 : 0;
+    if (env.fuse == 2) return c2 >= 0 ? 2 : 0;
     const double c0 = generic(Bk.c1) + generic(Bk.c2) + generic(Bk.c3);
     int best = 0;
     double bc = c0;
@@ -446,206 +526,116 @@ struct Runner {
     if (c2 >= 0 && c2 < bc) { best = 2; bc = c2; }
     return best;
   }
+  // Deep levels at batch 1: the three body convs in ONE launch (conv_block3_kernel) where the shape fits -- on the caller's
+  // stream only (its workgroups wait for each other: one such kernel at a time), not while profiling per layer.  False: not
+  // taken, nothing launched.  OFF by default (option block3): 41.7 / 42.3 us per fused launch (C = 512 / 256) against 44.3 /
+  // 44.1 us for the three launches with their gaps, and the enhance as a whole 0.1 ms SLOWER with it.
+  bool body_block3(const BlockL& Bk, const Tensor& hu, const Tensor& c1, const Tensor& c2, const Tensor& v, const std::string& nm,
+                   const Epi& e1, const Epi& e3) {
+    if (dry || !ok() || env.block3 == 0 || B != 1 || ragged || st != main_st || !block3_bar || h->profile || h->tstamps ||
+        h->force_cfg >= 0 || env.conv_direct < 2)
+      return false;
+    const ConvArgs cv[3] = {conv_args(Bk.c1, hu, c1, e1), conv_args(Bk.c2, c1, c2, Epi()), conv_args(Bk.c3, c2, v, e3)};
+    int cfg = -1;
+    const hipError_t le = launch_conv_block3(cv, block3_bar, status_words, h->num_cu, st, &cfg);
+    if (le == hipErrorInvalidConfiguration) return false;  // (not a shape for it)
+    if (le != hipSuccess) { launch(nm.c_str(), [le] { return le; }); return false; }
+    h->last_cfg = cfg;
+    h->n_conv++;
+    if (h->trace) std::fprintf(stderr, "OU_TRACE block3 %-62s cfg=%d C=%d T=%d\n", nm.c_str(), cfg, Bk.C, hu.T);
+    return true;
+  }
+  // blocks.py:377-399: conv1 (+ cond add, FiLM: e1), conv2, conv3 (+ the block's residual), hu -> c1 -> c2 -> v.  One fused launch
+  // on the wide, shallow levels (conv_chain kernels: all three, or conv1 + a fused (conv2, conv3)), else conv_block3_kernel or
+  // three launches.  `need_c1`: the caller reads the raw conv1 result; `c1_private`: nobody but conv2 reads c1.
+  void body(const BlockL& Bk, const Tensor& hu, const Tensor& c1, const Tensor& c2, const Tensor& v, const std::string& nm,
+            Epi e1, bool need_c1, bool c1_private) {
+    const int depth = dry ? 0 : plan_chain(Bk, hu, c1, v, e1, need_c1);
+    if (depth == 3 || depth == 2) {
+      if (depth == 2) conv(Bk.c1, hu, nm + ".c1", e1, &c1);
+      if (!ok()) return;
+      ChainArgs ca = chain_args(Bk, depth, hu, c1, v, e1, need_c1);
+      if (!env.chain_ts.empty() && nm == env.chain_ts) ca.tstamps = (long long*)(base + cap - (16u << 20));
+      double flops = 0, wbytes = 0;
+      for (int s2 = 0; s2 < depth; s2++) {
+        flops += 2.0 * Bk.C * (double)hu.T * Bk.C * ca.cv[s2].KW * B;
+        wbytes += 4.0 * Bk.C * Bk.C * ca.cv[s2].KW;
+      }
+      // activations: block input (also the residual) once, output once, the cond add when present
+      ca.prof = prof_open(flops, 4.0 * B * (double)Bk.C * hu.T * (2 + (depth == 2 ? 1 : 0) + (ca.add ? 1 : 0)) + wbytes, -1);
+      int variant = -1;
+      launch(nm.c_str(), [&] { return launch_chain(ca, h->num_cu, st, &variant); });
+      prof_close(ca.prof, variant);
+      if (h->trace)
+        std::fprintf(stderr, "OU_TRACE chain %-63s variant=%d depth=%d C=%d T=%d B=%d\n", nm.c_str(), variant, depth, Bk.C, hu.T, B);
+      h->n_conv++;
+      return;
+    }
+    Epi e3;
+    e3.res = dry ? nullptr : hu.p; e3.res_scale = kInvSqrt2;  // blocks.py:399
+    if (body_block3(Bk, hu, c1, c2, v, nm, e1, e3)) return;
+    // c1 (unless it is exported as a condition) and c2 are read by the next conv only: stored ACTIVATED by the epilogue of the
+    // conv that produces them, so that the reader's operand path has no PReLU (ConvArgs::out_act; bit-identical)
+    if (env.preact && c1_private && Bk.c2.act) { e1.out_act = true; e1.out_alpha = h->alphas[Bk.c2.a_off]; }
+    Epi e2;
+    e2.act = !conv(Bk.c1, hu, nm + ".c1", e1, &c1).stored_act;
+    if (env.preact && Bk.c3.act) { e2.out_act = true; e2.out_alpha = h->alphas[Bk.c3.a_off]; }
+    e3.act = !conv(Bk.c2, c1, nm + ".c2", e2, &c2).stored_act;
+    conv(Bk.c3, c2, nm + ".v", e3, &v);
+  }
 
+  // blocks.py:401-410: the block's output brought to the next block's rate
+  Tensor down_path(const BlockL& Bk, const Tensor& v, const std::string& nm) {
+    if (Bk.dir != 1) return v;
+    const ConvL& rc = Bk.rc;
+    Epi e;
+    // wide levels: FIR + strided conv in one launch
+    if (rc.fir_mode <= 1 && env.rate_small != 0 && rate_down_supported(rate_probe(rc, v.T))) {
+      e.rate_down = true;
+      if (rc.fir_mode == 1) { e.fir = W(rc.fir_off); e.fir_len = rc.fir_len; }
+      return conv(rc, v, nm + ".h", e).out;
+    }
+    if (rc.fir_mode != 1) return conv(rc, v, nm + ".h", e).out;  // (fir_mode 3: FIR folded into the 3r-tap weights)
+    const Tensor xf = alloc(nm + ".fir", v.C, v.T);
+    launch("fir(down)", [&] {
+      return launch_fir(v.p, W(rc.fir_off), rc.fir_len, h->alphas[rc.a_off], 1, nullptr, nullptr, 1.f, xf.p, B, v.C, v.T, st);
+    });
+    // (ragged batch: no mask needed -- the k = s = r conv that reads xf has no halo, and its own output is masked)
+    e.act = false;  // PReLU applied by the FIR pass
+    return conv(rc, xf, nm + ".h", e).out;
+  }
+
+  struct BlockOut { Tensor h_next, v, c1; };
   // `c1_dst` / `v_dst`: caller-provided (persistent) tensors for the conv1 result / the block output, so that
   // conditioner outputs are produced in place instead of being copied out of the scratch area afterwards
   BlockOut block(const BlockL& Bk, const Tensor& hin, const std::string& nm, const float* film, int film_bs,
                  const float* input_cond, const float* res, bool need_c1 = false, const Tensor* c1_dst = nullptr,
                  const Tensor* v_dst = nullptr) {
-    Tensor hu = hin;
-    bool small_up = false;
-    if (Bk.dir == 2 && (Bk.rc.fir_mode == 0 || Bk.rc.fir_mode == 2)) {  // pure function of the layer shape
-      ConvArgs probe;
-      probe.up = Bk.rc.up; probe.stride = Bk.rc.stride; probe.KW = Bk.rc.KW; probe.pad = Bk.rc.pad; probe.Tin = hin.T;
-      probe.Nq = hin.T; probe.Tout = hin.T * Bk.rc.up; probe.M = Bk.rc.M; probe.Cout = Bk.rc.Cout; probe.Cin = Bk.rc.Cin;
-      probe.fir = Bk.rc.fir_mode == 2 ? h->W : nullptr; probe.fir_len = Bk.rc.fir_len;
-      small_up = env.rate_small != 0 && rate_up_supported(probe);
-    }
-    if (small_up) {
-      Epi e;
-      e.rate_up = true;
-      e.res = res; e.res_scale = kInvSqrt2;
-      if (Bk.rc.fir_mode == 2) { e.fir = W(Bk.rc.fir_off); e.fir_len = Bk.rc.fir_len; e.fir_bias = W(Bk.rc.fbias_off); }
-      hu = conv(Bk.rc, hin, nm + ".up", e);
-    } else if (Bk.dir == 2) {
-      if (Bk.rc.fir_mode == 2) {
-        // PReLU -> transposed conv (r phase GEMMs) -> FIR + bias + residual add: fused into the conv's epilogue where
-        // the direct kernel takes the layer, else as one bandwidth pass after it
-        Tensor u = alloc(nm + ".upc", Bk.rc.Cout, hin.T * Bk.rc.up);
-        hu = alloc(nm + ".up", u.C, u.T);
-        if (!dry && ok()) {
-          const bool fuse = env.fuse_upfir != 0;
-          bool done = false;
-          if (fuse) {
-            Epi e;
-            e.res = res; e.res_scale = kInvSqrt2;
-            e.fir = W(Bk.rc.fir_off); e.fir_len = Bk.rc.fir_len; e.fir_bias = W(Bk.rc.fbias_off);
-            conv(Bk.rc, hin, nm + ".up", e, &hu);
-            done = !unsupported;
-          }
-          if (!done) {
-            conv(Bk.rc, hin, nm + ".upc", Epi(), &u);
-            if (ok())
-            {
-              const int* ln = env.mask_fused ? lens_of(u.T) : nullptr;
-              chk(launch_fir(u.p, W(Bk.rc.fir_off), Bk.rc.fir_len, 0.f, 0, W(Bk.rc.fbias_off), res, kInvSqrt2, hu.p, B,
-                             u.C, u.T, st, ln), "fir(up)");
-              if (!ln) mask(hu);
-            }
-          }
-        }
-      } else {
-        // (fir_mode 4: FIR folded into 3-tap phase GEMMs by the packer, its manual bias = the conv bias)
-        Epi e;
-        e.res = res; e.res_scale = kInvSqrt2;  // blocks.py:374-376 fused into the up-conv epilogue
-        hu = conv(Bk.rc, hin, nm + ".up", e);
-      }
-    }
+    const Tensor hu = up_path(Bk, hin, nm, res);
     Epi e1;
     if (input_cond) { e1.add = input_cond; e1.add_scale = kInvSqrt2; }  // blocks.py:384-386
     e1.film = film; e1.film_bstride = film_bs;                           // blocks.py:393-394
-    Tensor c1 = c1_dst ? *c1_dst : alloc(nm + ".c1", Bk.c1.Cout, hu.T);
-    Tensor c2 = alloc(nm + ".c2", Bk.c2.Cout, hu.T);
-    Tensor v = v_dst ? *v_dst : alloc(nm + ".v", Bk.c3.Cout, hu.T);
-    auto chain_conv = [&](const ConvL& L) {
-      ChainConv c;
-      c.w = W(L.w_off); c.bias = W(L.b_off); c.alpha = h->alphas[L.a_off]; c.KW = L.KW; c.CK = L.CK;
-      if (L.KWP) c.wu = W(L.wu_off);
-      return c;
-    };
-    // wide, shallow levels: the body runs as one fused launch (conv_chain_kernel), or conv1 + a fused (conv2, conv3)
-    const int depth = dry ? 0 : plan_chain(Bk, hu.T);
-
-    if (depth == 3 || depth == 2) {
-      if (depth == 2) conv(Bk.c1, hu, nm + ".c1", e1, &c1);
-      if (ok()) {
-        ChainArgs ca;
-        ca.depth = depth; ca.B = B; ca.C = Bk.C; ca.T = hu.T; ca.Mp = Bk.c1.Mp;
-        ca.x = depth == 3 ? hu.p : c1.p;
-        ca.y = v.p; ca.res = hu.p; ca.res_scale = kInvSqrt2;
-        if (depth == 3) {
-          ca.add = e1.add; ca.add_scale = e1.add_scale; ca.film = e1.film; ca.film_bstride = e1.film_bstride;
-          ca.c1_out = need_c1 ? c1.p : nullptr;
-          ca.cv[0] = chain_conv(Bk.c1); ca.cv[1] = chain_conv(Bk.c2); ca.cv[2] = chain_conv(Bk.c3);
-        } else {
-          ca.cv[0] = chain_conv(Bk.c2); ca.cv[1] = chain_conv(Bk.c3);
-        }
-        ca.force_nc = h->fuse_nc;
-        ca.wino = env.wino && env.conv_direct >= 5;
-        ca.lens = lens_of(hu.T);
-        if (!env.chain_ts.empty() && nm == env.chain_ts) ca.tstamps = (long long*)(base + cap - (16u << 20));
-        int variant = -1;
-        if (h->profile && h->prof_dev && h->prof_used < kProfSlots) {
-          ou_handle::ProfRec rec;
-          rec.flops = 0;
-          double wbytes = 0;
-          for (int s2 = 0; s2 < depth; s2++) {
-            rec.flops += 2.0 * Bk.C * (double)hu.T * Bk.C * ca.cv[s2].KW * B;
-            wbytes += 4.0 * Bk.C * Bk.C * ca.cv[s2].KW;
-          }
-          // activations: block input (also the residual) once, output once, the cond add when present
-          rec.bytes = 4.0 * B * (double)Bk.C * hu.T * (2 + (depth == 2 ? 1 : 0) + (ca.add ? 1 : 0)) + wbytes;
-          rec.cfg = -1;
-          ca.prof = h->prof_dev + 32 * h->prof_used;
-          h->prof.push_back(rec);
-          h->prof_used++;
-        }
-        chk(launch_chain(ca, h->num_cu, st, &variant), nm.c_str());
-        if (ca.prof) h->prof.back().cfg = variant;
-        if (h->trace)
-          std::fprintf(stderr, "OU_TRACE chain %-63s variant=%d depth=%d C=%d T=%d B=%d\n", nm.c_str(), variant, depth,
-                       Bk.C, hu.T, B);
-        h->n_conv++;
-      }
-    } else {
-      Epi e3;
-      e3.res = hu.p; e3.res_scale = kInvSqrt2;  // blocks.py:399
-      if (dry) e3.res = nullptr;
-      // Deep levels at batch 1: the three convs in ONE launch (conv_block3_kernel) where the shape fits -- on the caller's
-      // stream only (its workgroups wait for each other: one such kernel at a time), not while profiling per layer.
-      // OFF by default (OU_BLOCK3=1): 41.7 / 42.3 us per fused launch (C = 512 / 256) against 44.3 / 44.1 us for the three
-      // launches with their gaps, and the enhance as a whole 0.1 ms SLOWER with it.
-      bool fused = false;
-      if (!dry && ok() && env.block3 != 0 && B == 1 && !ragged && st == main_st && block3_bar && !h->profile && !h->tstamps &&
-          h->force_cfg < 0 && env.conv_direct >= 2) {
-        std::vector<ConvArgs> cv;
-        collect = &cv;
-        conv(Bk.c1, hu, nm + ".c1", e1, &c1);
-        conv(Bk.c2, c1, nm + ".c2", Epi(), &c2);
-        conv(Bk.c3, c2, nm + ".v", e3, &v);
-        collect = nullptr;
-        int cfg = -1;
-        const hipError_t le = cv.size() == 3 ? launch_conv_block3(cv.data(), block3_bar, status_words, h->num_cu, st, &cfg)
-                                             : hipErrorInvalidConfiguration;
-        if (le == hipSuccess) {
-          fused = true;
-          h->last_cfg = cfg;
-          h->n_conv++;
-          if (h->trace)
-            std::fprintf(stderr, "OU_TRACE block3 %-62s cfg=%d C=%d T=%d\n", nm.c_str(), cfg, Bk.C, hu.T);
-        } else if (le != hipErrorInvalidConfiguration) {
-          chk(le, nm.c_str());
-        }
-      }
-      if (!fused) {
-        // c1 (unless it is exported as a condition) and c2 are read by the next conv only: stored ACTIVATED by the epilogue of the
-        // conv that produces them, so that the reader's operand path has no PReLU (ConvArgs::out_act; bit-identical)
-        const bool c1_private = !need_c1 && !c1_dst;
-        if (env.preact && c1_private && Bk.c2.act) { e1.out_act = true; e1.out_alpha = h->alphas[Bk.c2.a_off]; }
-        conv(Bk.c1, hu, nm + ".c1", e1, &c1);
-        Epi e2;
-        e2.act = !stored_act;
-        if (env.preact && Bk.c3.act) { e2.out_act = true; e2.out_alpha = h->alphas[Bk.c3.a_off]; }
-        conv(Bk.c2, c1, nm + ".c2", e2, &c2);
-        e3.act = !stored_act;
-        conv(Bk.c3, c2, nm + ".v", e3, &v);
-      }
-    }
     BlockOut o;
-    o.v = v; o.c1 = c1; o.h_next = v;
-    if (Bk.dir == 1) {  // blocks.py:401-410
-      bool small = false;
-      if (Bk.rc.fir_mode <= 1) {  // wide levels: FIR + strided conv in one launch (pure function of the layer shape)
-          ConvArgs probe;
-        probe.up = Bk.rc.up; probe.stride = Bk.rc.stride; probe.KW = Bk.rc.KW; probe.pad = Bk.rc.pad; probe.Tin = v.T;
-        probe.Nq = v.T / Bk.rc.stride; probe.M = Bk.rc.M; probe.Cin = Bk.rc.Cin;
-        probe.fir = Bk.rc.fir_mode == 1 ? h->W : nullptr; probe.fir_len = Bk.rc.fir_len;
-        small = env.rate_small != 0 && rate_down_supported(probe);
-      }
-      if (small) {
-        Epi e;
-        e.rate_down = true;
-        if (Bk.rc.fir_mode == 1) { e.fir = W(Bk.rc.fir_off); e.fir_len = Bk.rc.fir_len; }
-        o.h_next = conv(Bk.rc, v, nm + ".h", e);
-      } else if (Bk.rc.fir_mode == 1) {
-        Tensor xf = alloc(nm + ".fir", v.C, v.T);
-        if (!dry && ok())
-          chk(launch_fir(v.p, W(Bk.rc.fir_off), Bk.rc.fir_len, h->alphas[Bk.rc.a_off], 1, nullptr, nullptr, 1.f, xf.p, B,
-                         v.C, v.T, st), "fir(down)");
-        // (ragged batch: no mask needed -- the k = s = r conv that reads xf has no halo, and its own output is masked)
-        Epi e;
-        e.act = false;  // PReLU applied by the FIR pass
-        o.h_next = conv(Bk.rc, xf, nm + ".h", e);
-      } else {
-        o.h_next = conv(Bk.rc, v, nm + ".h", Epi());  // (fir_mode 3: FIR folded into the 3r-tap weights)
-      }
-    }
+    o.c1 = c1_dst ? *c1_dst : alloc(nm + ".c1", Bk.c1.Cout, hu.T);
+    const Tensor c2 = alloc(nm + ".c2", Bk.c2.Cout, hu.T);
+    o.v = v_dst ? *v_dst : alloc(nm + ".v", Bk.c3.Cout, hu.T);
+    body(Bk, hu, o.c1, c2, o.v, nm, e1, need_c1, !need_c1 && !c1_dst);
+    o.h_next = down_path(Bk, o.v, nm);
     return o;
   }
 
-  // one bidirectional GRU layer: projection GEMM + cluster recurrence
+  // one bidirectional GRU layer: projection GEMM + cluster recurrence.  `before`: an event to take and record right in front of
+  // the recurrence launch (null when none could be had)
   Tensor gru(const GruL& G, const Tensor& in, const std::string& nm, unsigned long long* xchg, unsigned* errw,
-             unsigned* epoch, const float* res, float res_scale) {
+             unsigned* epoch, const float* res, float res_scale, hipEvent_t* before = nullptr) {
     Epi e;
     e.act = false;
     e.no_mask = true;
-    Tensor gx = conv(G.proj, in, nm + ".gx", e);
+    Tensor gx = conv(G.proj, in, nm + ".gx", e).out;
     Tensor out = alloc(nm, 2 * G.H, in.T);
     if (dry || !ok()) return out;
-    if (ragged) {  // frames behind a row's own end hold the state (z = 1): see launch_gru_tail_fill
-      const int* ln = lens_of(in.T);
-      if (ln) chk(launch_gru_tail_fill(gx.p, ln, B, G.H, in.T, st), "gru tail fill");
-    }
+    // ragged batch: frames behind a row's own end hold the state (z = 1): see launch_gru_tail_fill
+    if (const int* ln = lens_of(in.T)) launch("gru tail fill", [&] { return launch_gru_tail_fill(gx.p, ln, B, G.H, in.T, st); });
     GruArgs a;
     a.gx = gx.p; a.whh = W(G.whh_off); a.bhn = W(G.bhn_off); a.out = out.p; a.res = res; a.res_scale = res_scale;
     a.xchg = xchg; a.err = errw; a.epoch = epoch; a.B = B; a.T = in.T; a.H = G.H;
@@ -669,23 +659,20 @@ struct Runner {
     // merely late).  A hipGraph captured before such a switch keeps the publish form it was captured with: re-capture.
     a.agent_stores = env.gru_agent >= 0 ? (env.gru_agent != 0) : h->gru_agent_stores;
     a.dbg = env.gru_dbg;
-    if (h->profile && h->prof_dev && h->prof_used < kProfSlots) {
-      // the recurrence proper (the input projection is a conv launch of its own): 2 directions x T steps x (3H x H) MACs
-      ou_handle::ProfRec rec;
-      rec.flops = 2.0 * 2.0 * 3.0 * G.H * G.H * (double)in.T * B;
-      rec.bytes = 4.0 * ((double)B * (6.0 + 2.0 + (res ? 2.0 : 0.0)) * G.H * in.T + 2.0 * 3.0 * G.H * G.H);
-      rec.cfg = 1000 + in.T;  // 1000 + steps per pass
-      a.prof = h->prof_dev + 32 * h->prof_used;
-      h->prof.push_back(rec);
-      h->prof_used++;
-    }
-    if (want_pre_gru) {
-      pre_gru = next_event();
-      if (pre_gru) chk(hipEventRecord(pre_gru, st), "pre-gru record");
-    }
-    chk(launch_gru(a, h->num_cu, st), G.name.c_str());
+    // the recurrence proper (the input projection is a conv launch of its own): 2 directions x T steps x (3H x H) MACs;
+    // variant code 1000 + steps per pass
+    a.prof = prof_open(2.0 * 2.0 * 3.0 * G.H * G.H * (double)in.T * B,
+                       4.0 * ((double)B * (6.0 + 2.0 + (res ? 2.0 : 0.0)) * G.H * in.T + 2.0 * 3.0 * G.H * G.H), 1000 + in.T);
+    if (before && (*before = next_event())) launch("pre-gru record", [&] { return hipEventRecord(*before, st); });
+    launch(G.name.c_str(), [&] { return launch_gru(a, h->num_cu, st); });
     mask(out);
     return out;
+  }
+
+ private:
+  void chk(hipError_t e, const char* w) {
+    if (e != hipSuccess && herr == hipSuccess) { herr = e; where = w; }
+    h->n_launch++;
   }
 };
 
@@ -754,26 +741,23 @@ void run_condition(Runner& r, Persist& P, const float* mix_norm, int T) {
   if (ov) { r.fork(main, 0); r.st = r.h->aux[0]; }
   Tensor mel = r.alloc("cond.mel", m.mel.n_mels, L);
   float* esum = r.alloc_raw((size_t)r.B * L);
-  if (!r.dry && r.ok()) {
-    r.chk(launch_mel(mix_norm, r.W(m.mel.win_off), r.W(m.mel.tw_off), r.W(m.mel.fb_off), mel.p, esum, r.B, T,
-                     m.mel.n_fft, m.mel.hop, m.mel.pad_left, m.mel.n_freq, m.mel.n_mels, L, r.st), "mel");
-    if (!r.mel_scale_preset) r.chk(launch_mel_scale(esum, P.mel_scale, r.B, L, r.st, r.lens_of(L)), "mel_scale");
-    r.mask(mel);  // (frames behind a row's end still see its last samples)
-  }
+  r.launch("mel", [&] {
+    return launch_mel(mix_norm, r.W(m.mel.win_off), r.W(m.mel.tw_off), r.W(m.mel.fb_off), mel.p, esum, r.B, T, m.mel.n_fft,
+                      m.mel.hop, m.mel.pad_left, m.mel.n_freq, m.mel.n_mels, L, r.st);
+  });
+  if (!r.mel_scale_preset) r.launch("mel_scale", [&] { return launch_mel_scale(esum, P.mel_scale, r.B, L, r.st, r.lens_of(L)); });
+  r.mask(mel);  // (frames behind a row's end still see its last samples)
   Runner::Epi em;
   em.in_scale = P.mel_scale;  // the global mel normalisation is linear: folded into the conv's input scale
   em.act = false;
-  Tensor m0 = r.conv(m.c_melconv, mel, "cond.melconv", em);
+  Tensor m0 = r.conv(m.c_melconv, mel, "cond.melconv", em).out;
   Tensor x_mel = r.block(m.c_melblock, m0, "cond.melblock", nullptr, 0, nullptr, nullptr).v;
   r.st = main;
   // --- input conv + encoder  condition.py:360, 189-206
   Tensor e0 = r.alloc("cond.in", m.C0, T);
-  {
-    const int* ln = r.env.mask_fused ? r.lens_of(T) : nullptr;
-    if (!r.dry && r.ok())
-      r.chk(launch_in_conv(mix_norm, r.W(m.c_in.w_off), r.W(m.c_in.b_off), nullptr, 0, e0.p, r.B, m.C0, T, m.c_in.KW, r.st, ln), "cond.in");
-    if (!ln) r.mask(e0);
-  }
+  r.launch_masked("cond.in", e0.p, e0.C, e0.T, [&](const int* ln) {
+    return launch_in_conv(mix_norm, r.W(m.c_in.w_off), r.W(m.c_in.b_off), nullptr, 0, e0.p, r.B, m.C0, T, m.c_in.KW, r.st, ln);
+  });
   Tensor hcur = e0;
   std::vector<Tensor> outs;
   for (int i = 0; i < m.n_blocks; i++) {
@@ -784,10 +768,10 @@ void run_condition(Runner& r, Persist& P, const float* mix_norm, int T) {
       const ConvL& S = m.c_st[i];
       const int R = S.rate, C = S.Cin / R;
       Tensor sd = r.alloc("cond.s2d" + std::to_string(i), S.Cin, bo.v.T / R);
-      if (!r.dry && r.ok()) r.chk(launch_s2d(bo.v.p, r.W(S.a_off), sd.p, r.B, C, bo.v.T, R, r.st), "s2d");
+      r.launch("s2d", [&] { return launch_s2d(bo.v.p, r.W(S.a_off), sd.p, r.B, C, bo.v.T, R, r.st); });
       Runner::Epi es;
       es.act = false;  // PReLU already applied by the space-to-depth pass
-      outs.push_back(r.conv(S, sd, "cond.st" + std::to_string(i), es));
+      outs.push_back(r.conv(S, sd, "cond.st" + std::to_string(i), es).out);
       r.st = main;
     }
     hcur = bo.h_next;
@@ -795,13 +779,13 @@ void run_condition(Runner& r, Persist& P, const float* mix_norm, int T) {
   outs.push_back(hcur);
   if (ov) { r.join(0, main); r.join(1, main); }
   Tensor sum = r.alloc("cond.enc_sum", m.OC, L);
-  if (!r.dry && r.ok()) {
+  if (!r.dry && r.ok() && outs.size() > 4) { r.herr = hipErrorInvalidValue; r.where = "too many encoder outputs"; return; }
+  r.launch("enc_sum", [&] {
     const float* q[4] = {nullptr, nullptr, nullptr, nullptr};
-    if (outs.size() > 4) { r.herr = hipErrorInvalidValue; r.where = "too many encoder outputs"; return; }
     for (size_t i = 0; i < outs.size(); i++) q[i] = outs[i].p;
-    r.chk(launch_sum(x_mel.p, q[0], q[1], q[2], q[3], 1.0f / std::sqrt((float)(outs.size() + 1)), sum.p,
-                     (size_t)r.B * m.OC * L, r.st), "enc_sum");
-  }
+    return launch_sum(x_mel.p, q[0], q[1], q[2], q[3], 1.0f / std::sqrt((float)(outs.size() + 1)), sum.p, (size_t)r.B * m.OC * L,
+                      r.st);
+  });
   // --- conv_block1 -> 2-layer GRU (+residual) -> conv_block2   condition.py:208-216
   Tensor cb1 = r.block(m.c_cb1, sum, "cond.cb1", nullptr, 0, nullptr, nullptr).v;
   // status block: [0] error word, [2..3] / [4..5] = {tag epoch, finished-block count} of the two GRU exchange areas
@@ -834,19 +818,16 @@ struct ScoreEnc {
   Tensor hg;
   bool fuse_res = false;
 };
+// `pre_gru`: an event to record right in front of the GRU launch (Runner::gru)
 ScoreEnc run_score_enc(Runner& r, Persist& P, const float* x, const StepCoef* coef, int coef_bs,
-                       const float* film_row, int film_bs, int T) {
+                       const float* film_row, int film_bs, int T, hipEvent_t* pre_gru = nullptr) {
   const Model& m = r.h->m;
   ScoreEnc E;
   Tensor e0 = r.alloc("score.in", m.C0, T);
   // the w_in scaling of the EDM wrapper (universe.py:199,202) rides on the input conv
-  {
-    const int* ln = r.env.mask_fused ? r.lens_of(T) : nullptr;
-    if (!r.dry && r.ok())
-      r.chk(launch_in_conv(x, r.W(m.s_in.w_off), r.W(m.s_in.b_off), coef, coef_bs, e0.p, r.B, m.C0, T, m.s_in.KW, r.st, ln),
-            "score.in");
-    if (!ln) r.mask(e0);
-  }
+  r.launch_masked("score.in", e0.p, e0.C, e0.T, [&](const int* ln) {
+    return launch_in_conv(x, r.W(m.s_in.w_off), r.W(m.s_in.b_off), coef, coef_bs, e0.p, r.B, m.C0, T, m.s_in.KW, r.st, ln);
+  });
   Tensor hcur = e0;
   for (int i = 0; i < m.n_blocks; i++) {
     const float* fr = film_row ? film_row + m.film.enc_off[i] : nullptr;
@@ -857,7 +838,7 @@ ScoreEnc run_score_enc(Runner& r, Persist& P, const float* x, const StepCoef* co
   // GRU bottleneck; when decoder block 0 has no rate change its residual add (blocks.py:374-376) is fused here
   E.fuse_res = m.s_dec[0].dir == 0;
   E.hg = r.gru(m.s_gru, hcur, "score.gru", P.xchg2, P.status, P.status + 4,
-               E.fuse_res && !r.dry ? E.residuals[m.n_blocks - 1].p : nullptr, kInvSqrt2);
+               E.fuse_res && !r.dry ? E.residuals[m.n_blocks - 1].p : nullptr, kInvSqrt2, pre_gru);
   return E;
 }
 void run_score_dec(Runner& r, Persist& P, const ScoreEnc& E, const float* x, const float* noise, float* out, int mode,
@@ -872,11 +853,10 @@ void run_score_dec(Runner& r, Persist& P, const ScoreEnc& E, const float* x, con
     auto bo = r.block(m.s_dec[j], y, "score.dec" + std::to_string(j), fr, film_bs, P.sc[j].p, resp);
     y = bo.v;
   }
-  const int* ln = r.env.mask_fused ? r.lens_of(T) : nullptr;
-  if (!r.dry && r.ok())
-    r.chk(launch_out_conv(y.p, r.W(m.s_out.w_off), r.W(m.s_out.b_off), r.W(m.s_out.a_off), x, noise, out, coef,
-                          coef_bs, m.cfg.has_edm, mode, r.B, m.C0, T, m.s_out.KW, r.st, ln), "score.out");
-  if (!ln) r.mask(out, 1, T);
+  r.launch_masked("score.out", out, 1, T, [&](const int* ln) {
+    return launch_out_conv(y.p, r.W(m.s_out.w_off), r.W(m.s_out.b_off), r.W(m.s_out.a_off), x, noise, out, coef, coef_bs,
+                           m.cfg.has_edm, mode, r.B, m.C0, T, m.s_out.KW, r.st, ln);
+  });
 }
 static bool m_blocks_ok(const Runner& r) { return r.h->m.n_blocks >= 1 && r.h->m.s_dec[0].dir == 0; }
 void run_score(Runner& r, Persist& P, const float* x, const float* noise, float* out, int mode,
@@ -886,13 +866,12 @@ void run_score(Runner& r, Persist& P, const float* x, const float* noise, float*
   // written so far).  The time of a forward in this mode is a lower bound for any scheme that gates those convs on the
   // recurrence's progress: the gated version can only start later and wait more.
   const bool dec0_under = r.env.dbg_dec0_under_gru != 0 && !r.dry && r.h->overlap && r.h->lanes <= 1 && m_blocks_ok(r);
-  r.want_pre_gru = dec0_under;
-  ScoreEnc E = run_score_enc(r, P, x, coef, coef_bs, film_row, film_bs, T);
-  r.want_pre_gru = false;
-  if (dec0_under && r.pre_gru && r.ok()) {
+  hipEvent_t pre_gru = nullptr;
+  ScoreEnc E = run_score_enc(r, P, x, coef, coef_bs, film_row, film_bs, T, dec0_under ? &pre_gru : nullptr);
+  if (dec0_under && pre_gru && r.ok()) {
     const Model& m = r.h->m;
     hipStream_t main = r.st;
-    r.chk(hipStreamWaitEvent(r.h->aux[0], r.pre_gru, 0), "dec0 wait");
+    r.launch("dec0 wait", [&] { return hipStreamWaitEvent(r.h->aux[0], pre_gru, 0); });
     r.st = r.h->aux[0];
     const float* fr = film_row ? film_row + m.film.dec_off[0] : nullptr;
     const Tensor& res = E.residuals[m.n_blocks - 1];
@@ -950,8 +929,15 @@ void upload_coefs(Runner& r, StepCoef* dst, const std::vector<StepCoef>& rows) {
     CoefBlock blk;
     int n = (int)std::min<size_t>(64, rows.size() - i);
     for (int k = 0; k < n; k++) blk.c[k] = rows[i + k];
-    r.chk(launch_upload_coef(dst + i, blk, n, r.st), "upload coef");
+    r.launch("upload coef", [&] { return launch_upload_coef(dst + i, blk, n, r.st); });
   }
+}
+
+// the FiLM rows of the first n coefficient rows at P.coef
+void upload_film_rows(Runner& r, Persist& P, int n) {
+  const Model& m = r.h->m;
+  r.launch("sigma", [&] { return launch_sigma_embed(P.coef, n, r.W(m.sigma.p_off), m.sigma.simple, m.sigma.n_rff, m.film.D, P.g, r.st); });
+  r.launch("film", [&] { return launch_film(P.g, r.W(m.film.w_off), r.W(m.film.b_off), P.film, n, m.film.rows, m.film.D, r.st); });
 }
 
 long long max_walk_length(ou_handle* h, bool need_wav);
@@ -1227,8 +1213,7 @@ int ou_score(ou_handle* h, const float* x, const float* sigma_host, float* score
   }
   upload_coefs(r, P.coef, rows);
   const Model& m = h->m;
-  r.chk(launch_sigma_embed(P.coef, B, r.W(m.sigma.p_off), m.sigma.simple, m.sigma.n_rff, m.film.D, P.g, r.st), "sigma");
-  r.chk(launch_film(P.g, r.W(m.film.w_off), r.W(m.film.b_off), P.film, B, m.film.rows, m.film.D, r.st), "film");
+  upload_film_rows(r, P, B);
   run_score(r, P, x, nullptr, score_out, OUT_SCORE, P.coef, 1, P.film, m.film.rows, T);
   return finish(h, r);
 }
@@ -1247,8 +1232,10 @@ int ou_aux_to_wav(ou_handle* h, float* wav_out, int32_t B, int32_t T, void* ws, 
   size_t need = (size_t)B * m.C0 * 2 * T * 4;
   if (ws_bytes < need + r.off) return fail(h, OU_ENOMEM, "workspace too small");
   float* tmp = (float*)((char*)ws + ((ws_bytes - need) & ~size_t(255)));
-  r.chk(launch_decoupling(P.aux.p, r.W(m.dec.alpha_off), r.W(m.dec.up_off), r.W(m.dec.down_off), r.W(m.dec.conv.w_off),
-                          r.W(m.dec.conv.b_off), tmp, wav_out, B, m.C0, T, r.st), "decoupling");
+  r.launch("decoupling", [&] {
+    return launch_decoupling(P.aux.p, r.W(m.dec.alpha_off), r.W(m.dec.up_off), r.W(m.dec.down_off), r.W(m.dec.conv.w_off),
+                             r.W(m.dec.conv.b_off), tmp, wav_out, B, m.C0, T, r.st);
+  });
   return finish(h, r);
 }
 
@@ -1289,7 +1276,7 @@ void fill_noise_plane(Runner& r, float* dst, long long cols, int n_rows, unsigne
       blk.stream[i] = 0; blk.t0[i] = 0; blk.len[i] = 0;
       if (i < n) row(off + i, blk.stream[i], blk.t0[i], blk.len[i]);
     }
-    r.chk(launch_noise_fill(dst + (size_t)off * cols, cols, cols, blk, n, seed, draw, r.st), "noise fill");
+    r.launch("noise fill", [&] { return launch_noise_fill(dst + (size_t)off * cols, cols, cols, blk, n, seed, draw, r.st); });
   }
 }
 
@@ -1385,9 +1372,7 @@ struct SamplerTables {
   void upload_coef(Runner& r, Persist& P) const { upload_coefs(r, P.coef, coef); }
   // the FiLM rows of every step, from the uploaded coefficients (only a call that runs the score net needs them)
   void upload_film(Runner& r, Persist& P) const {
-    const Model& m = r.h->m;
-    r.chk(launch_sigma_embed(P.coef, n_steps(), r.W(m.sigma.p_off), m.sigma.simple, m.sigma.n_rff, m.film.D, P.g, r.st), "sigma");
-    r.chk(launch_film(P.g, r.W(m.film.w_off), r.W(m.film.b_off), P.film, n_steps(), m.film.rows, m.film.D, r.st), "film");
+    upload_film_rows(r, P, n_steps());
   }
   void upload(Runner& r, Persist& P) const { upload_coef(r, P); upload_film(r, P); }
 };
@@ -1415,15 +1400,17 @@ void upload_row_lengths(Runner& r, RowInfo* rows_dst, int* lens_dst, const int32
     RowBlock blk;
     const int k = n - off < 64 ? n - off : 64;
     for (int i = 0; i < 64; i++) blk.t_raw[i] = i < k ? t_raw[off + i] : 1;
-    r.chk(launch_upload_rows(rows_dst, lens_dst, blk, k, off, n, r.h->m.tot_ds, r.lv, r.st), "upload rows");
+    r.launch("upload rows", [&] { return launch_upload_rows(rows_dst, lens_dst, blk, k, off, n, r.h->m.tot_ds, r.lv, r.st); });
   }
 }
 
 // universe.py:219-223 + the level normalisation of `rows` inputs of T_raw samples (a ragged walk: of their own lengths) -> P.mixn
 void normalize(Runner& r, Persist& P, const float* mix, int rows, int T_raw, int T) {
   const float level = (float)std::pow(10.0, (double)r.h->m.cfg.level_db / 20.0);
-  if (r.ragged) r.chk(launch_pad_normalize_var(mix, P.mixn.p, P.stats, P.rows, rows, T_raw, T, level, r.st), "normalize");
-  else r.chk(launch_pad_normalize(mix, P.mixn.p, P.stats, rows, T_raw, T, (T - T_raw) / 2, level, r.st), "normalize");
+  r.launch("normalize", [&] {
+    return r.ragged ? launch_pad_normalize_var(mix, P.mixn.p, P.stats, P.rows, rows, T_raw, T, level, r.st)
+                    : launch_pad_normalize(mix, P.mixn.p, P.stats, rows, T_raw, T, (T - T_raw) / 2, level, r.st);
+  });
 }
 struct PostFlags {
   int keep_rms, peak;
@@ -1431,18 +1418,20 @@ struct PostFlags {
 };
 // unpad, de-normalise, keep_rms and the peak guard of `rows` rows of x -> out
 void post(Runner& r, Persist& P, const float* x, float* out, int rows, int T_raw, int T, PostFlags f) {
-  if (!r.ok()) return;
-  if (r.ragged) r.chk(launch_post_var(x, P.stats, out, P.rows, rows, T_raw, T, f.keep_rms, f.peak, r.st), "post");
-  else r.chk(launch_post(x, P.stats, out, rows, T_raw, T, (T - T_raw) / 2, f.keep_rms, f.peak, r.st), "post");
+  r.launch("post", [&] {
+    return r.ragged ? launch_post_var(x, P.stats, out, P.rows, rows, T_raw, T, f.keep_rms, f.peak, r.st)
+                    : launch_post(x, P.stats, out, rows, T_raw, T, (T - T_raw) / 2, f.keep_rms, f.peak, r.st);
+  });
 }
 // the signal decoupling layer: P.aux -> P.wav for the rows of r (scratch from the walk's bump allocator)
 void decouple(Runner& r, Persist& P) {
   const Model& m = r.h->m;
   const int T = P.wav.T;
   float* tmp = r.alloc_raw((size_t)r.B * m.C0 * 2 * T);
-  if (r.ok())
-    r.chk(launch_decoupling(P.aux.p, r.W(m.dec.alpha_off), r.W(m.dec.up_off), r.W(m.dec.down_off), r.W(m.dec.conv.w_off),
-                            r.W(m.dec.conv.b_off), tmp, P.wav.p, r.B, m.C0, T, r.st, r.lens_of(T), r.lens_of(2 * T)), "decoupling");
+  r.launch("decoupling", [&] {
+    return launch_decoupling(P.aux.p, r.W(m.dec.alpha_off), r.W(m.dec.up_off), r.W(m.dec.down_off), r.W(m.dec.conv.w_off),
+                             r.W(m.dec.conv.b_off), tmp, P.wav.p, r.B, m.C0, T, r.st, r.lens_of(T), r.lens_of(2 * T));
+  });
 }
 
 // Noise provider of the calls whose rows are whole signals: draw d is plane (d ? d - n_start : 0) of the caller's tensor, or --
@@ -1468,7 +1457,7 @@ auto row_noise(Runner& r, const float* noise, int n_start, int T, const int32_t*
 
 // universe.py:325-327: x = sigma * z_0 (+ the warm start's signal).  `mask`: the plane may hold noise behind a row's own end.
 void init_x(Runner& r, Persist& P, const float* z0, const float* warm, float sigma, int T, bool mask) {
-  r.chk(launch_init_x(z0, warm, sigma, P.x.p, (size_t)r.B * T, r.st), "init x");
+  r.launch("init x", [&] { return launch_init_x(z0, warm, sigma, P.x.p, (size_t)r.B * T, r.st); });
   if (mask) r.mask(P.x);
 }
 // A first score-encoder pass that already ran on side stream 2 (ou_enhance's overlap with the conditioner): its results and
@@ -1538,9 +1527,7 @@ int enhance_impl(ou_handle* h, const float* mix, float* out, const float* noise,
   if (t_raw) {
     if (const int rc = set_levels(r, T)) return rc;
     upload_row_lengths(r, P.rows, P.lens, t_raw, B);
-    r.ragged = true;
-    r.lens_dev = P.lens;
-    r.rows_dev = P.rows;
+    r.set_ragged(P.lens, P.rows);
   }
   if (need_wav && (!m.dec.present || m.dec.act != OU_ACT_SNAKE))
     return fail(h, OU_ENOTIMPL, "aux_to_wav needs the snake signal-decoupling layer (UNIVERSE++)");
@@ -1639,6 +1626,43 @@ EnsArea ens_area(int B, int E, long long cols) {
   return a;
 }
 
+// Replication over the members of an ensemble: the first n words at p (rows [0, rows) of a tensor laid out for E * rows rows)
+// -> the E - 1 blocks behind them, kReplicateEntries tensors per launch.
+class Replicator {
+  Runner& r;
+  const int E;
+  ReplicateTable tab;
+  int n = 0;
+
+ public:
+  Replicator(Runner& r_, int E_) : r(r_), E(E_) {}
+  void add(void* p, size_t words) {
+    if (n == kReplicateEntries) flush();
+    tab.p[n] = (unsigned*)p;
+    tab.n[n] = (long long)words;
+    n++;
+  }
+  void add(const Tensor& t, int rows) { add(t.p, (size_t)rows * t.C * t.T); }
+  void flush() {
+    if (n) r.launch("replicate rows", [&] { return launch_replicate_rows(tab, n, E, r.st); });
+    n = 0;
+  }
+};
+// What the score passes read per row of a conditioner that ran over the first `rows` rows only -> the rows of the other members.
+// `with_stats`: the input statistics the post step reads per member row (a call whose post step works on whole long rows keeps
+// them elsewhere); `with_wav`: the decoupling layer's output (warm start).
+void replicate_conditioned(Runner& r, Persist& P, int rows, int E, bool with_stats, bool with_wav) {
+  Replicator rep(r, E);
+  for (size_t j = 0; j < P.cond.size(); j++) { rep.add(P.cond[j], rows); rep.add(P.sc[j], rows); }
+  rep.add(P.aux, rows);
+  rep.add(P.latent, rows);
+  rep.add(P.mixn, rows);
+  if (with_stats) rep.add(P.stats, (size_t)rows * 4);
+  rep.add(P.mel_scale, (size_t)rows);
+  if (with_wav) rep.add(P.wav, rows);
+  rep.flush();
+}
+
 // ou_enhance_ensemble: the shared pieces as ONE chain on the caller's stream for the E * B member rows.  Its own: the area
 // behind the persistent block, the conditioner (and, for a warm start, the decoupling layer) run once over the B inputs on a
 // second runner and replicated -- ens_share = 0: run over all E * B rows --, the post step per member row and the reduce.
@@ -1687,10 +1711,6 @@ int ensemble_impl(ou_handle* h, const float* mix, float* out, float* members_out
   const SamplerTables tab(m.cfg, n_steps, epsilon, sigma_host);
   tab.upload_coef(r, P);
 
-  Runner rc(h, ws, ws_bytes, false, st, Bc);  // the conditioner's runner: Bc rows on the prefix of the persistent tensors
-  rc.status_words = r.status_words;
-  rc.block3_bar = r.block3_bar;
-  rc.gru_area_rows = EB;
   std::vector<int32_t> t_rep;  // member-major lengths: row e * B + b has t_raw[b]
   if (t_raw) {
     t_rep.resize(EB);
@@ -1700,59 +1720,31 @@ int ensemble_impl(ou_handle* h, const float* mix, float* out, float* members_out
     // E copies of the per-row geometry for the sampler loop; the length table is [level][rows], so the conditioner's B-row pass
     // gets a table of its own ([level][B]; the RowInfo entries of rows 0 .. B - 1 serve both)
     upload_row_lengths(r, P.rows, P.lens, t_rep.data(), EB);
-    r.ragged = true;
-    r.lens_dev = P.lens;
-    r.rows_dev = P.rows;
-    rc.ragged = true;
-    rc.rows_dev = P.rows;
-    rc.lv = r.lv;
-    for (int l = 0; l < kMaxLenLevels; l++) rc.level_T[l] = r.level_T[l];
+    r.set_ragged(P.lens, P.rows);
     // (its RowInfo output goes to rows 0 .. B - 1 of P.rows once more: the same values)
     if (share) upload_row_lengths(r, P.rows, lens_b, t_raw, B);
-    rc.lens_dev = share ? lens_b : P.lens;
   }
   tab.upload_film(r, P);
 
   // ---- pad + normalise the B inputs (one workgroup per row: what the replicated batch would give, bit for bit)
   normalize(r, P, mix, B, T_raw, T);
-  // Replication: rows [0, B) of a tensor laid out for E * B rows -> rows [e B, (e + 1) B), up to 16 tensors per launch
-  ReplicateTable tab_rep;
-  int n_tab = 0;
-  auto flush_tab = [&]() {
-    if (n_tab && r.ok()) r.chk(launch_replicate_rows(tab_rep, n_tab, E, st), "replicate rows");
-    n_tab = 0;
-  };
-  auto replicate = [&](void* p, size_t words_per_b_rows) {
-    if (E == 1) return;
-    if (n_tab == kReplicateEntries) flush_tab();
-    tab_rep.p[n_tab] = (unsigned*)p;
-    tab_rep.n[n_tab] = (long long)words_per_b_rows;
-    n_tab++;
-  };
-  auto replicate_t = [&](const Tensor& t) { replicate(t.p, (size_t)B * t.C * t.T); };
-  if (!share) {  // the conditioner runs over all member rows: only its input is replicated
-    replicate_t(P.mixn);
-    replicate(P.stats, (size_t)B * 4);
-    flush_tab();
+  if (!share && E > 1) {  // the conditioner runs over all member rows: only its input is replicated
+    Replicator rep(r, E);
+    rep.add(P.mixn, B);
+    rep.add(P.stats, (size_t)B * 4);
+    rep.flush();
   }
 
-  // ---- conditioner (+ decoupling layer for a warm start) over Bc rows
-  rc.off = r.off;
+  // ---- conditioner (+ decoupling layer for a warm start) over Bc rows, on a runner of its own (ragged: with its own [level][B]
+  // length table when it runs B of the E * B rows; the RowInfo entries of rows 0 .. B - 1 serve both)
+  Runner rc = Runner::conditioner_of(r, Bc);
+  if (r.ragged) rc.set_ragged(share ? lens_b : P.lens, P.rows);
   run_condition(rc, P, P.mixn.p, T);
   h->cond_B = 0;  // (the operator seams ou_score / ou_aux_to_wav do not take this layout)
   h->cond_T = T;
   if (need_wav) decouple(rc, P);
   if (!rc.ok()) return finish(h, rc);
-  if (share) {
-    for (size_t j = 0; j < P.cond.size(); j++) { replicate_t(P.cond[j]); replicate_t(P.sc[j]); }
-    replicate_t(P.aux);
-    replicate_t(P.latent);
-    replicate_t(P.mixn);
-    replicate(P.stats, (size_t)B * 4);
-    replicate(P.mel_scale, (size_t)B);
-    if (need_wav) replicate_t(P.wav);
-    flush_tab();
-  }
+  if (share) replicate_conditioned(r, P, B, E, true, need_wav);
 
   // ---- the sampler loop at E * B rows
   r.off = rc.off;
@@ -1765,10 +1757,10 @@ int ensemble_impl(ou_handle* h, const float* mix, float* out, float* members_out
   // ---- reduce over the members
   std::vector<long long> len64;
   if (t_raw) len64.assign(t_raw, t_raw + B);
-  if (r.ok()) {
-    r.chk(launch_ensemble_reduce(members, out, E, B, T_raw, T_raw, t_raw ? len64.data() : nullptr, stat, hist, hist + (size_t)B * E,
-                                 st), "ensemble reduce");
-  }
+  r.launch("ensemble reduce", [&] {
+    return launch_ensemble_reduce(members, out, E, B, T_raw, T_raw, t_raw ? len64.data() : nullptr, stat, hist, hist + (size_t)B * E,
+                                  st);
+  });
   return finish(h, r);
 }
 }  // namespace
@@ -2020,9 +2012,10 @@ auto seg_noise(ou_handle* h, Runner& r, const float* noise, size_t step_noise, f
 }
 // every member's last real window of the group -> `carry` (E, T): the window in front of the next group
 void seg_carry(Runner& r, float* carry, const float* x, int T, int Bw, int E, int n_real) {
-  for (int e = 0; e < E && r.ok(); e++)
-    r.chk(hipMemcpyAsync(carry + (size_t)e * T, x + ((size_t)e * Bw + n_real - 1) * T, (size_t)T * 4, hipMemcpyDeviceToDevice, r.st),
-          "carry");
+  for (int e = 0; e < E; e++)
+    r.launch("carry", [&] {
+      return hipMemcpyAsync(carry + (size_t)e * T, x + ((size_t)e * Bw + n_real - 1) * T, (size_t)T * 4, hipMemcpyDeviceToDevice, r.st);
+    });
 }
 // after the last group: what the operator seams see, and the post step over the E * C long rows
 template <class Rows>
@@ -2068,49 +2061,27 @@ int seg_enhance(ou_handle* h, const char* who, const char* sizer, const float* m
     const int n_real = (int)std::min<long long>(Bw, g.n_entries - e0);
     const SegEntriesArith ents{e0, g.n_entries, g.n_win, g.L, g.hop, g.overlap};
     Runner r(h, ws, w.walk, false, st, B);
+    r.mel_scale_preset = true;
     Persist P = layout_persist(r, L);
     if (r.oom) return finish(h, r);
     if (e0 == 0) tab.upload(r, P);  // (the persistent area of the workspace keeps the tables from group to group)
-    // the conditioner's runner: Bc rows on the prefix of the persistent tensors (ensemble_impl)
-    Runner rc(h, ws, w.walk, false, st, Bc);
-    rc.mel_scale_preset = true;
-    rc.status_words = r.status_words;
-    rc.block3_bar = r.block3_bar;
-    rc.gru_area_rows = B;
-    rc.off = r.off;
+    Runner rc = Runner::conditioner_of(r, Bc);
     // the group's inputs: once into the prefix, or -- the conditioner over all rows -- once per member
     for (int e = 0; e < (share ? 1 : E); e++)
-      rc.chk(launch_seg_gather_input(mix, w.stats, w.row_scale, P.mixn.p + (size_t)e * Bw * L, P.mel_scale + (size_t)e * Bw, rows,
-                                     ents, Bw, L, st), "segment gather");
+      rc.launch("segment gather", [&] {
+        return launch_seg_gather_input(mix, w.stats, w.row_scale, P.mixn.p + (size_t)e * Bw * L, P.mel_scale + (size_t)e * Bw, rows,
+                                       ents, Bw, L, st);
+      });
     run_condition(rc, P, P.mixn.p, L);
-    if (share && rc.ok()) {  // what the score passes read per row: rows [0, Bw) -> the rows of the other members
-      ReplicateTable rep;
-      int n_rep = 0;
-      auto flush_rep = [&]() {
-        if (n_rep && rc.ok()) rc.chk(launch_replicate_rows(rep, n_rep, E, st), "replicate rows");
-        n_rep = 0;
-      };
-      auto replicate = [&](void* p, size_t words) {
-        if (n_rep == kReplicateEntries) flush_rep();
-        rep.p[n_rep] = (unsigned*)p;
-        rep.n[n_rep] = (long long)words;
-        n_rep++;
-      };
-      auto replicate_t = [&](const Tensor& t) { replicate(t.p, (size_t)Bw * t.C * t.T); };
-      for (size_t j = 0; j < P.cond.size(); j++) { replicate_t(P.cond[j]); replicate_t(P.sc[j]); }
-      replicate_t(P.aux);
-      replicate_t(P.latent);
-      replicate_t(P.mixn);
-      replicate(P.mel_scale, (size_t)Bw);
-      flush_rep();
-    }
+    // (the statistics of the post step are those of the whole long rows, w.stats: P.stats is not written; no warm start)
+    if (share) replicate_conditioned(rc, P, Bw, E, false, false);
     if (const int rc2 = finish(h, rc)) return rc2;
     r.off = rc.off;
     // walk row e * Bw + j: window k of long row e * C + c, positions s_k + i of that row's noise.  The filler rows of a short
     // last group repeat their member's last real entry.
     auto z = seg_noise(h, r, noise, (size_t)E * C * g.T_pad, w.zbuf, L, B,
                        [&](const float* slice) {
-                         if (r.ok()) r.chk(launch_seg_gather_noise(slice, w.zbuf, rows, ents, Bw, L, Bw, E, C, st), "segment noise");
+                         r.launch("segment noise", [&] { return launch_seg_gather_noise(slice, w.zbuf, rows, ents, Bw, L, Bw, E, C, st); });
                        },
                        [&](int row, long long& stream_row, long long& t0, long long& len) {
                          const int e = row / Bw;
@@ -2120,7 +2091,7 @@ int seg_enhance(ou_handle* h, const char* who, const char* sizer, const float* m
                          len = L;
                        });
     sample(r, P, L, tab, 0, nullptr, false, z);
-    if (r.ok()) r.chk(launch_seg_stitch(P.x.p, w.carry, members, rows, ents, n_real, L, Bw, E, C, st), "segment stitch");
+    r.launch("segment stitch", [&] { return launch_seg_stitch(P.x.p, w.carry, members, rows, ents, n_real, L, Bw, E, C, st); });
     if (e0 + Bw < g.n_entries) seg_carry(r, w.carry, P.x.p, L, Bw, E, n_real);
     if (const int rc2 = finish(h, r)) return rc2;
   }
@@ -2340,20 +2311,21 @@ int ou_enhance_segments_var(ou_handle* h, const float* mix, float* out, const fl
       // length is the level-0 length itself)
       if (const int rc = set_levels(r, T)) return rc;
       for_blocks(B, [&](const SegEntriesList& ents, int n) {
-        r.chk(launch_seg_upload_lens(P.lens, ents.blk, n, ents.j0, B, r.lv, st), "segment lens");
+        r.launch("segment lens", [&] { return launch_seg_upload_lens(P.lens, ents.blk, n, ents.j0, B, r.lv, st); });
       });
-      r.ragged = true;
-      r.lens_dev = P.lens;
+      r.set_ragged(P.lens, nullptr);  // (no RowInfo: the windows are gathered and stitched by their entries)
     }
     for_blocks(B, [&](const SegEntriesList& ents, int n) {
-      r.chk(launch_seg_gather_input(mix, w.stats, w.row_scale, P.mixn.p, P.mel_scale, rows, ents, n, T, st), "segment gather");
+      r.launch("segment gather", [&] {
+        return launch_seg_gather_input(mix, w.stats, w.row_scale, P.mixn.p, P.mel_scale, rows, ents, n, T, st);
+      });
     });
     run_condition(r, P, P.mixn.p, T);
     // walk row j: window k of row c, positions s_k + i of that row's noise
     auto z = seg_noise(h, r, noise, (size_t)C * T_pad_max, w.zbuf, T, B,
                        [&](const float* slice) {
                          for_blocks(B, [&](const SegEntriesList& ents, int n) {
-                           if (r.ok()) r.chk(launch_seg_gather_noise(slice, w.zbuf, rows, ents, n, T, B, 1, C, st), "segment noise");
+                           r.launch("segment noise", [&] { return launch_seg_gather_noise(slice, w.zbuf, rows, ents, n, T, B, 1, C, st); });
                          });
                        },
                        [&](int j, long long& stream_row, long long& t0, long long& len) {
@@ -2363,10 +2335,9 @@ int ou_enhance_segments_var(ou_handle* h, const float* mix, float* out, const fl
                          len = e.len;
                        });
     sample(r, P, T, tab, 0, nullptr, false, z);
-    if (r.ok())
-      for_blocks(n_real, [&](const SegEntriesList& ents, int n) {
-        r.chk(launch_seg_stitch(P.x.p, w.carry, out, rows, ents, n, T, B, 1, C, st), "segment stitch");
-      });
+    for_blocks(n_real, [&](const SegEntriesList& ents, int n) {
+      r.launch("segment stitch", [&] { return launch_seg_stitch(P.x.p, w.carry, out, rows, ents, n, T, B, 1, C, st); });
+    });
     if (full && e_end < G.n_full) seg_carry(r, w.carry, P.x.p, T, B, 1, n_real);  // the window in front of the next group
     if (const int rc = finish(h, r)) return rc;
   }
@@ -2427,7 +2398,7 @@ int ou_workspace_init(ou_handle* h, int32_t B, int32_t T, void* ws, size_t ws_by
   if (r.oom) return finish(h, r);
   // header: status word, coefficient rows, statistics, both GRU exchange areas (everything in front of mel_scale)
   const size_t hdr = (size_t)((char*)P.mel_scale - (char*)ws);
-  r.chk(hipMemsetAsync(ws, 0, hdr, r.st), "workspace init");
+  r.launch("workspace init", [&] { return hipMemsetAsync(ws, 0, hdr, r.st); });
   const int rc = finish(h, r);
   if (rc == OU_OK) {
     // remember (pointer, size, shape); a buffer that comes back at the same address is re-registered by its own init
@@ -2737,14 +2708,14 @@ int ou_bench_conv(ou_handle* h, const char* layer, int32_t B, int32_t Tin, int32
   r.alloc_raw(64);
   Tensor in = r.alloc("", L->Cin, Tin);
   if (r.oom) return finish(h, r);
-  r.chk(hipMemsetAsync(in.p, 0x3c, (size_t)B * L->Cin * Tin * 4, st), "fill");
+  r.launch("fill", [&] { return hipMemsetAsync(in.p, 0x3c, (size_t)B * L->Cin * Tin * 4, st); });
   h->force_cfg = cfg; h->force_sc = sc < 0 ? 0 : sc;
   if (h->opt.ts) h->tstamps = (long long*)((char*)ws + ws_bytes - (16u << 20));
   hipEvent_t e0, e1;
   (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
   size_t mark = r.off;
   Runner::Epi e;
-  Tensor out = r.conv(*L, in, "", e);  // warm-up + output allocation
+  Tensor out = r.conv(*L, in, "", e).out;  // warm-up + output allocation
   if (with_res) e.res = out.p;
   for (int w = 0; w < 2 && r.ok(); w++) { r.off = mark; r.conv(*L, in, "", e); }
   (void)hipEventRecord(e0, st);

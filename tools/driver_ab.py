@@ -10,7 +10,9 @@ generators, `pad_batch`, the `ensemble=` glue of `enhance`, noise handed over as
 tool also compares two versions of the Python front end on ONE library (the second use below).  The segmented entry points are
 also called on edge shapes:
 rows of 1, 2, 3 and 5 samples, of tot_ds + 1, 16 tot_ds + 2 and 33 tot_ds + 3, so that the longest row is 1, 2 and 3 past a
-multiple of 4 -- the word-by-word head and tail of the 16-byte row moves and the guards of rows shorter than a quad.  Run it
+multiple of 4 -- the word-by-word head and tail of the 16-byte row moves and the guards of rows shorter than a quad.  The `opt.*`
+calls repeat the batch-1, the ragged and the two-row call with one option off its default each, for the branches of the network
+walk that the defaults never take, and one `layout` line per model holds workspace sizes and tensor offsets.  Run it
 once per library and compare the files byte for byte:
 
     OU_LIBRARY=/path/to/parent/libouniverse.so timeout -k 10 600 python tools/driver_ab.py --out parent.json
@@ -158,6 +160,42 @@ def calls(model, spec):
             mix, 3, n_steps=N, rng=g[0], return_members=True)
     yield "py.enhance_long_many.shared", [125], lambda g: model.enhance_long_many(six, g[0], **seg)
 
+    # the branches of the network walk (Runner::conv / block in ou_api.cpp) that the default options never take: one option off
+    # its default per call, reset afterwards
+    def with_option(key, value, fn):
+        default = model.get_option(key)
+        model.set_option(key, value)
+        try:
+            return fn()
+        finally:
+            model.set_option(key, default)
+    walk = [("rate_small", 0), ("fuse_upfir", 0), ("preact", 0)] + [("fuse", v) for v in (0, 2, 3)]
+    walk += [("conv_direct", v) for v in range(5)] + [("wino", 0), ("split", 1), ("no_overlap", 1)]
+    for key, value in walk:
+        yield f"opt.{key}{value}.enhance.b1", [11], lambda g, k=key, v=value: with_option(
+            k, v, lambda: model.enhance(one, n_steps=N, rng=g[0]))
+        yield f"opt.{key}{value}.enhance_many.ragged.tensor", three, lambda g, k=key, v=value: with_option(
+            k, v, lambda: model.enhance_many(ragged, g, n_steps=N))
+    yield "opt.mask_fused0.enhance_many.ragged.tensor", three, lambda g: with_option(
+        "mask_fused", 0, lambda: model.enhance_many(ragged, g, n_steps=N))
+    # (rows 0 .. 3 of `six`: the windows of the long row, then the three short rows as one group of different lengths)
+    yield "opt.mask_fused0.enhance_long_many.ragged_group", many6[:4], lambda g: with_option(
+        "mask_fused", 0, lambda: model.enhance_long_many(six[:4], g, **seg))
+    yield "opt.gru_bmax1.enhance.b2", [130], lambda g: with_option("gru_bmax", 1, lambda: model.enhance(two, n_steps=N, rng=g[0]))
+
+
+def layout(model, spec):
+    """The workspace layout of a model as one record: ou_workspace_bytes at three shapes, and where `Universe.tensor` finds
+    seven tensors of the walk after `enhance.b1` -- (byte offset into the workspace, C, T) each."""
+    td = spec.tot_ds
+    model.enhance(synth_mix(spec, 1, 23 * td + 5, seed=1500)[0].cuda(), n_steps=N, rng=gen(11))
+    torch.cuda.synchronize()
+    where = {}
+    for name in ("mixn", "x", "cond.aux", "cond.latent", "cond.enc0.c1", "score.dec0.v", "score.gru"):
+        t = model.tensor(name)
+        where[name] = [t.data_ptr() - model._ws.data_ptr(), t.shape[1], t.shape[2]]
+    return {"workspace_bytes": [model._workspace_bytes(B, n * td) for B, n in ((1, 23), (2, 19), (3, 41))], "tensors": where}
+
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
@@ -175,6 +213,8 @@ def main():
             lines.append(json.dumps({"call": f"{name}.{call}", "launches": launches, "convs": convs, "sha256": digest(out),
                                      "rng": rng_digest(gens)}))
             print(lines[-1], flush=True)
+        lines.append(json.dumps({"call": f"{name}.layout", **layout(model, spec)}))
+        print(lines[-1], flush=True)
     if args.out:
         with open(args.out, "w") as f:
             f.write("\n".join(lines) + "\n")
