@@ -710,7 +710,9 @@ Persist layout_persist(Runner& r, int T) {
   P.xchg2 = (unsigned long long*)r.alloc_raw(gru_granules(r.B, m.OC / 2) * 2);
   r.h->tensors["mel_scale"] = TensorRef{r.off, 1, 1};  // (B, 1, 1): the conditioner's mel normalisation of each row
   P.mel_scale = r.alloc_raw(r.B);
+  r.h->tensors["sigma.g"] = TensorRef{r.off, m.film.D, 1};  // (B, D, 1): the noise-level embedding of the first B coefficient rows
   P.g = r.alloc_raw((size_t)ncoef * m.film.D);
+  r.h->tensors["sigma.film"] = TensorRef{r.off, m.film.rows, 1};  // (B, rows, 1): their FiLM rows (gamma, beta per block)
   P.film = r.alloc_raw((size_t)ncoef * m.film.rows);
   P.mixn = r.alloc("mixn", 1, T);
   P.x = r.alloc("x", 1, T);
