@@ -276,11 +276,15 @@ __global__ __launch_bounds__(64 * NWV) void conv_chain_kernel(ChainArgs p, int T
 //   conv1 (k5, F(2, 5)) -> (+cond)/sqrt2 -> FiLM -> conv2 (k3, F(2, 3)) -> conv3 (k3) -> (+h)/sqrt2      (blocks.py:377-399)
 // conv_chain_kernel spends 55 % of a block's life in its MFMA phases (two waves per SIMD, 84 % of the pipe there) and the rest
 // staging, in epilogues and at one barrier per weight slot (tools/chain_ts.py: 27 k of 48.5 k cycles).  Here:
-//   * F(2, KW) (see conv_direct2w_kernel): a wave owns 32 rows x 32 tile positions = 64 columns of every stage; per channel
-//     pair KW + 1 MFMAs on independent accumulators instead of 2 KW -- 224 MFMAs per wave and block instead of 352;
+//   * F(2, KW) (see conv_direct2w_kernel): a wave owns 32 rows x 16 tile positions = 32 columns of every stage as two 16-row
+//     tiles of v_mfma_f32_16x16x4_f32; per group of FOUR channels 2 (KW + 1) MFMAs of 32 cycles on independent accumulators
+//     (lane = (k = lane / 16, row or position = lane % 16) for the operands, rows 4 k .. 4 k + 3 of its position for the results);
 //   * ALL weights of the three convs sit in LDS in the Winograd domain for the whole block (C = 32: 24 + 16 + 16 KB, loaded
 //     once beside the input tile): no slot ring, no per-slot barrier -- three barriers per block in all;
-//   * four waves, one per SIMD, 256 columns per block (252 finished: the halo of 2 + 1 + 1 is recomputed, as before);
+//   * EIGHT waves, two per SIMD (waves w and w + 4), 256 columns per block (252 finished: the halo of 2 + 1 + 1 is recomputed,
+//     as before).  One block per CU (123 / 99 KB of LDS), so the second wave of a SIMD is what fills the first one's LDS latencies,
+//     epilogue waits and store drain: with four waves of 32 x 32 positions the pipe was busy for 40 % of a block (36 k cycles,
+//     now 31 k).  The two waves are not held in step -- no barrier beyond the three.  <= 256 VGPRs per wave (194 / 181);
 //     operands come from LDS with 16- / 8-byte reads (A: the KW + 1 values U_x of (channel, row) are adjacent; B: the window of
 //     a tile position starts at an even column of the activation tile, whatever the stage -- stage s writes its output u
 //     where stage s + 1 reads input u), ~3-5 LDS instructions per 4-6 MFMAs;
@@ -290,13 +294,13 @@ __global__ __launch_bounds__(64 * NWV) void conv_chain_kernel(ChainArgs p, int T
 // =========================================================================================================
 // MT: 32-row tiles (C = 32 MT).  D3: depth 3 = conv1 (k5), conv2, conv3 (k3); else depth 2 = conv2, conv3 (conv1 was a launch of
 // its own -- the 64-channel level: a depth-3 tile of 128 columns finishes 124 of them, 259 tiles for T = 32 080 on 256 CUs).
-//   C = 32, depth 3: four waves = four column groups of 64; all weights resident (U1a | U1b | U2 | U3), two activation tiles.
-//   C = 64, depth 2: four waves = two row tiles x two column groups, 128 columns per block (126 finished); ONE weight region
+//   C = 32, depth 3: eight waves = eight column groups of 32; all weights resident (U1a | U1b | U2 | U3), two activation tiles.
+//   C = 64, depth 2: eight waves = two row tiles x four column groups, 128 columns per block (126 finished); ONE weight region
 //     (64 KB) that holds U2 during stage 0 and U3 -- parked in registers since kernel entry -- from the barrier behind it; one
 //     activation tile.
 template <int MT, bool D3>
-__global__ __launch_bounds__(256) void conv_chainw_kernel(ChainArgs p, int TN, int ntiles) {
-  constexpr int C = 32 * MT, NW = 4, NWN = NW / MT, NC = 64 * NWN, XS = NC + 8, NTH = 64 * NW, NS = D3 ? 3 : 2;
+__global__ __launch_bounds__(512) void conv_chainw_kernel(ChainArgs p, int TN, int ntiles) {
+  constexpr int C = 32 * MT, NW = 8, NWN = NW / MT, NC = 32 * NWN, XS = NC + 8, NTH = 64 * NW, NS = D3 ? 3 : 2;
   constexpr int WI = C * C / NTH;  // (ci, m) items per thread and conv
   static_assert(!D3 || MT == 1, "depth 3: the 32-channel level");
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -311,7 +315,7 @@ __global__ __launch_bounds__(256) void conv_chainw_kernel(ChainArgs p, int TN, i
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave % MT, wn = wave / MT;
-  const int lhalf = lane >> 5, l31 = lane & 31;
+  const int lk = lane >> 4, l15 = lane & 15;  // operands: channel lk of a group of four, row / position l15; results: rows 4 lk ..
   const int tile = blockIdx.x % ntiles, b = blockIdx.x / ntiles;
   const int T = p.T, Mp = p.Mp;
   // ragged batch: every stage's tile is zero from the row's own end on (what 'same' padding is for a row alone); x, add and res
@@ -343,26 +347,26 @@ __global__ __launch_bounds__(256) void conv_chainw_kernel(ChainArgs p, int TN, i
       wa[k] = *reinterpret_cast<const f32x4*>(p.cv[0].wu + ((size_t)ci * Mp + m) * 4);
     }
   }
-  // ---- stage 0's B operands come STRAIGHT FROM GLOBAL MEMORY into registers (as in conv_direct2w_kernel): lane (position, half)
-  // loads the KW + 1 samples of its window of channel 2 I + half for all C / 2 channel pairs, issued here, consumed in order by
+  // ---- stage 0's B operands come STRAIGHT FROM GLOBAL MEMORY into registers (as in conv_direct2w_kernel): lane (position, k)
+  // loads the KW + 1 samples of its window of channel 4 I + k for all C / 4 channel groups, issued here, consumed in order by
   // the stage-0 loop -- the first conv starts as soon as the first rows and its weights are there instead of after the whole
   // input tile has been staged through LDS and a barrier (7 k + 2 k of 42 k cycles per block in the first version).
-  const int pcol = 64 * wn + 2 * l31;     // this lane's tile position: outputs u = pcol, pcol + 1 of every stage
+  const int pcol = 32 * wn + 2 * l15;     // this lane's tile position: outputs u = pcol, pcol + 1 of every stage
   const int tw = t0 - R0 - PAD0 + pcol;   // time of window element 0 (even)
   const int sh = tw < 0 ? -tw : 0;        // samples cut off in front of the row (first tile: 4 / 2)
   unsigned wmask = 0;                     // bit i: window element i is inside the signal
 #pragma unroll
   for (int i = 0; i <= KW0; i++) wmask |= (tw + i >= 0 && tw + i < T) ? (1u << i) : 0u;
   const bool edge = __builtin_amdgcn_readfirstlane((t0 - R0 - PAD0 < 0 || t0 - R0 - PAD0 + NC + KW0 - 1 > T) ? 1 : 0) != 0;
-  f32x4 gw4[C / 2];
-  f32x2 gw2[D3 ? C / 2 : 1];
+  f32x4 gw4[C / 4];
+  f32x2 gw2[D3 ? C / 4 : 1];
   {
     const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x + rowbase, plane);
-    const int wvo = wmask ? (lhalf * T + tw + sh) * 4 : (int)0x80000000;  // (windows wholly outside: out of range, reads 0)
+    const int wvo = wmask ? (lk * T + tw + sh) * 4 : (int)0x80000000;  // (windows wholly outside: out of range, reads 0)
 #pragma unroll
-    for (int I = 0; I < C / 2; I++) {
-      gw4[I] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, wvo, 2 * I * Tb, 0));
-      if constexpr (D3) gw2[I] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rx, wvo + 16, 2 * I * Tb, 0));
+    for (int I = 0; I < C / 4; I++) {
+      gw4[I] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, wvo, 4 * I * Tb, 0));
+      if constexpr (D3) gw2[I] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rx, wvo + 16, 4 * I * Tb, 0));
     }
   }
   if constexpr (!D3) {  // the second conv's weights: parked in registers until the weight region is free (behind stage 0)
@@ -393,7 +397,7 @@ __global__ __launch_bounds__(256) void conv_chainw_kernel(ChainArgs p, int TN, i
   __syncthreads();
   if (ts_on) tsv[2] = __builtin_readcyclecounter();
 
-  const int lrow = 32 * wm + 4 * lhalf;   // lane part of the accumulator row: row(r) = lrow + (r & 3) + 8 (r >> 2)
+  const int lrow = 32 * wm + 4 * lk;      // lane part of the accumulator row: row(r) = lrow + (r & 3) + 16 (r >> 2)
 
   auto run_stage = [&](auto SC) {
     constexpr int s = decltype(SC)::value;
@@ -408,41 +412,44 @@ __global__ __launch_bounds__(256) void conv_chainw_kernel(ChainArgs p, int TN, i
     const bool in0 = t >= 0 && t < Tl, in1 = t + 1 >= 0 && t + 1 < Tl;   // live samples of this row
     const bool on0 = t >= 0 && t < T, on1 = t + 1 >= 0 && t + 1 < T;     // samples of the tensor
     // epilogue operand (cond add of conv1 / residual of the last conv), requested before the channel loop
-    f32x2 ev[16];
+    f32x2 ev[8];
     const float* src = last ? p.res : (first3 ? p.add : nullptr);
     if (src) {
       const __amdgpu_buffer_rsrc_t rs = make_rsrc(src + rowbase, plane);
       const int vo = (on0 || on1) ? (lrow * T + t) * 4 : (int)0x80000000;  // (t even, T even: whole pairs inside or outside)
 #pragma unroll
-      for (int r = 0; r < 16; r++)
-        ev[r] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rs, vo, ((r & 3) + 8 * (r >> 2)) * Tb, 0));
+      for (int r = 0; r < 8; r++)
+        ev[r] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rs, vo, ((r & 3) + 16 * (r >> 2)) * Tb, 0));
     }
-    floatx16 acc[NX];
+    f32x4 acc[2][NX];  // [row tile][U_x]
 #pragma unroll
-    for (int x = 0; x < NX; x++)
+    for (int rt = 0; rt < 2; rt++)
 #pragma unroll
-      for (int r = 0; r < 16; r++) acc[x][r] = 0.f;
-    const float* ap = Ua + (lhalf * C + 32 * wm + l31) * 4;  // U_0..3 of (ci = half, m); + 2 I C 4 per channel pair
-    const float* ap2 = Ub0 + (lhalf * C + 32 * wm + l31) * 2;
-    const float* bp = inb + lhalf * XS + pcol;               // window of (ci = half, position); + 2 I XS per channel pair
-    // ONE wave per SIMD: nothing but this wave's own instruction stream can fill the matrix pipe's 64 cycles per MFMA.  The
-    // loop is software-pipelined by hand -- the MFMAs of channel pair I are interleaved with B^T of pair I + 1 and with the LDS
-    // reads of pair I + 4 -- and the interleaving is pinned with sched_group_barrier (one MFMA, then a few VALU / one LDS
+      for (int x = 0; x < NX; x++) acc[rt][x] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const float* ap = Ua + (lk * C + 32 * wm + l15) * 4;   // U_0..3 of (ci = k, m); + 16 * 4 for row tile 1, + 4 I C 4 per channel group
+    const float* ap2 = Ub0 + (lk * C + 32 * wm + l15) * 2;
+    const float* bp = inb + lk * XS + pcol;                // window of (ci = k, position); + 4 I XS per channel group
+    // The loop is software-pipelined by hand -- the MFMAs of channel group I are interleaved with B^T of group I + 1 and with the
+    // LDS reads of group I + 4 -- and the interleaving is pinned with sched_group_barrier (one MFMA, then a few VALU / one LDS
     // read), or the scheduler clusters the MFMAs and the wave sits in their issue queue with the transform still to do.
-    struct Ops { f32x4 a4; f32x2 a2, d01, d23; };
+    struct Ops { f32x4 a4[2]; f32x2 a2[2], d01, d23; };
     auto fetch = [&](int I) {
       Ops o;
-      o.a4 = *reinterpret_cast<const f32x4*>(ap + I * (2 * C * 4));
-      o.a2 = f32x2{0.f, 0.f}; o.d01 = f32x2{0.f, 0.f}; o.d23 = f32x2{0.f, 0.f};
-      if constexpr (KW == 5) o.a2 = *reinterpret_cast<const f32x2*>(ap2 + I * (2 * C * 2));
+#pragma unroll
+      for (int rt = 0; rt < 2; rt++) {
+        o.a4[rt] = *reinterpret_cast<const f32x4*>(ap + I * (4 * C * 4) + rt * 64);
+        o.a2[rt] = f32x2{0.f, 0.f};
+        if constexpr (KW == 5) o.a2[rt] = *reinterpret_cast<const f32x2*>(ap2 + I * (4 * C * 2) + rt * 32);
+      }
+      o.d01 = f32x2{0.f, 0.f}; o.d23 = f32x2{0.f, 0.f};
       if constexpr (s > 0) {
-        const float* bq = bp + I * (2 * XS);
+        const float* bq = bp + I * (4 * XS);
         o.d01 = *reinterpret_cast<const f32x2*>(bq);
         o.d23 = *reinterpret_cast<const f32x2*>(bq + 2);
       }
       return o;
     };
-    // V = B^T d of channel pair I: later stages from the LDS tile (PReLU applied by the producer), stage 0 from the window
+    // V = B^T d of channel group I: later stages from the LDS tile (PReLU applied by the producer), stage 0 from the window
     // registers -- edge fix-up (first / last tile only: shift what was loaded from the row start, zero what is outside the
     // signal), then the first conv's PReLU
     auto transform = [&](const Ops& o, int I, float (&V)[NX]) {
@@ -468,9 +475,9 @@ __global__ __launch_bounds__(256) void conv_chainw_kernel(ChainArgs p, int TN, i
       }
       wino_bt<KW>(X, V);
     };
-    // (LDS read latency under four waves' traffic is ~300 cycles -- more than the 256 MFMA cycles of a k3 channel pair: with
-    // the reads one pair ahead the loop ran at 55 % of the pipe.  Ring of four pairs: reads three pairs ahead.)
-    constexpr int NP = C / 2, RD = 4;
+    // (LDS read latency under a block's traffic is ~300 cycles -- more than the 256 MFMA cycles of a k3 channel group: with
+    // the reads one group ahead the loop ran at 55 % of the pipe.  Ring of four groups: reads three groups ahead.)
+    constexpr int NP = C / 4, RD = 4;
     static_assert(NP % RD == 0, "ring");
     Ops ring[RD];
 #pragma unroll
@@ -483,16 +490,19 @@ __global__ __launch_bounds__(256) void conv_chainw_kernel(ChainArgs p, int TN, i
       for (int k = 0; k < RD; k++) {
         const int I = I0 + k;
         float Vn[NX];
-        transform(ring[(k + 1) % RD], I + 1 < NP ? I + 1 : NP - 1, Vn);   // pair I + 1
+        transform(ring[(k + 1) % RD], I + 1 < NP ? I + 1 : NP - 1, Vn);   // group I + 1
         const Ops cur = ring[k];
-        const float A[6] = {cur.a4.x, cur.a4.y, cur.a4.z, cur.a4.w, cur.a2.x, cur.a2.y};
 #pragma unroll
-        for (int x = 0; x < NX; x++) acc[x] = __builtin_amdgcn_mfma_f32_32x32x2f32(A[x], Vc[x], acc[x], 0, 0, 0);
-        ring[k] = fetch(I + RD < NP ? I + RD : NP - 1);     // pair I + 4 into the slot that has just been consumed
+        for (int rt = 0; rt < 2; rt++) {
+          const float A[6] = {cur.a4[rt].x, cur.a4[rt].y, cur.a4[rt].z, cur.a4[rt].w, cur.a2[rt].x, cur.a2[rt].y};
 #pragma unroll
-        for (int x = 0; x < NX; x++) {
+          for (int x = 0; x < NX; x++) acc[rt][x] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[x], Vc[x], acc[rt][x], 0, 0, 0);
+        }
+        ring[k] = fetch(I + RD < NP ? I + RD : NP - 1);     // group I + 4 into the slot that has just been consumed
+#pragma unroll
+        for (int x = 0; x < 2 * NX; x++) {
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);               // one MFMA
-          __builtin_amdgcn_sched_group_barrier(0x002, KW == 5 ? 6 : 2, 0);  // a slice of the next pair's transform
+          __builtin_amdgcn_sched_group_barrier(0x002, KW == 5 ? 3 : 1, 0);  // a slice of the next group's transform
           __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);               // one LDS read
         }
 #pragma unroll
@@ -501,13 +511,19 @@ __global__ __launch_bounds__(256) void conv_chainw_kernel(ChainArgs p, int TN, i
     }
     if (ts_on) tsv[3 + 2 * s] = __builtin_readcyclecounter();
     // A^T -> outputs u = pcol (o0), pcol + 1 (o1)
-    floatx16 o0, o1;
-    if constexpr (KW == 3) {
-      o0 = acc[0] + acc[1] + acc[2];
-      o1 = acc[1] - acc[2] - acc[3];
-    } else {
-      o0 = acc[0] + acc[1] + acc[2] + acc[3] + acc[4];
-      o1 = acc[1] - acc[2] + 0.5f * acc[3] - 2.0f * acc[4] + acc[5];
+    float o0[8], o1[8];
+#pragma unroll
+    for (int rt = 0; rt < 2; rt++) {
+      f32x4 q0, q1;
+      if constexpr (KW == 3) {
+        q0 = acc[rt][0] + acc[rt][1] + acc[rt][2];
+        q1 = acc[rt][1] - acc[rt][2] - acc[rt][3];
+      } else {
+        q0 = acc[rt][0] + acc[rt][1] + acc[rt][2] + acc[rt][3] + acc[rt][4];
+        q1 = acc[rt][1] - acc[rt][2] + 0.5f * acc[rt][3] - 2.0f * acc[rt][4] + acc[rt][5];
+      }
+#pragma unroll
+      for (int i = 0; i < 4; i++) { o0[4 * rt + i] = q0[i]; o1[4 * rt + i] = q1[i]; }
     }
     const float* bias_l = prm + s * C + lrow;
     if constexpr (!last) {
@@ -515,21 +531,21 @@ __global__ __launch_bounds__(256) void conv_chainw_kernel(ChainArgs p, int TN, i
       float* out_l = outb + lrow * XS + pcol;
       const __amdgpu_buffer_rsrc_t rc = make_rsrc((p.c1_out ? p.c1_out : p.y) + rowbase, plane);
       const bool own0 = on0 && t >= t0 && t < t0 + TN, own1 = on1 && t + 1 >= t0 && t + 1 < t0 + TN;
-      float v0[16], v1[16];
+      float v0[8], v1[8];
 #pragma unroll
-      for (int r = 0; r < 16; r++) {
-        const int kr = (r & 3) + 8 * (r >> 2);
+      for (int r = 0; r < 8; r++) {
+        const int kr = (r & 3) + 16 * (r >> 2);
         v0[r] = o0[r] + bias_l[kr]; v1[r] = o1[r] + bias_l[kr];
       }
       if constexpr (first3) {
         if (p.add) {
 #pragma unroll
-          for (int r = 0; r < 16; r++) { v0[r] = (v0[r] + ev[r].x) * p.add_scale; v1[r] = (v1[r] + ev[r].y) * p.add_scale; }
+          for (int r = 0; r < 8; r++) { v0[r] = (v0[r] + ev[r].x) * p.add_scale; v1[r] = (v1[r] + ev[r].y) * p.add_scale; }
         }
         if (p.film) {
 #pragma unroll
-          for (int r = 0; r < 16; r++) {
-            const int kr = (r & 3) + 8 * (r >> 2);
+          for (int r = 0; r < 8; r++) {
+            const int kr = (r & 3) + 16 * (r >> 2);
             const float ga = prm[3 * C + lrow + kr], be = prm[4 * C + lrow + kr];
             v0[r] = ga * v0[r] + be; v1[r] = ga * v1[r] + be;
           }
@@ -537,16 +553,16 @@ __global__ __launch_bounds__(256) void conv_chainw_kernel(ChainArgs p, int TN, i
         if (p.c1_out) {
           const int vo0 = own0 ? (lrow * T + t) * 4 : (int)0x80000000, vo1 = own1 ? (lrow * T + t + 1) * 4 : (int)0x80000000;
 #pragma unroll
-          for (int r = 0; r < 16; r++) {
-            const int kr = (r & 3) + 8 * (r >> 2);
+          for (int r = 0; r < 8; r++) {
+            const int kr = (r & 3) + 16 * (r >> 2);
             buf_store(in0 ? v0[r] : 0.f, rc, vo0, kr * Tb);
             buf_store(in1 ? v1[r] : 0.f, rc, vo1, kr * Tb);
           }
         }
       }
 #pragma unroll
-      for (int r = 0; r < 16; r++) {
-        const int kr = (r & 3) + 8 * (r >> 2);
+      for (int r = 0; r < 8; r++) {
+        const int kr = (r & 3) + 16 * (r >> 2);
         float a = in0 ? v0[r] : 0.f;  // the zero padding the next conv sees outside the signal
         float c = in1 ? v1[r] : 0.f;
         a = a >= 0.f ? a : an * a;
@@ -559,8 +575,8 @@ __global__ __launch_bounds__(256) void conv_chainw_kernel(ChainArgs p, int TN, i
       // (pairs are whole: t, T and TN are even; a store past the signal or the tile goes to an out-of-range offset = dropped)
       const int vo = (st0 && st1) ? (lrow * T + t) * 4 : (int)0x80000000;
 #pragma unroll
-      for (int r = 0; r < 16; r++) {
-        const int kr = (r & 3) + 8 * (r >> 2);
+      for (int r = 0; r < 8; r++) {
+        const int kr = (r & 3) + 16 * (r >> 2);
         float v0 = o0[r] + bias_l[kr], v1 = o1[r] + bias_l[kr];
         if (p.res) { v0 = (v0 + ev[r].x) * p.res_scale; v1 = (v1 + ev[r].y) * p.res_scale; }
         v0 = in0 ? v0 : 0.f; v1 = in1 ? v1 : 0.f;
@@ -656,11 +672,13 @@ static double chain_variant_cost(const ChainArgs& a, const ChainVariant& v, int 
 
 double chain_cost(const ChainArgs& a, int num_cu, int* nc_out) {
   if (!chain_shape_ok(a)) return -1.0;
-  if (const int kind = chainw_kind(a)) {  // one wave per SIMD, 224 / 256 MFMAs per wave at ~70 %, ~12 k cycles of everything else
+  // two waves per SIMD, 224 / 256 MFMA-equivalents of 64 cycles per SIMD; fitted to the phase stamps of both forms
+  // (tools/chainw_ts.py: 30.7 k / 33.1 k cycles per block): ~85 % of the pipe inside the loops, ~14 k cycles of everything else
+  if (const int kind = chainw_kind(a)) {
     const int TN = kind == 1 ? 252 : 126;
     const long blocks = (long)a.B * ((a.T + TN - 1) / TN);
     if (nc_out) *nc_out = kind == 1 ? 256 : 128;
-    return (double)((blocks + num_cu - 1) / num_cu) * ((kind == 1 ? 224 : 256) * 64.0 / 0.7 + 12000.0);
+    return (double)((blocks + num_cu - 1) / num_cu) * ((kind == 1 ? 224 : 256) * 64.0 / 0.85 + 14000.0);
   }
   if (a.lens) return -1.0;  // (only conv_chainw_kernel zeroes its stages behind a row's own end)
   double best = -1.0;
@@ -696,8 +714,8 @@ hipError_t launch_chain(const ChainArgs& a, int num_cu, hipStream_t st, int* var
   if (const int kind = chainw_kind(a)) {  // the minimal-filtering forms: 252 (C = 32, depth 3) / 126 (C = 64, depth 2) finished columns
     const int TN = kind == 1 ? 252 : 126, ntiles = (a.T + TN - 1) / TN;
     if (variant) *variant = 190 + a.depth;
-    if (kind == 1) hipLaunchKernelGGL((conv_chainw_kernel<1, true>), dim3(ntiles * a.B), dim3(256), kChainwSmem32, st, a, TN, ntiles);
-    else hipLaunchKernelGGL((conv_chainw_kernel<2, false>), dim3(ntiles * a.B), dim3(256), kChainwSmem64, st, a, TN, ntiles);
+    if (kind == 1) hipLaunchKernelGGL((conv_chainw_kernel<1, true>), dim3(ntiles * a.B), dim3(512), kChainwSmem32, st, a, TN, ntiles);
+    else hipLaunchKernelGGL((conv_chainw_kernel<2, false>), dim3(ntiles * a.B), dim3(512), kChainwSmem64, st, a, TN, ntiles);
     return hipGetLastError();
   }
   for (int i = 0; i < kNumChainVariants; i++) {

@@ -1,4 +1,5 @@
-"""Phase cycle counts of conv_chainw_kernel (OU_CHAIN_TS=<block name>), averaged over blocks and waves."""
+"""Phase cycle counts of conv_chainw_kernel (OU_CHAIN_TS=<block name>), averaged over blocks and waves.
+Usage: python tools/chainw_ts.py [block name] [blocks] [waves per block: 8; 4 for a library from before the two-waves-per-SIMD form]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "tests")):
@@ -9,7 +10,7 @@ from helpers import get_spec, synth_mix
 from open_universe_amd import Universe, state_dict as S, _lib
 from open_universe_amd.universe import Universe as _U; _U.steer_from_env = True  # tools only: OU_<OPTION>=v env vars -> ou_set_option
 name = sys.argv[1] if len(sys.argv) > 1 else "score.enc0"
-nblk, nw = int(sys.argv[2]) if len(sys.argv) > 2 else 255, 4
+nblk, nw = int(sys.argv[2]) if len(sys.argv) > 2 else 255, int(sys.argv[3]) if len(sys.argv) > 3 else 8
 os.environ["OU_CHAIN_TS"] = name
 spec = get_spec("PP16")
 model = Universe(spec, state_dict=S.synthetic_state_dict(spec, 0), device="cuda:0")
