@@ -350,6 +350,48 @@ int ou_enhance_segments_ensemble(ou_handle* h, const float* mix, float* out, flo
                                  int32_t n_steps, double epsilon, const float* sigma_host, int32_t warm_start, uint32_t flags,
                                  void* ws, size_t ws_bytes, ou_stream_t stream);
 
+/* ---- ensembles of segmented rows with lengths of their own (extension): ou_enhance_segments_ensemble for a batch in which every
+ * row has its own length, as ou_enhance_segments_var is to ou_enhance_segments.  Member e of row c is, by definition,
+ * ou_enhance_segments(C = 1, T_raw = t_raw[c]) of row c on that member's own noise: the row's own pad split, whole-row mean /
+ * gain / mix_rms and mel scale, crossfades only between the row's own consecutive windows, keep_rms with the mix_rms of row c and
+ * the peak guard over the member row's own samples.  out[c] is ou_ensemble_reduce over the E post-processed members of row c with
+ * len = t_raw[c].  Only the grouping is new.
+ *
+ * Everything is MEMBER-MAJOR: member row e * C + c.
+ *   mix, out : (C, T_raw_max) device, the ou_enhance_segments_var conventions: the rest of a mix row is ignored, the rest of an out
+ *              row is zeroed, and out holds the whole-row mel frame energies until the reduce writes it
+ *   members  : (E * C, T_raw_max) device, caller-owned and REQUIRED; every row is zeroed behind its own end
+ *   t_raw    : HOST, C lengths, 1 <= t_raw[c] <= T_raw_max = the longest
+ *   noise    : (n_steps, E * C, T_pad_max) device; member row e * C + c uses its first T_pad_c columns, window k reads the
+ *              positions s_k + i.  With a noise source: NULL, n_streams == E * C, stream e * C + c belongs to that member row.
+ *   stat     : as ou_enhance_ensemble;  flags, warm_start: as ou_enhance_segments.
+ *
+ * Groups.  Entries, classes (FULL, then SHORT), group boundaries and `ragged` marks are exactly those of ou_segment_groups(tot_ds,
+ * C, t_raw, segment, overlap, floor(max_batch / E)); with Bw that call's `batch`, the walk runs batch = E * Bw rows, walk row e *
+ * Bw + j = member e of the group's entry j.  A short last group repeats its last real entry per member (the filler of member e
+ * repeats member e's own window and noise and is never stitched); a ragged group runs the ragged walk, member rows repeating
+ * their entry's lengths; the window carried across a FULL group boundary is per member.  The conditioner runs ONCE over the Bw
+ * entries of a group, plain or ragged, and its results and mel scales are replicated to the other members' rows (option
+ * `ens_share`, default 1; 0: the input is gathered E times and the conditioner runs over all E * Bw rows -- the arithmetic of
+ * ou_enhance_segments_var on E stacked copies of the rows).  Members agree with the single-row calls to fp32 round-off, not bit
+ * for bit; E = 1 is ou_enhance_segments_var bit for bit, rows of one length are ou_enhance_segments_ensemble bit for bit.
+ *
+ * Workspace: ou_segments_var_ensemble_workspace_bytes returns batch = E * Bw and length = min(S, max T_pad_c); prepare the buffer
+ * with ou_workspace_init(h, batch, length, ..).  Behind the walk's workspace it holds what ou_segments_ensemble_workspace_bytes
+ * lists plus the per-row geometry table and the length table of a ragged group's conditioner pass.
+ * OU_EINVAL, decided on the host before anything is launched: E < 1, E > OU_MAX_ENSEMBLE, E > max_batch, E * C > 65535, an
+ * unknown stat, members == NULL, t_raw == NULL or a length outside [1, T_raw_max], warm_start >= 0, OU_ENH_USE_AUX_SIGNAL, a
+ * non-NULL `noise` while a source is set or none while no source is set, n_streams != E * C, a segment too long for one pass.
+ * OU_ENOMEM and the unprepared-workspace refusal as in ou_enhance_segments_var.  Everything is enqueued on `stream`: no
+ * allocation, no host synchronisation, no side streams, no float atomics; geometry and entries travel as kernel arguments
+ * (capturable). */
+int ou_segments_var_ensemble_workspace_bytes(const ou_handle* h, int32_t C, const int64_t* t_raw, int32_t segment, int32_t overlap,
+                                             int32_t max_batch, int32_t E, size_t* nbytes, int32_t* batch, int32_t* length);
+int ou_enhance_segments_var_ensemble(ou_handle* h, const float* mix, float* out, float* members, const float* noise, int32_t C,
+                                     int64_t T_raw_max, const int64_t* t_raw, int32_t E, int32_t stat, int32_t segment,
+                                     int32_t overlap, int32_t max_batch, int32_t n_steps, double epsilon, const float* sigma_host,
+                                     int32_t warm_start, uint32_t flags, void* ws, size_t ws_bytes, ou_stream_t stream);
+
 /* ---- counter-based sampler noise (extension; the reference draws its noise with torch.randn on the model's device) --------
  * By default every enhance entry point reads its noise from a tensor the caller has drawn.  With a noise SOURCE set on the
  * handle the library produces the noise itself, one step's (B, T) plane at a time, from a pure function

@@ -132,6 +132,10 @@ def load():
                                                        POINTER(i32)]),
         "ou_enhance_segments_ensemble": (i32, [vp, vp, vp, vp, vp, i32, c_int64, i32, i32, i32, i32, i32, i32, c_double,
                                                POINTER(c_float), i32, c_uint32, vp, sz, vp]),
+        "ou_segments_var_ensemble_workspace_bytes": (i32, [vp, i32, POINTER(c_int64), i32, i32, i32, i32, POINTER(sz),
+                                                           POINTER(i32), POINTER(i32)]),
+        "ou_enhance_segments_var_ensemble": (i32, [vp, vp, vp, vp, vp, i32, c_int64, POINTER(c_int64), i32, i32, i32, i32, i32,
+                                                   i32, c_double, POINTER(c_float), i32, c_uint32, vp, sz, vp]),
         "ou_set_noise_source": (i32, [vp, POINTER(NoiseSpec)]),
         "ou_noise_scratch_bytes": (i32, [vp, i32, i32, POINTER(sz)]),
         "ou_noise_fill": (i32, [vp, c_int64, c_int64, i32, POINTER(c_uint64), POINTER(c_int64), POINTER(c_int64), c_uint64,
@@ -188,6 +192,7 @@ EXPORTED_SYMBOLS = [
     "ou_segment_groups", "ou_segments_var_workspace_bytes", "ou_enhance_segments_var",
     "ou_ensemble_workspace_bytes", "ou_enhance_ensemble", "ou_ensemble_reduce_scratch_bytes", "ou_ensemble_reduce",
     "ou_segments_ensemble_workspace_bytes", "ou_enhance_segments_ensemble",
+    "ou_segments_var_ensemble_workspace_bytes", "ou_enhance_segments_var_ensemble",
     "ou_set_noise_source", "ou_noise_scratch_bytes", "ou_noise_fill",
     "ou_resample_plan", "ou_resample_table", "ou_resample_length", "ou_resample_tile", "ou_resample",
     "ou_set_option", "ou_get_option", "ou_reset_options", "ou_option_count", "ou_option_name", "ou_option_doc", "ou_option_default", "ou_plan_json",

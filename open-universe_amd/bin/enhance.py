@@ -120,6 +120,11 @@ def build_parser():
                         help="With --segment-seconds: enhance every file as an ensemble of this many samples, reduced with "
                              "--ensemble_stat (Universe.enhance_long_ensemble: the windows of all members share the window "
                              "groups and the conditioner runs once per window).  Not with --ensemble or --segment-files > 1")
+    parser.add_argument("--segment-ensemble-files", type=int, default=1,
+                        help="With --segment-seconds and --segment-ensemble E: enhance this many consecutive files of the sorted "
+                             "list in one call (Universe.enhance_long_many_ensemble: the windows of all files share the window "
+                             "groups, all E members of a window in one group; every file gets the noise and, to round-off, the "
+                             "result of the one-file-per-call loop).  Default 1: one file per call.  Not with --segment-files > 1")
     parser.add_argument("--pad-batch", action="store_true",
                         help="With --batch-size: files of different lengths are zero-padded to the longest WITHOUT a mask "
                              "(the reference's batch semantics: the padding changes every result)")
@@ -158,6 +163,14 @@ def check_segment_args(args, enhance_kwargs):
             raise ValueError("--segment-ensemble must be at least 1")
         if getattr(args, "segment_files", 1) > 1:
             raise ValueError("--segment-ensemble cannot be combined with --segment-files > 1 (one file per call)")
+    ens_files = getattr(args, "segment_ensemble_files", 1)
+    if ens_files != 1:
+        if ens_files < 1:
+            raise ValueError("--segment-ensemble-files must be at least 1")
+        if args.segment_seconds is None or seg_ens is None:
+            raise ValueError("--segment-ensemble-files needs --segment-seconds and --segment-ensemble")
+        if getattr(args, "segment_files", 1) > 1:
+            raise ValueError("--segment-ensemble-files cannot be combined with --segment-files > 1")
     if args.segment_seconds is None:
         if args.segment_overlap is not None:
             raise ValueError("--segment-overlap needs --segment-seconds")
@@ -360,6 +373,45 @@ def main(argv=None, model=None):
                 output_path = out_path(path)
                 save(output_path, enh.cpu(), fs)
                 done.append(output_path)
+        return done
+    if args.segment_seconds is not None and getattr(args, "segment_ensemble_files", 1) > 1:
+        # --segment-ensemble-files N: up to N consecutive files of one sample rate per enhance_long_many_ensemble call.  Every file
+        # gets the generator or counter source the serial loop below would hand it (the shared generator advances file by file
+        # inside the call, in input order).
+        ov = 1.0 if args.segment_overlap is None else args.segment_overlap
+        kw = {key: v for key, v in enhance_kwargs.items() if key in ("n_steps", "epsilon", "keep_rms") and v is not None}
+        stat = enhance_kwargs.get("ensemble_stat") or "median"
+
+        def run_group(grp):
+            """grp: list of (k, path, audio at the model's rate, fs), one fs"""
+            with torch.no_grad():
+                rngs = []
+                for k, _, _, _ in grp:
+                    if counter:
+                        rngs.append(file_noise(args, k))
+                    elif per_file_seed:
+                        file_rng = torch.Generator(device=device)
+                        file_rng.manual_seed(args.seed + k)
+                        rngs.append(file_rng)
+                enhs = model.enhance_long_many_ensemble([a for _, _, a, _ in grp], args.segment_ensemble, stat,
+                                                        rngs=rngs if rngs else rng, segment_s=args.segment_seconds,
+                                                        overlap_s=ov, **kw)
+                outs = [resample(e, model.fs, fs, backend=args.resampler) for e, (_, _, _, fs) in zip(enhs, grp)]
+            for (_, path, _, fs), enh in zip(grp, outs):
+                output_path = out_path(path)
+                save(output_path, enh.cpu(), fs)
+                done.append(output_path)
+
+        grp = []
+        for k, path in todo:
+            audio, fs = load(path)
+            if grp and (fs != grp[0][3] or len(grp) >= args.segment_ensemble_files):  # a new sample rate ends a group
+                run_group(grp)
+                grp = []
+            with torch.no_grad():
+                grp.append((k, path, resample(audio.to(device), fs, model.fs, backend=args.resampler), fs))
+        if grp:
+            run_group(grp)
         return done
     if args.batch_size <= 1:
         for k, path in todo:

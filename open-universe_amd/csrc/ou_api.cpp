@@ -1853,9 +1853,10 @@ int seg_batch(long long entries, int max_batch) {
   return (int)((entries + groups - 1) / groups);
 }
 // The segmented call's own area behind the walk's workspace (offsets in bytes): E member rows per input row, Bw entries (E * Bw
-// walk rows of L samples) per group.  `with_hist`: the scratch of the ensemble reduce; `with_table`: the SegRow table.
+// walk rows of L samples) per group.  `with_hist`: the scratch of the ensemble reduce; `with_table`: the SegRow table and -- E > 1
+// -- the [level][Bw] length table of a ragged group's shared conditioner pass (the walk's own table is [level][E * Bw]).
 struct SegArea {
-  size_t stats, row_scale, part, zbuf, carry, hist, geom, total;
+  size_t stats, row_scale, part, zbuf, carry, hist, geom, lens_b, total;
 };
 SegArea seg_area(int C, int E, int Bw, long long L, bool with_hist, bool with_table) {
   SegArea a;
@@ -1868,6 +1869,7 @@ SegArea seg_area(int C, int E, int Bw, long long L, bool with_hist, bool with_ta
   a.carry = off; off += align256((size_t)E * L * 4);
   a.hist = off; off += with_hist ? ou_ensemble_reduce_scratch_bytes(E, C) : 0;
   a.geom = off; off += with_table ? align256((size_t)C * sizeof(SegRow)) : 0;
+  a.lens_b = off; off += with_table && E > 1 ? align256((size_t)Bw * kMaxLenLevels * 4) : 0;
   a.total = off;
   return a;
 }
@@ -1885,7 +1887,7 @@ struct SegWs {
   size_t walk;  // bytes of the walk's part
   float *stats, *row_scale, *zbuf, *carry;
   double* part;
-  int* hist;
+  int *hist, *lens_b;
   SegRow* geom;
 };
 int seg_workspace(ou_handle* h, void* ws, size_t ws_bytes, int B, int L, const SegArea& A, const char* sizer, SegWs& w) {
@@ -1903,15 +1905,21 @@ int seg_workspace(ou_handle* h, void* ws, size_t ws_bytes, int B, int L, const S
   w.carry = (float*)(seg + A.carry);
   w.hist = (int*)(seg + A.hist);
   w.geom = (SegRow*)(seg + A.geom);
+  w.lens_b = (int*)(seg + A.lens_b);
   return OU_OK;
 }
-// what both entry points of the segmented ensemble refuse, and the plan of the call.  Bw: entries per group
-int seg_ens_plan(ou_handle* h, const char* who, int C, long long T_raw, int segment, int overlap, int max_batch, int E, SegGeom& g,
-                 int& Bw) {
-  if (C < 1 || T_raw < 1 || max_batch < 1) return fail(h, OU_EINVAL, "bad argument");
+// what every entry point of the segmented ensembles refuses about its member count
+int seg_ens_members(ou_handle* h, const char* who, int C, int max_batch, int E) {
   if (E < 1 || E > OU_MAX_ENSEMBLE) return fail(h, OU_EINVAL, std::string(who) + ": 1 <= E <= " + std::to_string(OU_MAX_ENSEMBLE));
   if (E > max_batch) return fail(h, OU_EINVAL, std::string(who) + ": E must not exceed max_batch (a group holds all E members of its entries)");
   if ((long long)E * C > 65535) return fail(h, OU_EINVAL, std::string(who) + ": too many member rows (E * C <= 65535)");
+  return OU_OK;
+}
+// ... and the plan of the call on rows of one length.  Bw: entries per group
+int seg_ens_plan(ou_handle* h, const char* who, int C, long long T_raw, int segment, int overlap, int max_batch, int E, SegGeom& g,
+                 int& Bw) {
+  if (C < 1 || T_raw < 1 || max_batch < 1) return fail(h, OU_EINVAL, "bad argument");
+  if (const int rc = seg_ens_members(h, who, C, max_batch, E)) return rc;
   SegPlan plan;
   if (!seg_plan(h->m.tot_ds, T_raw, segment, overlap, plan)) return fail(h, OU_EINVAL, plan.err);
   g = plan.g;
@@ -2104,6 +2112,141 @@ int seg_enhance(ou_handle* h, const char* who, const char* sizer, const float* m
     return OU_EHIP;
   return OU_OK;
 }
+
+// ou_enhance_segments_var (E = 1, members = out, no reduce) and ou_enhance_segments_var_ensemble behind their own refusals: rows
+// with lengths of their own, their windows in the groups `G` of Bw = G.batch entries (seg_groups at max_batch / E), every group
+// one walk of E * Bw rows (member-major) -- the plain one, or the ragged one where the entries differ in length -- whose
+// conditioner runs once over the Bw entries (seg_enhance's arrangement) or -- not shared, E = 1 -- over all rows; the members are
+// stitched into the (E * C, T_raw_max) rows `members`, post-processed there and, `reduce`, reduced into `out` at the rows' lengths.
+int seg_var_enhance(ou_handle* h, const char* who, const char* sizer, const float* mix, float* out, float* members,
+                    const float* noise, int C, long long T_raw_max, const int64_t* t_raw, int E, bool reduce, int stat,
+                    const SegGroups& G, int n_steps, double epsilon, const float* sigma_host, uint32_t flags, void* ws,
+                    size_t ws_bytes, ou_stream_t stream) {
+  const Model& m = h->m;
+  const int tot = m.tot_ds;
+  if (G.length > max_walk_length(h, false)) return fail(h, OU_EINVAL, std::string(who) + ": segment too long for one pass of the walk");
+  const int Bw = G.batch;  // entries per group
+  const int B = E * Bw;    // rows of the walk
+  SegWs w;
+  if (const int rc = seg_workspace(h, ws, ws_bytes, B, (int)G.length, seg_area(C, E, Bw, G.length, reduce, true), sizer, w)) return rc;
+
+  CallScope scope(h, true);  // one chain on the caller's stream
+  hipStream_t st = (hipStream_t)stream;
+  const bool share = h->opt.ens_share != 0 && E > 1;
+  const int Bc = share ? Bw : B;  // rows of the conditioner pass
+
+  // ---- the geometry table, then every row's statistics and mel scale in one set of launches (the output rows hold the frame
+  // energies until the first stitch -- with members of their own: until the reduce)
+  long long T_pad_max = 0, frames_max = 0;
+  for (int c = 0; c < C; c++) {
+    T_pad_max = std::max(T_pad_max, G.rows[c].T_pad);
+    const long long Lf = G.rows[c].T_pad / tot;  // mel frames of the whole row (run_condition)
+    if (Lf > G.rows[c].T_raw) return fail(h, OU_EINVAL, "internal: mel frames do not fit into the output row");
+    frames_max = std::max(frames_max, Lf);
+  }
+  if (frames_max > 0x7fffffffll) return fail(h, OU_EINVAL, "input too long");
+  const SegVar v{G.S, G.hop, tot};
+  for (int off = 0; off < C; off += kSegRowsPerLaunch) {
+    SegRowBlock blk;
+    const int n = std::min(C - off, kSegRowsPerLaunch);
+    for (int i = 0; i < kSegRowsPerLaunch; i++) {
+      blk.t_raw[i] = i < n ? t_raw[off + i] : 1;
+      blk.first[i] = i < n ? G.first[off + i] : 0;
+    }
+    if (!launched(h, launch_seg_upload_rows(w.geom, blk, n, off, v, st), "segment rows")) return OU_EHIP;
+  }
+  const SegRowsTable rows{w.geom, T_raw_max, T_pad_max};
+  if (!seg_row_stats(h, mix, out, w, rows, C, frames_max, st)) return OU_EHIP;
+  if (!launched(h, launch_seg_mel_scale_var(out, w.row_scale, w.geom, C, T_raw_max, st), "segment mel scale")) return OU_EHIP;
+
+  // ---- the groups: Bw entries at a time, E * Bw rows through the walk
+  const SamplerTables tab(m.cfg, n_steps, epsilon, sigma_host);
+  const long long n_entries = (long long)G.entries.size();
+  for (size_t gi = 0; gi < G.group_first.size(); gi++) {
+    const long long e0 = G.group_first[gi];
+    const bool full = e0 < G.n_full;
+    const long long e_end = std::min<long long>(e0 + Bw, full ? G.n_full : n_entries);
+    const int n_real = (int)(e_end - e0);
+    // entry j of the group (the filler rows of a short last group repeat the last real one) and the length of the walk
+    auto entry = [&](int j) -> const SegEntry& { return G.entries[(size_t)(e0 + std::min(j, n_real - 1))]; };
+    int T = 0;
+    for (int j = 0; j < n_real; j++) T = std::max(T, entry(j).len);
+    // fn(entries, n) for the entries [0, count) of the group, kSegEntriesPerLaunch at a time
+    auto for_blocks = [&](int count, auto fn) {
+      for (int j0 = 0; j0 < count; j0 += kSegEntriesPerLaunch) {
+        SegEntriesList ents;
+        ents.j0 = j0; ents.hop = G.hop; ents.overlap = G.O;
+        const int n = std::min(count - j0, kSegEntriesPerLaunch);
+        for (int i = 0; i < kSegEntriesPerLaunch; i++) {
+          const SegEntry& e = entry(j0 + std::min(i, n - 1));
+          ents.blk.row[i] = e.row; ents.blk.win[i] = e.win; ents.blk.len[i] = e.len;
+        }
+        fn(ents, n);
+      }
+    };
+    Runner r(h, ws, w.walk, false, st, B);
+    r.mel_scale_preset = true;
+    Persist P = layout_persist(r, T);
+    if (r.oom) return finish(h, r);
+    if (gi == 0) tab.upload(r, P);  // (the persistent area keeps the tables from group to group: its layout depends on B alone)
+    const bool ragged = G.group_ragged[gi] != 0;
+    if (ragged) {
+      // the entries' lengths on every level of the network (as ou_enhance_var; an entry is an already padded window, so its
+      // length is the level-0 length itself): every member's rows in one set of launches, and the [level][Bw] table of a
+      // conditioner pass over the entries alone
+      if (const int rc = set_levels(r, T)) return rc;
+      for_blocks(Bw, [&](const SegEntriesList& ents, int n) {
+        r.launch("segment lens", [&] { return launch_seg_upload_lens(P.lens, ents.blk, n, ents.j0, Bw, E, r.lv, st); });
+        if (share) r.launch("segment lens", [&] { return launch_seg_upload_lens(w.lens_b, ents.blk, n, ents.j0, Bw, 1, r.lv, st); });
+      });
+      r.set_ragged(P.lens, nullptr);  // (no RowInfo: the windows are gathered and stitched by their entries)
+    }
+    Runner rc = Runner::conditioner_of(r, Bc);
+    if (ragged) rc.set_ragged(share ? w.lens_b : P.lens, nullptr);
+    // the group's inputs: once into the prefix, or -- the conditioner over all rows -- once per member
+    for (int e = 0; e < (share ? 1 : E); e++)
+      for_blocks(Bw, [&](const SegEntriesList& ents, int n) {
+        rc.launch("segment gather", [&] {
+          return launch_seg_gather_input(mix, w.stats, w.row_scale, P.mixn.p + (size_t)e * Bw * T, P.mel_scale + (size_t)e * Bw, rows,
+                                         ents, n, T, st);
+        });
+      });
+    run_condition(rc, P, P.mixn.p, T);
+    // (the statistics of the post step are those of the whole long rows, w.stats: P.stats is not written; no warm start)
+    if (share) replicate_conditioned(rc, P, Bw, E, false, false);
+    if (const int rc2 = finish(h, rc)) return rc2;
+    r.off = rc.off;
+    // walk row e * Bw + j: window k of long row e * C + c, positions s_k + i of that row's noise
+    auto z = seg_noise(h, r, noise, (size_t)E * C * T_pad_max, w.zbuf, T, B,
+                       [&](const float* slice) {
+                         for_blocks(Bw, [&](const SegEntriesList& ents, int n) {
+                           r.launch("segment noise", [&] { return launch_seg_gather_noise(slice, w.zbuf, rows, ents, n, T, Bw, E, C, st); });
+                         });
+                       },
+                       [&](int row, long long& stream_row, long long& t0, long long& len) {
+                         const int e = row / Bw;
+                         const SegEntry& en = entry(row - e * Bw);
+                         stream_row = (long long)e * C + en.row;
+                         t0 = en.win < G.rows[en.row].n_win - 1 ? en.win * G.hop : G.rows[en.row].T_pad - en.len;
+                         len = en.len;
+                       });
+    sample(r, P, T, tab, 0, nullptr, false, z);
+    for_blocks(n_real, [&](const SegEntriesList& ents, int n) {
+      r.launch("segment stitch", [&] { return launch_seg_stitch(P.x.p, w.carry, members, rows, ents, n, T, Bw, E, C, st); });
+    });
+    if (full && e_end < G.n_full) seg_carry(r, w.carry, P.x.p, T, Bw, E, n_real);  // the window in front of the next group
+    if (const int rc2 = finish(h, r)) return rc2;
+  }
+  // ---- the post step over every long row (keep_rms: the mix_rms of the member's own input row), then the reduce over e
+  if (const int rc = seg_epilogue(h, members, w, rows, E, C, (int)G.length, flags, st)) return rc;
+  if (reduce) {
+    const std::vector<long long> len64(t_raw, t_raw + C);
+    if (!launched(h, launch_ensemble_reduce(members, out, E, C, T_raw_max, T_raw_max, len64.data(), stat, w.hist,
+                                            w.hist + (size_t)C * E, st), "ensemble reduce"))
+      return OU_EHIP;
+  }
+  return OU_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -2239,111 +2382,46 @@ int ou_enhance_segments_var(ou_handle* h, const float* mix, float* out, const fl
   if (warm_start >= 0 || (flags & OU_ENH_USE_AUX_SIGNAL))
     return fail(h, OU_EINVAL, "ou_enhance_segments_var: warm_start and use_aux_signal are not supported");
   if (const int rc = check_steps(h, n_steps, warm_start)) return rc;
-  const Model& m = h->m;
-  const int tot = m.tot_ds;
   SegGroups G;
-  if (!seg_groups(tot, C, t_raw, segment, overlap, max_batch, G)) return fail(h, OU_EINVAL, G.err);
-  if (G.length > max_walk_length(h, false))
-    return fail(h, OU_EINVAL, "ou_enhance_segments_var: segment too long for one pass of the walk");
-  const int B = G.batch;
-  SegWs w;
-  if (const int rc = seg_workspace(h, ws, ws_bytes, B, (int)G.length, seg_area(C, 1, B, G.length, false, true),
-                                   "ou_segments_var_workspace_bytes", w))
-    return rc;
+  if (!seg_groups(h->m.tot_ds, C, t_raw, segment, overlap, max_batch, G)) return fail(h, OU_EINVAL, G.err);
+  return seg_var_enhance(h, "ou_enhance_segments_var", "ou_segments_var_workspace_bytes", mix, out, out, noise, C, T_raw_max, t_raw,
+                         1, false, 0, G, n_steps, epsilon, sigma_host, flags, ws, ws_bytes, stream);
+}
 
-  CallScope scope(h, true);  // one chain on the caller's stream
-  hipStream_t st = (hipStream_t)stream;
+int ou_segments_var_ensemble_workspace_bytes(const ou_handle* hc, int32_t C, const int64_t* t_raw, int32_t segment,
+                                             int32_t overlap, int32_t max_batch, int32_t E, size_t* nbytes, int32_t* batch,
+                                             int32_t* length) {
+  ou_handle* h = const_cast<ou_handle*>(hc);
+  if (!h || !nbytes || !t_raw || C < 1 || max_batch < 1) return fail(h, OU_EINVAL, "bad argument");
+  if (const int rc = seg_ens_members(h, "ou_segments_var_ensemble_workspace_bytes", C, max_batch, E)) return rc;
+  SegGroups G;
+  if (!seg_groups(h->m.tot_ds, C, t_raw, segment, overlap, max_batch / E, G)) return fail(h, OU_EINVAL, G.err);
+  return seg_workspace_bytes(h, E * G.batch, G.length, seg_area(C, E, G.batch, G.length, true, true), nbytes, batch, length);
+}
 
-  // ---- the geometry table, then every row's statistics and mel scale in one set of launches (the output rows hold the frame
-  // energies until the first stitch)
-  long long T_pad_max = 0, frames_max = 0;
-  for (int c = 0; c < C; c++) {
-    T_pad_max = std::max(T_pad_max, G.rows[c].T_pad);
-    const long long Lf = G.rows[c].T_pad / tot;  // mel frames of the whole row (run_condition)
-    if (Lf > G.rows[c].T_raw) return fail(h, OU_EINVAL, "internal: mel frames do not fit into the output row");
-    frames_max = std::max(frames_max, Lf);
-  }
-  if (frames_max > 0x7fffffffll) return fail(h, OU_EINVAL, "input too long");
-  const SegVar v{G.S, G.hop, tot};
-  for (int off = 0; off < C; off += kSegRowsPerLaunch) {
-    SegRowBlock blk;
-    const int n = std::min(C - off, kSegRowsPerLaunch);
-    for (int i = 0; i < kSegRowsPerLaunch; i++) {
-      blk.t_raw[i] = i < n ? t_raw[off + i] : 1;
-      blk.first[i] = i < n ? G.first[off + i] : 0;
-    }
-    if (!launched(h, launch_seg_upload_rows(w.geom, blk, n, off, v, st), "segment rows")) return OU_EHIP;
-  }
-  const SegRowsTable rows{w.geom, T_raw_max, T_pad_max};
-  if (!seg_row_stats(h, mix, out, w, rows, C, frames_max, st)) return OU_EHIP;
-  if (!launched(h, launch_seg_mel_scale_var(out, w.row_scale, w.geom, C, T_raw_max, st), "segment mel scale")) return OU_EHIP;
-
-  // ---- the groups: B entries at a time through the walk -- the plain one, or the ragged one where the entries differ in length
-  const SamplerTables tab(m.cfg, n_steps, epsilon, sigma_host);
-  const long long n_entries = (long long)G.entries.size();
-  for (size_t gi = 0; gi < G.group_first.size(); gi++) {
-    const long long e0 = G.group_first[gi];
-    const bool full = e0 < G.n_full;
-    const long long e_end = std::min<long long>(e0 + B, full ? G.n_full : n_entries);
-    const int n_real = (int)(e_end - e0);
-    // entry j of the group (the filler rows of a short last group repeat the last real one) and the length of the walk
-    auto entry = [&](int j) -> const SegEntry& { return G.entries[(size_t)(e0 + std::min(j, n_real - 1))]; };
-    int T = 0;
-    for (int j = 0; j < n_real; j++) T = std::max(T, entry(j).len);
-    // fn(entries, n) for the entries [0, count) of the group, kSegEntriesPerLaunch at a time
-    auto for_blocks = [&](int count, auto fn) {
-      for (int j0 = 0; j0 < count; j0 += kSegEntriesPerLaunch) {
-        SegEntriesList ents;
-        ents.j0 = j0; ents.hop = G.hop; ents.overlap = G.O;
-        const int n = std::min(count - j0, kSegEntriesPerLaunch);
-        for (int i = 0; i < kSegEntriesPerLaunch; i++) {
-          const SegEntry& e = entry(j0 + std::min(i, n - 1));
-          ents.blk.row[i] = e.row; ents.blk.win[i] = e.win; ents.blk.len[i] = e.len;
-        }
-        fn(ents, n);
-      }
-    };
-    Runner r(h, ws, w.walk, false, st, B);
-    r.mel_scale_preset = true;
-    Persist P = layout_persist(r, T);
-    if (r.oom) return finish(h, r);
-    if (gi == 0) tab.upload(r, P);  // (the persistent area keeps the tables from group to group: its layout depends on B alone)
-    if (G.group_ragged[gi]) {
-      // the entries' lengths on every level of the network (as ou_enhance_var; an entry is an already padded window, so its
-      // length is the level-0 length itself)
-      if (const int rc = set_levels(r, T)) return rc;
-      for_blocks(B, [&](const SegEntriesList& ents, int n) {
-        r.launch("segment lens", [&] { return launch_seg_upload_lens(P.lens, ents.blk, n, ents.j0, B, r.lv, st); });
-      });
-      r.set_ragged(P.lens, nullptr);  // (no RowInfo: the windows are gathered and stitched by their entries)
-    }
-    for_blocks(B, [&](const SegEntriesList& ents, int n) {
-      r.launch("segment gather", [&] {
-        return launch_seg_gather_input(mix, w.stats, w.row_scale, P.mixn.p, P.mel_scale, rows, ents, n, T, st);
-      });
-    });
-    run_condition(r, P, P.mixn.p, T);
-    // walk row j: window k of row c, positions s_k + i of that row's noise
-    auto z = seg_noise(h, r, noise, (size_t)C * T_pad_max, w.zbuf, T, B,
-                       [&](const float* slice) {
-                         for_blocks(B, [&](const SegEntriesList& ents, int n) {
-                           r.launch("segment noise", [&] { return launch_seg_gather_noise(slice, w.zbuf, rows, ents, n, T, B, 1, C, st); });
-                         });
-                       },
-                       [&](int j, long long& stream_row, long long& t0, long long& len) {
-                         const SegEntry& e = entry(j);
-                         stream_row = e.row;
-                         t0 = e.win < G.rows[e.row].n_win - 1 ? e.win * G.hop : G.rows[e.row].T_pad - e.len;
-                         len = e.len;
-                       });
-    sample(r, P, T, tab, 0, nullptr, false, z);
-    for_blocks(n_real, [&](const SegEntriesList& ents, int n) {
-      r.launch("segment stitch", [&] { return launch_seg_stitch(P.x.p, w.carry, out, rows, ents, n, T, B, 1, C, st); });
-    });
-    if (full && e_end < G.n_full) seg_carry(r, w.carry, P.x.p, T, B, 1, n_real);  // the window in front of the next group
-    if (const int rc = finish(h, r)) return rc;
-  }
-  return seg_epilogue(h, out, w, rows, 1, C, (int)G.length, flags, st);
+int ou_enhance_segments_var_ensemble(ou_handle* h, const float* mix, float* out, float* members, const float* noise, int32_t C,
+                                     int64_t T_raw_max, const int64_t* t_raw, int32_t E, int32_t stat, int32_t segment,
+                                     int32_t overlap, int32_t max_batch, int32_t n_steps, double epsilon, const float* sigma_host,
+                                     int32_t warm_start, uint32_t flags, void* ws, size_t ws_bytes, ou_stream_t stream) {
+  const char* who = "ou_enhance_segments_var_ensemble";
+  // (the lengths and the member count first: what they decide needs neither the handle nor a device)
+  if (!t_raw || C < 1 || T_raw_max < 1) return fail(h, OU_EINVAL, std::string(who) + ": bad argument (t_raw must be given, C >= 1)");
+  if (max_batch < 1) return fail(h, OU_EINVAL, std::string(who) + ": max_batch must be at least 1");
+  if (const int rc = seg_ens_members(h, who, C, max_batch, E)) return rc;
+  if (const int rc = check_rows(h, who, 'c', t_raw, C, T_raw_max, false)) return rc;
+  if (!h || !mix || !out || !ws) return fail(h, OU_EINVAL, "bad argument");
+  if (stat != OU_ENS_MEAN && stat != OU_ENS_MEDIAN && stat != OU_ENS_SIGNAL_MEDIAN)
+    return fail(h, OU_EINVAL, std::string(who) + ": stat must be OU_ENS_MEAN, OU_ENS_MEDIAN or OU_ENS_SIGNAL_MEDIAN");
+  if (!members)
+    return fail(h, OU_EINVAL, std::string(who) + ": `members` must be given ((E * C, T_raw_max): the post step runs over whole member rows)");
+  if (warm_start >= 0 || (flags & OU_ENH_USE_AUX_SIGNAL))
+    return fail(h, OU_EINVAL, std::string(who) + ": warm_start and use_aux_signal are not supported");
+  if (const int rc = check_noise_source(h, noise, E * C, "the member rows of the call (E * C = ", true)) return rc;
+  if (const int rc = check_steps(h, n_steps, warm_start)) return rc;
+  SegGroups G;
+  if (!seg_groups(h->m.tot_ds, C, t_raw, segment, overlap, max_batch / E, G)) return fail(h, OU_EINVAL, G.err);
+  return seg_var_enhance(h, who, "ou_segments_var_ensemble_workspace_bytes", mix, out, members, noise, C, T_raw_max, t_raw, E, true,
+                         stat, G, n_steps, epsilon, sigma_host, flags, ws, ws_bytes, stream);
 }
 
 int ou_transform_frames(int32_t T, int32_t n_fft, int32_t hop) {

@@ -300,9 +300,10 @@ struct SegVar {
 constexpr int kSegRowsPerLaunch = 64;
 struct SegRowBlock { long long t_raw[kSegRowsPerLaunch]; long long first[kSegRowsPerLaunch]; };
 hipError_t launch_seg_upload_rows(SegRow* rows, const SegRowBlock& blk, int n, int off, const SegVar& v, hipStream_t st);
-// lens[l * B + j0 + i] <- len[i] * num_l / den_l: the per-level lengths of a ragged group, from the entry lengths directly (an
-// entry is an already padded window: no pad split as in launch_upload_rows)
-hipError_t launch_seg_upload_lens(int* lens, const SegEntryBlock& blk, int n, int j0, int B, const LevelSpec& lv, hipStream_t st);
+// lens[l * E * Bw + m * Bw + j0 + i] <- len[i] * num_l / den_l for every member m < E: the per-level lengths of a ragged group's
+// E * Bw walk rows, from the entry lengths directly (an entry is an already padded window: no pad split as in launch_upload_rows)
+hipError_t launch_seg_upload_lens(int* lens, const SegEntryBlock& blk, int n, int j0, int Bw, int E, const LevelSpec& lv,
+                                  hipStream_t st);
 
 // Counter-based sampler noise (ou_noise.hip; the function z(seed, stream, draw, t) is defined in include/ouniverse.h).
 // One launch fills up to 64 rows: out[j][col] = col < len[j] ? z(seed, stream[j], draw, t0[j] + col) : 0 for col < cols.

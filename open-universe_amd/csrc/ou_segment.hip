@@ -367,10 +367,11 @@ __global__ void seg_upload_rows_kernel(SegRow* rows, SegRowBlock blk, int n, int
   r.frames = r.T_pad / v.tot_ds;
   rows[off + i] = r;
 }
-__global__ void seg_upload_lens_kernel(int* lens, SegEntryBlock blk, int n, int j0, int B, LevelSpec lv) {
-  const int i = threadIdx.x;
+// (member m = blockIdx.x writes walk rows m * Bw + j0 + i of the [level][E * Bw] table: member rows repeat their entry's lengths)
+__global__ void seg_upload_lens_kernel(int* lens, SegEntryBlock blk, int n, int j0, int Bw, LevelSpec lv) {
+  const int i = threadIdx.x, m = blockIdx.x, B = (int)gridDim.x * Bw;
   if (i >= n) return;
-  for (int l = 0; l < lv.n; l++) lens[l * B + j0 + i] = (int)((long long)blk.len[i] * lv.num[l] / lv.den[l]);
+  for (int l = 0; l < lv.n; l++) lens[l * B + m * Bw + j0 + i] = (int)((long long)blk.len[i] * lv.num[l] / lv.den[l]);
 }
 
 // ---- what the launch wrappers check ------------------------------------------------------------------------------------------
@@ -472,9 +473,10 @@ hipError_t launch_seg_upload_rows(SegRow* rows, const SegRowBlock& blk, int n, i
   hipLaunchKernelGGL(seg_upload_rows_kernel, dim3(1), dim3(64), 0, st, rows, blk, n, off, v);
   return hipGetLastError();
 }
-hipError_t launch_seg_upload_lens(int* lens, const SegEntryBlock& blk, int n, int j0, int B, const LevelSpec& lv, hipStream_t st) {
-  if (n < 1 || n > kSegEntriesPerLaunch || j0 < 0 || j0 + n > B) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(seg_upload_lens_kernel, dim3(1), dim3(64), 0, st, lens, blk, n, j0, B, lv);
+hipError_t launch_seg_upload_lens(int* lens, const SegEntryBlock& blk, int n, int j0, int Bw, int E, const LevelSpec& lv,
+                                  hipStream_t st) {
+  if (n < 1 || n > kSegEntriesPerLaunch || j0 < 0 || j0 + n > Bw || E < 1 || E > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(seg_upload_lens_kernel, dim3(E), dim3(64), 0, st, lens, blk, n, j0, Bw, lv);
   return hipGetLastError();
 }
 

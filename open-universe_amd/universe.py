@@ -1065,10 +1065,13 @@ class Universe:
         return out if mix.ndim == 2 else out[0]
 
     def _segments_plan(self, C, T, segment, overlap, max_batch, ensemble=None, t_raw=None):
-        """What tells the three segmented entry points apart -- plain, `ensemble` = (E, stat), `t_raw` = a length per row --, sized:
-        -> (library function, its arguments between the noise pointer and n_steps, workspace)."""
+        """What tells the four segmented entry points apart -- plain, `ensemble` = (E, stat), `t_raw` = a length per row, or both --,
+        sized: -> (library function, its arguments between the noise pointer and n_steps, workspace)."""
         geo = (segment, overlap, int(max_batch))
-        if ensemble is not None:
+        if ensemble is not None and t_raw is not None:
+            fn, sizer = self._L.ou_enhance_segments_var_ensemble, self._L.ou_segments_var_ensemble_workspace_bytes
+            sized, dims = (C, t_raw) + geo + (ensemble[0],), (C, T, t_raw, ensemble[0], _lib.ENSEMBLE_STATS[ensemble[1]]) + geo
+        elif ensemble is not None:
             fn, sizer = self._L.ou_enhance_segments_ensemble, self._L.ou_segments_ensemble_workspace_bytes
             sized, dims = (C, T) + geo + (ensemble[0],), (C, T, ensemble[0], _lib.ENSEMBLE_STATS[ensemble[1]]) + geo
         elif t_raw is not None:
@@ -1151,6 +1154,43 @@ class Universe:
         if counter is None:  # the draws of `enhance_long` on every input alone, input by input: (C_i, 1, T_i) per step, x0 first
             noise = draw_noise(self.tot_ds, pk.entries(rngs), n_steps, device=self.device)
         return unpack_rows(pk, self._segments_run(plan, pk.batch, n_steps, epsilon, keep_rms, noise, counter))[0]
+
+    @torch.no_grad()
+    def enhance_long_many_ensemble(self, signals, ensemble: int, ensemble_stat: str = "median", rngs=None,
+                                   segment_s: float = SEGMENT_S, overlap_s: float = OVERLAP_S, max_batch: int = 32,
+                                   n_steps: Optional[int] = None, epsilon: Optional[float] = None, keep_rms: bool = False,
+                                   return_members: bool = False, **other):
+        """`enhance_long_ensemble` of several independent inputs of ANY lengths in ONE call (extension;
+        ou_enhance_segments_var_ensemble).  `signals`: list of (L,) or (C, L) tensors, channels are rows as in `enhance_long_many`.
+        The windows of all rows share the window groups of floor(max_batch / E) entries, all E members of a window in one group;
+        every row still gets what `enhance_long_ensemble` gives it alone (to fp32 round-off, since the kernels a group selects
+        differ).  `rngs`: one generator per input, ONE shared generator (it advances input by input: it ends where the loop of
+        `advance_generator_like_enhance(g, E * C_i, L_i)` over the inputs leaves it), or None -- or `noise.CounterNoise` objects
+        as in `enhance_long_many` (input i draws from `CounterNoise(seed, stream + i).stream_ids(C_i, E)`).  Returns the list of
+        results, each with the shape of its input; return_members=True: -> (results, [members (E,) + that shape])."""
+        self._refuse_long_options("enhance_long_many_ensemble", other)
+        E = int(ensemble)
+        if not 1 <= E <= _lib.OU_MAX_ENSEMBLE:
+            raise ValueError(f"enhance_long_many_ensemble: 1 <= ensemble <= {_lib.OU_MAX_ENSEMBLE}")
+        if ensemble_stat not in _lib.ENSEMBLE_STATS:
+            raise NotImplementedError()  # universe.py:368
+        if not signals:
+            return ([], []) if return_members else []
+        n_steps, epsilon, segment, overlap = self._begin(n_steps, epsilon, segment_s, overlap_s)
+        pk = pack_rows(signals, "enhance_long_many_ensemble", self._prep)
+        C, l_max = pk.batch.shape
+        plan = self._segments_plan(C, l_max, segment, overlap, max_batch, ensemble=(E, ensemble_stat),
+                                   t_raw=(ctypes.c_int64 * C)(*pk.row_lens))
+        counter = self._counter_plan(rngs, pk.chans)
+        noise = None
+        if counter is not None:  # member e of a row: the row's id + (e << ENSEMBLE_SHIFT), member-major over all rows
+            counter = (counter[0], [s + (e << ENSEMBLE_SHIFT) for e in range(E) for s in counter[1]])
+        else:  # the draws of `enhance_long_ensemble` on every input alone, input by input: (E * C_i, 1, T_i) per step, x0 first,
+            # each written straight into its member-major slice of the library's (n_steps, E * C, T_pad_max) tensor
+            noise = draw_noise(self.tot_ds, pk.entries(rngs), n_steps, E, device=self.device)
+        members = torch.empty(E, C, l_max, dtype=torch.float32, device=self.device)
+        res, mems = unpack_rows(pk, self._segments_run(plan, pk.batch, n_steps, epsilon, keep_rms, noise, counter, members), members)
+        return (res, mems) if return_members else res
 
     def _segments_workspace(self, B, L, need):
         """The workspace of enhance_long: one buffer kept for re-use (outside the per-batch-size cache of `enhance`)."""
