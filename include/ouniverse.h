@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define OU_ABI_VERSION 7 /* 7: ensembles of segmented rows (ou_segments_ensemble_workspace_bytes, ou_enhance_segments_ensemble: additive, the number stays); segmented enhance of rows with lengths of their own (ou_segment_groups, ou_segments_var_workspace_bytes, ou_enhance_segments_var: additive, the number stays); ensembles in the library (ou_enhance_ensemble, ou_ensemble_workspace_bytes, ou_ensemble_reduce, ou_ensemble_reduce_scratch_bytes; option ens_share); existing entry points unchanged; 6: counter-based sampler noise (ou_set_noise_source, ou_noise_scratch_bytes, ou_noise_fill); existing entry points unchanged; 5: ou_enhance_var (batches whose rows have lengths of their own), workspace header carries the per-row geometry; ou_set_option / ou_get_option replace every OU_* environment switch (the library reads no environment variable), ou_config.fir_fold; 4: the packed blob carries a bf16-split weight copy (conv_split_kernel); 3: a Winograd-domain copy (round 5), ou_set_lane_batch, ou_lane_capacity */
+#define OU_ABI_VERSION 7 /* 7: Snake activations of the ConvBlock body convs (ou_config tail score_enc_act .. cond_dec_act, OU_ACT_SNAKEBETA, ou_snake_act, ou_snake_tile: additive, the number stays -- a zeroed tail is the PReLU model); ensembles of segmented rows (ou_segments_ensemble_workspace_bytes, ou_enhance_segments_ensemble: additive, the number stays); segmented enhance of rows with lengths of their own (ou_segment_groups, ou_segments_var_workspace_bytes, ou_enhance_segments_var: additive, the number stays); ensembles in the library (ou_enhance_ensemble, ou_ensemble_workspace_bytes, ou_ensemble_reduce, ou_ensemble_reduce_scratch_bytes; option ens_share); existing entry points unchanged; 6: counter-based sampler noise (ou_set_noise_source, ou_noise_scratch_bytes, ou_noise_fill); existing entry points unchanged; 5: ou_enhance_var (batches whose rows have lengths of their own), workspace header carries the per-row geometry; ou_set_option / ou_get_option replace every OU_* environment switch (the library reads no environment variable), ou_config.fir_fold; 4: the packed blob carries a bf16-split weight copy (conv_split_kernel); 3: a Winograd-domain copy (round 5), ou_set_lane_batch, ou_lane_capacity */
 
 enum {
   OU_OK = 0,
@@ -40,7 +40,9 @@ enum {
 };
 
 enum { OU_KIND_UNIVERSE = 0, OU_KIND_UNIVERSE_GAN = 1 };
-enum { OU_ACT_NONE = 0, OU_ACT_PRELU = 1, OU_ACT_SNAKE = 2 };
+enum { OU_ACT_NONE = 0, OU_ACT_PRELU = 1, OU_ACT_SNAKE = 2, OU_ACT_SNAKEBETA = 3 };
+/* act_type "none" in the four *_act fields at the end of ou_config, where 0 has to mean "not set" = PReLU */
+#define OU_ACT_IDENTITY (-1)
 
 #define OU_MAX_RATES 8
 
@@ -85,6 +87,12 @@ typedef struct ou_config {
   int32_t no_split_copy; /* packing choice: 1 = leave the bf16-split weight copy (conv_split_kernel: a quarter of the blob, PP16
                           * 162 of 648 MB) out -- for handles that never run a batch of 8 or more utterances per call (the
                           * launcher's rule selects that kernel from batch 8 / 16 on).  Same value for the packer and ou_create. */
+  /* encoder_act_type / decoder_act_type of ScoreNetwork (score.py:223-224) and ConditionerNetwork (condition.py:283-284): the
+   * activation in front of conv1 .. conv3 of every ConvBlock of that half (blocks.py:176-187, 289-312; rate-change convs, st
+   * convs and the conditioner's mel ConvBlock always keep their PReLU).  0 (a zeroed tail: every caller older than these
+   * fields) or OU_ACT_PRELU: PReLU; OU_ACT_SNAKE / OU_ACT_SNAKEBETA: bigvgan.AliasFreeSnake(alpha_logscale=True[, beta=True]);
+   * OU_ACT_IDENTITY: "none".  The plan and the blob depend on them: same values for the packer and ou_create. */
+  int32_t score_enc_act, score_dec_act, cond_enc_act, cond_dec_act;
 } ou_config;
 
 typedef struct ou_packer ou_packer;
@@ -483,6 +491,27 @@ int32_t ou_resample_tile(int32_t fs_in, int32_t fs_out);
 int ou_resample(const float* x, int64_t x_stride, const int64_t* len_host, float* y, int64_t y_stride, int64_t cols,
                 int32_t rows, int32_t fs_in, int32_t fs_out, const void* table, size_t table_bytes, ou_stream_t stream);
 
+/* ---- alias-free Snake activation (bigvgan Activation1d, alias_free_act.py:25-30, around Snake / SnakeBeta, snake.py:53-64,
+ * 115-128, with log-scale parameters): what a PReLU_Conv with act_type snake / snakebeta applies in front of its conv.
+ * Stateless: no handle.  For row (b, c) = x[(b * C + c) * row_stride ..], with n = len[b] (T when len_host is NULL), x zero
+ * outside [0, n):
+ *     u[2 q + p] = sum_k up[p][k] x[q + k - 7]                      0 <= k < 15     Resample(1 -> 2): width 7, see "resampling"
+ *     s[j]       = u[j] + (1 / (eb[c] + 1e-9)) * sin(u[j] * ea[c])^2   for 0 <= j < 2 n, 0 outside
+ *     y[t]       = sum_k down[k] s[2 t + k - 13]                     0 <= k < 28     Resample(2 -> 1): width 13
+ * for 0 <= t < n, and y[t] = 0 for n <= t < T: row b IS the call on that row alone (the ou_enhance_var convention).  ea =
+ * exp(alpha), eb = exp(beta) per channel (device, C floats; exp_beta NULL: eb = ea, plain Snake); up_kernel (2, 15) and
+ * down_kernel (28) are the two torchaudio kernels (device).  Every sum is one fp32 FMA per tap, taps ascending; sin is the
+ * precise sinf and the reciprocal a true division, so a value depends on neither the tiling nor the batch it is in.  The x2
+ * signal exists in LDS only.  y must not overlap x.
+ * OU_EINVAL, decided on the host before any HIP call: a NULL tensor, B, C or T < 1, C > 65535, T > 2^31 - 1024, row_stride < T, a length outside
+ * [0, T], B * C * row_stride > 2^60.  Enqueued on `stream`, 64 rows of B per launch when lengths are given (they travel as
+ * kernel arguments), else one launch: no allocation, no host synchronisation, capturable. */
+int ou_snake_act(const float* x, float* y, int32_t B, int32_t C, int32_t T, int64_t row_stride, const int32_t* len_host,
+                 const float* exp_alpha, const float* exp_beta, const float* up_kernel, const float* down_kernel,
+                 ou_stream_t stream);
+/* Consecutive outputs of one (row, channel) that one workgroup of ou_snake_act owns (tests sit on its edges). */
+int32_t ou_snake_tile(void);
+
 /* One sampler update on caller-owned buffers, for bindings that keep the reference's Python loop
  * (universe.py:339 `x = x + s_now^2 * eta * score + beta * z`, :343 `x = x + s_last^2 * score`):
  *   x[i] += c1 * score[i] + c2 * z[i]     over n = B*T elements; z may be NULL (last step).
@@ -568,7 +597,8 @@ const char* ou_option_doc(int32_t index);
 double ou_option_default(int32_t index);
 
 /* ---- introspection (tests, profiling) ------------------------------------------------------------------- */
-/* JSON description of the packed layers (name, kind, shapes, offsets into the blob); for a handle also "options": the current
+/* JSON description of the packed layers (name, kind, shapes, offsets into the blob, "activation": "prelu" | "snake" | "snakebeta" |
+ * "none" with the offsets of a Snake layer's exp(alpha) / exp(beta), and the offsets of the two Snake resampling kernels); for a handle also "options": the current
  * value of every ou_set_option key. */
 const char* ou_plan_json(const ou_handle* h);
 const char* ou_packer_plan_json(const ou_packer* p);

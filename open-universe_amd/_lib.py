@@ -13,7 +13,10 @@ OU_MAX_RATES = 8
 OU_ABI_VERSION = 7
 OU_OK, OU_EINVAL, OU_ENOTIMPL, OU_EMISSING, OU_ESHAPE, OU_EHIP, OU_ENOMEM, OU_ESYNC = 0, -1, -2, -3, -4, -5, -6, -7
 OU_KIND_UNIVERSE, OU_KIND_UNIVERSE_GAN = 0, 1
-OU_ACT_NONE, OU_ACT_PRELU, OU_ACT_SNAKE = 0, 1, 2
+OU_ACT_NONE, OU_ACT_PRELU, OU_ACT_SNAKE, OU_ACT_SNAKEBETA = 0, 1, 2, 3
+OU_ACT_IDENTITY = -1  # act_type "none" in the four *_act fields of ou_config, where 0 means "not set" = PReLU
+# encoder_act_type / decoder_act_type -> ou_config.*_act ("prelu" stays 0: the config of a PReLU model is what it always was)
+BODY_ACTS = {"prelu": 0, "snake": OU_ACT_SNAKE, "snakebeta": OU_ACT_SNAKEBETA, "none": OU_ACT_IDENTITY}
 OU_ENH_KEEP_RMS, OU_ENH_USE_AUX_SIGNAL, OU_ENH_NO_PEAK_GUARD, OU_ENH_SERIAL = 1, 2, 4, 8
 OU_MAX_ENSEMBLE = 32
 OU_ENS_MEAN, OU_ENS_MEDIAN, OU_ENS_SIGNAL_MEDIAN = 0, 1, 2
@@ -56,6 +59,10 @@ class Config(Structure):
         ("edm_data_level_db", c_float),
         ("fir_fold", c_int32),
         ("no_split_copy", c_int32),
+        ("score_enc_act", c_int32),
+        ("score_dec_act", c_int32),
+        ("cond_enc_act", c_int32),
+        ("cond_dec_act", c_int32),
     ]
 
 
@@ -160,6 +167,8 @@ def load():
         "ou_launch_stats": (i32, [vp, POINTER(i32), POINTER(i32)]),
         "ou_workspace_init": (i32, [vp, i32, i32, vp, sz, vp]),
         "ou_sampler_step": (i32, [vp, vp, vp, vp, c_float, c_float, sz, vp]),
+        "ou_snake_act": (i32, [vp, vp, i32, i32, i32, c_int64, POINTER(i32), vp, vp, vp, vp, vp]),
+        "ou_snake_tile": (i32, []),
         "ou_set_gru_publish_mode": (i32, [vp, i32]),
         "ou_get_gru_publish_mode": (i32, [vp]),
         "ou_set_lanes": (i32, [vp, i32, i32]),
@@ -195,6 +204,7 @@ EXPORTED_SYMBOLS = [
     "ou_segments_var_ensemble_workspace_bytes", "ou_enhance_segments_var_ensemble",
     "ou_set_noise_source", "ou_noise_scratch_bytes", "ou_noise_fill",
     "ou_resample_plan", "ou_resample_table", "ou_resample_length", "ou_resample_tile", "ou_resample",
+    "ou_snake_act", "ou_snake_tile",
     "ou_set_option", "ou_get_option", "ou_reset_options", "ou_option_count", "ou_option_name", "ou_option_doc", "ou_option_default", "ou_plan_json",
     "ou_packer_plan_json", "ou_tensor", "ou_launch_stats", "ou_workspace_init", "ou_sampler_step",
     "ou_set_gru_publish_mode", "ou_get_gru_publish_mode", "ou_set_lanes", "ou_set_lane_batch", "ou_lane_capacity",
@@ -356,6 +366,17 @@ def make_config(spec, fir_fold=0, split_copy=True):
     cfg.edm_data_level_db = float(data_level) if data_level is not None else 0.0
     cfg.fir_fold = int(fir_fold)
     cfg.no_split_copy = 0 if split_copy else 1
+
+    def body_act(n, key):
+        v = getattr(n, key, "prelu")
+        if v not in BODY_ACTS:
+            raise ValueError(f"{key}={v!r}: 'act_type' should be one of [{' | '.join(BODY_ACTS)}]")
+        return BODY_ACTS[v]
+
+    cfg.score_enc_act = body_act(spec.score, "encoder_act_type")
+    cfg.score_dec_act = body_act(spec.score, "decoder_act_type")
+    cfg.cond_enc_act = body_act(spec.cond, "encoder_act_type")
+    cfg.cond_dec_act = body_act(spec.cond, "decoder_act_type")
     return cfg
 
 

@@ -39,6 +39,10 @@ class NetSpec:
     use_antialiasing: bool = False
     time_embedding: Optional[str] = None
     encoder_gru_conv_sandwich: bool = False
+    # act_type of conv1 .. conv3 of every ConvBlock of the encoder / decoder half (score.py:223-224, condition.py:283-284,
+    # blocks.py:176-187): prelu | snake | snakebeta | none
+    encoder_act_type: str = "prelu"
+    decoder_act_type: str = "prelu"
     # conditioner only
     n_mels: int = 80
     n_mel_oversample: int = 4
@@ -82,6 +86,9 @@ class ModelSpec:
                           n_steps=self.n_steps, epsilon=self.epsilon)
 
 
+ACT_TYPES = ("prelu", "snake", "snakebeta", "none")
+
+
 _INTERP = re.compile(r"^\$\{([^}]+)\}$")
 
 
@@ -118,6 +125,9 @@ def _net_spec(d, is_cond):
     for k in ("n_channels", "fb_kernel_size", "n_rff", "noise_cond_dim", "n_mels", "n_mel_oversample"):
         if k in kw:
             kw[k] = int(kw[k])
+    for k in ("encoder_act_type", "decoder_act_type"):
+        if kw.get(k, "prelu") not in ACT_TYPES:
+            raise ValueError(f"{k}={kw[k]!r}: 'act_type' should be one of [{' | '.join(ACT_TYPES)}]")  # blocks.py:187
     if d.get("seq_model", "gru") != "gru":
         raise NotImplementedError("only seq_model=gru is supported (all shipped configs)")
     if d.get("precoding"):

@@ -498,6 +498,8 @@ struct Runner {
   int plan_chain(const BlockL& Bk, const Tensor& hu, const Tensor& c1, const Tensor& v, const Epi& e1, bool need_c1) {
     const int T = hu.T;
     if (env.fuse == 0) return 0;
+    // a fused body applies the PReLU of its three convs itself: not a form for a block with a Snake layer or with none
+    if (!Bk.all_prelu()) return 0;
     // (ragged batch: conv_chainw_kernel zeroes its LDS tiles and its output behind every row's own end -- ChainArgs::lens)
     if (ragged && !env.mask_fused) return 0;  // (the separate-mask form has no place to mask inside a fused body)
     // Throughput regime: with >= ~2 wave tiles per SIMD the three convs run unfused on conv_direct3_kernel at 70-100 TFLOP/s
@@ -532,7 +534,7 @@ struct Runner {
   // 44.1 us for the three launches with their gaps, and the enhance as a whole 0.1 ms SLOWER with it.
   bool body_block3(const BlockL& Bk, const Tensor& hu, const Tensor& c1, const Tensor& c2, const Tensor& v, const std::string& nm,
                    const Epi& e1, const Epi& e3) {
-    if (dry || !ok() || env.block3 == 0 || B != 1 || ragged || st != main_st || !block3_bar || h->profile || h->tstamps ||
+    if (dry || !ok() || env.block3 == 0 || !Bk.all_prelu() || B != 1 || ragged || st != main_st || !block3_bar || h->profile || h->tstamps ||
         h->force_cfg >= 0 || env.conv_direct < 2)
       return false;
     const ConvArgs cv[3] = {conv_args(Bk.c1, hu, c1, e1), conv_args(Bk.c2, c1, c2, Epi()), conv_args(Bk.c3, c2, v, e3)};
@@ -548,8 +550,23 @@ struct Runner {
   // blocks.py:377-399: conv1 (+ cond add, FiLM: e1), conv2, conv3 (+ the block's residual), hu -> c1 -> c2 -> v.  One fused launch
   // on the wide, shallow levels (conv_chain kernels: all three, or conv1 + a fused (conv2, conv3)), else conv_block3_kernel or
   // three launches.  `need_c1`: the caller reads the raw conv1 result; `c1_private`: nobody but conv2 reads c1.
+  // The input of body conv L as its conv has to read it: `in` itself, or -- act_type snake / snakebeta -- its alias-free Snake in
+  // `plane` (one snake_act_kernel launch; the conv then runs with its activation off, ConvL::act = 0).  "none" and PReLU: `in`.
+  Tensor activated(const ConvL& L, const Tensor& in, const Tensor& plane) {
+    if (L.act_kind != OU_ACT_SNAKE && L.act_kind != OU_ACT_SNAKEBETA) return in;
+    Tensor s = plane;
+    s.C = in.C; s.T = in.T;
+    const Model& m = h->m;
+    const int* ln = lens_of(in.T);
+    launch("snake", [&] {
+      return launch_snake_act(in.p, s.p, B, in.C, in.T, in.T, ln, nullptr, W(L.sa_off), L.sb_off != L.sa_off ? W(L.sb_off) : nullptr,
+                              W(m.snake_up_off), W(m.snake_down_off), st);
+    });
+    return s;
+  }
+  // `act`: the block's plane for activated inputs (allocated by block() when a body conv has a Snake activation)
   void body(const BlockL& Bk, const Tensor& hu, const Tensor& c1, const Tensor& c2, const Tensor& v, const std::string& nm,
-            Epi e1, bool need_c1, bool c1_private) {
+            Epi e1, bool need_c1, bool c1_private, const Tensor& act = Tensor()) {
     const int depth = dry ? 0 : plan_chain(Bk, hu, c1, v, e1, need_c1);
     if (depth == 3 || depth == 2) {
       if (depth == 2) conv(Bk.c1, hu, nm + ".c1", e1, &c1);
@@ -578,10 +595,10 @@ struct Runner {
     // conv that produces them, so that the reader's operand path has no PReLU (ConvArgs::out_act; bit-identical)
     if (env.preact && c1_private && Bk.c2.act) { e1.out_act = true; e1.out_alpha = h->alphas[Bk.c2.a_off]; }
     Epi e2;
-    e2.act = !conv(Bk.c1, hu, nm + ".c1", e1, &c1).stored_act;
+    e2.act = !conv(Bk.c1, activated(Bk.c1, hu, act), nm + ".c1", e1, &c1).stored_act;
     if (env.preact && Bk.c3.act) { e2.out_act = true; e2.out_alpha = h->alphas[Bk.c3.a_off]; }
-    e3.act = !conv(Bk.c2, c1, nm + ".c2", e2, &c2).stored_act;
-    conv(Bk.c3, c2, nm + ".v", e3, &v);
+    e3.act = !conv(Bk.c2, activated(Bk.c2, c1, act), nm + ".c2", e2, &c2).stored_act;
+    conv(Bk.c3, activated(Bk.c3, c2, act), nm + ".v", e3, &v);
   }
 
   // blocks.py:401-410: the block's output brought to the next block's rate
@@ -619,7 +636,10 @@ struct Runner {
     o.c1 = c1_dst ? *c1_dst : alloc(nm + ".c1", Bk.c1.Cout, hu.T);
     const Tensor c2 = alloc(nm + ".c2", Bk.c2.Cout, hu.T);
     o.v = v_dst ? *v_dst : alloc(nm + ".v", Bk.c3.Cout, hu.T);
-    body(Bk, hu, o.c1, c2, o.v, nm, e1, need_c1, !need_c1 && !c1_dst);
+    // (a plane per block, from the walk's own bump allocator: blocks of the conditioner and of the first score-encoder pass run
+    // side by side on different streams; a model without Snake layers allocates nothing here)
+    const Tensor act = Bk.has_snake() ? alloc(nm + ".act", Bk.C, hu.T) : Tensor();
+    body(Bk, hu, o.c1, c2, o.v, nm, e1, need_c1, !need_c1 && !c1_dst, act);
     o.h_next = down_path(Bk, o.v, nm);
     return o;
   }
@@ -2731,6 +2751,45 @@ int ou_resample(const float* x, int64_t x_stride, const int64_t* len_host, float
                                          y_stride, cols, blk, n, pl.orig, pl.nw, pl.taps, copy ? nullptr : table,
                                          (hipStream_t)stream);
     if (e != hipSuccess) return fail(nullptr, OU_EHIP, std::string("HIP error at resample: ") + hipGetErrorString(e));
+  }
+  return OU_OK;
+}
+
+int32_t ou_snake_tile(void) { return snake_tile(); }
+
+int ou_snake_act(const float* x, float* y, int32_t B, int32_t C, int32_t T, int64_t row_stride, const int32_t* len_host,
+                 const float* exp_alpha, const float* exp_beta, const float* up_kernel, const float* down_kernel,
+                 ou_stream_t stream) {
+  // everything is decided here, on the host, before the first HIP call
+  if (!x || !y || !exp_alpha || !up_kernel || !down_kernel) return fail(nullptr, OU_EINVAL, "ou_snake_act: null argument");
+  if (B < 1 || C < 1 || T < 1) return fail(nullptr, OU_EINVAL, "ou_snake_act: B, C and T must be at least 1");
+  if (C > 65535) return fail(nullptr, OU_EINVAL, "ou_snake_act: at most 65535 channels");
+  if (T > 0x7fffffff - 1024) return fail(nullptr, OU_EINVAL, "ou_snake_act: T must not exceed 2^31 - 1024");
+  if (row_stride < T) return fail(nullptr, OU_EINVAL, "ou_snake_act: row_stride must be at least T");
+  // 64-bit offsets of the kernel: (b * C + c) * row_stride + t, in floats
+  if ((long long)row_stride > (1ll << 60) / ((long long)B * C))
+    return fail(nullptr, OU_EINVAL, "ou_snake_act: B * C * row_stride overflows the 64-bit offsets (at most 2^60)");
+  if (len_host)
+    for (int b = 0; b < B; b++)
+      if (len_host[b] < 0 || len_host[b] > T) return fail(nullptr, OU_EINVAL, "ou_snake_act: 0 <= len[b] <= T");
+  if (!len_host) {
+    for (int off = 0; off < B; off += 65535) {  // (the grid's z extent)
+      const int n = B - off < 65535 ? B - off : 65535;
+      const size_t skip = (size_t)off * (size_t)C * (size_t)row_stride;
+      const hipError_t e = launch_snake_act(x + skip, y + skip, n, C, T, row_stride, nullptr, nullptr, exp_alpha, exp_beta, up_kernel,
+                                            down_kernel, (hipStream_t)stream);
+      if (e != hipSuccess) return fail(nullptr, OU_EHIP, std::string("ou_snake_act: ") + hipGetErrorString(e));
+    }
+    return OU_OK;
+  }
+  for (int off = 0; off < B; off += kSnakeRowsPerLaunch) {
+    SnakeRows blk;
+    const int n = B - off < kSnakeRowsPerLaunch ? B - off : kSnakeRowsPerLaunch;
+    for (int i = 0; i < kSnakeRowsPerLaunch; i++) blk.len[i] = i < n ? len_host[off + i] : 0;
+    const size_t skip = (size_t)off * (size_t)C * (size_t)row_stride;
+    const hipError_t e = launch_snake_act(x + skip, y + skip, n, C, T, row_stride, nullptr, &blk, exp_alpha, exp_beta, up_kernel,
+                                          down_kernel, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, OU_EHIP, std::string("ou_snake_act: ") + hipGetErrorString(e));
   }
   return OU_OK;
 }

@@ -438,4 +438,16 @@ hipError_t launch_decoupling(const float* aux, const float* alpha_exp, const flo
                              const float* w, const float* bias, float* tmp_up, float* out, int B, int C, int T,
                              hipStream_t st, const int* lens = nullptr, const int* lens2 = nullptr);
 
+// Alias-free Snake of a whole (B, C, T) tensor in one launch (ou_snake.hip; ou_snake_act of include/ouniverse.h): row (b, c)
+// starts at (b * C + c) * row_stride.  The rows' lengths: `lens_dev` (B ints on the device: the ragged walk), else `rows` (by
+// value, B <= kSnakeRowsPerLaunch: the stateless entry point), else every row is T long.
+constexpr int kSnakeRowsPerLaunch = 64;
+struct SnakeRows {
+  int len[kSnakeRowsPerLaunch];
+};
+int snake_tile();
+hipError_t launch_snake_act(const float* x, float* y, int B, int C, int T, long long row_stride, const int* lens_dev,
+                            const SnakeRows* rows, const float* exp_alpha, const float* exp_beta, const float* up_k,
+                            const float* down_k, hipStream_t st);
+
 }  // namespace ou

@@ -73,6 +73,8 @@ std::string make_conv(ConvL& L, Alloc& a, const std::string& name, int kind, int
   L.name = name;
   L.kind = kind;
   L.act = act ? 1 : 0;
+  L.wrapped = L.act;
+  L.act_kind = act ? OU_ACT_PRELU : OU_ACT_NONE;
   L.rate = rate;
   switch (kind) {
     case CK_CONV:
@@ -109,7 +111,9 @@ std::string make_conv(ConvL& L, Alloc& a, const std::string& name, int kind, int
   return finish_conv(L, a);
 }
 
-std::string make_block(BlockL& B, Alloc& a, const std::string& name, int C, int dir, int rate, bool aa) {
+// `act_cfg`: the *_act field of ou_config that governs the block (0 = not set = PReLU), see body_act()
+int body_act(int act_cfg) { return act_cfg == 0 ? OU_ACT_PRELU : act_cfg == OU_ACT_IDENTITY ? OU_ACT_NONE : act_cfg; }
+std::string make_block(BlockL& B, Alloc& a, const std::string& name, int C, int dir, int rate, bool aa, int act_cfg = 0) {
   B = BlockL();
   B.name = name; B.C = C; B.dir = dir; B.rate = rate;
   std::string e;
@@ -119,6 +123,8 @@ std::string make_block(BlockL& B, Alloc& a, const std::string& name, int C, int 
   if (!(e = make_conv(B.c1, a, name + ".conv1", CK_CONV, C, C, 5, 1, false, true)).empty()) return e;
   if (!(e = make_conv(B.c2, a, name + ".conv2", CK_CONV, C, C, 3, 1, false, true)).empty()) return e;
   if (!(e = make_conv(B.c3, a, name + ".conv3", CK_CONV, C, C, 3, 1, false, true)).empty()) return e;
+  // blocks.py:289-312: act_type reaches conv1 .. conv3 only (the rate-change conv keeps the PReLU_Conv default)
+  for (ConvL* l : {&B.c1, &B.c2, &B.c3}) { l->act_kind = body_act(act_cfg); l->act = l->act_kind == OU_ACT_PRELU; }
   return "";
 }
 
@@ -133,6 +139,9 @@ std::string make_gru(GruL& G, Alloc& a, const std::string& name, int layer, int 
   return "";
 }
 
+const char* act_name(int kind) {
+  return kind == OU_ACT_PRELU ? "prelu" : kind == OU_ACT_SNAKE ? "snake" : kind == OU_ACT_SNAKEBETA ? "snakebeta" : "none";
+}
 void json_conv(std::ostringstream& os, const ConvL& L, bool& first) {
   if (!first) os << ",\n";
   first = false;
@@ -141,7 +150,8 @@ void json_conv(std::ostringstream& os, const ConvL& L, bool& first) {
      << ",\"M\":" << L.M << ",\"Mp\":" << L.Mp << ",\"CK\":" << L.CK << ",\"rate\":" << L.rate << ",\"act\":" << L.act
      << ",\"w_off\":" << L.w_off << ",\"b_off\":" << L.b_off << ",\"a_off\":" << L.a_off
      << ",\"fir_mode\":" << L.fir_mode << ",\"fir_len\":" << L.fir_len << ",\"fir_off\":" << L.fir_off
-     << ",\"fbias_off\":" << L.fbias_off << ",\"wd_off\":" << L.wd_off << ",\"wu_off\":" << L.wu_off << ",\"KWP\":" << L.KWP << ",\"ws_on\":" << L.ws_on << ",\"ws_off\":" << L.ws_off << ",\"wsw_on\":" << L.wsw_on << ",\"wsw_off\":" << L.wsw_off << "}";
+     << ",\"fbias_off\":" << L.fbias_off << ",\"wd_off\":" << L.wd_off << ",\"wu_off\":" << L.wu_off << ",\"KWP\":" << L.KWP << ",\"ws_on\":" << L.ws_on << ",\"ws_off\":" << L.ws_off << ",\"wsw_on\":" << L.wsw_on << ",\"wsw_off\":" << L.wsw_off
+     << ",\"activation\":\"" << act_name(L.act_kind) << "\",\"sa_off\":" << L.sa_off << ",\"sb_off\":" << L.sb_off << "}";
 }
 void json_block(std::ostringstream& os, const BlockL& B, bool& first) {
   if (B.dir) json_conv(os, B.rc, first);
@@ -157,6 +167,9 @@ std::string build_model(const ou_config& cfg, Model& m) {
   m.cfg = cfg;
   if (cfg.abi_version != OU_ABI_VERSION) return "ou_config.abi_version mismatch";
   if (cfg.fir_fold < 0 || cfg.fir_fold > 3) return "ou_config.fir_fold must be 0 .. 3";
+  for (int v : {cfg.score_enc_act, cfg.score_dec_act, cfg.cond_enc_act, cfg.cond_dec_act})
+    if (v != 0 && v != OU_ACT_PRELU && v != OU_ACT_SNAKE && v != OU_ACT_SNAKEBETA && v != OU_ACT_IDENTITY)
+      return "ou_config.*_act must be 0, OU_ACT_PRELU, OU_ACT_SNAKE, OU_ACT_SNAKEBETA or OU_ACT_IDENTITY";
   g_fir_fold = cfg.fir_fold;
   g_no_split = cfg.no_split_copy != 0;
   const ou_net_config& s = cfg.score;
@@ -209,8 +222,8 @@ std::string build_model(const ou_config& cfg, Model& m) {
   int frow = 0;
   for (int i = 0; i < m.n_blocks; i++) {
     int C = C0 << (i < n ? i : n);
-    if (i < n) e = make_block(m.s_enc[i], a, sp + ".encoder.ds_modules." + std::to_string(i), C, 1, s.rate_factors[i], aa);
-    else e = make_block(m.s_enc[i], a, sp + ".encoder.ds_modules." + std::to_string(i), C, 0, 1, false);
+    if (i < n) e = make_block(m.s_enc[i], a, sp + ".encoder.ds_modules." + std::to_string(i), C, 1, s.rate_factors[i], aa, cfg.score_enc_act);
+    else e = make_block(m.s_enc[i], a, sp + ".encoder.ds_modules." + std::to_string(i), C, 0, 1, false, cfg.score_enc_act);
     if (!e.empty()) return e;
     m.film.enc_off.push_back(frow);
     frow += 2 * C;
@@ -224,7 +237,7 @@ std::string build_model(const ou_config& cfg, Model& m) {
       if (j == 0) { C = OC; dir = 0; rate = 1; }
       else { C = C0 << (n - j); dir = 2; rate = s.rate_factors[n - j]; }
     } else { C = C0 << (n - j - 1); dir = 2; rate = s.rate_factors[n - j - 1]; }
-    if (!(e = make_block(m.s_dec[j], a, sp + ".decoder.up_modules." + std::to_string(j), C, dir, rate, aa)).empty()) return e;
+    if (!(e = make_block(m.s_dec[j], a, sp + ".decoder.up_modules." + std::to_string(j), C, dir, rate, aa, cfg.score_dec_act)).empty()) return e;
     if (!(e = make_conv(m.s_sig[j], a, sp + ".decoder.signal_cond_proj." + std::to_string(j), CK_CONV, C, C, 1, 1, false, false)).empty()) return e;
     m.film.dec_off.push_back(frow);
     frow += 2 * C;
@@ -254,8 +267,8 @@ std::string build_model(const ou_config& cfg, Model& m) {
   m.c_enc.resize(m.n_blocks);
   for (int i = 0; i < m.n_blocks; i++) {
     int C = C0 << (i < n ? i : n);
-    if (i < n) e = make_block(m.c_enc[i], a, cp + ".encoder.ds_modules." + std::to_string(i), C, 1, c.rate_factors[i], false);
-    else e = make_block(m.c_enc[i], a, cp + ".encoder.ds_modules." + std::to_string(i), C, 0, 1, false);
+    if (i < n) e = make_block(m.c_enc[i], a, cp + ".encoder.ds_modules." + std::to_string(i), C, 1, c.rate_factors[i], false, cfg.cond_enc_act);
+    else e = make_block(m.c_enc[i], a, cp + ".encoder.ds_modules." + std::to_string(i), C, 0, 1, false, cfg.cond_enc_act);
     if (!e.empty()) return e;
   }
   m.c_st.resize(n - 1);
@@ -266,9 +279,9 @@ std::string build_model(const ou_config& cfg, Model& m) {
   }
   if (!(e = make_gru(m.c_gru0, a, cp + ".encoder.gru", 0, OC, OC / 2)).empty()) return e;
   if (!(e = make_gru(m.c_gru1, a, cp + ".encoder.gru", 1, OC, OC / 2)).empty()) return e;
-  if (!(e = make_block(m.c_cb1, a, cp + ".encoder.conv_block1", OC, 0, 1, false)).empty()) return e;
-  if (!(e = make_block(m.c_cb2, a, cp + ".encoder.conv_block2", OC, 0, 1, false)).empty()) return e;
-  if (!(e = make_block(m.c_decin, a, cp + ".decoder.input_conv_block", OC, 0, 1, false)).empty()) return e;
+  if (!(e = make_block(m.c_cb1, a, cp + ".encoder.conv_block1", OC, 0, 1, false, cfg.cond_enc_act)).empty()) return e;
+  if (!(e = make_block(m.c_cb2, a, cp + ".encoder.conv_block2", OC, 0, 1, false, cfg.cond_enc_act)).empty()) return e;
+  if (!(e = make_block(m.c_decin, a, cp + ".decoder.input_conv_block", OC, 0, 1, false, cfg.cond_dec_act)).empty()) return e;
   m.c_dec.resize(m.n_blocks);
   for (int j = 0; j < m.n_blocks; j++) {
     int C, dir, rate;
@@ -276,7 +289,7 @@ std::string build_model(const ou_config& cfg, Model& m) {
       if (j == 0) { C = OC; dir = 0; rate = 1; }
       else { C = C0 << (n - j); dir = 2; rate = c.rate_factors[n - j]; }
     } else { C = C0 << (n - j - 1); dir = 2; rate = c.rate_factors[n - j - 1]; }
-    if (!(e = make_block(m.c_dec[j], a, cp + ".decoder.up_modules." + std::to_string(j), C, dir, rate, c.use_antialiasing != 0)).empty()) return e;
+    if (!(e = make_block(m.c_dec[j], a, cp + ".decoder.up_modules." + std::to_string(j), C, dir, rate, c.use_antialiasing != 0, cfg.cond_dec_act)).empty()) return e;
   }
   // ---- signal decoupling layer (UNIVERSE++ aux_to_wav) ----------------------------------------------
   m.dec = DecouplingL();
@@ -286,11 +299,30 @@ std::string build_model(const ou_config& cfg, Model& m) {
     m.dec.conv.name = "signal_decoupling_layer.conv"; m.dec.conv.Cin = C0; m.dec.conv.Cout = 1; m.dec.conv.KW = 3;
     m.dec.conv.w_off = a.take((size_t)C0 * 3); m.dec.conv.b_off = a.take(1);
   }
+  // ---- Snake activations (encoder_act_type / decoder_act_type): behind everything else, so that a model without them keeps
+  // the layout it always had.  exp(alpha) [, exp(beta)] per channel and layer, then the model's one copy of the two kernels.
+  {
+    std::vector<BlockL*> blocks;
+    for (auto& b : m.s_enc) blocks.push_back(&b);
+    for (auto& b : m.s_dec) blocks.push_back(&b);
+    for (auto& b : m.c_enc) blocks.push_back(&b);
+    blocks.push_back(&m.c_cb1); blocks.push_back(&m.c_cb2); blocks.push_back(&m.c_decin);
+    for (auto& b : m.c_dec) blocks.push_back(&b);
+    for (BlockL* b : blocks)
+      for (ConvL* l : {&b->c1, &b->c2, &b->c3}) {
+        if (l->act_kind != OU_ACT_SNAKE && l->act_kind != OU_ACT_SNAKEBETA) continue;
+        l->sa_off = a.take(l->Cin);
+        l->sb_off = l->act_kind == OU_ACT_SNAKEBETA ? a.take(l->Cin) : l->sa_off;
+        m.n_snake++;
+      }
+    if (m.n_snake) { m.snake_up_off = a.take(30); m.snake_down_off = a.take(28); }
+  }
   m.total_floats = a.n;
 
   std::ostringstream os;
   os << "{\"total_floats\":" << m.total_floats << ",\"tot_ds\":" << m.tot_ds << ",\"film_rows\":" << m.film.rows
-     << ",\"film_w_off\":" << m.film.w_off << ",\"film_b_off\":" << m.film.b_off << ",\n\"convs\":[\n";
+     << ",\"film_w_off\":" << m.film.w_off << ",\"film_b_off\":" << m.film.b_off << ",\"n_snake\":" << m.n_snake
+     << ",\"snake_up_off\":" << m.snake_up_off << ",\"snake_down_off\":" << m.snake_down_off << ",\n\"convs\":[\n";
   bool first = true;
   for (auto& b : m.s_enc) json_block(os, b, first);
   json_conv(os, m.s_gru.proj, first);
@@ -316,11 +348,34 @@ std::string build_model(const ou_config& cfg, Model& m) {
 // ======================================================================================================
 namespace {
 
+// torchaudio's resampling kernel for orig -> nw (already reduced), [nw][2 width + orig] with width = ceil(6 orig / base):
+// k[p][i] = sinc(pi t) cos^2(pi t / 12) base / orig, t = clamp((-p / nw + (i - width) / orig) base, -6, 6) -- the definition
+// ouniverse.h states for ou_resample, evaluated in the same order in double
+void sinc_resample_kernel(int orig, int nw, std::vector<float>& k) {
+  const double pi = 3.14159265358979323846;
+  const double base = (orig < nw ? orig : nw) * 0.99;
+  const int width = (int)std::ceil(6.0 * orig / base);
+  const int n = 2 * width + orig;
+  k.assign((size_t)nw * n, 0.f);
+  for (int p = 0; p < nw; p++)
+    for (int i = 0; i < n; i++) {
+      double t = ((double)(-p) / nw + (double)(i - width) / orig) * base;
+      t = t < -6.0 ? -6.0 : (t > 6.0 ? 6.0 : t);
+      const double c = std::cos(t * pi / 6.0 / 2.0);
+      const double window = c * c;
+      t *= pi;
+      const double sinc = t == 0.0 ? 1.0 : std::sin(t) / t;
+      k[(size_t)p * n + i] = (float)(sinc * (window * (base / orig)));
+    }
+}
+
 struct Packer {
   const std::map<std::string, HostTensor>& sd;
   std::vector<float>& blob;
   std::string err;
   int code = OU_OK;
+  const Model* model = nullptr;
+  bool snake_up_set = false, snake_down_set = false;
 
   const HostTensor* get(const std::string& key, std::initializer_list<int64_t> shape) {
     auto it = sd.find(key);
@@ -435,15 +490,55 @@ struct Packer {
     std::vector<double> w, W;
     std::vector<double> bias(L.Cout, 0.0);
     const std::string& p = L.name;
-    if (L.act) {
-      const HostTensor* a = get(p + ".prelu.weight", {1});
-      if (!a) return;
-      blob[L.a_off] = a->data[0];
+    if (L.wrapped) {
+      // the checkpoint's activation tensors must be those of the configured act_type (blocks.py:176-187)
+      const std::string k_prelu = p + ".prelu.weight", k_alpha = p + ".prelu.act.act.alpha", k_beta = p + ".prelu.act.act.beta";
+      const bool snake = L.act_kind == OU_ACT_SNAKE || L.act_kind == OU_ACT_SNAKEBETA;
+      const std::string* stray = nullptr;
+      if (L.act_kind != OU_ACT_PRELU && has(k_prelu)) stray = &k_prelu;
+      else if (!snake && has(k_alpha)) stray = &k_alpha;
+      else if (L.act_kind != OU_ACT_SNAKEBETA && has(k_beta)) stray = &k_beta;
+      if (stray) {
+        if (err.empty()) {
+          err = "activation mismatch at " + p + ": the configured act_type is '" + act_name(L.act_kind) + "', the checkpoint carries " + *stray;
+          code = OU_EMISSING;
+        }
+        return;
+      }
+      if (L.act_kind == OU_ACT_PRELU) {
+        const HostTensor* a = get(k_prelu, {1});
+        if (!a) return;
+        blob[L.a_off] = a->data[0];
+      } else if (snake) {
+        // log-scale parameters (alpha_logscale=True): the kernel gets exp(alpha), exp(beta), as the decoupling layer's does
+        const HostTensor* al = get(k_alpha, {L.Cin});
+        if (!al) return;
+        for (int i = 0; i < L.Cin; i++) blob[L.sa_off + i] = std::exp(al->data[i]);
+        if (L.act_kind == OU_ACT_SNAKEBETA) {
+          const HostTensor* be = get(k_beta, {L.Cin});
+          if (!be) return;
+          for (int i = 0; i < L.Cin; i++) blob[L.sb_off + i] = std::exp(be->data[i]);
+        }
+        // the Resample kernels are buffers, the same in every layer: taken from a checkpoint that carries them
+        const std::string k_up = p + ".prelu.act.upsample.kernel", k_dn = p + ".prelu.act.downsample.kernel";
+        if (has(k_up)) {
+          const HostTensor* up = get(k_up, {2, 1, 15});
+          if (!up) return;
+          putf(model->snake_up_off, up->data.data(), 30);
+          snake_up_set = true;
+        }
+        if (has(k_dn)) {
+          const HostTensor* dn = get(k_dn, {1, 1, 28});
+          if (!dn) return;
+          putf(model->snake_down_off, dn->data.data(), 28);
+          snake_down_set = true;
+        }
+      }
     }
     switch (L.kind) {
       case CK_CONV: {
         // PReLU_Conv wraps the conv as "<p>.conv"; bare convs (mel conv, signal_cond_proj) are "<p>" itself
-        std::string cpfx = L.act ? p + ".conv" : p;
+        std::string cpfx = L.wrapped ? p + ".conv" : p;
         if (!eff_weight(cpfx, {L.Cout, L.Cin, L.KW}, W)) return;
         const HostTensor* b = get(cpfx + ".bias", {L.Cout});
         if (!b) return;
@@ -594,6 +689,7 @@ std::string pack_weights(const Model& m, const std::map<std::string, HostTensor>
                          int& code) {
   blob.assign(m.total_floats, 0.0f);
   Packer P{sd, blob};
+  P.model = &m;
   const std::string& sp = m.score_prefix;
   // sigma block
   if (m.sigma.simple) {
@@ -702,6 +798,13 @@ std::string pack_weights(const Model& m, const std::map<std::string, HostTensor>
     const HostTensor* w = P.get(p + ".conv.weight", {1, m.dec.C, 3});
     const HostTensor* b = P.get(p + ".conv.bias", {1});
     if (w && b) { P.putf(m.dec.conv.w_off, w->data.data(), (size_t)m.dec.C * 3); blob[m.dec.conv.b_off] = b->data[0]; }
+  }
+  // a checkpoint without the Resample buffers (torchaudio registers them non-persistent in some versions): the documented
+  // sinc_interp_hann kernel (lowpass_filter_width 6, rolloff 0.99), in double, rounded once
+  if (m.n_snake) {
+    std::vector<float> k;
+    if (!P.snake_up_set) { sinc_resample_kernel(1, 2, k); P.putf(m.snake_up_off, k.data(), 30); }
+    if (!P.snake_down_set) { sinc_resample_kernel(2, 1, k); P.putf(m.snake_down_off, k.data(), 28); }
   }
   code = P.code;
   return P.err;

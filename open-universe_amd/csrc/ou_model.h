@@ -23,6 +23,10 @@ struct ConvL {
   int CK = 2;             // input-channel chunk (power of two, divides Cin)
   int rate = 1;           // original rate-change factor (down/up/st convs)
   int act = 0;            // PReLU prologue
+  int wrapped = 0;        // a PReLU_Conv (blocks.py:133-227): the conv's tensors live under "<name>.conv", the activation under "<name>.prelu"
+  int act_kind = OU_ACT_NONE;  // OU_ACT_*: what that PReLU_Conv applies in front of its conv.  `act` is 1 for OU_ACT_PRELU alone: a Snake
+                               // layer's activation is a launch of its own (snake_act_kernel), its conv runs with act = 0
+  size_t sa_off = 0, sb_off = 0;  // Snake: exp(alpha)[Cin], exp(beta)[Cin] (snakebeta; else sb_off = sa_off)
   size_t wd_off = 0;      // stride-1 k3 / k5 layers: second copy of the weights with the taps innermost, [Cin][Mp][KWP]
   int KWP = 0;            // ... 4 (k3) / 8 (k5); 0 = no such copy
   size_t wu_off = 0;      // ... and a third copy in the Winograd / Cook-Toom domain, U = G w: F(2, 3) -> 4 floats, F(2, 5) -> 6 (of
@@ -59,6 +63,14 @@ struct BlockL {  // ConvBlock (blocks.py:230-412)
   int dir = 0;   // 0 none, 1 down, 2 up
   int rate = 1;
   ConvL rc, c1, c2, c3;
+  // a body conv with a Snake activation: the walk needs a plane for the activated input, and no fused body takes the block
+  bool has_snake() const {
+    for (const ConvL* l : {&c1, &c2, &c3})
+      if (l->act_kind == OU_ACT_SNAKE || l->act_kind == OU_ACT_SNAKEBETA) return true;
+    return false;
+  }
+  // ... or with none at all (act_type "none"): not a body for the fused kernels either
+  bool all_prelu() const { return c1.act_kind == OU_ACT_PRELU && c2.act_kind == OU_ACT_PRELU && c3.act_kind == OU_ACT_PRELU; }
 };
 
 struct GruL {  // one bidirectional GRU layer
@@ -129,6 +141,11 @@ struct Model {
   BlockL c_cb1, c_cb2, c_decin;
   GruL c_gru0, c_gru1;
   DecouplingL dec;
+  // the two resampling kernels of the Snake layers' Activation1d (alias_free_act.py:21-22), one copy for the whole model; present
+  // only when a ConvBlock has a Snake activation -- an all-PReLU model's blob is what it was before these existed
+  int n_snake = 0;
+  size_t snake_up_off = 0;    // (2, 15)
+  size_t snake_down_off = 0;  // (28)
   size_t total_floats = 0;
   std::string json;  // plan description
 };

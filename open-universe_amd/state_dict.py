@@ -37,25 +37,40 @@ def _linear(p, cout, cin, wn) -> List[Entry]:
     return [(p + ".weight", (cout, cin), True), (p + ".bias", (cout,), True)]
 
 
-def _prelu_conv(p, cin, cout, k, wn, aa=False, transpose=False) -> List[Entry]:
+def _activation(p, cin, act) -> List[Entry]:
+    """What PReLU_Conv registers as `prelu` for its act_type (blocks.py:176-187): a PReLU slope; AliasFreeSnake -> Activation1d ->
+    Snake / SnakeBeta (bigvgan/snake.py:131-154, alias_free_act.py:17-22): alpha [, beta], then the two Resample kernels; nothing."""
+    if act == "prelu":
+        return [(p + ".prelu.weight", (1,), True)]
+    if act in ("snake", "snakebeta"):
+        out = [(p + ".prelu.act.act.alpha", (cin,), True)]
+        if act == "snakebeta":
+            out += [(p + ".prelu.act.act.beta", (cin,), True)]
+        return out + [(p + ".prelu.act.upsample.kernel", (2, 1, 15), False), (p + ".prelu.act.downsample.kernel", (1, 1, 28), False)]
+    if act == "none":
+        return []
+    raise ValueError(f"'act_type' should be one of [prelu | snake | snakebeta | none], got {act!r}")
+
+
+def _prelu_conv(p, cin, cout, k, wn, aa=False, transpose=False, act="prelu") -> List[Entry]:
     """blocks.py:133-203 registration order: [bias, low_pass_filter.weights], prelu, conv."""
     out: List[Entry] = []
     if aa:
         out += [(p + ".bias", (cout,), True), (p + ".low_pass_filter.weights", (2 * k + 1,), False)]
-    out += [(p + ".prelu.weight", (1,), True)]
+    out += _activation(p, cin, act)
     out += _conv(p + ".conv", cout, cin, k, wn, bias=not aa, transpose=transpose)
     return out
 
 
-def _conv_block(p, c, wn, rate=None, direction="none", aa=False) -> List[Entry]:
-    """blocks.py:236-312: rate_change_conv is registered before conv1..3."""
+def _conv_block(p, c, wn, rate=None, direction="none", aa=False, act="prelu") -> List[Entry]:
+    """blocks.py:236-312: rate_change_conv is registered before conv1..3; `act` (act_type) reaches conv1..3 only."""
     out: List[Entry] = []
     if direction == "down":
         out += _prelu_conv(p + ".rate_change_conv", c, 2 * c, rate, wn, aa)
     elif direction == "up":
         out += _prelu_conv(p + ".rate_change_conv", 2 * c, c, rate, wn, aa, transpose=True)
     for name, k in (("conv1", 5), ("conv2", 3), ("conv3", 3)):
-        out += _prelu_conv(f"{p}.{name}", c, c, k, wn)
+        out += _prelu_conv(f"{p}.{name}", c, c, k, wn, act=act)
     return out
 
 
@@ -73,6 +88,7 @@ def _gru(p, inp, hid, layers) -> List[Entry]:
 def score_schema(p: str, s: NetSpec) -> List[Entry]:
     """score.py:213-273 ScoreNetwork (+ encoder :26-102, decoder :130-194)."""
     c0, rates, wn, aa, D = s.n_channels, s.rate_factors, s.use_weight_norm, s.use_antialiasing, s.noise_cond_dim
+    ea, da = getattr(s, "encoder_act_type", "prelu"), getattr(s, "decoder_act_type", "prelu")
     out: List[Entry] = []
     if s.time_embedding == "simple":
         out += [(p + ".sigma_block.weight", (1, 1), True), (p + ".sigma_block.bias", (1, 1), True)]
@@ -87,9 +103,9 @@ def score_schema(p: str, s: NetSpec) -> List[Entry]:
     n = len(rates)
     oc = c0 * 2 ** n
     for i, r in enumerate(rates):
-        out += _conv_block(f"{p}.encoder.ds_modules.{i}", c0 * 2 ** i, wn, r, "down", aa)
+        out += _conv_block(f"{p}.encoder.ds_modules.{i}", c0 * 2 ** i, wn, r, "down", aa, act=ea)
     if s.extra_conv_block:
-        out += _conv_block(f"{p}.encoder.ds_modules.{n}", oc, wn)
+        out += _conv_block(f"{p}.encoder.ds_modules.{n}", oc, wn, act=ea)
     for i in range(n):
         out += _linear(f"{p}.encoder.cond_proj.{i}", c0 * 2 ** (i + 1), D, wn)
     if s.extra_conv_block:
@@ -99,7 +115,7 @@ def score_schema(p: str, s: NetSpec) -> List[Entry]:
     up = rates[::-1]
     blocks = ([(oc, None, "none")] if s.extra_conv_block else []) + [(c, r, "up") for c, r in zip(chans, up)]
     for j, (c, r, d) in enumerate(blocks):
-        out += _conv_block(f"{p}.decoder.up_modules.{j}", c, wn, r, d, aa)
+        out += _conv_block(f"{p}.decoder.up_modules.{j}", c, wn, r, d, aa, act=da)
     for j, (c, r, d) in enumerate(blocks):
         out += _linear(f"{p}.decoder.noise_cond_proj.{j}", 2 * c, D, wn)
     for j, (c, r, d) in enumerate(blocks):
@@ -112,6 +128,7 @@ def score_schema(p: str, s: NetSpec) -> List[Entry]:
 def cond_schema(p: str, c: NetSpec) -> List[Entry]:
     """condition.py:273-342 ConditionerNetwork (MelAdapter :68-90, encoder :117-187, decoder :223-262)."""
     c0, rates, wn = c.n_channels, c.rate_factors, c.use_weight_norm
+    ea, da = getattr(c, "encoder_act_type", "prelu"), getattr(c, "decoder_act_type", "prelu")
     n = len(rates)
     oc = c0 * 2 ** n
     hop = math.prod(rates)
@@ -122,19 +139,19 @@ def cond_schema(p: str, c: NetSpec) -> List[Entry]:
     out += _conv(p + ".input_mel.conv", oc, c.n_mels, 3, wn)
     out += _conv_block(p + ".input_mel.conv_block", oc, wn)
     for i, r in enumerate(rates):  # encoder never uses anti-aliasing (condition.py:333)
-        out += _conv_block(f"{p}.encoder.ds_modules.{i}", c0 * 2 ** i, wn, r, "down", False)
+        out += _conv_block(f"{p}.encoder.ds_modules.{i}", c0 * 2 ** i, wn, r, "down", False, act=ea)
     if c.extra_conv_block:
-        out += _conv_block(f"{p}.encoder.ds_modules.{n}", oc, wn)
+        out += _conv_block(f"{p}.encoder.ds_modules.{n}", oc, wn, act=ea)
     for i in range(n - 1):  # make_st_convs condition.py:33-65
         out += _prelu_conv(f"{p}.encoder.st_convs.{i}", c0 * 2 ** i, oc, math.prod(rates[i:]), wn)
     out += _gru(p + ".encoder.gru", oc, oc // 2, 2)
-    out += _conv_block(p + ".encoder.conv_block1", oc, wn)
-    out += _conv_block(p + ".encoder.conv_block2", oc, wn)
-    out += _conv_block(p + ".decoder.input_conv_block", oc, wn)
+    out += _conv_block(p + ".encoder.conv_block1", oc, wn, act=ea)
+    out += _conv_block(p + ".encoder.conv_block2", oc, wn, act=ea)
+    out += _conv_block(p + ".decoder.input_conv_block", oc, wn, act=da)
     chans = [c0 * 2 ** (n - i - 1) for i in range(n)]
     blocks = ([(oc, None, "none")] if c.extra_conv_block else []) + [(ch, r, "up") for ch, r in zip(chans, rates[::-1])]
     for j, (ch, r, d) in enumerate(blocks):
-        out += _conv_block(f"{p}.decoder.up_modules.{j}", ch, wn, r, d, c.use_antialiasing)
+        out += _conv_block(f"{p}.decoder.up_modules.{j}", ch, wn, r, d, c.use_antialiasing, act=da)
     return out
 
 
@@ -256,8 +273,12 @@ def synthetic_state_dict(spec: ModelSpec, seed: int = 0, gain: float = 1.0, tail
                 v = v / 4.0  # the unit-RMS binomial FIR has a DC gain of 4..8
         elif "prelu.weight" in key or key.endswith(".prelu.weight"):
             v = 0.25 + 0.05 * rn(*shape)
-        elif leaf == "alpha":
+        elif leaf == "alpha" and key.startswith("signal_decoupling_layer"):
             v = 0.3 * rn(*shape)
+        elif leaf in ("alpha", "beta"):
+            # Snake layers of the networks: log-scale parameters spread over exp(+-1.5) (the reference's zero init, exp(0) = 1 in
+            # every channel, would hide a channel mix-up)
+            v = 0.75 * rn(*shape).clamp(-2.0, 2.0)
         elif key.endswith("sigma_block.weight"):
             v = torch.full(shape, 0.9)
         elif key.endswith("sigma_block.bias"):
