@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define OU_ABI_VERSION 7 /* 7: Snake activations of the ConvBlock body convs (ou_config tail score_enc_act .. cond_dec_act, OU_ACT_SNAKEBETA, ou_snake_act, ou_snake_tile: additive, the number stays -- a zeroed tail is the PReLU model); ensembles of segmented rows (ou_segments_ensemble_workspace_bytes, ou_enhance_segments_ensemble: additive, the number stays); segmented enhance of rows with lengths of their own (ou_segment_groups, ou_segments_var_workspace_bytes, ou_enhance_segments_var: additive, the number stays); ensembles in the library (ou_enhance_ensemble, ou_ensemble_workspace_bytes, ou_ensemble_reduce, ou_ensemble_reduce_scratch_bytes; option ens_share); existing entry points unchanged; 6: counter-based sampler noise (ou_set_noise_source, ou_noise_scratch_bytes, ou_noise_fill); existing entry points unchanged; 5: ou_enhance_var (batches whose rows have lengths of their own), workspace header carries the per-row geometry; ou_set_option / ou_get_option replace every OU_* environment switch (the library reads no environment variable), ou_config.fir_fold; 4: the packed blob carries a bf16-split weight copy (conv_split_kernel); 3: a Winograd-domain copy (round 5), ou_set_lane_batch, ou_lane_capacity */
+#define OU_ABI_VERSION 7 /* 7: level normalisation modes (ou_set_normalization, OU_NORM_*: additive, the number stays -- a handle nobody sets is normalization_norm 2 with zero_mean, and ou_config is what it was); Snake activations of the ConvBlock body convs (ou_config tail score_enc_act .. cond_dec_act, OU_ACT_SNAKEBETA, ou_snake_act, ou_snake_tile: additive, the number stays -- a zeroed tail is the PReLU model); ensembles of segmented rows (ou_segments_ensemble_workspace_bytes, ou_enhance_segments_ensemble: additive, the number stays); segmented enhance of rows with lengths of their own (ou_segment_groups, ou_segments_var_workspace_bytes, ou_enhance_segments_var: additive, the number stays); ensembles in the library (ou_enhance_ensemble, ou_ensemble_workspace_bytes, ou_ensemble_reduce, ou_ensemble_reduce_scratch_bytes; option ens_share); existing entry points unchanged; 6: counter-based sampler noise (ou_set_noise_source, ou_noise_scratch_bytes, ou_noise_fill); existing entry points unchanged; 5: ou_enhance_var (batches whose rows have lengths of their own), workspace header carries the per-row geometry; ou_set_option / ou_get_option replace every OU_* environment switch (the library reads no environment variable), ou_config.fir_fold; 4: the packed blob carries a bf16-split weight copy (conv_split_kernel); 3: a Winograd-domain copy (round 5), ou_set_lane_batch, ou_lane_capacity */
 
 enum {
   OU_OK = 0,
@@ -43,6 +43,8 @@ enum { OU_KIND_UNIVERSE = 0, OU_KIND_UNIVERSE_GAN = 1 };
 enum { OU_ACT_NONE = 0, OU_ACT_PRELU = 1, OU_ACT_SNAKE = 2, OU_ACT_SNAKEBETA = 3 };
 /* act_type "none" in the four *_act fields at the end of ou_config, where 0 has to mean "not set" = PReLU */
 #define OU_ACT_IDENTITY (-1)
+/* normalization_norm (utils/norm.py:31-44) for ou_set_normalization: 2 | "max" | "2-max" */
+enum { OU_NORM_2 = 0, OU_NORM_MAX = 1, OU_NORM_2MAX = 2 };
 
 #define OU_MAX_RATES 8
 
@@ -512,6 +514,20 @@ int ou_snake_act(const float* x, float* y, int32_t B, int32_t C, int32_t T, int6
 /* Consecutive outputs of one (row, channel) that one workgroup of ou_snake_act owns (tests sit on its edges). */
 int32_t ou_snake_tile(void);
 
+/* ---- level normalisation: normalization_norm and normalization_kwargs.zero_mean / .eps of the model yaml (utils/norm.py:22-87):
+ * how every enhance entry point (ou_enhance, _var, _ensemble, the four ou_enhance_segments*) levels a row before the networks
+ * see it.  With m the mean of the padded row, sd its unbiased std (around m) and mx = max |x - mu| over the padded row,
+ * mu = zero_mean ? m : 0, the row becomes (x - mu) * gain:
+ *   OU_NORM_2:    gain = level / max(sd, 1e-5)          OU_NORM_MAX:  gain = level / max(mx, 1e-5)
+ *   OU_NORM_2MAX: gain = min(level / max(sd, eps), 1 / max(mx, eps))
+ * level = 10^(ou_config.level_db / 20).  eps: 0 = 1e-5; as in the reference it reaches the OU_NORM_2MAX branch alone.
+ * A handle is created with (OU_NORM_2, 1, 0) -- every shipped config -- and then runs the kernels, launches and results it always
+ * had; neither the plan, the blob, ou_workspace_bytes nor the ou_segments*_workspace_bytes answers depend on the mode (the block
+ * maxima of the segmented statistics have their words in every segment workspace), so the call may come at any time between
+ * two enhance calls; Universe makes it right after ou_create.  A setter and not a field of ou_config: the struct's size is part of what version 7 callers compiled against.  ou_plan_json(handle) reports
+ * "norm", "zero_mean", "norm_eps".  OU_EINVAL: an unknown mode, zero_mean not 0 / 1, eps negative or not finite. */
+int ou_set_normalization(ou_handle* h, int32_t norm_mode, int32_t zero_mean, float eps);
+
 /* One sampler update on caller-owned buffers, for bindings that keep the reference's Python loop
  * (universe.py:339 `x = x + s_now^2 * eta * score + beta * z`, :343 `x = x + s_last^2 * score`):
  *   x[i] += c1 * score[i] + c2 * z[i]     over n = B*T elements; z may be NULL (last step).
@@ -597,7 +613,7 @@ const char* ou_option_doc(int32_t index);
 double ou_option_default(int32_t index);
 
 /* ---- introspection (tests, profiling) ------------------------------------------------------------------- */
-/* JSON description of the packed layers (name, kind, shapes, offsets into the blob, "activation": "prelu" | "snake" | "snakebeta" |
+/* JSON description of the packed layers (for a handle: "norm": "2" | "max" | "2-max", "zero_mean", "norm_eps", see ou_set_normalization; name, kind, shapes, offsets into the blob, "activation": "prelu" | "snake" | "snakebeta" |
  * "none" with the offsets of a Snake layer's exp(alpha) / exp(beta), and the offsets of the two Snake resampling kernels); for a handle also "options": the current
  * value of every ou_set_option key. */
 const char* ou_plan_json(const ou_handle* h);

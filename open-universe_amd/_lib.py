@@ -16,6 +16,9 @@ OU_KIND_UNIVERSE, OU_KIND_UNIVERSE_GAN = 0, 1
 OU_ACT_NONE, OU_ACT_PRELU, OU_ACT_SNAKE, OU_ACT_SNAKEBETA = 0, 1, 2, 3
 OU_ACT_IDENTITY = -1  # act_type "none" in the four *_act fields of ou_config, where 0 means "not set" = PReLU
 # encoder_act_type / decoder_act_type -> ou_config.*_act ("prelu" stays 0: the config of a PReLU model is what it always was)
+# normalization_norm -> the mode of ou_set_normalization
+OU_NORM_2, OU_NORM_MAX, OU_NORM_2MAX = 0, 1, 2
+NORM_MODES = {"2": OU_NORM_2, "max": OU_NORM_MAX, "2-max": OU_NORM_2MAX}
 BODY_ACTS = {"prelu": 0, "snake": OU_ACT_SNAKE, "snakebeta": OU_ACT_SNAKEBETA, "none": OU_ACT_IDENTITY}
 OU_ENH_KEEP_RMS, OU_ENH_USE_AUX_SIGNAL, OU_ENH_NO_PEAK_GUARD, OU_ENH_SERIAL = 1, 2, 4, 8
 OU_MAX_ENSEMBLE = 32
@@ -169,6 +172,7 @@ def load():
         "ou_sampler_step": (i32, [vp, vp, vp, vp, c_float, c_float, sz, vp]),
         "ou_snake_act": (i32, [vp, vp, i32, i32, i32, c_int64, POINTER(i32), vp, vp, vp, vp, vp]),
         "ou_snake_tile": (i32, []),
+        "ou_set_normalization": (i32, [vp, i32, i32, c_float]),
         "ou_set_gru_publish_mode": (i32, [vp, i32]),
         "ou_get_gru_publish_mode": (i32, [vp]),
         "ou_set_lanes": (i32, [vp, i32, i32]),
@@ -204,7 +208,7 @@ EXPORTED_SYMBOLS = [
     "ou_segments_var_ensemble_workspace_bytes", "ou_enhance_segments_var_ensemble",
     "ou_set_noise_source", "ou_noise_scratch_bytes", "ou_noise_fill",
     "ou_resample_plan", "ou_resample_table", "ou_resample_length", "ou_resample_tile", "ou_resample",
-    "ou_snake_act", "ou_snake_tile",
+    "ou_snake_act", "ou_snake_tile", "ou_set_normalization",
     "ou_set_option", "ou_get_option", "ou_reset_options", "ou_option_count", "ou_option_name", "ou_option_doc", "ou_option_default", "ou_plan_json",
     "ou_packer_plan_json", "ou_tensor", "ou_launch_stats", "ou_workspace_init", "ou_sampler_step",
     "ou_set_gru_publish_mode", "ou_get_gru_publish_mode", "ou_set_lanes", "ou_set_lane_batch", "ou_lane_capacity",
@@ -327,6 +331,18 @@ def resample_table(fs_in, fs_out):
     return raw[:4 * n].view(np.int32), raw[4 * n:].view(np.float32).reshape(plan["taps"], n), raw
 
 
+def norm_args(spec):
+    """ModelSpec.norm / zero_mean / norm_eps -> the arguments of ou_set_normalization (mode, zero_mean, eps).  (0, 1, 0.0) is
+    the handle's state after ou_create -- normalization_norm 2 with zero_mean, every shipped config -- and is never sent."""
+    norm = str(spec.norm)
+    if norm not in NORM_MODES:
+        raise NotImplementedError(f"Norm {norm} is not implemented for batch normalization")  # utils/norm.py:41-43
+    eps = float(spec.norm_eps)
+    if not eps > 0.0:
+        raise ValueError(f"normalization_kwargs.eps={eps!r} must be positive")
+    return NORM_MODES[norm], 1 if spec.zero_mean else 0, 0.0 if eps == 1e-5 else eps
+
+
 def make_config(spec, fir_fold=0, split_copy=True):
     """ModelSpec -> ou_config.  `fir_fold`, `split_copy`: packing choices (ou_config.fir_fold / .no_split_copy), the same for the
     packer and ou_create."""
@@ -377,6 +393,7 @@ def make_config(spec, fir_fold=0, split_copy=True):
     cfg.score_dec_act = body_act(spec.score, "decoder_act_type")
     cfg.cond_enc_act = body_act(spec.cond, "encoder_act_type")
     cfg.cond_dec_act = body_act(spec.cond, "decoder_act_type")
+    norm_args(spec)  # (an unknown norm is refused here, where every other key is; the values travel by ou_set_normalization)
     return cfg
 
 

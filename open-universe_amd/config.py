@@ -67,6 +67,11 @@ class ModelSpec:
     ema_decay: float = 0.0
     norm_ref: str = "both"                       # normalization_kwargs.ref (only the `target` mode looks at it)
     edm_data_level_db: Optional[float] = None    # edm.data_level_db (universe.py:176-178); None: level_db
+    # normalization_norm and normalization_kwargs.zero_mean / .eps (utils/norm.py:22-87): "2" | "max" | "2-max".  As in the
+    # reference, eps reaches the norms in the "2-max" branch only (the other two clamp at 1e-5 whatever it says).
+    norm: str = "2"
+    zero_mean: bool = True
+    norm_eps: float = 1e-5
 
     @property
     def tot_ds(self):
@@ -87,6 +92,17 @@ class ModelSpec:
 
 
 ACT_TYPES = ("prelu", "snake", "snakebeta", "none")
+NORMS = ("2", "max", "2-max")
+
+
+def _norm_name(v):
+    """normalization_norm as utils/norm.py:32-43 reads it: 2 (the numbers 2 and 2.0, or the string "2"; the string "2.0" is
+    refused, there and here) | "max" | "2-max"."""
+    if isinstance(v, (int, float)) and not isinstance(v, bool) and v == 2:
+        return "2"
+    if v in NORMS:
+        return v
+    raise NotImplementedError(f"Norm {v} is not implemented for batch normalization")
 
 
 _INTERP = re.compile(r"^\$\{([^}]+)\}$")
@@ -151,8 +167,12 @@ def spec_from_config(config):
     if m.get("transform") is not None and kind != "universe_gan":
         raise NotImplementedError("only the identity transform is supported (all shipped configs)")
     nk = m.get("normalization_kwargs", {}) or {}
-    if m.get("normalization_norm", 2) not in (2, "2", 2.0) or nk.get("ref", "noisy") not in ("noisy", "both"):
-        raise NotImplementedError("only normalization_norm=2 is supported (all shipped configs)")
+    norm = _norm_name(m.get("normalization_norm", 2))
+    if nk.get("ref", "noisy") not in ("noisy", "both"):
+        raise NotImplementedError(f"normalization_kwargs.ref={nk.get('ref')!r} (noisy | both)")  # utils/norm.py:61
+    norm_eps = float(nk.get("eps", 1e-5))
+    if not norm_eps > 0.0:
+        raise ValueError(f"normalization_kwargs.eps={norm_eps!r} must be positive")
     edm = m.get("edm")
     diff = m["diffusion"]
     if diff.get("schedule", "geometric") != "geometric":
@@ -180,6 +200,9 @@ def spec_from_config(config):
         norm_ref=str(nk.get("ref", "noisy")),  # utils/norm.py:47 default
         edm_data_level_db=(float(edm["data_level_db"]) if edm is not None and edm.get("data_level_db") is not None
                            else None),
+        norm=norm,
+        zero_mean=bool(nk.get("zero_mean", True)),
+        norm_eps=norm_eps,
     )
 
 

@@ -63,6 +63,7 @@ struct ou_handle {
   int cond_B = 0, cond_T = 0;
   bool trace = false;
   Options opt;                    // ou_set_option
+  NormMode norm;                  // ou_set_normalization (as created: norm 2, zero_mean -- the kernels' plain instantiations)
   std::string plan_with_options;  // ou_plan_json's answer (the plan + the current option values)
   int last_cfg = -1;
   long long* tstamps = nullptr;
@@ -723,6 +724,7 @@ Persist layout_persist(Runner& r, int T) {
   r.block3_bar = (unsigned long long*)(P.status + 64);
   int ncoef = kMaxSteps > r.B ? kMaxSteps : r.B;
   P.coef = (StepCoef*)r.alloc_raw((size_t)ncoef * 8);
+  r.h->tensors["stats"] = TensorRef{r.off, 4, 1};  // (B, 4, 1): {mean removed, gain, mix_rms, 0} of each row's normalisation
   P.stats = r.alloc_raw((size_t)r.B * 4);
   P.rows = (RowInfo*)r.alloc_raw((size_t)r.B * 4);
   P.lens = (int*)r.alloc_raw((size_t)r.B * kMaxLenLevels);
@@ -1041,10 +1043,29 @@ const char* ou_plan_json(const ou_handle* hc) {
   }
   o += "}";
   o += std::string(", \"noise_source\": \"") + (h->noise_src.on ? "counter" : "tensor") + "\"";
+  {
+    char buf[96];
+    std::snprintf(buf, sizeof buf, ", \"norm\": \"%s\", \"zero_mean\": %d, \"norm_eps\": %.9g",
+                  h->norm.norm == OU_NORM_MAX ? "max" : h->norm.norm == OU_NORM_2MAX ? "2-max" : "2", h->norm.zero_mean, h->norm.eps);
+    o += buf;
+  }
   const std::string& j = h->m.json;
   const size_t close = j.rfind('}');
   h->plan_with_options = close == std::string::npos ? "{" + o + "}" : j.substr(0, close) + ", " + o + j.substr(close);
   return h->plan_with_options.c_str();
+}
+
+int ou_set_normalization(ou_handle* h, int32_t norm_mode, int32_t zero_mean, float eps) {
+  if (!h) return OU_EINVAL;
+  if (norm_mode != OU_NORM_2 && norm_mode != OU_NORM_MAX && norm_mode != OU_NORM_2MAX)
+    return fail(h, OU_EINVAL, "ou_set_normalization: norm_mode must be OU_NORM_2, OU_NORM_MAX or OU_NORM_2MAX");
+  if (zero_mean != 0 && zero_mean != 1) return fail(h, OU_EINVAL, "ou_set_normalization: zero_mean must be 0 or 1");
+  if (!(eps >= 0.f) || !std::isfinite(eps)) return fail(h, OU_EINVAL, "ou_set_normalization: eps must be finite and >= 0 (0: 1e-5)");
+  h->norm.norm = norm_mode;
+  h->norm.zero_mean = zero_mean;
+  // utils/norm.py:31-39: normalization_kwargs.eps reaches the norms in the 2-max branch only
+  h->norm.eps = norm_mode == OU_NORM_2MAX && eps > 0.f ? eps : 1e-5f;
+  return OU_OK;
 }
 
 int ou_set_option(ou_handle* h, const char* key, double value) {
@@ -1429,9 +1450,10 @@ void upload_row_lengths(Runner& r, RowInfo* rows_dst, int* lens_dst, const int32
 // universe.py:219-223 + the level normalisation of `rows` inputs of T_raw samples (a ragged walk: of their own lengths) -> P.mixn
 void normalize(Runner& r, Persist& P, const float* mix, int rows, int T_raw, int T) {
   const float level = (float)std::pow(10.0, (double)r.h->m.cfg.level_db / 20.0);
+  const NormMode nm = r.h->norm;
   r.launch("normalize", [&] {
-    return r.ragged ? launch_pad_normalize_var(mix, P.mixn.p, P.stats, P.rows, rows, T_raw, T, level, r.st)
-                    : launch_pad_normalize(mix, P.mixn.p, P.stats, rows, T_raw, T, (T - T_raw) / 2, level, r.st);
+    return r.ragged ? launch_pad_normalize_var(mix, P.mixn.p, P.stats, P.rows, rows, T_raw, T, level, nm, r.st)
+                    : launch_pad_normalize(mix, P.mixn.p, P.stats, rows, T_raw, T, (T - T_raw) / 2, level, nm, r.st);
   });
 }
 struct PostFlags {
@@ -1883,8 +1905,10 @@ SegArea seg_area(int C, int E, int Bw, long long L, bool with_hist, bool with_ta
   size_t off = 0;
   a.stats = off; off += align256((size_t)C * 4 * 4);
   a.row_scale = off; off += align256((size_t)C * 4);
-  // the statistics' partials of the C input rows ([C][nb][3]), then the post partials of the E * C long rows ([E * C][nb][2])
-  a.part = off; off += align256(std::max((size_t)C * 3, (size_t)E * C * 2) * 1024 * 8);
+  // the statistics' partials of the C input rows ([C][nb][3] sums and the [C][nb] block maxima behind them, nb <= 1024: the
+  // fourth is reserved whatever the handle's NormMode, so the area does not depend on ou_set_normalization, called early or
+  // late, and every instantiation of seg_stats2_kernel writes inside it), then the post partials of the E * C long rows ([E * C][nb][2])
+  a.part = off; off += align256(std::max((size_t)C * 4, (size_t)E * C * 2) * 1024 * 8);
   a.zbuf = off; off += align256((size_t)E * Bw * L * 4);
   a.carry = off; off += align256((size_t)E * L * 4);
   a.hist = off; off += with_hist ? ou_ensemble_reduce_scratch_bytes(E, C) : 0;
@@ -1905,6 +1929,7 @@ int seg_workspace_bytes(ou_handle* h, int B, long long L, const SegArea& A, size
 // The caller's workspace against that answer (`sizer`: the name of the function that gives it), and the area's pointers.
 struct SegWs {
   size_t walk;  // bytes of the walk's part
+  size_t stats_off;  // `stats` in bytes from the workspace's start (ou_tensor "seg.stats")
   float *stats, *row_scale, *zbuf, *carry;
   double* part;
   int *hist, *lens_b;
@@ -1919,6 +1944,7 @@ int seg_workspace(ou_handle* h, void* ws, size_t ws_bytes, int B, int L, const S
     return fail(h, OU_EINVAL, std::string("workspace was not prepared by ou_workspace_init for (batch, length) of ") + sizer);
   char* seg = (char*)ws + w.walk;
   w.stats = (float*)(seg + A.stats);
+  w.stats_off = w.walk + A.stats;
   w.row_scale = (float*)(seg + A.row_scale);
   w.part = (double*)(seg + A.part);
   w.zbuf = (float*)(seg + A.zbuf);
@@ -2015,7 +2041,8 @@ bool seg_row_stats(ou_handle* h, const float* mix, float* esum, const SegWs& w, 
                    hipStream_t st) {
   const Model& m = h->m;
   const float level = (float)std::pow(10.0, (double)m.cfg.level_db / 20.0);
-  return launched(h, launch_seg_stats(mix, w.part, w.stats, rows, C, level, st), "segment stats") &&
+  h->tensors["seg.stats"] = TensorRef{w.stats_off, 4, 1};  // rows 0 .. C - 1: {mean removed, gain, mix_rms, 0} of the input rows
+  return launched(h, launch_seg_stats(mix, w.part, w.stats, rows, C, level, h->norm, st), "segment stats") &&
          launched(h, launch_seg_mel_energy(mix, w.stats, h->W + m.mel.win_off, h->W + m.mel.tw_off, h->W + m.mel.fb_off, esum, rows,
                                            C, m.mel.n_fft, m.mel.hop, m.mel.pad_left, m.mel.n_freq, m.mel.n_mels, frames_max, st),
                   "segment mel energy");

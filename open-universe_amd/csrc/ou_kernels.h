@@ -134,6 +134,26 @@ hipError_t launch_upload_coef(StepCoef* dst, const CoefBlock& blk, int n, hipStr
 // `lens` pointer keep the invariant themselves (null = all rows have the tensor's length); after the others the runner
 // launches launch_mask_tail.
 struct RowInfo { int t_raw, pad_left, t_pad, _r; };
+// The level normalisation of a row (utils/norm.py:22-87), by value into every kernel that forms a row's mean and gain.  With
+// m = the mean of the padded row, sd = its unbiased std (around m, whatever zero_mean says: torch's std removes the mean
+// itself) and mx = max |x - mu| over the padded row, mu = zero_mean ? m : 0:
+//   norm 2:      gain = level / max(sd, 1e-5)                        norm max:  gain = level / max(mx, 1e-5)
+//   norm 2-max:  gain = min(level / max(sd, eps), 1 / max(mx, eps))  (norm.py:36-39 hands normalization_kwargs.eps to this
+//                                                                     branch alone; the other two clamp at 1e-5 whatever it is)
+// and y = (x - mu) * gain, stats = {mu, gain, mix_rms, 0}.  plain() = norm 2 with zero_mean: the kernels' <false>
+// instantiation, which never looks at this struct -- the code every model had before the other modes existed.
+struct NormMode {
+  int norm = 0;        // OU_NORM_2 | OU_NORM_MAX | OU_NORM_2MAX
+  int zero_mean = 1;
+  float eps = 1e-5f;   // the clamp in force for `norm` (see above)
+  bool plain() const { return norm == 0 && zero_mean; }
+  // sd, mx: unclamped.  (fmaxf / fminf and true divisions: a row's gain has the same bits in every kernel that forms it)
+  __host__ __device__ float gain(float level, float sd, float mx) const {
+    if (norm == 1) return level / fmaxf(mx, eps);
+    if (norm == 2) return fminf(level / fmaxf(sd, eps), 1.f / fmaxf(mx, eps));
+    return level / fmaxf(sd, eps);
+  }
+};
 constexpr int kMaxLenLevels = 8;
 struct LevelSpec { int n = 0; int num[kMaxLenLevels]; int den[kMaxLenLevels]; };  // len_l[b] = t_pad[b] * num / den
 struct RowBlock { int t_raw[64]; };
@@ -149,13 +169,13 @@ hipError_t launch_mask_tail(float* y, const int* lens, int B, int C, int T, hipS
 hipError_t launch_gru_tail_fill(float* gx, const int* lens, int B, int H, int T, hipStream_t st);
 // pad + normalize / unpad + post with per-row geometry (rows: RowInfo[B]); mix and out are (B, T_raw_max), y / x (B, T_pad_max)
 hipError_t launch_pad_normalize_var(const float* mix, float* y, float* stats, const RowInfo* rows, int B, int T_raw_max,
-                                    int T_pad_max, float level, hipStream_t st);
+                                    int T_pad_max, float level, const NormMode& nm, hipStream_t st);
 hipError_t launch_post_var(const float* x, const float* stats, float* out, const RowInfo* rows, int B, int T_raw_max,
                            int T_pad_max, int keep_rms, int peak_guard, hipStream_t st);
 
 // pad (universe.py:219-223) + normalize_batch (utils/norm.py:47-87).  stats[b] = {mean, gain, mix_rms, 0}
 hipError_t launch_pad_normalize(const float* mix, float* y, float* stats, int B, int T_raw, int T_pad, int pad_left,
-                                float level, hipStream_t st);
+                                float level, const NormMode& nm, hipStream_t st);
 // unpad + keep_rms + peak guard (universe.py:349-357)
 hipError_t launch_post(const float* x, const float* stats, float* out, int B, int T_raw, int T_pad, int pad_left,
                        int keep_rms, int peak_guard, hipStream_t st);
@@ -255,9 +275,11 @@ struct SegEntriesList {
 };
 
 // stats[c] = {mean, gain, mix_rms, 0} of the padded whole row (pad_normalize_kernel's layout and arithmetic); part: [C]
-// [part_stride][3] doubles
+// [part_stride][3] doubles and [C][part_stride] more behind them: the blocks' maxima, written for every mode but nm.plain() (the
+// <true> kernels form it whatever the norm; gain() reads it for max and 2-max).  The caller reserves all four (seg_area).
 template <class Rows>
-hipError_t launch_seg_stats(const float* mix, double* part, float* stats, const Rows& rows, int C, float level, hipStream_t st);
+hipError_t launch_seg_stats(const float* mix, double* part, float* stats, const Rows& rows, int C, float level, const NormMode& nm,
+                            hipStream_t st);
 // esum[c * frame_stride + f] = frame energies of the mel front-end over the whole normalised row (mel_kernel without the mel
 // output), f < frames_c <= frames_max
 template <class Rows>

@@ -110,10 +110,17 @@ __global__ __launch_bounds__(1024) void seg_stats1_kernel(const float* __restric
   double* pc = part + ((size_t)c * rows.part_stride() + j) * 3;
   if (threadIdx.x == 0) { pc[0] = s; pc[1] = sq; }
 }
-// pass 2: per-block sum of (x - mean)^2 around the mean of the padded row (each block sums the partials of pass 1 in order)
-template <class Rows>
-__global__ __launch_bounds__(1024) void seg_stats2_kernel(const float* __restrict__ mix, double* __restrict__ part, Rows rows) {
+// (pass 1 is the same for every NormMode: the raw sums do not depend on it)
+// pass 2: per-block sum of (x - mean)^2 around the mean of the padded row (each block sums the partials of pass 1 in order).
+// GEN (any NormMode, ou_kernels.h; false: norm 2 with zero_mean, `nm` not looked at): also the block's max |x - mu|, mu = mean
+// or 0, into pmax[c][j] behind the [C][part_stride][3] sums -- formed and stored for every mode that is not plain(), zero_mean
+// false under norm 2 included (which never reads it); the area holds the fourth partial for every handle.  A maximum does not depend on the order it is taken in: whatever
+// the number of blocks, the finish kernel's maximum over them has the bits of pad_normalize_kernel's over one.
+template <class Rows, bool GEN>
+__global__ __launch_bounds__(1024) void seg_stats2_kernel(const float* __restrict__ mix, double* __restrict__ part, Rows rows,
+                                                          NormMode nm) {
   __shared__ double shd[16];
+  __shared__ float shf[GEN ? 16 : 1];
   const int j = blockIdx.x, c = blockIdx.y;
   const SegRow r = rows.row(c);
   const int nb = rows.blocks(r);
@@ -123,17 +130,26 @@ __global__ __launch_bounds__(1024) void seg_stats2_kernel(const float* __restric
   for (int i = 1; i < nb; i++) s += pc[i * 3];
   const float mean = (float)(s / (double)r.T_pad);  // norm.py:62  (mean over the padded signal)
   const float* xb = mix + (size_t)c * rows.stride();
+  const float mu = GEN && !nm.zero_mean ? 0.f : mean;
   double ss = 0;
+  float mx = 0.f;
   for (long long t = (long long)j * 1024 + threadIdx.x; t < r.t_raw; t += (long long)nb * 1024) {
     const double d = (double)(xb[t] - mean);
     ss += d * d;
+    if constexpr (GEN) mx = fmaxf(mx, fabsf(xb[t] - mu));
   }
   ss = seg_block_sum(ss, shd);
   if (threadIdx.x == 0) pc[j * 3 + 2] = ss;
+  if constexpr (GEN) {
+    mx = seg_block_max(mx, shf);
+    double* pmax = part + (size_t)gridDim.y * rows.part_stride() * 3;
+    if (threadIdx.x == 0) pmax[(size_t)c * rows.part_stride() + j] = (double)mx;
+  }
 }
 // finish: stats[c] = {mean, gain, mix_rms, 0}  (the layout of pad_normalize_kernel's stats)
-template <class Rows>
-__global__ void seg_stats_finish_kernel(const double* __restrict__ part, float* __restrict__ stats, Rows rows, float level) {
+template <class Rows, bool GEN>
+__global__ void seg_stats_finish_kernel(const double* __restrict__ part, float* __restrict__ stats, Rows rows, float level,
+                                        NormMode nm) {
   const int c = blockIdx.x;
   if (threadIdx.x != 0) return;
   const SegRow r = rows.row(c);
@@ -144,9 +160,20 @@ __global__ void seg_stats_finish_kernel(const double* __restrict__ part, float* 
   const float mean = (float)(s / (double)r.T_pad);
   ss += (double)(r.T_pad - r.t_raw) * (double)(0.f - mean) * (double)(0.f - mean);
   float sd = (float)sqrt(ss / (double)(r.T_pad - 1));  // unbiased std, norm.py:22-23
-  sd = fmaxf(sd, 1e-5f);
-  stats[c * 4 + 0] = mean;
-  stats[c * 4 + 1] = level / sd;
+  const float mu = GEN && !nm.zero_mean ? 0.f : mean;
+  float gain;
+  if constexpr (GEN) {
+    const double* pmax = part + (size_t)gridDim.x * rows.part_stride() * 3 + (size_t)c * rows.part_stride();
+    float mx = (float)pmax[0];
+    for (int i = 1; i < nb; i++) mx = fmaxf(mx, (float)pmax[i]);
+    if (r.T_pad > r.t_raw) mx = fmaxf(mx, fabsf(0.f - mu));  // norm.py:26-28 over the padded row
+    gain = nm.gain(level, sd, mx);
+  } else {
+    sd = fmaxf(sd, 1e-5f);
+    gain = level / sd;
+  }
+  stats[c * 4 + 0] = mu;
+  stats[c * 4 + 1] = gain;
   stats[c * 4 + 2] = (float)sqrt(sq / (double)r.t_raw);
   stats[c * 4 + 3] = 0.f;
 }
@@ -393,12 +420,18 @@ bool seg_entry_grid(const Entries& ents, int n, bool real, long long T, int Bw, 
 }  // namespace
 
 template <class Rows>
-hipError_t launch_seg_stats(const float* mix, double* part, float* stats, const Rows& rows, int C, float level, hipStream_t st) {
+hipError_t launch_seg_stats(const float* mix, double* part, float* stats, const Rows& rows, int C, float level, const NormMode& nm,
+                            hipStream_t st) {
   if (C < 1 || C > 65535 || rows.stride() < 1) return hipErrorInvalidValue;
   const dim3 grid(rows.part_stride(), C);
   hipLaunchKernelGGL(seg_stats1_kernel<Rows>, grid, dim3(1024), 0, st, mix, part, rows);
-  hipLaunchKernelGGL(seg_stats2_kernel<Rows>, grid, dim3(1024), 0, st, mix, part, rows);
-  hipLaunchKernelGGL(seg_stats_finish_kernel<Rows>, dim3(C), dim3(64), 0, st, part, stats, rows, level);
+  if (nm.plain()) {
+    hipLaunchKernelGGL((seg_stats2_kernel<Rows, false>), grid, dim3(1024), 0, st, mix, part, rows, nm);
+    hipLaunchKernelGGL((seg_stats_finish_kernel<Rows, false>), dim3(C), dim3(64), 0, st, part, stats, rows, level, nm);
+  } else {
+    hipLaunchKernelGGL((seg_stats2_kernel<Rows, true>), grid, dim3(1024), 0, st, mix, part, rows, nm);
+    hipLaunchKernelGGL((seg_stats_finish_kernel<Rows, true>), dim3(C), dim3(64), 0, st, part, stats, rows, level, nm);
+  }
   return hipGetLastError();
 }
 template <class Rows>
@@ -454,7 +487,7 @@ hipError_t launch_seg_post(float* out, double* part, const float* stats, const R
 }
 // the two calls there are: rows alike with arithmetic entries, a table of rows with listed entries
 #define OU_SEG_INSTANTIATE(Rows, Entries)                                                                                          \
-  template hipError_t launch_seg_stats<Rows>(const float*, double*, float*, const Rows&, int, float, hipStream_t);                 \
+  template hipError_t launch_seg_stats<Rows>(const float*, double*, float*, const Rows&, int, float, const NormMode&, hipStream_t);                 \
   template hipError_t launch_seg_mel_energy<Rows>(const float*, const float*, const float*, const float*, const float*, float*,    \
                                                   const Rows&, int, int, int, int, int, int, long long, hipStream_t);              \
   template hipError_t launch_seg_gather_input<Rows, Entries>(const float*, const float*, const float*, float*, float*, const Rows&, \

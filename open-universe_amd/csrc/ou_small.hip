@@ -261,11 +261,17 @@ __device__ float block_max(float v, float* sh) {
   return r;
 }
 
-// pad + zero-mean + unit-level normalisation, one block per batch element
+// pad + zero-mean + unit-level normalisation, one block per batch element.
+// GEN = false: normalization_norm 2 with zero_mean, the code this kernel always was (`nm` is not looked at).  GEN = true: any
+// NormMode (ou_kernels.h) in the same loops -- the pass over (x - mean)^2 also takes max |x - mu|, mu = mean or 0; the padding
+// contributes |0 - mu| once.  A maximum does not depend on the order it is taken in, so it has the same bits here, in
+// pad_normalize_var_kernel and over any number of blocks of seg_stats2_kernel.
+template <bool GEN>
 __global__ __launch_bounds__(1024) void pad_normalize_kernel(const float* __restrict__ mix, float* __restrict__ y,
                                                              float* __restrict__ stats, int T_raw, int T_pad,
-                                                             int pad_left, float level) {
+                                                             int pad_left, float level, NormMode nm) {
   __shared__ double shd[16];
+  __shared__ float shf[GEN ? 16 : 1];
   const int b = blockIdx.x, tid = threadIdx.x;
   const float* xb = mix + (size_t)b * T_raw;
   // (one CU per utterance and three dependent passes: the loops are unrolled by hand so that 8 loads are in flight per
@@ -295,25 +301,35 @@ __global__ __launch_bounds__(1024) void pad_normalize_kernel(const float* __rest
     s = block_sum(s, shd);
     sq = block_sum(sq, shd);
     const float mean = (float)(s / T_pad);  // norm.py:62  (mean over the padded signal)
+    const float mu = GEN && !nm.zero_mean ? 0.f : mean;  // what is removed from the row (norm.py:65-69)
     double ss = 0;
+    float mx = 0.f;
 #pragma unroll
     for (int k = 0; k < NREG; k++) {
       asm volatile("" : "+v"(v[k]), "+v"(ss));
       const double d = k < nk ? (double)(v[k] - mean) : 0.0; ss += d * d;
+      if constexpr (GEN) mx = fmaxf(mx, k < nk ? fabsf(v[k] - mu) : 0.f);
     }
     ss = block_sum(ss, shd);
     ss += (double)(T_pad - T_raw) * (double)(0.f - mean) * (double)(0.f - mean);
     float sd = (float)sqrt(ss / (double)(T_pad - 1));  // unbiased std, norm.py:22-23
-    sd = fmaxf(sd, 1e-5f);
-    const float gain = level / sd;
+    float gain;
+    if constexpr (GEN) {
+      mx = block_max(mx, shf);
+      if (T_pad > T_raw) mx = fmaxf(mx, fabsf(0.f - mu));  // norm.py:26-28 over the padded row
+      gain = nm.gain(level, sd, mx);
+    } else {
+      sd = fmaxf(sd, 1e-5f);
+      gain = level / sd;
+    }
     // a sample past the end is 0 here, i.e. exactly the padding value (0 - mean) * gain of the position it lands on
 #pragma unroll
-    for (int k = 0; k < NREG; k++) buf_store((v[k] - mean) * gain, ry, (pad_left + tid) * 4, k * 4096);
-    const float pv = (0.f - mean) * gain;  // the rest of the padding
+    for (int k = 0; k < NREG; k++) buf_store((v[k] - mu) * gain, ry, (pad_left + tid) * 4, k * 4096);
+    const float pv = (0.f - mu) * gain;  // the rest of the padding
     for (int t = tid; t < pad_left; t += 1024) yb[t] = pv;
     for (int t = pad_left + NREG * 1024 + tid; t < T_pad; t += 1024) yb[t] = pv;
     if (tid == 0) {
-      stats[b * 4 + 0] = mean;
+      stats[b * 4 + 0] = mu;
       stats[b * 4 + 1] = gain;
       stats[b * 4 + 2] = (float)sqrt(sq / (double)T_raw);
       stats[b * 4 + 3] = 0.f;
@@ -335,7 +351,9 @@ __global__ __launch_bounds__(1024) void pad_normalize_kernel(const float* __rest
   s = block_sum(s, shd);
   sq = block_sum(sq, shd);
   const float mean = (float)(s / T_pad);  // norm.py:62  (mean over the padded signal)
+  const float mu = GEN && !nm.zero_mean ? 0.f : mean;
   double ss = 0;
+  float mx = 0.f;
   {
     int t = tid;
     for (; t + (U - 1) * 1024 < T_raw; t += U * 1024) {
@@ -343,31 +361,47 @@ __global__ __launch_bounds__(1024) void pad_normalize_kernel(const float* __rest
 #pragma unroll
       for (int u = 0; u < U; u++) v[u] = xb[t + u * 1024];
 #pragma unroll
-      for (int u = 0; u < U; u++) { const double d = (double)(v[u] - mean); ss += d * d; }
+      for (int u = 0; u < U; u++) {
+        const double d = (double)(v[u] - mean); ss += d * d;
+        if constexpr (GEN) mx = fmaxf(mx, fabsf(v[u] - mu));
+      }
     }
-    for (; t < T_raw; t += 1024) { const double d = (double)(xb[t] - mean); ss += d * d; }
+    for (; t < T_raw; t += 1024) {
+      const double d = (double)(xb[t] - mean); ss += d * d;
+      if constexpr (GEN) mx = fmaxf(mx, fabsf(xb[t] - mu));
+    }
   }
   ss = block_sum(ss, shd);
   ss += (double)(T_pad - T_raw) * (double)(0.f - mean) * (double)(0.f - mean);
   float sd = (float)sqrt(ss / (double)(T_pad - 1));  // unbiased std, norm.py:22-23
-  sd = fmaxf(sd, 1e-5f);
-  const float gain = level / sd;
+  float gain;
+  if constexpr (GEN) {
+    mx = block_max(mx, shf);
+    if (T_pad > T_raw) mx = fmaxf(mx, fabsf(0.f - mu));
+    gain = nm.gain(level, sd, mx);
+  } else {
+    sd = fmaxf(sd, 1e-5f);
+    gain = level / sd;
+  }
 #pragma unroll 8
   for (int t = tid; t < T_pad; t += 1024) {
     int tr = t - pad_left;
     float v = (tr >= 0 && tr < T_raw) ? xb[tr] : 0.f;
-    yb[t] = (v - mean) * gain;
+    yb[t] = (v - mu) * gain;
   }
   if (tid == 0) {
-    stats[b * 4 + 0] = mean;
+    stats[b * 4 + 0] = mu;
     stats[b * 4 + 1] = gain;
     stats[b * 4 + 2] = (float)sqrt(sq / T_raw);  // mix_rms, universe.py:259
     stats[b * 4 + 3] = 0.f;
   }
 }
 hipError_t launch_pad_normalize(const float* mix, float* y, float* stats, int B, int T_raw, int T_pad, int pad_left,
-                                float level, hipStream_t st) {
-  hipLaunchKernelGGL(pad_normalize_kernel, dim3(B), dim3(1024), 0, st, mix, y, stats, T_raw, T_pad, pad_left, level);
+                                float level, const NormMode& nm, hipStream_t st) {
+  if (nm.plain())
+    hipLaunchKernelGGL(pad_normalize_kernel<false>, dim3(B), dim3(1024), 0, st, mix, y, stats, T_raw, T_pad, pad_left, level, nm);
+  else
+    hipLaunchKernelGGL(pad_normalize_kernel<true>, dim3(B), dim3(1024), 0, st, mix, y, stats, T_raw, T_pad, pad_left, level, nm);
   return hipGetLastError();
 }
 
@@ -1009,11 +1043,14 @@ hipError_t launch_gru_tail_fill(float* gx, const int* lens, int B, int H, int T,
 }
 
 // pad_normalize_kernel's general loops with the row's own (T_raw, pad_left, T_pad): same elements per thread and the same
-// order of the double sums as the call on that row alone; the row is ZERO (not the padding value) from its own T_pad on
+// order of the double sums as the call on that row alone; the row is ZERO (not the padding value) from its own T_pad on.
+// GEN: as in pad_normalize_kernel.
+template <bool GEN>
 __global__ __launch_bounds__(1024) void pad_normalize_var_kernel(const float* __restrict__ mix, float* __restrict__ y,
                                                                  float* __restrict__ stats, const RowInfo* __restrict__ rows,
-                                                                 int T_raw_max, int T_pad_max, float level) {
+                                                                 int T_raw_max, int T_pad_max, float level, NormMode nm) {
   __shared__ double shd[16];
+  __shared__ float shf[GEN ? 16 : 1];
   const int b = blockIdx.x, tid = threadIdx.x;
   const RowInfo ri = rows[b];
   const int T_raw = ri.t_raw, T_pad = ri.t_pad, pad_left = ri.pad_left;
@@ -1024,28 +1061,43 @@ __global__ __launch_bounds__(1024) void pad_normalize_var_kernel(const float* __
   s = block_sum(s, shd);
   sq = block_sum(sq, shd);
   const float mean = (float)(s / T_pad);  // norm.py:62  (mean over the padded signal)
+  const float mu = GEN && !nm.zero_mean ? 0.f : mean;
   double ss = 0;
-  for (int t = tid; t < T_raw; t += 1024) { const double d = (double)(xb[t] - mean); ss += d * d; }
+  float mx = 0.f;
+  for (int t = tid; t < T_raw; t += 1024) {
+    const double d = (double)(xb[t] - mean); ss += d * d;
+    if constexpr (GEN) mx = fmaxf(mx, fabsf(xb[t] - mu));
+  }
   ss = block_sum(ss, shd);
   ss += (double)(T_pad - T_raw) * (double)(0.f - mean) * (double)(0.f - mean);
   float sd = (float)sqrt(ss / (double)(T_pad - 1));  // unbiased std, norm.py:22-23
-  sd = fmaxf(sd, 1e-5f);
-  const float gain = level / sd;
+  float gain;
+  if constexpr (GEN) {
+    mx = block_max(mx, shf);
+    if (T_pad > T_raw) mx = fmaxf(mx, fabsf(0.f - mu));
+    gain = nm.gain(level, sd, mx);
+  } else {
+    sd = fmaxf(sd, 1e-5f);
+    gain = level / sd;
+  }
   for (int t = tid; t < T_pad_max; t += 1024) {
     const int tr = t - pad_left;
     const float v = (tr >= 0 && tr < T_raw) ? xb[tr] : 0.f;
-    yb[t] = t < T_pad ? (v - mean) * gain : 0.f;
+    yb[t] = t < T_pad ? (v - mu) * gain : 0.f;
   }
   if (tid == 0) {
-    stats[b * 4 + 0] = mean;
+    stats[b * 4 + 0] = mu;
     stats[b * 4 + 1] = gain;
     stats[b * 4 + 2] = (float)sqrt(sq / T_raw);  // mix_rms, universe.py:259
     stats[b * 4 + 3] = 0.f;
   }
 }
 hipError_t launch_pad_normalize_var(const float* mix, float* y, float* stats, const RowInfo* rows, int B, int T_raw_max,
-                                    int T_pad_max, float level, hipStream_t st) {
-  hipLaunchKernelGGL(pad_normalize_var_kernel, dim3(B), dim3(1024), 0, st, mix, y, stats, rows, T_raw_max, T_pad_max, level);
+                                    int T_pad_max, float level, const NormMode& nm, hipStream_t st) {
+  if (nm.plain())
+    hipLaunchKernelGGL(pad_normalize_var_kernel<false>, dim3(B), dim3(1024), 0, st, mix, y, stats, rows, T_raw_max, T_pad_max, level, nm);
+  else
+    hipLaunchKernelGGL(pad_normalize_var_kernel<true>, dim3(B), dim3(1024), 0, st, mix, y, stats, rows, T_raw_max, T_pad_max, level, nm);
   return hipGetLastError();
 }
 // post_kernel with the row's own geometry; out (B, T_raw_max), 0 behind the row's own T_raw

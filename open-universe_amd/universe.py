@@ -175,8 +175,12 @@ class Universe:
         self.spec = spec
         self.fs = spec.fs
         self.diff_kwargs = spec.diff_kwargs
-        self.normalization_norm = 2
+        self.normalization_norm = 2 if spec.norm == "2" else spec.norm
         self.normalization_kwargs = {"ref": spec.norm_ref, "level_db": spec.level_db}
+        if not spec.zero_mean:
+            self.normalization_kwargs["zero_mean"] = False
+        if spec.norm_eps != 1e-5:
+            self.normalization_kwargs["eps"] = spec.norm_eps
         self.with_edm = spec.edm_noise is not None
         self.tot_ds = spec.tot_ds
         self.n_channels = spec.score.n_channels
@@ -204,6 +208,9 @@ class Universe:
         with torch.cuda.device(device):
             _lib.check(self._L.ou_create(byref(self._cfg), c_void_p(self._weights.data_ptr()),
                                          c_size_t(self._weights.numel() * 4), device.index, byref(self._handle)))
+        norm = _lib.norm_args(spec)
+        if norm != (0, 1, 0.0):  # (every shipped config: the handle is never told, and is what it always was)
+            _lib.check(self._L.ou_set_normalization(self._handle, *norm), self._handle)
         self._ws = None
         self._ws_key = None
         self._ws_cache = {}
@@ -1284,10 +1291,17 @@ class Universe:
         score of a known target, so no kernel of this library is involved -- plain device tensor glue."""
         tot = self.tot_ds
         level = 10 ** (self.spec.level_db / 20.0)
+        norm, zero_mean, eps = self.spec.norm, self.spec.zero_mean, self.spec.norm_eps
 
-        def stats(t):
-            mean = t.mean(dim=(1, 2), keepdim=True)
-            return mean, level / (t - mean).std(dim=(1, 2), keepdim=True).clamp(min=1e-5)
+        def stats(t):  # utils/norm.py:22-44, 65-71: the model's normalization_norm, zero_mean and eps
+            mean = t.mean(dim=(1, 2), keepdim=True) if zero_mean else torch.zeros_like(t[:, :1, :1])
+            d = t - mean
+            if norm == "2":
+                return mean, level / d.std(dim=(1, 2), keepdim=True).clamp(min=1e-5)
+            peak = d.abs().amax(dim=(1, 2), keepdim=True)
+            if norm == "max":
+                return mean, level / peak.clamp(min=1e-5)
+            return mean, torch.minimum(level / d.std(dim=(1, 2), keepdim=True).clamp(min=eps), 1.0 / peak.clamp(min=eps))
 
         def padded(t):
             return torch.nn.functional.pad(t, (pad // 2, pad - pad // 2))
