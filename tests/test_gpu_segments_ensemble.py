@@ -298,7 +298,10 @@ def test_refusals_launch_nothing():
     assert call(flags=_lib.OU_ENH_USE_AUX_SIGNAL) == _lib.OU_EINVAL
     assert call(noise_p=None) == _lib.OU_EINVAL  # tensor mode without a tensor
     assert call(ws_t=small) == _lib.OU_ENOMEM  # the walk's workspace of another batch size: too small
-    assert call(ws_t=torch.empty_like(ws)) == _lib.OU_EINVAL  # large enough, never prepared by ou_workspace_init
+    # large enough, never prepared by ou_workspace_init (a view 256 bytes into a fresh block: the caching allocator may hand
+    # torch.empty_like(ws) the address of a freed workspace this handle once prepared, and the library knows workspaces by address)
+    never = torch.empty(ws.numel() + 256, dtype=ws.dtype, device=ws.device)[256:]
+    assert call(ws_t=never) == _lib.OU_EINVAL
     assert call(ws_n=1 << 20) == _lib.OU_ENOMEM
     with model._counter_source(3, CounterNoise(3, 0).stream_ids(C)):  # n_streams = C != E * C
         assert call(noise_p=None) == _lib.OU_EINVAL

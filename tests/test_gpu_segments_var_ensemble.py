@@ -376,7 +376,10 @@ def test_refusals_launch_nothing():
     big = (1 << 30) + 5
     bad(call(C_=1, tr=(ctypes.c_int64 * 1)(big), T_max=big, seg=1 << 30, E_=1))
     bad(call(ws_t=small), _lib.OU_ENOMEM)  # the walk's workspace of another batch size: too small
-    bad(call(ws_t=torch.empty_like(ws)))  # large enough, never prepared by ou_workspace_init
+    # large enough, never prepared by ou_workspace_init.  (Not torch.empty_like(ws): the caching allocator may hand back the
+    # address of a freed workspace this handle once prepared for the same batch size, and the library knows workspaces by
+    # address.  A view 256 bytes into a fresh block is an address no workspace ever started at.)
+    bad(call(ws_t=torch.empty(ws.numel() + 256, dtype=ws.dtype, device=ws.device)[256:]))
     bad(call(ws_n=1 << 20), _lib.OU_ENOMEM)
     with model._counter_source(3, CounterNoise(3, 0).stream_ids(C)):  # n_streams = C != E * C
         bad(call(noise_p=None))
