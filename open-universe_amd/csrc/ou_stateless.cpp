@@ -1,0 +1,237 @@
+// Entry points that take no handle: the STFT pair, the resampler (plan, table, call) and the Snake activation.
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "ou_handle.h"
+
+using namespace ou;
+
+extern "C" {
+
+int ou_transform_frames(int32_t T, int32_t n_fft, int32_t hop) {
+  if (T < 1 || n_fft < 2 || hop < 1) return OU_EINVAL;
+  return 1 + (T + 2 * (n_fft / 2) - n_fft) / hop;
+}
+
+int ou_transform_forward(const float* x, int32_t B, int32_t T, const float* window, int32_t n_fft, int32_t hop,
+                         int32_t transform_type, float abs_exponent, float factor, float* out, ou_stream_t stream) {
+  if (!x || !window || !out || B < 1) return fail(nullptr, OU_EINVAL, "bad argument");
+  if (transform_type < 0 || transform_type > 2) return fail(nullptr, OU_ENOTIMPL, "transform_type must be none | exponent | log");
+  hipError_t e = launch_stft_forward(x, window, out, B, T, n_fft, hop, transform_type, abs_exponent, factor, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(nullptr, e == hipErrorInvalidValue ? OU_EINVAL : OU_EHIP, hipGetErrorString(e));
+  return OU_OK;
+}
+
+int ou_transform_inverse(const float* spec, int32_t B, int32_t n_frames, const float* window, int32_t n_fft, int32_t hop,
+                         int32_t transform_type, float abs_exponent, float factor, int32_t length, float* y,
+                         float* scratch, ou_stream_t stream) {
+  if (!spec || !window || !y || !scratch || B < 1) return fail(nullptr, OU_EINVAL, "bad argument");
+  if (transform_type < 0 || transform_type > 2) return fail(nullptr, OU_ENOTIMPL, "transform_type must be none | exponent | log");
+  hipError_t e = launch_stft_inverse(spec, window, scratch, y, B, n_frames, n_fft, hop, transform_type, abs_exponent, factor,
+                                     length, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(nullptr, e == hipErrorInvalidValue ? OU_EINVAL : OU_EHIP, hipGetErrorString(e));
+  return OU_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// Resampler plan (include/ouniverse.h, "resampling"): a pure host function of the two rates.
+struct RsPlan {
+  int fs_in = 0, fs_out = 0;
+  int orig = 0, nw = 0, width = 0, taps = 0;
+  double base = 0.0;
+  size_t bytes = 0;
+};
+constexpr double kRsLowpassWidth = 6.0, kRsRolloff = 0.99;
+
+long long gcd_ll(long long a, long long b) {
+  while (b) { const long long t = a % b; a = b; b = t; }
+  return a;
+}
+// the window argument of entry (p, u) of the dense kernel, u = i - width, before the clamp -- in the operation order of the
+// definition, so the double is the one the dense kernel is computed from
+inline double rs_arg(const RsPlan& pl, int p, long long u) {
+  return ((double)(-p) / (double)pl.nw + (double)u / (double)pl.orig) * pl.base;
+}
+inline bool rs_inside(const RsPlan& pl, int p, long long u) { return std::fabs(rs_arg(pl, p, u)) < kRsLowpassWidth; }
+// support of phase p: the run [first, last] of u whose argument lies strictly inside (-6, 6), within the dense range
+void rs_support(const RsPlan& pl, int p, long long& first, long long& last) {
+  const double c = kRsLowpassWidth / pl.base, ph = (double)p / (double)pl.nw;
+  first = (long long)std::floor((double)pl.orig * (ph - c)) - 2;
+  while (!rs_inside(pl, p, first)) first++;
+  last = (long long)std::ceil((double)pl.orig * (ph + c)) + 2;
+  while (!rs_inside(pl, p, last)) last--;
+  if (first < -(long long)pl.width) first = -(long long)pl.width;
+  if (last > (long long)pl.width + pl.orig - 1) last = (long long)pl.width + pl.orig - 1;
+}
+// false: non-positive rates, or a rate pair whose filter does not fit 32-bit table indices
+bool rs_plan(int fs_in, int fs_out, RsPlan& pl) {
+  thread_local RsPlan cache;
+  if (fs_in < 1 || fs_out < 1) return false;
+  if (cache.fs_in == fs_in && cache.fs_out == fs_out) { pl = cache; return true; }
+  const long long g = gcd_ll(fs_in, fs_out);
+  pl.fs_in = fs_in; pl.fs_out = fs_out;
+  pl.orig = (int)(fs_in / g);
+  pl.nw = (int)(fs_out / g);
+  pl.base = (double)(pl.orig < pl.nw ? pl.orig : pl.nw) * kRsRolloff;
+  const double w = std::ceil(kRsLowpassWidth * (double)pl.orig / pl.base);
+  if (w > (double)(1 << 28)) return false;
+  pl.width = (int)w;
+  long long taps = 0;
+  for (int p = 0; p < pl.nw; p++) {
+    long long a, b;
+    rs_support(pl, p, a, b);
+    if (b - a + 1 > taps) taps = b - a + 1;
+  }
+  if ((taps + 1) * (long long)pl.nw > 0x7fffffffll / 4) return false;
+  pl.taps = (int)taps;
+  pl.bytes = (size_t)(taps + 1) * (size_t)pl.nw * 4;
+  cache = pl;
+  return true;
+}
+}  // namespace
+
+extern "C" {
+
+int ou_resample_plan(int32_t fs_in, int32_t fs_out, int32_t* orig, int32_t* new_, int32_t* width, int32_t* taps,
+                     size_t* table_bytes) {
+  RsPlan pl;
+  if (!rs_plan(fs_in, fs_out, pl))
+    return fail(nullptr, OU_EINVAL, "ou_resample_plan: rates must be positive (and their reduced ratio within 32-bit table indices)");
+  if (orig) *orig = pl.orig;
+  if (new_) *new_ = pl.nw;
+  if (width) *width = pl.width;
+  if (taps) *taps = pl.taps;
+  if (table_bytes) *table_bytes = pl.bytes;
+  return OU_OK;
+}
+
+int ou_resample_table(int32_t fs_in, int32_t fs_out, void* table, size_t table_bytes) {
+  RsPlan pl;
+  if (!rs_plan(fs_in, fs_out, pl)) return fail(nullptr, OU_EINVAL, "ou_resample_table: bad rates");
+  if (!table || table_bytes != pl.bytes)
+    return fail(nullptr, OU_EINVAL, "ou_resample_table: table_bytes must be what ou_resample_plan returns");
+  int32_t* first = static_cast<int32_t*>(table);
+  float* coef = reinterpret_cast<float*>(first + pl.nw);
+  const double scale = pl.base / (double)pl.orig;
+  for (int p = 0; p < pl.nw; p++) {
+    long long a, b;
+    rs_support(pl, p, a, b);
+    first[p] = (int32_t)a;
+    for (int t = 0; t < pl.taps; t++) {
+      double k = 0.0;
+      if (a + t <= b) {
+        // audio._sinc_kernel, operation by operation (the argument is strictly inside the clamp)
+        double v = rs_arg(pl, p, a + t);
+        const double c = std::cos(v * M_PI / kRsLowpassWidth / 2.0);
+        const double window = c * c;
+        v = v * M_PI;
+        k = (v == 0.0 ? 1.0 : std::sin(v) / v) * window * scale;
+      }
+      coef[(size_t)t * pl.nw + p] = (float)k;
+    }
+  }
+  return OU_OK;
+}
+
+int64_t ou_resample_length(int32_t fs_in, int32_t fs_out, int64_t n) {
+  if (fs_in < 1 || fs_out < 1 || n < 0) return -1;
+  const long long g = gcd_ll(fs_in, fs_out);
+  const long long orig = fs_in / g, nw = fs_out / g;
+  if (n > (0x7fffffffffffffffll - orig) / nw) return -1;
+  return (nw * n + orig - 1) / orig;
+}
+
+int32_t ou_resample_tile(int32_t fs_in, int32_t fs_out) {
+  RsPlan pl;
+  if (!rs_plan(fs_in, fs_out, pl)) return -1;
+  return resample_tile(pl.orig, pl.nw, pl.taps);
+}
+
+int ou_resample(const float* x, int64_t x_stride, const int64_t* len_host, float* y, int64_t y_stride, int64_t cols,
+                int32_t rows, int32_t fs_in, int32_t fs_out, const void* table, size_t table_bytes, ou_stream_t stream) {
+  if (fs_in < 1 || fs_out < 1) return fail(nullptr, OU_EINVAL, "ou_resample: the rates must be positive");
+  if (!x || !y || !len_host || rows < 1 || x_stride < 0 || cols < 0 || y_stride < cols)
+    return fail(nullptr, OU_EINVAL, "ou_resample: bad argument (rows >= 1, 0 <= cols <= y_stride, x_stride >= 0)");
+  RsPlan pl;
+  if (!rs_plan(fs_in, fs_out, pl))
+    return fail(nullptr, OU_EINVAL, "ou_resample: the reduced ratio of the rates does not fit 32-bit table indices");
+  const bool copy = pl.orig == pl.nw;
+  if (!copy && (!table || table_bytes != pl.bytes))
+    return fail(nullptr, OU_EINVAL, "ou_resample: table / table_bytes must be those of ou_resample_plan / ou_resample_table "
+                                    "for this rate pair");
+  // what the kernels index with: 64-bit element offsets rows * stride and output positions nw * len + orig
+  constexpr long long kMaxOffset = 1ll << 60;
+  if ((x_stride && rows > kMaxOffset / x_stride) || (y_stride && rows > kMaxOffset / y_stride))
+    return fail(nullptr, OU_EINVAL, "ou_resample: rows * stride overflows the kernel's 64-bit offsets");
+  std::vector<long long> ylen((size_t)rows);
+  for (int b = 0; b < rows; b++) {
+    const long long n = len_host[b];
+    if (n < 0 || n > x_stride) return fail(nullptr, OU_EINVAL, "ou_resample: 0 <= len[b] <= x_stride");
+    if (n > (kMaxOffset - pl.orig) / pl.nw)
+      return fail(nullptr, OU_EINVAL, "ou_resample: new * len[b] overflows the kernel's 64-bit positions");
+    ylen[b] = copy ? n : ((long long)pl.nw * n + pl.orig - 1) / pl.orig;
+    if (ylen[b] > cols)
+      return fail(nullptr, OU_EINVAL, "ou_resample: row " + std::to_string(b) + " needs " + std::to_string(ylen[b]) +
+                                          " output columns, cols = " + std::to_string(cols));
+  }
+  if (cols == 0) return OU_OK;  // (every row is empty and there is nothing to zero)
+  const long long tile = resample_tile(pl.orig, pl.nw, pl.taps);
+  if ((cols + tile - 1) / tile > 0x7fffffffll) return fail(nullptr, OU_EINVAL, "ou_resample: cols exceeds the launch grid");
+  for (int off = 0; off < rows; off += kResampleRowsPerLaunch) {
+    ResampleRows blk;
+    const int n = rows - off < kResampleRowsPerLaunch ? rows - off : kResampleRowsPerLaunch;
+    for (int i = 0; i < kResampleRowsPerLaunch; i++) {
+      blk.len[i] = i < n ? len_host[off + i] : 0;
+      blk.ylen[i] = i < n ? ylen[off + i] : 0;
+    }
+    const hipError_t e = launch_resample(x + (size_t)off * (size_t)x_stride, x_stride, y + (size_t)off * (size_t)y_stride,
+                                         y_stride, cols, blk, n, pl.orig, pl.nw, pl.taps, copy ? nullptr : table,
+                                         (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, OU_EHIP, std::string("HIP error at resample: ") + hipGetErrorString(e));
+  }
+  return OU_OK;
+}
+
+int32_t ou_snake_tile(void) { return snake_tile(); }
+
+int ou_snake_act(const float* x, float* y, int32_t B, int32_t C, int32_t T, int64_t row_stride, const int32_t* len_host,
+                 const float* exp_alpha, const float* exp_beta, const float* up_kernel, const float* down_kernel,
+                 ou_stream_t stream) {
+  // everything is decided here, on the host, before the first HIP call
+  if (!x || !y || !exp_alpha || !up_kernel || !down_kernel) return fail(nullptr, OU_EINVAL, "ou_snake_act: null argument");
+  if (B < 1 || C < 1 || T < 1) return fail(nullptr, OU_EINVAL, "ou_snake_act: B, C and T must be at least 1");
+  if (C > 65535) return fail(nullptr, OU_EINVAL, "ou_snake_act: at most 65535 channels");
+  if (T > 0x7fffffff - 1024) return fail(nullptr, OU_EINVAL, "ou_snake_act: T must not exceed 2^31 - 1024");
+  if (row_stride < T) return fail(nullptr, OU_EINVAL, "ou_snake_act: row_stride must be at least T");
+  // 64-bit offsets of the kernel: (b * C + c) * row_stride + t, in floats
+  if ((long long)row_stride > (1ll << 60) / ((long long)B * C))
+    return fail(nullptr, OU_EINVAL, "ou_snake_act: B * C * row_stride overflows the 64-bit offsets (at most 2^60)");
+  if (len_host)
+    for (int b = 0; b < B; b++)
+      if (len_host[b] < 0 || len_host[b] > T) return fail(nullptr, OU_EINVAL, "ou_snake_act: 0 <= len[b] <= T");
+  if (!len_host) {
+    for (int off = 0; off < B; off += 65535) {  // (the grid's z extent)
+      const int n = B - off < 65535 ? B - off : 65535;
+      const size_t skip = (size_t)off * (size_t)C * (size_t)row_stride;
+      const hipError_t e = launch_snake_act(x + skip, y + skip, n, C, T, row_stride, nullptr, nullptr, exp_alpha, exp_beta, up_kernel,
+                                            down_kernel, (hipStream_t)stream);
+      if (e != hipSuccess) return fail(nullptr, OU_EHIP, std::string("ou_snake_act: ") + hipGetErrorString(e));
+    }
+    return OU_OK;
+  }
+  for (int off = 0; off < B; off += kSnakeRowsPerLaunch) {
+    SnakeRows blk;
+    const int n = B - off < kSnakeRowsPerLaunch ? B - off : kSnakeRowsPerLaunch;
+    for (int i = 0; i < kSnakeRowsPerLaunch; i++) blk.len[i] = i < n ? len_host[off + i] : 0;
+    const size_t skip = (size_t)off * (size_t)C * (size_t)row_stride;
+    const hipError_t e = launch_snake_act(x + skip, y + skip, n, C, T, row_stride, nullptr, &blk, exp_alpha, exp_beta, up_kernel,
+                                          down_kernel, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, OU_EHIP, std::string("ou_snake_act: ") + hipGetErrorString(e));
+  }
+  return OU_OK;
+}
+
+}  // extern "C"

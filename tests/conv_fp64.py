@@ -163,7 +163,7 @@ class BlockP:
 
 
 def blocks_of(spec):
-    """Every ConvBlock of both networks in walk order (run_condition, run_score_enc / run_score_dec of ou_api.cpp):
+    """Every ConvBlock of both networks in walk order (run_condition, run_score_enc / run_score_dec of ou_walk.cpp):
     [(tap prefix, state-dict prefix, input tap or None for '<prefix>.up', film index or None, cond add tap or None, c1 tap, v tap,
     c1 exported)]."""
     cp, sp = "condition_model", spec.score_prefix

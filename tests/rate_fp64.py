@@ -1,4 +1,4 @@
-"""float64 references of the rate-change / 1x1 / phase-GEMM layers (all of Runner::conv outside Runner::body, ou_api.cpp) for the
+"""float64 references of the rate-change / 1x1 / phase-GEMM layers (all of Runner::conv outside Runner::body, ou_walk.cpp) for the
 tests, written from the operation's definition on the library's tap layout, each with a per-element bound.  Teacher-forced like
 tests/small_fp64.py and tests/conv_fp64.py, whose Report, ulp32, valid_mask, prelu, Epi, _epilogue, blocks_of and chain
 convention are used, not copied: the reference of a layer takes the tap the kernel read.

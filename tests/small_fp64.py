@@ -191,7 +191,7 @@ class Params:
 
 
 def edm_coef(spec, sigma):
-    """make_coef of ou_api.cpp for per-row sigmas, in its fp32 arithmetic: dict of fp32 tensors (B,)."""
+    """make_coef of ou_walk.cpp for per-row sigmas, in its fp32 arithmetic: dict of fp32 tensors (B,)."""
     s = torch.as_tensor(sigma, dtype=torch.float32)
     s2 = s * s
     if spec.edm_noise is None:

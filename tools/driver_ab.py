@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """A/B of the enhance entry points between two builds of the library: same bits, same launches.
 
-Every way into the sampler -- the six entry points ou_enhance, ou_enhance_var, ou_enhance_ensemble, ou_enhance_segments,
-ou_enhance_segments_var and ou_enhance_segments_ensemble -- is called on the reduced-width models of the GPU tests, 3 steps,
-fixed seeds, and one JSON line per call is printed: the call's name, both counters of ou_launch_stats, the SHA-256 of the
+Every way into the sampler -- the seven entry points ou_enhance, ou_enhance_var, ou_enhance_ensemble, ou_enhance_segments,
+ou_enhance_segments_var, ou_enhance_segments_ensemble and ou_enhance_segments_var_ensemble -- is called on the reduced-width
+models of the GPU tests, 3 steps, fixed seeds, and one JSON line per call is printed: the call's name, both counters of
+ou_launch_stats, the SHA-256 of the
 output bytes and `rng`, the SHA-256 of the end states (`get_state()`, concatenated) of the generators handed to the call (empty
 for counter sources and calls without a generator).  The Python paths in front of the entry points are covered too: shared
 generators, `pad_batch`, the `ensemble=` glue of `enhance`, noise handed over as a list or a tensor, `return_members`.  So the
@@ -12,7 +13,10 @@ also called on edge shapes:
 rows of 1, 2, 3 and 5 samples, of tot_ds + 1, 16 tot_ds + 2 and 33 tot_ds + 3, so that the longest row is 1, 2 and 3 past a
 multiple of 4 -- the word-by-word head and tail of the 16-byte row moves and the guards of rows shorter than a quad.  The `opt.*`
 calls repeat the batch-1, the ragged and the two-row call with one option off its default each, for the branches of the network
-walk that the defaults never take, and one `layout` line per model holds workspace sizes and tensor offsets.  Run it
+walk that the defaults never take, and one `layout` line per model holds workspace sizes and tensor offsets.  Behind the two
+default models come the models of tests/snake_cases.py with Snake and with mixed ConvBlock activations (ou_enhance and a ragged
+ou_enhance_var each, one `layout` line with the `.act` planes) and PP16s in every level-normalisation mode of
+tests/norm_cases.py (normalization_norm max and 2-max, zero_mean false: ou_enhance and ou_enhance_segments each).  Run it
 once per library and compare the files byte for byte:
 
     OU_LIBRARY=/path/to/parent/libouniverse.so timeout -k 10 600 python tools/driver_ab.py --out parent.json
@@ -33,6 +37,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import norm_cases  # noqa: E402
+import snake_cases  # noqa: E402
 from helpers import get_spec, synth_mix  # noqa: E402
 from open_universe_amd import Universe, UniverseGAN, _lib, state_dict as S  # noqa: E402
 from open_universe_amd.noise import CounterNoise  # noqa: E402
@@ -131,6 +137,20 @@ def calls(model, spec):
     yield "enhance_long_ensemble.share0.tensor.median", [90], lambda g: long_ensemble(0, two_long, g[0], "median")
     yield "enhance_long_ensemble.share1.counter.mean", [], lambda g: long_ensemble(1, two_long, CounterNoise(91, 4), "mean")
 
+    # rows with lengths of their own (groups of 12 // 3 = 4 entries: the windows of the two long rows, then the short rows as
+    # ragged groups); results and members in one digest
+    def long_many_ensemble(share, rngs):
+        model.set_option("ens_share", share)
+        try:
+            res, mems = model.enhance_long_many_ensemble(six, 3, rngs=rngs, return_members=True, **ens)
+            return list(res) + list(mems)
+        finally:
+            model.set_option("ens_share", 1)
+    for share in (1, 0):
+        yield f"enhance_long_many_ensemble.share{share}.tensor", many6, lambda g, share=share: long_many_ensemble(share, g)
+        yield f"enhance_long_many_ensemble.share{share}.counter", [], lambda g, share=share: long_many_ensemble(
+            share, [CounterNoise(95, 5 + i) for i in range(6)])
+
     # edge shapes (keep_rms: the post scale moves every row)
     edge = [1, 2, 3, 5, td + 1, 16 * td + 2, 33 * td + 3]
     for T in edge:
@@ -160,7 +180,7 @@ def calls(model, spec):
             mix, 3, n_steps=N, rng=g[0], return_members=True)
     yield "py.enhance_long_many.shared", [125], lambda g: model.enhance_long_many(six, g[0], **seg)
 
-    # the branches of the network walk (Runner::conv / block in ou_api.cpp) that the default options never take: one option off
+    # the branches of the network walk (Runner::conv / block in ou_walk.cpp) that the default options never take: one option off
     # its default per call, reset afterwards
     def with_option(key, value, fn):
         default = model.get_option(key)
@@ -184,17 +204,60 @@ def calls(model, spec):
     yield "opt.gru_bmax1.enhance.b2", [130], lambda g: with_option("gru_bmax", 1, lambda: model.enhance(two, n_steps=N, rng=g[0]))
 
 
-def layout(model, spec):
+WALK_TENSORS = ("mixn", "x", "cond.aux", "cond.latent", "cond.enc0.c1", "score.dec0.v", "score.gru")
+
+
+def layout(model, spec, names=WALK_TENSORS):
     """The workspace layout of a model as one record: ou_workspace_bytes at three shapes, and where `Universe.tensor` finds
-    seven tensors of the walk after `enhance.b1` -- (byte offset into the workspace, C, T) each."""
+    the tensors `names` of the walk after `enhance.b1` -- (byte offset into the workspace, C, T) each."""
     td = spec.tot_ds
     model.enhance(synth_mix(spec, 1, 23 * td + 5, seed=1500)[0].cuda(), n_steps=N, rng=gen(11))
     torch.cuda.synchronize()
     where = {}
-    for name in ("mixn", "x", "cond.aux", "cond.latent", "cond.enc0.c1", "score.dec0.v", "score.gru"):
+    for name in names:
         t = model.tensor(name)
         where[name] = [t.data_ptr() - model._ws.data_ptr(), t.shape[1], t.shape[2]]
     return {"workspace_bytes": [model._workspace_bytes(B, n * td) for B, n in ((1, 23), (2, 19), (3, 41))], "tensors": where}
+
+
+def build_case(cases, *key):
+    """A model of tests/snake_cases.py or tests/norm_cases.py: the case's spec on the case's seeded weights."""
+    spec = cases.spec_of(*key)
+    cls = UniverseGAN if spec.kind == "universe_gan" else Universe
+    return cls(spec, state_dict=cases.state_dict_of(*key), device="cuda:0"), spec
+
+
+def snake_calls(model, spec):
+    """Networks with Snake (and with mixed) ConvBlock activations: the batch-1 call and one ragged batch."""
+    td = spec.tot_ds
+    one = synth_mix(spec, 1, 23 * td + 5, seed=1500)[0].cuda()
+    ragged = [synth_mix(spec, 1, n, seed=1700 + i)[0].cuda() for i, n in enumerate([41 * td + 7, 57, 16 * td])]
+    yield "enhance.b1", [11], lambda g: model.enhance(one, n_steps=N, rng=g[0])
+    yield "enhance_many.ragged.tensor", [20, 21, 22], lambda g: model.enhance_many(ragged, g, n_steps=N)
+
+
+def norm_calls(model, spec):
+    """The level normalisation modes: the cases' own batch (a smooth row and one with a spike, both on a DC offset) through
+    `enhance`, and two such rows of 70 tot_ds + 3 samples through `enhance_long`."""
+    td = spec.tot_ds
+    mix = norm_cases.batch_mix(spec).cuda()
+    long2 = synth_mix(spec, 2, 70 * td + 3, seed=1800) + norm_cases.DC
+    long2[1] = norm_cases.with_spike(long2[1], 31 * td)
+    long2 = long2.cuda()
+    seg = dict(segment_s=16 * td / spec.fs, overlap_s=2 * td / spec.fs, max_batch=4, n_steps=N)
+    yield "enhance.b2", [140], lambda g: model.enhance(mix, n_steps=N, rng=g[0])
+    yield "enhance_long.c2.tensor", [141], lambda g: model.enhance_long(long2, rng=g[0], **seg)
+
+
+def suites(models):
+    """-> (name, build, calls, tensors of the layout line or None) for every model of the comparison"""
+    for name in models:
+        yield name, lambda name=name: build(name), calls, WALK_TENSORS
+    # Snake activations: a plane of activated inputs per block (`.act`) in the workspace
+    yield "snake.snake", lambda: build_case(snake_cases, "snake"), snake_calls, ("x", "score.enc0.act", "score.dec0.act", "score.gru")
+    yield "snake.mixed", lambda: build_case(snake_cases, "mixed"), snake_calls, None
+    for mode in norm_cases.MODES:  # max, 2max, keepmean (norm 2, zero_mean false)
+        yield f"norm.PP16s.{mode}", lambda mode=mode: build_case(norm_cases, "PP16s", mode), norm_calls, None
 
 
 def main():
@@ -203,9 +266,9 @@ def main():
     ap.add_argument("--models", nargs="+", default=["PP16s", "PP24s"])
     args = ap.parse_args()
     lines = []
-    for name in args.models:
-        model, spec = build(name)
-        for call, seeds, fn in calls(model, spec):
+    for name, make, calls_of, tensors in suites(args.models):
+        model, spec = make()
+        for call, seeds, fn in calls_of(model, spec):
             gens = [gen(s) for s in seeds]
             out = fn(gens)
             torch.cuda.synchronize()
@@ -213,8 +276,9 @@ def main():
             lines.append(json.dumps({"call": f"{name}.{call}", "launches": launches, "convs": convs, "sha256": digest(out),
                                      "rng": rng_digest(gens)}))
             print(lines[-1], flush=True)
-        lines.append(json.dumps({"call": f"{name}.layout", **layout(model, spec)}))
-        print(lines[-1], flush=True)
+        if tensors:
+            lines.append(json.dumps({"call": f"{name}.layout", **layout(model, spec, tensors)}))
+            print(lines[-1], flush=True)
     if args.out:
         with open(args.out, "w") as f:
             f.write("\n".join(lines) + "\n")
