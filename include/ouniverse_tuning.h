@@ -29,6 +29,11 @@ int ou_profile_read(ou_handle* h, int32_t max_records, float* ms, double* flops,
 int ou_profile_read_ticks(ou_handle* h, int32_t max_records, uint64_t* t_start, uint64_t* t_end, int32_t* cfg,
                           int32_t* n_records);
 
+/* The kernel family a variant code names -- the `cfg` of a profile record, `cfg_used` of ou_bench_conv, a forced `cfg` --
+ * e.g. "lds", "direct2w", "fused", "split"; NULL for a code that names none.  The one table of these codes (csrc/ou_variants.h);
+ * pure host code, needs no device.  Profile records from 1000 on are GRU passes whatever this says about them as forced codes. */
+const char* ou_variant_family(int32_t code);
+
 /* Per-wave phase stamps of the fused ConvBlock kernel for ONE block of the network (its name as in ou_tensor, e.g.
  * "score.enc0"; NULL / "": off) -- written into the last 16 MB of the workspace (tools/chain_ts.py). */
 int ou_set_stamp_layer(ou_handle* h, const char* block_name);

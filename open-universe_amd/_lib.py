@@ -185,6 +185,7 @@ def load():
         "ou_flac_info": (i32, [vp, sz, POINTER(i32), POINTER(i32), POINTER(i32), POINTER(ctypes.c_int64), vp]),
         "ou_flac_decode": (i32, [vp, sz, vp, ctypes.c_int64, POINTER(ctypes.c_int64)]),
         "ou_profile_enable": (i32, [vp, i32]),
+        "ou_variant_family": (c_char_p, [i32]),
         "ou_bench_conv": (i32, [vp, c_char_p, i32, i32, i32, i32, i32, i32, vp, sz, vp, POINTER(c_float), POINTER(i32)]),
         "ou_profile_read": (i32, [vp, i32, POINTER(c_float), POINTER(c_double), POINTER(c_double), POINTER(i32), POINTER(i32)]),
         "ou_profile_read_ticks": (i32, [vp, i32, POINTER(ctypes.c_uint64), POINTER(ctypes.c_uint64), POINTER(i32), POINTER(i32)]),
@@ -216,6 +217,7 @@ EXPORTED_SYMBOLS = [
     "ou_flac_last_error", "ou_flac_info", "ou_flac_decode",
 ]
 TUNING_SYMBOLS = ["ou_profile_enable", "ou_profile_read", "ou_profile_read_ticks", "ou_bench_conv", "ou_set_stamp_layer",
+                  "ou_variant_family",
 ]
 
 _EXC = {OU_EINVAL: ValueError, OU_ENOTIMPL: NotImplementedError, OU_EMISSING: KeyError, OU_ESHAPE: ValueError,

@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "ou_variants.h"
 #include "ou_walk.h"
 
 using namespace ou;
@@ -541,6 +542,9 @@ int ou_profile_enable(ou_handle* h, int32_t on) {
   }
   return OU_OK;
 }
+
+// the family a variant code names (ou_variants.h), or null: pure host code, works without a device
+const char* ou_variant_family(int32_t code) { return ou::variant_family(code); }
 
 // ... and the raw stamps of the same records: first block start / last block end of every launch on the device's 100 MHz
 // constant clock (10 ns ticks; one clock for all handles of a process, so that the launches of several lanes can be laid on

@@ -2,6 +2,7 @@
 // (one translation unit per kernel family; shared device helpers in ou_dev.h, cross-file launchers in ou_internal.h)
 #include "ou_kernels.h"
 #include "ou_internal.h"
+#include "ou_variants.h"
 #include "ou_dev.h"
 
 #include <cmath>
@@ -863,24 +864,16 @@ static const RateDownCfg kRateDownCfgs[] = {
     {2, 64, 32, rate_down_kernel<2, 2, 2, 32>, 256, 64},    // PP16 / OR16: 32 -> 64 channels, T -> T/2
     {2, 96, 48, rate_down_kernel<2, 3, 1, 48>, 192, 32},    // PP24: 48 -> 96
 };
-bool rate_down_supported(const ConvArgs& a) {
+ConvPlan plan_rate_down(const ConvArgs& a, int) {
   if (a.up != 1 || a.stride != a.KW || a.pad != 0 || a.Tin != a.Nq * a.stride || a.add || a.film || a.res || a.in_scale)
-    return false;
-  if (a.fir && a.fir_len != 2 * a.stride + 1) return false;
-  for (const RateDownCfg& c : kRateDownCfgs)
-    if (c.R == a.stride && c.M == a.M && c.Cin == a.Cin) return true;
-  return false;
-}
-hipError_t launch_rate_down(const ConvArgs& a, hipStream_t st, int* cfg_out) {
-  if (!rate_down_supported(a)) return hipErrorNotSupported;
+    return no_plan(hipErrorNotSupported);
+  if (a.fir && a.fir_len != 2 * a.stride + 1) return no_plan(hipErrorNotSupported);
   for (const RateDownCfg& c : kRateDownCfgs) {
     if (c.R != a.stride || c.M != a.M || c.Cin != a.Cin) continue;
     const size_t smem = (size_t)a.Cin * (c.bq * c.R + 4) * 4;
-    if (cfg_out) *cfg_out = 40 + c.R;
-    hipLaunchKernelGGL(c.kern, dim3((a.Nq + c.bq - 1) / c.bq, a.B), dim3(c.threads), smem, st, a);
-    return hipGetLastError();
+    return {hipSuccess, kVarRateDown + c.R, c.kern, dim3((a.Nq + c.bq - 1) / c.bq, a.B), dim3(c.threads), smem, a};
   }
-  return hipErrorNotSupported;
+  return no_plan(hipErrorNotSupported);
 }
 
 //   up:    y = FIR_{2R+1}(convT_{k=s=R}(prelu(x))) + bias ; y = res ? (y + res) res_scale : y      K = Cin <= 96
@@ -1041,26 +1034,18 @@ static const RateUpCfg kRateUpCfgs[] = {
     //  was built, parity-green, and measured: 8 launches fewer per enhance, the enhance 0.03-0.09 ms SLOWER at batch 1 and 1-2 %
     //  slower at batch 8 (profiles/r06_rate_up_deeper_level_ab.txt): the fused block's phases run back to back, as on the down path)
 };
-bool rate_up_supported(const ConvArgs& a) {
+ConvPlan plan_rate_up(const ConvArgs& a, int) {
   if (a.up < 2 || a.stride != 1 || a.KW != 1 || a.pad != 0 || a.add || a.film || a.in_scale || a.Nq != a.Tin ||
       a.Tout != a.Tin * a.up || a.M != a.Cout * a.up)
-    return false;
-  if (a.fir && a.fir_len != 2 * a.up + 1) return false;
-  for (const RateUpCfg& c : kRateUpCfgs)
-    if (c.R == a.up && c.M == a.M && c.Cin == a.Cin) return true;
-  return false;
-}
-hipError_t launch_rate_up(const ConvArgs& a, hipStream_t st, int* cfg_out) {
-  if (!rate_up_supported(a)) return hipErrorNotSupported;
+    return no_plan(hipErrorNotSupported);
+  if (a.fir && a.fir_len != 2 * a.up + 1) return no_plan(hipErrorNotSupported);
   for (const RateUpCfg& c : kRateUpCfgs) {
     if (c.R != a.up || c.M != a.M || c.Cin != a.Cin) continue;
     const int bv = c.bf - (a.fir ? 2 : 0);
     const size_t smem = (size_t)c.M * (c.bf + 1) * 4;
-    if (cfg_out) *cfg_out = 45 + c.R;
-    hipLaunchKernelGGL(c.kern, dim3((a.Tin + bv - 1) / bv, a.B), dim3(c.threads), smem, st, a);
-    return hipGetLastError();
+    return {hipSuccess, kVarRateUp + c.R, c.kern, dim3((a.Tin + bv - 1) / bv, a.B), dim3(c.threads), smem, a};
   }
-  return hipErrorNotSupported;
+  return no_plan(hipErrorNotSupported);
 }
 
 

@@ -2,6 +2,8 @@
 // (one translation unit per kernel family; shared device helpers in ou_dev.h, cross-file launchers in ou_internal.h)
 #include "ou_kernels.h"
 #include "ou_internal.h"
+#include "ou_conv_fields.h"
+#include "ou_variants.h"
 #include "ou_dev.h"
 
 #include <cmath>
@@ -1100,10 +1102,10 @@ static void direct2_pick(const ConvArgs& a, int num_cu, int& tn, int& wk, bool& 
   if (a.force_cfg == 110 && a.wu && wk4_ok) { tn = 2; wk = 4; wino = true; }
 }
 
-// Launches a direct kernel when the layer fits one; hipErrorInvalidConfiguration = "use conv_mfma_kernel".
-hipError_t launch_conv_direct(const ConvArgs& a, int num_cu, hipStream_t stream, int* cfg_out) {
-  if (a.Cin % 16 || (a.in_scale != nullptr && a.act)) return hipErrorInvalidConfiguration;
-  if ((long)a.Cin * a.Tin * 4 >= (1L << 31) || (long)a.Cin * a.KW * a.Mp * 4 >= (1L << 31)) return hipErrorInvalidConfiguration;
+// Plans a direct kernel when the layer fits one; hipErrorInvalidConfiguration = "use conv_mfma_kernel".
+ConvPlan plan_conv_direct(const ConvArgs& a, int num_cu) {
+  if (a.Cin % 16 || (a.in_scale != nullptr && a.act)) return no_plan(hipErrorInvalidConfiguration);
+  if ((long)a.Cin * a.Tin * 4 >= (1L << 31) || (long)a.Cin * a.KW * a.Mp * 4 >= (1L << 31)) return no_plan(hipErrorInvalidConfiguration);
   const int npw = a.Cin / 16;  // channel pairs per wave
   const long gm = (a.M + 31) / 32;
   // 64- or 32-column tiles: all blocks of these launches start together, so a launch takes about ceil(blocks / CUs)
@@ -1128,7 +1130,7 @@ hipError_t launch_conv_direct(const ConvArgs& a, int num_cu, hipStream_t stream,
   long gm_fir = gm;
   if (a.fir) {  // fused up-path FIR: whole output channels per tile, one halo frame either side
     if ((a.up != 2 && a.up != 3 && a.up != 4 && a.up != 5 && a.up != 8) || a.KW != 1 || a.stride != 1 || a.pad != 0 || a.fir_len != 2 * a.up + 1 || a.add || a.film)
-      return hipErrorNotSupported;
+      return no_plan(hipErrorNotSupported);
     bm_step = (32 / a.up) * a.up;
     halo = 1;
     gm_fir = (a.M + bm_step - 1) / bm_step;
@@ -1143,7 +1145,7 @@ hipError_t launch_conv_direct(const ConvArgs& a, int num_cu, hipStream_t stream,
     const long slots = (long)num_cu * (tn == 2 ? 2 : 4);
     const long fused = gm_fir * ((a.Nq + 32 * tn - 3) / (32 * tn - 2)) * a.B;
     const long plain = gm * ((a.Nq + 32 * tn - 1) / (32 * tn)) * a.B;
-    if (a.force_cfg < 0 && (fused + slots - 1) / slots > (plain + slots - 1) / slots) return hipErrorNotSupported;
+    if (a.force_cfg < 0 && (fused + slots - 1) / slots > (plain + slots - 1) / slots) return no_plan(hipErrorNotSupported);
   }
   int wk = 8;
   const bool wide = a.stride == 1 && a.wd && a.direct >= 2 && !a.fir && a.up == 1 && (a.KW == 3 || a.KW == 5) && npw % 4 == 0 &&
@@ -1155,7 +1157,7 @@ hipError_t launch_conv_direct(const ConvArgs& a, int num_cu, hipStream_t stream,
     if (wino) {
       if (wk == 8) kern = a.KW == 3 ? conv_direct2w_kernel<3, 8> : conv_direct2w_kernel<5, 8>;
       else kern = a.KW == 3 ? conv_direct2w_kernel<3, 4> : conv_direct2w_kernel<5, 4>;
-      variant = 400 + 10 * wk + a.KW;  // minimal-filtering variants (64-column tiles): 483 / 485 (eight slices), 443 / 445
+      variant = kVarDirect2w + 10 * wk + a.KW;  // minimal-filtering variants (64-column tiles): 483 / 485 (eight slices), 443 / 445
     } else {
       if (wk == 8)
         kern = a.KW == 3 ? (tn == 2 ? conv_direct2_kernel<3, 2, 8> : conv_direct2_kernel<3, 1, 8>)
@@ -1163,63 +1165,50 @@ hipError_t launch_conv_direct(const ConvArgs& a, int num_cu, hipStream_t stream,
       else
         kern = a.KW == 3 ? (tn == 2 ? conv_direct2_kernel<3, 2, 4> : conv_direct2_kernel<3, 1, 4>)
                          : (tn == 2 ? conv_direct2_kernel<5, 2, 4> : conv_direct2_kernel<5, 1, 4>);
-      variant = (wk == 8 ? 56 : 57) + 10 * tn;  // 66 / 76 (eight K slices), 67 / 77 (four)
+      variant = kVarDirect2 + (wk == 8 ? 0 : 1) + 10 * tn;  // 66 / 76 (eight K slices), 67 / 77 (four)
     }
   } else if (a.stride == 1) {
-    if (a.KW != 1 && a.KW != 3 && a.KW != 5) return hipErrorInvalidConfiguration;
+    if (a.KW != 1 && a.KW != 3 && a.KW != 5) return no_plan(hipErrorInvalidConfiguration);
     for (const DirectCfg& c : kDirectCfgs) {
       if (c.KW != a.KW || c.TN != tn || npw % (c.GP * 4)) continue;
       kern = c.kern;
-      variant = 50 + 10 * tn + c.GP;  // 6x / 7x: stride-1 direct variants (profile records)
+      variant = kVarDirect + 10 * tn + c.GP;  // 6x / 7x: stride-1 direct variants (profile records)
       break;
     }
   } else {
     // k = s = r, or 3r taps with the anti-alias FIR folded in; whole frames only
     const int R = a.stride, G = a.KW / R;
     if (a.up != 1 || a.KW != G * R || (G != 1 && G != 3) || a.pad != (G - 1) / 2 * R || a.Tin != a.Nq * R)
-      return hipErrorInvalidConfiguration;
-    if ((npw * G) % 4) return hipErrorInvalidConfiguration;
+      return no_plan(hipErrorInvalidConfiguration);
+    if ((npw * G) % 4) return no_plan(hipErrorInvalidConfiguration);
     tn = 2;
     for (const StridedCfg& c : kStridedCfgs) {
       if (c.R != R || c.G != G || c.TN != tn) continue;
       kern = c.kern;
-      variant = 80 + 10 * (tn - 1) + G;  // 8x / 9x: strided direct variants
+      variant = kVarStrided + 10 * (tn - 1) + G;  // 8x / 9x: strided direct variants
       break;
     }
   }
-  if (!kern) return a.fir ? hipErrorNotSupported : hipErrorInvalidConfiguration;
-  if (a.out_act && !wide) return hipErrorNotSupported;  // (only Direct2Epilogue -- the wide-load kernels -- has the activating form)
-  ConvArgs aa = a;
+  if (!kern) return no_plan(a.fir ? hipErrorNotSupported : hipErrorInvalidConfiguration);
+  if (a.out_act && !wide) return no_plan(hipErrorNotSupported);  // (only Direct2Epilogue -- the wide-load kernels -- has the activating form)
   const int BN = 32 * tn;
-  aa.magic_up = a.up == 1 ? 0u : (unsigned)(0x100000000ull / (unsigned)a.up) + 1u;
+  ConvPlan p = {hipSuccess, variant, kern, dim3(), dim3(64 * wk), (size_t)wk * 32 * (BN + 4) * 4, a};
+  ConvArgs& aa = p.args;
+  fill_magic_up(aa);
   aa.tile_bm = bm_step; aa.tile_bn = BN - 2 * halo; aa.tile_halo = halo;
   aa.grid_n = (a.Nq + aa.tile_bn - 1) / aa.tile_bn;
   aa.grid_m = (int)gm_fir;
-  const bool is_d2 = variant == 66 || variant == 76 || variant == 67 || variant == 77 || (variant >= 400 && variant < 500);
-  {
-    const double xb = (double)a.Cin * a.Nq * a.stride, wb = (double)a.M * a.Cin * a.KW;
-    aa.xcd_map = 0;
-    if (aa.grid_m % 8 == 0 && wb >= xb) aa.xcd_map = 1;
-    else if (aa.grid_n >= 8) aa.xcd_map = 2;
-    if (is_d2 && aa.xcd_map == 2 && aa.grid_m % 2 == 0) {
+  fill_xcd_map(aa, is_direct2(variant), a.d2_map, [&aa] {
       // 2-D ownership instead of "column tiles x mod 8 per XCD": an XCD then owns a CONTIGUOUS quarter of the time axis and
       // half of the rows.  Measured (tools/d2_sweep.py, PP16 B = 1): 19.3 -> 18.3 us (64 channels, T = 32 080), 16.5 -> 15.5 /
       // 11.2 -> 10.9 us (128 channels), no difference at 256 channels; (4 x 2) the same where it fits and a disaster where the
       // row groups do not divide (two row tiles: half the blocks are padding).  A per-XCD byte count (W/2 + X/4 against
       // W + X/8) predicts the opposite for the 128-channel level: with interleaved ownership every XCD also pulls the halo
       // lines of its neighbours' tiles, and the weights are the smaller operand there anyway.
-      if (direct_grid_blocks(3, aa.grid_m, aa.grid_n) * 16 <= (long)aa.grid_m * ((aa.grid_n + 7) / 8 * 8) * 17) aa.xcd_map = 3;
-    }
-    if (is_d2 && a.d2_map >= 0) aa.xcd_map = a.d2_map;
-    if (a.force_xcd_map >= 0) aa.xcd_map = a.force_xcd_map;
-    if (aa.xcd_map == 1 && aa.grid_m % 8) aa.xcd_map = 0;
-    if ((aa.xcd_map == 3 || aa.xcd_map == 4) && !is_d2) aa.xcd_map = 0;
-  }
-  const int nblocks = direct_grid_blocks(aa.xcd_map, aa.grid_m, aa.grid_n);
-  const size_t smem = (size_t)wk * 32 * (BN + 4) * 4;
-  if (cfg_out) *cfg_out = variant;
-  hipLaunchKernelGGL(kern, dim3(nblocks, 1, a.B), dim3(64 * wk), smem, stream, aa);
-  return hipGetLastError();
+      return direct_grid_blocks(3, aa.grid_m, aa.grid_n) * 16 <= (long)aa.grid_m * ((aa.grid_n + 7) / 8 * 8) * 17 ? 3 : 2;
+  });
+  p.grid = dim3(direct_grid_blocks(aa.xcd_map, aa.grid_m, aa.grid_n), 1, a.B);
+  return p;
 }
 
 

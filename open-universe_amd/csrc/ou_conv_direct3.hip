@@ -3,6 +3,8 @@
 // (one translation unit per kernel family; shared device helpers in ou_dev.h, cross-file launchers in ou_internal.h)
 #include "ou_kernels.h"
 #include "ou_internal.h"
+#include "ou_conv_fields.h"
+#include "ou_variants.h"
 #include "ou_dev.h"
 
 #include <cmath>
@@ -722,55 +724,49 @@ static const Direct3sCfg kDirect3sCfgs[] = {
     {1, conv_direct3s_kernel<1, 4>}, {2, conv_direct3s_kernel<2, 4>}, {3, conv_direct3s_kernel<3, 2>},
     {4, conv_direct3s_kernel<4, 2>}, {5, conv_direct3s_kernel<5, 2>},
 };
-// Launches the throughput kernel when the layer fits it AND supplies enough wave tiles to fill the machine without
+// Plans the throughput kernel when the layer fits it AND supplies enough wave tiles to fill the machine without
 // splitting K; hipErrorInvalidConfiguration = "use the other kernels".
-static hipError_t launch_conv_direct3s(const ConvArgs& a, int num_cu, hipStream_t stream, int* cfg_out, double tile_min) {
+static ConvPlan plan_conv_direct3s(const ConvArgs& a, int num_cu, double tile_min) {
   // 1x1 / phase GEMMs (KW = 1, any up) and k = s = R rate-change convs on whole frames
   const int R = a.stride > 1 ? a.stride : 1;
   if (a.KW != R || a.pad != 0 || (a.stride > 1 && (a.up != 1 || a.Tin != a.Nq * R)) || a.Cin % 16 || a.CK % 4 || a.fir ||
       (a.in_scale != nullptr && a.act))
-    return hipErrorInvalidConfiguration;
-  if ((long)a.Cin * a.Tin * 4 >= (1L << 31) || (long)a.Cin * a.KW * a.Mp * 4 >= (1L << 31)) return hipErrorInvalidConfiguration;
+    return no_plan(hipErrorInvalidConfiguration);
+  if ((long)a.Cin * a.Tin * 4 >= (1L << 31) || (long)a.Cin * a.KW * a.Mp * 4 >= (1L << 31)) return no_plan(hipErrorInvalidConfiguration);
   void (*kern)(ConvArgs) = nullptr;
   for (const Direct3sCfg& c : kDirect3sCfgs)
     if (c.R == R) { kern = c.kern; break; }
-  if (!kern) return hipErrorInvalidConfiguration;
+  if (!kern) return no_plan(hipErrorInvalidConfiguration);
   const long gy = (a.M + 63) / 64, ct = (a.Nq + 63) / 64;
   const double per_simd = (double)gy * ct * a.B / (4.0 * num_cu);
-  if (a.force_cfg < 200 && per_simd < tile_min) return hipErrorInvalidConfiguration;
-  if (a.out_act) return hipErrorNotSupported;  // (this kernel would take the layer, but has no activating epilogue)
-  ConvArgs aa = a;
-  aa.grid_m = (int)gy;
-  aa.magic_up = a.up == 1 ? 0u : (unsigned)(0x100000000ull / (unsigned)a.up) + 1u;
+  if (a.force_cfg < kVarDirect3 && per_simd < tile_min) return no_plan(hipErrorInvalidConfiguration);
+  if (a.out_act) return no_plan(hipErrorNotSupported);  // (this kernel would take the layer, but has no activating epilogue)
   const long chunks = (ct + 3) / 4, total8 = (chunks * a.B + 7) / 8 * 8;
-  aa.grid_n = (int)chunks;
-  if (cfg_out) *cfg_out = 260 + R;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(total8 * gy)), dim3(256), 0, stream, aa);
-  return hipGetLastError();
+  ConvPlan p = {hipSuccess, kVarDirect3s + R, kern, dim3((unsigned)(total8 * gy)), dim3(256), 0, a};
+  p.args.grid_m = (int)gy;
+  fill_magic_up(p.args);
+  p.args.grid_n = (int)chunks;
+  return p;
 }
-hipError_t launch_conv_direct3(const ConvArgs& a, int num_cu, hipStream_t stream, int* cfg_out) {
+ConvPlan plan_conv_direct3(const ConvArgs& a, int num_cu) {
   const double tile_min_s = a.tile_min >= 0 ? a.tile_min : 1.2;
   if (a.KW == 1 || a.stride > 1) {
-    if (tile_min_s > 0 && a.Nq < 1024 && a.force_cfg < 200) return hipErrorInvalidConfiguration;
+    if (tile_min_s > 0 && a.Nq < 1024 && a.force_cfg < kVarDirect3) return no_plan(hipErrorInvalidConfiguration);
 
     // (with the up-path FIR requested as a fused epilogue: refuse, so that the caller runs conv + FIR pass -- unless the layer
     // is too small for this kernel anyway, then the split-K kernel with its fused FIR gets its chance)
     if (a.fir) {
-      ConvArgs probe = a;
-      probe.fir = nullptr;
-      const int R = 1;
-      const double per_simd = (double)((a.M + 63) / 64) * ((a.Nq + 63) / 64) * a.B / (4.0 * num_cu);
-      if (a.KW == R && a.stride == 1 && a.pad == 0 && a.Cin % 16 == 0 && a.CK % 4 == 0 && per_simd >= tile_min_s &&
-          !(a.in_scale != nullptr && a.act) && a.force_cfg < 0)
-        return hipErrorNotSupported;
-      return hipErrorInvalidConfiguration;
+      ConvArgs unfused = a;
+      unfused.fir = nullptr; unfused.out_act = 0;
+      const bool takes = a.stride == 1 && a.force_cfg < 0 && plan_conv_direct3s(unfused, num_cu, tile_min_s).status == hipSuccess;
+      return no_plan(takes ? hipErrorNotSupported : hipErrorInvalidConfiguration);
     }
-    return launch_conv_direct3s(a, num_cu, stream, cfg_out, tile_min_s);
+    return plan_conv_direct3s(a, num_cu, tile_min_s);
   }
   if (!a.wd || a.stride != 1 || a.up != 1 || (a.KW != 3 && a.KW != 5) || a.pad != (a.KW - 1) / 2 || a.fir || a.Cin % 16 ||
       (a.in_scale != nullptr && a.act))
-    return hipErrorInvalidConfiguration;
-  if ((long)a.Cin * a.Tin * 4 >= (1L << 31) || (long)a.Cin * a.Mp * 8 * 4 >= (1L << 31)) return hipErrorInvalidConfiguration;
+    return no_plan(hipErrorInvalidConfiguration);
+  if ((long)a.Cin * a.Tin * 4 >= (1L << 31) || (long)a.Cin * a.Mp * 8 * 4 >= (1L << 31)) return no_plan(hipErrorInvalidConfiguration);
   // wave tiles per SIMD below which the split-K kernels are ahead (measured, PP16 / PP24 at B = 1 .. 16: break-even at
   // ~1 tile per SIMD, +8 .. +60 % from 1.5 up, 2-3x slower at 0.25; OU_TILE_MIN: tuning / tests, 0 = wherever it fits)
   const double tile_min = a.tile_min >= 0 ? a.tile_min : 1.2;
@@ -781,7 +777,7 @@ hipError_t launch_conv_direct3(const ConvArgs& a, int num_cu, hipStream_t stream
   const bool wino_ok = a.wino && a.direct >= 5 && a.wu && a.M % 16 == 0;
   const bool short_k5 = wino_ok && a.KW == 5 && a.M % 32 == 0 &&
                         (double)(a.M / 32) * ((a.Nq + 63) / 64) * a.B / (4.0 * num_cu) >= 0.85;
-  if (tile_min > 0 && a.Nq < 1024 && a.force_cfg < 200 && !short_k5) return hipErrorInvalidConfiguration;
+  if (tile_min > 0 && a.Nq < 1024 && a.force_cfg < kVarDirect3 && !short_k5) return no_plan(hipErrorInvalidConfiguration);
   int tm = direct3_tm(a.M);
   const long ct = (a.Nq + 63) / 64;
   // 32-row tiles where the preferred ones leave fewer than ~3 wave tiles per SIMD (and M tiles by 32): twice the waves, half the
@@ -793,12 +789,12 @@ hipError_t launch_conv_direct3(const ConvArgs& a, int num_cu, hipStream_t stream
   // minimal filtering: 32-row tiles (16-row tiles where the rows only tile by 16: PP24's 48 channels, 165 vs 184 us)
   bool wino = wino_ok;
   if (wino) tm = a.M % 32 == 0 ? 2 : 1;
-  if (a.force_cfg >= 200) { tm = (a.force_cfg / 10) % 10; wino = false; }
-  if (a.force_cfg >= 500 && a.force_cfg < 600 && a.wu) wino = true;  // 500 + 10 TM + KW: the minimal-filtering form (tests / sweeps)
-  if (tm < (wino ? 1 : 2) || tm > 4) return hipErrorInvalidConfiguration;
+  if (a.force_cfg >= kVarDirect3) { tm = (a.force_cfg / 10) % 10; wino = false; }
+  if (variant_in(a.force_cfg, "direct3w") && a.wu) wino = true;  // 500 + 10 TM + KW: the minimal-filtering form (tests / sweeps)
+  if (tm < (wino ? 1 : 2) || tm > 4) return no_plan(hipErrorInvalidConfiguration);
   const long gy = (a.M + 16 * tm - 1) / (16 * tm);
   const double per_simd = (double)gy * ct * a.B / (4.0 * num_cu);
-  if (a.force_cfg < 200 && per_simd < (short_k5 && a.Nq < 1024 ? 0.85 : tile_min)) return hipErrorInvalidConfiguration;
+  if (a.force_cfg < kVarDirect3 && per_simd < (short_k5 && a.Nq < 1024 ? 0.85 : tile_min)) return no_plan(hipErrorInvalidConfiguration);
   // 4 waves x 4 TM KB of LDS for the prefetched epilogue operand (OU_TILE_PREFETCH=0 switches it off)
   const bool prefetch = (a.res || a.add) && (a.Tout & 3) == 0 && a.tile_prefetch != 0;
   void (*kern)(ConvArgs) = nullptr;
@@ -809,15 +805,13 @@ hipError_t launch_conv_direct3(const ConvArgs& a, int num_cu, hipStream_t stream
     for (const Direct3Cfg& c : kDirect3Cfgs)
       if (c.KW == a.KW && c.TM == tm) { kern = prefetch ? c.kern_pre : c.kern; break; }
   }
-  if (!kern) return hipErrorInvalidConfiguration;
-  ConvArgs aa = a;
-  aa.grid_m = (int)gy;
+  if (!kern) return no_plan(hipErrorInvalidConfiguration);
   const long chunks = (ct + 3) / 4, total8 = (chunks * a.B + 7) / 8 * 8;
-  aa.grid_n = (int)chunks;
-  if (cfg_out) *cfg_out = (wino ? 500 : 200) + 10 * tm + a.KW;
   const size_t smem = prefetch ? (size_t)4 * 4 * tm * 1024 : 0;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(total8 * gy)), dim3(256), smem, stream, aa);
-  return hipGetLastError();
+  ConvPlan p = {hipSuccess, (wino ? kVarDirect3w : kVarDirect3) + 10 * tm + a.KW, kern, dim3((unsigned)(total8 * gy)), dim3(256), smem, a};
+  p.args.grid_m = (int)gy;
+  p.args.grid_n = (int)chunks;
+  return p;
 }
 
 

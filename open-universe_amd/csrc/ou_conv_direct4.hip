@@ -3,6 +3,8 @@
 // (one translation unit per kernel family; shared device helpers in ou_dev.h, cross-file launchers in ou_internal.h)
 #include "ou_kernels.h"
 #include "ou_internal.h"
+#include "ou_conv_fields.h"
+#include "ou_variants.h"
 #include "ou_dev.h"
 
 #include <cmath>
@@ -529,23 +531,23 @@ static const Direct4wCfg kDirect4wCfgs[] = {OU_D4W(3, 1, 8), OU_D4W(3, 2, 8), OU
 // The k3 / k5 layers of the 401-frame levels at small batch.  Tile height for an even fill of the CUs (cost = rounds x rows, as
 // direct4_pick); hipErrorInvalidConfiguration = "not a layer for it" (the caller goes on to the other kernels).
 // force_cfg 600 + 10 TM + KW (+ 100: four K slices instead of eight): tuning.
-hipError_t launch_conv_direct4w(const ConvArgs& a, int num_cu, hipStream_t stream, int* cfg_out) {
+ConvPlan plan_conv_direct4w(const ConvArgs& a, int num_cu) {
   if (!a.wu || a.stride != 1 || a.up != 1 || (a.KW != 3 && a.KW != 5) || a.pad != (a.KW - 1) / 2 || a.fir || a.Cin % 16 ||
       (a.in_scale != nullptr && a.act))
-    return hipErrorInvalidConfiguration;
-  if ((long)a.Cin * a.Tin * 4 >= (1L << 31) || (long)a.Cin * a.Mp * 8 * 4 >= (1L << 31)) return hipErrorInvalidConfiguration;
-  const bool forced = a.force_cfg >= 600 && a.force_cfg < 800;
-  if (!forced && !(a.wino && a.direct >= 5)) return hipErrorInvalidConfiguration;
+    return no_plan(hipErrorInvalidConfiguration);
+  if ((long)a.Cin * a.Tin * 4 >= (1L << 31) || (long)a.Cin * a.Mp * 8 * 4 >= (1L << 31)) return no_plan(hipErrorInvalidConfiguration);
+  const bool forced = variant_in(a.force_cfg, "direct4w");
+  if (!forced && !(a.wino && a.direct >= 5)) return no_plan(hipErrorInvalidConfiguration);
   const int slots = a.Cin / 4;
   const long ct = (a.Nq + 63) / 64;
   int tm = 0, wk = 8;
   if (forced) {
     tm = ((a.force_cfg % 100) / 10);
-    wk = a.force_cfg >= 700 ? 4 : 8;
+    wk = a.force_cfg >= kVarDirect4w4 ? 4 : 8;
   } else {
     // short layers only, and only where conv_direct2w_kernel's 64-column x 32-row tiles leave CUs idle
     const long b64 = (long)((a.M + 31) / 32) * ct * a.B;
-    if (a.Nq >= 1024 || b64 * 10 >= (long)num_cu * 8) return hipErrorInvalidConfiguration;
+    if (a.Nq >= 1024 || b64 * 10 >= (long)num_cu * 8) return no_plan(hipErrorInvalidConfiguration);
     long best = 0;
     for (int t = 1; t <= 2; t++) {
       const long blocks = (long)((a.M + 16 * t - 1) / (16 * t)) * ct * a.B;
@@ -553,19 +555,18 @@ hipError_t launch_conv_direct4w(const ConvArgs& a, int num_cu, hipStream_t strea
       if (!tm || cost <= best) { tm = t; best = cost; }  // (ties: the taller tile -- PP24's 768 x 401: 27.0 vs 32.4 us)
     }
   }
-  if (tm < 1 || tm > 2 || slots % (wk * 4) != 0) return hipErrorInvalidConfiguration;
+  if (tm < 1 || tm > 2 || slots % (wk * 4) != 0) return no_plan(hipErrorInvalidConfiguration);
   const Direct4wCfg* c = nullptr;
   for (const Direct4wCfg& k : kDirect4wCfgs)
     if (k.KW == a.KW && k.TM == tm && k.WK == wk) { c = &k; break; }
-  if (!c) return hipErrorInvalidConfiguration;
-  ConvArgs aa = a;
+  if (!c) return no_plan(hipErrorInvalidConfiguration);
   const long gy = (a.M + 16 * tm - 1) / (16 * tm);
-  aa.grid_m = (int)gy;
-  aa.grid_n = (int)ct;
   const long nblocks = 8L * ((gy + 7) / 8) * ct * a.B;
-  if (cfg_out) *cfg_out = (wk == 4 ? 700 : 600) + 10 * tm + a.KW;
-  hipLaunchKernelGGL(c->kern, dim3((unsigned)nblocks), dim3(64 * wk), (size_t)wk * 16 * tm * 68 * 4, stream, aa);
-  return hipGetLastError();
+  ConvPlan p = {hipSuccess, (wk == 4 ? kVarDirect4w4 : kVarDirect4w) + 10 * tm + a.KW, c->kern, dim3((unsigned)nblocks), dim3(64 * wk),
+                (size_t)wk * 16 * tm * 68 * 4, a};
+  p.args.grid_m = (int)gy;
+  p.args.grid_n = (int)ct;
+  return p;
 }
 
 // ---- dispatch -----------------------------------------------------------------------------------------------
@@ -636,13 +637,13 @@ static bool direct4_pick(int M, long ct_b, int slots, int R, int D, bool short_l
 }
 
 // force_cfg 300 + 10 * TM + log2(WK): tuning (ou_bench_conv / tools/direct_sweep.py)
-hipError_t launch_conv_direct4(const ConvArgs& a, int num_cu, hipStream_t stream, int* cfg_out, bool probe) {
+ConvPlan plan_conv_direct4(const ConvArgs& a, int num_cu) {
   const int R = a.stride > 1 ? a.stride : 1;
   if (a.KW != R || a.pad != 0 || (a.stride > 1 && (a.up != 1 || a.Tin != a.Nq * R)) || a.Cin % 16 || a.CK % 4 || a.fir ||
       (a.in_scale != nullptr && a.act))
-    return hipErrorInvalidConfiguration;
-  if ((long)a.Cin * a.Tin * 4 >= (1L << 31) || (long)a.Cin * a.KW * a.Mp * 4 >= (1L << 31)) return hipErrorInvalidConfiguration;
-  if (a.up > 1 && (a.Cout * a.up != a.M || a.Tout != a.Nq * a.up)) return hipErrorInvalidConfiguration;
+    return no_plan(hipErrorInvalidConfiguration);
+  if ((long)a.Cin * a.Tin * 4 >= (1L << 31) || (long)a.Cin * a.KW * a.Mp * 4 >= (1L << 31)) return no_plan(hipErrorInvalidConfiguration);
+  if (a.up > 1 && (a.Cout * a.up != a.M || a.Tout != a.Nq * a.up)) return no_plan(hipErrorInvalidConfiguration);
   const int slots = a.Cin / 4;
   const long ct = (a.Nq + 63) / 64;
   // The 401-frame levels (7 column tiles per element, M = 512 .. 1536: a few hundred tiles whatever the shape).  At batch 1
@@ -651,17 +652,18 @@ hipError_t launch_conv_direct4(const ConvArgs& a, int num_cu, hipStream_t stream
   // the first generation (profiles/r04_final_d4_sweep_PP16_B1.txt).  A transposed conv whose FIR the first generation fuses
   // stays there (conv + FIR pass: 11.8 + 5.3 vs 17.1 us fused), and so do batch 2 - 3 (12 .. 20 us either way); from batch 4
   // this kernel is 3-8 % ahead on these levels too.
-  const bool short_layer = a.Nq < 1024 && a.B < 4;
-  if (a.force_cfg < 300 && a.d4_force == 0 && short_layer && (!a.d4_short || a.B > 1 || (probe && a.up > 1)))
-    return hipErrorInvalidConfiguration;
+  // (try_direct4 keeps such a conv there: it does not ask on behalf of an up conv of a short layer)
+  const bool short_layer = direct4_short_layer(a);
+  if (a.force_cfg < kVarDirect4 && a.d4_force == 0 && short_layer && (!a.d4_short || a.B > 1))
+    return no_plan(hipErrorInvalidConfiguration);
   const Direct4Cfg* best = nullptr;
   auto code = [](const Direct4Cfg& c) { return 10 * c.TM + (c.WK == 1 ? 0 : c.WK == 2 ? 1 : c.WK == 4 ? 2 : 3); };
   const int D = R <= 2 ? 4 : 2;
-  int want = a.force_cfg >= 300 ? a.force_cfg - 300 : a.d4_force;
+  int want = a.force_cfg >= kVarDirect4 ? a.force_cfg - kVarDirect4 : a.d4_force;
   for (int pass = 0; pass < 2 && !best; pass++) {
     // pass 0: the shape asked for (force_cfg / OU_D4_FORCE) where the layer admits it; pass 1: the rule
     if (pass == 1) {
-      if (a.force_cfg >= 300) break;
+      if (a.force_cfg >= kVarDirect4) break;
       int tm = 0, wk = 0;
       if (!direct4_pick(a.M, ct * a.B, slots, R, D, short_layer, num_cu, &tm, &wk)) break;
       want = 10 * tm + (wk == 1 ? 0 : wk == 2 ? 1 : wk == 4 ? 2 : 3);
@@ -671,14 +673,14 @@ hipError_t launch_conv_direct4(const ConvArgs& a, int num_cu, hipStream_t stream
     for (const Direct4Cfg& c : kDirect4Cfgs)
       if (c.R == R && slots % (c.WK * c.D) == 0 && code(c) == want) { best = &c; break; }
   }
-  if (!best) return hipErrorInvalidConfiguration;
-  if (a.out_act) return hipErrorNotSupported;  // (this family would take the layer, but has no activating epilogue)
-  if (probe) return hipSuccess;
+  if (!best) return no_plan(hipErrorInvalidConfiguration);
+  if (a.out_act) return no_plan(hipErrorNotSupported);  // (this family would take the layer, but has no activating epilogue)
   const Direct4Cfg& c = *best;
-  ConvArgs aa = a;
+  ConvPlan p = {hipSuccess, kVarDirect4 + code(c), c.kern, dim3(), dim3(64 * c.WN * c.WK), direct4_smem(c), a};
+  ConvArgs& aa = p.args;
   const long gy = (a.M + 16 * c.TM - 1) / (16 * c.TM);
   aa.grid_m = (int)gy;
-  aa.magic_up = a.up == 1 ? 0u : (unsigned)(0x100000000ull / (unsigned)a.up) + 1u;
+  fill_magic_up(aa);
   const long chunks = (ct + c.WN - 1) / c.WN;
   aa.grid_n = (int)chunks;
   // which operand an XCD's L2 owns (see the kernel): the larger one
@@ -686,9 +688,8 @@ hipError_t launch_conv_direct4(const ConvArgs& a, int num_cu, hipStream_t stream
   aa.xcd_map = wb > xb ? 1 : 2;
   if (a.force_xcd_map == 1 || a.force_xcd_map == 2) aa.xcd_map = a.force_xcd_map;
   const long nblocks = aa.xcd_map == 1 ? 8L * ((gy + 7) / 8) * chunks * a.B : (chunks * a.B + 7) / 8 * 8 * gy;
-  if (cfg_out) *cfg_out = 300 + code(c);
-  hipLaunchKernelGGL(c.kern, dim3((unsigned)nblocks), dim3(64 * c.WN * c.WK), direct4_smem(c), stream, aa);
-  return hipGetLastError();
+  p.grid = dim3((unsigned)nblocks);
+  return p;
 }
 
 }  // namespace ou

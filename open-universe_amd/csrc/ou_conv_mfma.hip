@@ -2,6 +2,8 @@
 // (one translation unit per kernel family; shared device helpers in ou_dev.h, cross-file launchers in ou_internal.h)
 #include "ou_kernels.h"
 #include "ou_internal.h"
+#include "ou_conv_fields.h"
+#include "ou_variants.h"
 #include "ou_dev.h"
 
 #include <cmath>
@@ -487,12 +489,8 @@ hipError_t init_conv_kernels() {
   return init_chain_kernels();
 }
 
-// Every conv family but the fused ConvBlock bodies (variants 100 .. 199: their conv1 / conv2 tiles live in LDS, where nothing
-// zeroes them behind a row's end -- the runner does not fuse ragged batches) keeps ConvArgs::lens in its epilogue.
-bool conv_masks_rows(int cfg) { return cfg >= 0 && !(cfg >= 100 && cfg < 200); }
-
 // ---- the kernel families of a Conv1d launch, in the order they are asked ------------------------------------------------------
-// Each `try_*` answers for ONE family: hipSuccess / a launch error = it took the layer; hipErrorInvalidConfiguration = not a
+// Each `try_*` answers for ONE family with its plan: hipSuccess = it takes the layer; hipErrorInvalidConfiguration = not a
 // layer for this family (ask the next one); hipErrorNotSupported = the layer would be its, but the requested epilogue (fused
 // FIR, activating store) is not -- the caller's fallback.  `force_cfg` (ou_bench_conv, tests) names a variant code; a family
 // is asked only when the code lies in its range [lo, hi), and then its answer is final.
@@ -503,81 +501,92 @@ namespace {
 // along the rows, each weight fragment fetched once per block) and a whole device's worth of 256 x 128 output blocks, half a
 // device's worth for the k5 layers and on short rows (the 401-frame level, on the split-K fp32 kernels otherwise) -- PP16 /
 // OR16: the 256- and 512-channel levels from B = 16, the 256-channel k5 convs from B = 8.
-hipError_t try_split(const ConvArgs& a, int num_cu, hipStream_t stream, int* cfg_out) {
-  if (!a.wsplit || a.split == 0) return hipErrorInvalidConfiguration;
+ConvPlan try_split(const ConvArgs& a, int num_cu) {
+  if (!a.wsplit || a.split == 0) return no_plan(hipErrorInvalidConfiguration);
   const double tiles = (double)(a.M / 64) * ((a.Nq + 127) / 128) * a.B / 4.0;  // 256 x 128 blocks' worth of output
   const bool rule = a.M >= 256 && a.M % 256 == 0 && tiles >= ((a.Nq < 1024 || a.KW == 5) ? 0.45 : 0.9) * num_cu;
-  if (!(a.split == 1 || a.force_cfg >= 800 || rule)) return hipErrorInvalidConfiguration;
-  return launch_conv_split(a, num_cu, stream, cfg_out);
+  if (!(a.split == 1 || a.force_cfg >= kVarSplit || rule)) return no_plan(hipErrorInvalidConfiguration);
+  return plan_conv_split(a, num_cu);
 }
 // conv_direct3(w)(s)_kernel (2xx / 5xx): the no-split-K throughput kernels for launches with many columns
-hipError_t try_direct3(const ConvArgs& a, int num_cu, hipStream_t stream, int* cfg_out) {
-  if (a.direct < 3) return hipErrorInvalidConfiguration;
-  return launch_conv_direct3(a, num_cu, stream, cfg_out);
+ConvPlan try_direct3(const ConvArgs& a, int num_cu) {
+  if (a.direct < 3) return no_plan(hipErrorInvalidConfiguration);
+  return plan_conv_direct3(a, num_cu);
 }
 // conv_direct4_kernel (3xx): 1x1 convs, phase GEMMs and k = s = r rate-change convs with too few columns for the family above.
 // It has no fused up-path FIR: a layer it would take runs as conv + FIR pass (the caller's fallback on hipErrorNotSupported)
-// unless d4_fir_unfused is off.
-hipError_t try_direct4(const ConvArgs& a, int num_cu, hipStream_t stream, int* cfg_out) {
-  if (a.direct < 4) return hipErrorInvalidConfiguration;
+// unless d4_fir_unfused is off -- or the layer is short (direct4_short_layer): a transposed conv whose FIR the first generation
+// fuses stays there.
+ConvPlan try_direct4(const ConvArgs& a, int num_cu) {
+  if (a.direct < 4) return no_plan(hipErrorInvalidConfiguration);
   if (a.fir) {
-    if (a.d4_fir_unfused && a.force_cfg < 0) {
-      ConvArgs probe = a;
-      probe.fir = nullptr; probe.fir_len = 0;
-      if (launch_conv_direct4(probe, num_cu, stream, nullptr, true) == hipSuccess) return hipErrorNotSupported;
+    if (a.d4_fir_unfused && a.force_cfg < 0 && !(a.d4_force == 0 && direct4_short_layer(a) && a.up > 1)) {
+      ConvArgs unfused = a;
+      unfused.fir = nullptr; unfused.fir_len = 0;
+      if (plan_conv_direct4(unfused, num_cu).status == hipSuccess) return no_plan(hipErrorNotSupported);
     }
-    return a.force_cfg >= 0 ? hipErrorNotSupported : hipErrorInvalidConfiguration;  // (forced onto a family without the FIR epilogue)
+    return no_plan(a.force_cfg >= 0 ? hipErrorNotSupported : hipErrorInvalidConfiguration);  // (forced onto a family without the FIR epilogue)
   }
-  return launch_conv_direct4(a, num_cu, stream, cfg_out, false);
+  return plan_conv_direct4(a, num_cu);
 }
 // conv_direct4w_kernel (6xx / 7xx): stride-1 k3 / k5 layers with few columns (the 401-frame levels at batch 1), minimal filtering
-hipError_t try_direct4w(const ConvArgs& a, int num_cu, hipStream_t stream, int* cfg_out) {
-  if (a.direct < 5) return hipErrorInvalidConfiguration;
-  return launch_conv_direct4w(a, num_cu, stream, cfg_out);
+ConvPlan try_direct4w(const ConvArgs& a, int num_cu) {
+  if (a.direct < 5) return no_plan(hipErrorInvalidConfiguration);
+  return plan_conv_direct4w(a, num_cu);
 }
 // conv_direct_kernel / conv_direct2(w)_kernel / conv_direct_strided_kernel (1xx as a request; 50 .. 99 and 4xx as answers): the
 // split-K kernels of the deep levels.  Up to deep_factor blocks of 64 x 128 per CU (measured: PP16 B = 8 33.3 -> 32.3 ms, OR16
 // B = 16 63.4 -> 60.2 ms when the limit goes from 3 to 6-12; beyond that nothing moves); longer rows only for the wide-load
 // variant (a 64-channel k5 conv at T = 32 080 runs 19 vs 24 us on it).
-hipError_t try_direct(const ConvArgs& a, int num_cu, hipStream_t stream, int* cfg_out) {
-  if (a.direct == 0) return hipErrorInvalidConfiguration;
+ConvPlan try_direct(const ConvArgs& a, int num_cu) {
+  if (a.direct == 0) return no_plan(hipErrorInvalidConfiguration);
   const long wide = (long)((a.M + 63) / 64) * ((a.Nq + 127) / 128) * a.B;
   const bool wide_ok = a.wd && a.direct >= 2 && a.stride == 1 && a.up == 1;
-  const bool deep = ((a.Nq <= 16384 || wide_ok) && wide < (long)a.deep_factor * num_cu) || a.force_cfg >= 100;
-  if (!deep) return hipErrorInvalidConfiguration;
-  return launch_conv_direct(a, num_cu, stream, cfg_out);
+  const bool deep = ((a.Nq <= 16384 || wide_ok) && wide < (long)a.deep_factor * num_cu) || a.force_cfg >= kVarFused;
+  if (!deep) return no_plan(hipErrorInvalidConfiguration);
+  return plan_conv_direct(a, num_cu);
 }
 struct ConvFamily {
-  int lo, hi;          // force_cfg codes that name this family
+  int lo, hi;          // force_cfg codes that name this family (ou_variants.h)
+  int lo2, hi2;        // ... and a second range of them
   bool final_if_forced;  // a forced request ends with this family's answer (the first-generation family falls through to the
                          // LDS kernel even when forced: force_cfg 100 .. 199 also covers layers only that kernel takes)
-  hipError_t (*attempt)(const ConvArgs&, int, hipStream_t, int*);
+  ConvPlan (*attempt)(const ConvArgs&, int);
 };
 const ConvFamily kConvFamilies[] = {
-    {800, 1100, true, try_split},
-    {200, 300, true, try_direct3},   // (and 500 .. 599: see forced_into)
-    {300, 500, true, try_direct4},
-    {600, 800, true, try_direct4w},
-    {100, 200, false, try_direct},
+    {kVarSplit, variant_end("split"), 0, 0, true, try_split},  // (800 .. 1099: the tail is never an answer, see ou_variants.h)
+    {kVarDirect3, kVarDirect4, kVarDirect3w, variant_end("direct3w"), true, try_direct3},
+    {kVarDirect4, kVarDirect3w, 0, 0, true, try_direct4},      // (300 .. 499: the 4xx codes are answers of the family below only)
+    {kVarDirect4w, variant_end("direct4w"), 0, 0, true, try_direct4w},
+    {kVarFused, variant_end("fused"), 0, 0, false, try_direct},
 };
-bool forced_into(const ConvFamily& f, int cfg) {
-  if (cfg >= f.lo && cfg < f.hi) return true;
-  return f.attempt == try_direct3 && cfg >= 500 && cfg < 600;
-}
+bool forced_into(const ConvFamily& f, int cfg) { return (cfg >= f.lo && cfg < f.hi) || (cfg >= f.lo2 && cfg < f.hi2); }
 }  // namespace
 
+hipError_t launch_plan(const ConvPlan& p, hipStream_t stream) {
+  if (p.status != hipSuccess) return p.status;
+  hipLaunchKernelGGL(p.kern, p.grid, p.block, p.smem, stream, p.args);
+  return hipGetLastError();
+}
+
 hipError_t launch_conv(const ConvArgs& a, int num_cu, hipStream_t stream, int* cfg_out) {
-  if (a.Cin % a.CK || a.CK < 2 || (a.CK & (a.CK - 1)) || a.Mp % 64 || a.Nq <= 0) return hipErrorInvalidValue;
+  const ConvPlan p = plan_conv(a, num_cu);
+  if (cfg_out && p.status == hipSuccess) *cfg_out = p.variant;
+  return launch_plan(p, stream);
+}
+
+ConvPlan plan_conv(const ConvArgs& a, int num_cu) {
+  if (a.Cin % a.CK || a.CK < 2 || (a.CK & (a.CK - 1)) || a.Mp % 64 || a.Nq <= 0) return no_plan(hipErrorInvalidValue);
   // Deep levels and the throughput regime: the register-direct families, most specific first.  What none of them takes (wide
   // levels at small batch, layers without a direct form) stays on the LDS-tiled configs below.
   for (const ConvFamily& f : kConvFamilies) {
     const bool forced = a.force_cfg >= 0 && forced_into(f, a.force_cfg);
     if (a.force_cfg >= 0 && !forced) continue;
-    const hipError_t e = f.attempt(a, num_cu, stream, cfg_out);
-    if (e != hipErrorInvalidConfiguration) return e;
-    if (forced && f.final_if_forced) return e;
+    ConvPlan p = f.attempt(a, num_cu);
+    if (p.status != hipErrorInvalidConfiguration) return p;
+    if (forced && f.final_if_forced) return p;
   }
-  if (a.fir) return hipErrorNotSupported;  // only the direct kernel has the fused FIR epilogue
+  if (a.fir) return no_plan(hipErrorNotSupported);  // only the direct kernel has the fused FIR epilogue
   int pick = -1;
   for (int i = 0; i < kNumConvCfgs; i++) {
     const ConvCfg& c = kConvCfgs[i];
@@ -605,11 +614,11 @@ hipError_t launch_conv(const ConvArgs& a, int num_cu, hipStream_t stream, int* c
     long blocks = (long)((a.M + c.BM - 1) / c.BM) * ((a.Nq + c.BN - 1) / c.BN) * a.B;
     if (blocks >= want) break;
   }
-  if (pick < 0) return hipErrorInvalidConfiguration;
-  if (a.out_act) return hipErrorNotSupported;  // (the LDS-tiled kernels have no activating epilogue)
+  if (pick < 0) return no_plan(hipErrorInvalidConfiguration);
+  if (a.out_act) return no_plan(hipErrorNotSupported);  // (the LDS-tiled kernels have no activating epilogue)
   const ConvCfg& c = kConvCfgs[pick];
-  if (cfg_out) *cfg_out = pick;
-  ConvArgs aa = a;
+  ConvPlan p = {hipSuccess, pick, nullptr, dim3(), dim3(c.NT), 0, a};
+  ConvArgs& aa = p.args;
   {  // chunks per pipeline stage: as many as the per-thread staging registers and 128 KB of LDS allow
     const int span = (c.BN - 1) * a.stride + a.KW;
     const int nch = a.Cin / a.CK;
@@ -626,31 +635,20 @@ hipError_t launch_conv(const ConvArgs& a, int num_cu, hipStream_t stream, int* c
     }
     aa.SC = sc;
   }
-  // exact for the index ranges used (e < 2^13, divisor < 2^11): floor(e/d) == umulhi(e, 2^32/d + 1)
-  const int bns[3] = {128, 64, 32};
-  for (int i = 0; i < 3; i++) aa.magic_span[i] = (unsigned)(0x100000000ull / (unsigned)((bns[i] - 1) * a.stride + a.KW)) + 1u;
-  aa.magic_up = a.up == 1 ? 0u : (unsigned)(0x100000000ull / (unsigned)a.up) + 1u;
+  fill_magic_span(aa);
+  fill_magic_up(aa);
   aa.grid_n = (a.Nq + c.BN - 1) / c.BN;
   aa.grid_m = (a.M + c.BM - 1) / c.BM;
-  {  // which operand an XCD's L2 owns: memory-side bytes ~ 8 X + W (slabs) vs X + 8 W (time tiles)
-    const double xb = (double)a.Cin * a.Nq * a.stride, wb = (double)a.M * a.Cin * a.KW;
-    aa.xcd_map = 0;
-    if (aa.grid_m % 8 == 0 && wb >= xb) aa.xcd_map = 1;
-    else if (aa.grid_n >= 8) aa.xcd_map = 2;
-    if (a.force_xcd_map >= 0) aa.xcd_map = a.force_xcd_map;
-    if (aa.xcd_map == 1 && aa.grid_m % 8) aa.xcd_map = 0;
-  }
+  fill_xcd_map(aa);
   const int gn_pad = aa.xcd_map == 2 ? (aa.grid_n + 7) / 8 * 8 : aa.grid_n;
-  dim3 grid(gn_pad * aa.grid_m, 1, a.B);
-  size_t smem = conv_smem_bytes(c, aa);
+  p.grid = dim3(gn_pad * aa.grid_m, 1, a.B);
+  p.smem = conv_smem_bytes(c, aa);
   // channel pairs per wave and tap: exact groups of 4 or 2 when every wave gets the same whole number of them
   const int pairs = aa.SC * a.CK / 2;
   const bool even = pairs % c.WK == 0;
   const int per_wave = pairs / c.WK;
-  auto kern = (even && per_wave % 4 == 0) ? c.kern4 : ((even && per_wave % 2 == 0) ? c.kern2 : c.kern_g);
-  hipLaunchKernelGGL(kern, grid, dim3(c.NT), smem, stream, aa);
-  return hipGetLastError();
+  p.kern = (even && per_wave % 4 == 0) ? c.kern4 : ((even && per_wave % 2 == 0) ? c.kern2 : c.kern_g);
+  return p;
 }
-
 
 }  // namespace ou

@@ -29,6 +29,7 @@
 //   instruction in the pipe's own order -- fixed, different from every other family (results agree to fp32 rounding).
 #include "ou_kernels.h"
 #include "ou_internal.h"
+#include "ou_variants.h"
 #include "ou_dev.h"
 
 #include <cstdlib>
@@ -631,33 +632,33 @@ hipError_t init_split_kernels() {
   return hipSuccess;
 }
 
-// cfg_out: 800 + 100 (TNW == 2) + 10 log2(WM) + KW
-hipError_t launch_conv_split(const ConvArgs& a, int num_cu, hipStream_t stream, int* cfg_out) {
+// variant: 800 + 100 (TNW == 2) + 10 log2(WM) + KW
+ConvPlan plan_conv_split(const ConvArgs& a, int num_cu) {
   if (!a.wsplit || a.stride != 1 || a.up != 1 || (a.KW != 3 && a.KW != 5) || a.pad != (a.KW - 1) / 2 || a.fir || a.Cin % 16 ||
       a.M % 64 || (a.in_scale != nullptr && a.act))
-    return hipErrorInvalidConfiguration;
+    return no_plan(hipErrorInvalidConfiguration);
+  const bool forced_w = a.force_cfg >= kVarSplitw && a.force_cfg < kVarSplitw + 50;  // (conv_splitw_kernel's codes)
 #ifdef OU_EXPERIMENTS
   // minimal filtering on the bf16 pipe where the layer has the Winograd-domain split copy (k3, rows a multiple of 128) and
   // the 128-column wave tiles still fill the device: variant 850 + 10 log2(WM) + KW
-  if (a.wsplitw && a.split_wino && a.KW == 3 && a.M % 128 == 0 && (a.force_cfg < 0 || (a.force_cfg >= 850 && a.force_cfg < 900))) {
+  if (a.wsplitw && a.split_wino && a.KW == 3 && a.M % 128 == 0 && (a.force_cfg < 0 || forced_w)) {
     int wmw = a.M % 256 == 0 ? 4 : 2;
-    if (a.force_cfg >= 850) wmw = 1 << ((a.force_cfg - 850) / 10);
+    if (a.force_cfg >= kVarSplitw) wmw = 1 << ((a.force_cfg - kVarSplitw) / 10);
     if ((wmw == 4 || wmw == 2) && a.M % (64 * wmw) == 0) {
       const long bn = (4 / wmw) * 128L;
       const long blocks = (a.M / (64 * wmw)) * ((a.Nq + bn - 1) / bn) * a.B;
-      if (blocks >= num_cu || a.force_cfg >= 850 || a.split == 1) {
-        ConvArgs aa = a;
-        aa.grid_m = a.M / (64 * wmw);
-        aa.grid_n = (int)((a.Nq + bn - 1) / bn);
-        const long total8 = ((long)aa.grid_n * a.B + 7) / 8 * 8;
-        if (cfg_out) *cfg_out = 850 + 10 * (wmw == 4 ? 2 : 1) + a.KW;
+      if (blocks >= num_cu || a.force_cfg >= kVarSplitw || a.split == 1) {
         auto kern = wmw == 4 ? (a.act ? conv_splitw_kernel<4, true> : conv_splitw_kernel<4, false>)
                              : (a.act ? conv_splitw_kernel<2, true> : conv_splitw_kernel<2, false>);
-        hipLaunchKernelGGL(kern, dim3((unsigned)(total8 * aa.grid_m)), dim3(256), splitw_lds(wmw), stream, aa);
-        return hipGetLastError();
+        ConvPlan p = {hipSuccess, kVarSplitw + 10 * (wmw == 4 ? 2 : 1) + a.KW, kern, dim3(), dim3(256), splitw_lds(wmw), a};
+        p.args.grid_m = a.M / (64 * wmw);
+        p.args.grid_n = (int)((a.Nq + bn - 1) / bn);
+        const long total8 = ((long)p.args.grid_n * a.B + 7) / 8 * 8;
+        p.grid = dim3((unsigned)(total8 * p.args.grid_m));
+        return p;
       }
     }
-    if (a.force_cfg >= 850) return hipErrorInvalidConfiguration;
+    if (a.force_cfg >= kVarSplitw) return no_plan(hipErrorInvalidConfiguration);
   }
 #endif
   int wm = a.M % 256 == 0 ? 4 : (a.M % 128 == 0 ? 2 : 1);
@@ -668,23 +669,23 @@ hipError_t launch_conv_split(const ConvArgs& a, int num_cu, hipStream_t stream, 
   };
   // fill the device: narrower wave tiles, then fewer rows per block, while there are fewer blocks than CUs
   if (blocks(wm, tnw) < num_cu) tnw = 2;
-  if (a.force_cfg >= 800 && a.force_cfg < 1100 && !(a.force_cfg >= 850 && a.force_cfg < 900)) {
-    const int f = a.force_cfg - 800;
+  if (variant_in(a.force_cfg, "split") && !forced_w) {
+    const int f = a.force_cfg - kVarSplit;
     tnw = f >= 100 ? 2 : 4;
     wm = 1 << ((f % 100) / 10);
   }
   const SplitCfg* c = nullptr;
   for (const SplitCfg& k : kSplitCfgs)
     if (k.KW == a.KW && k.WM == wm && k.TNW == tnw) c = &k;
-  if (!c || a.M % (64 * wm)) return hipErrorInvalidConfiguration;
-  ConvArgs aa = a;
+  if (!c || a.M % (64 * wm)) return no_plan(hipErrorInvalidConfiguration);
   const long bn = (4 / wm) * 32L * tnw;
-  aa.grid_m = a.M / (64 * wm);
-  aa.grid_n = (int)((a.Nq + bn - 1) / bn);
-  const long total8 = ((long)aa.grid_n * a.B + 7) / 8 * 8;
-  if (cfg_out) *cfg_out = 800 + (tnw == 2 ? 100 : 0) + 10 * (wm == 4 ? 2 : (wm == 2 ? 1 : 0)) + a.KW;
-  hipLaunchKernelGGL(a.act ? c->kern_act : c->kern, dim3((unsigned)(total8 * aa.grid_m)), dim3(256), c->lds, stream, aa);
-  return hipGetLastError();
+  ConvPlan p = {hipSuccess, kVarSplit + (tnw == 2 ? 100 : 0) + 10 * (wm == 4 ? 2 : (wm == 2 ? 1 : 0)) + a.KW, a.act ? c->kern_act : c->kern,
+                dim3(), dim3(256), c->lds, a};
+  p.args.grid_m = a.M / (64 * wm);
+  p.args.grid_n = (int)((a.Nq + bn - 1) / bn);
+  const long total8 = ((long)p.args.grid_n * a.B + 7) / 8 * 8;
+  p.grid = dim3((unsigned)(total8 * p.args.grid_m));
+  return p;
 }
 
 }  // namespace ou

@@ -33,11 +33,11 @@ struct ConvArgs {
   int B = 1, Cin = 0, Tin = 0, Cout = 0, M = 0, Mp = 0, KW = 1, stride = 1, pad = 0, up = 1, CK = 2;
   int Nq = 0;    // GEMM columns (output positions per row)
   int Tout = 0;  // output length (<= Nq*up)
-  unsigned magic_span[3] = {0, 0, 0};  // filled by launch_conv: 2^32/span + 1 for BN = 128 / 64 / 32
+  unsigned magic_span[3] = {0, 0, 0};  // filled by plan_conv: 2^32/span + 1 for BN = 128 / 64 / 32
   unsigned magic_up = 0;               // 2^32/up + 1 (0 when up == 1)
-  int SC = 1;                          // filled by launch_conv: packed chunks per pipeline stage
-  int grid_n = 1, grid_m = 1;          // filled by launch_conv: tile counts (1-D grid, XCD-aware mapping)
-  int xcd_map = 0;                     // filled by launch_conv: block -> tile mapping (see the kernel)
+  int SC = 1;                          // filled by plan_conv: packed chunks per pipeline stage
+  int grid_n = 1, grid_m = 1;          // filled by plan_conv: tile counts (1-D grid, XCD-aware mapping)
+  int xcd_map = 0;                     // filled by plan_conv: block -> tile mapping (see the kernel)
   int force_cfg = -1, force_sc = 0;    // tuning overrides (ou_bench_conv)
   int force_xcd_map = -1;              // tuning: 0 / 1 / 2
   double tile_min = -1.0;              // OU_TILE_MIN (< 0: the launcher's default of 1.2 wave tiles per SIMD)
@@ -76,7 +76,7 @@ struct ConvArgs {
   const int* lens = nullptr;
   const float* fir = nullptr;
   int fir_len = 0;
-  int tile_bm = 32, tile_bn = 0, tile_halo = 0;  // filled by launch_conv_direct: rows / columns a tile advances by, left halo
+  int tile_bm = 32, tile_bn = 0, tile_halo = 0;  // filled by plan_conv_direct: rows / columns a tile advances by, left halo
   int dbg = 0;                         // phase ablation switches (tuning only)
   long long* tstamps = nullptr;        // per-wave phase cycle counts (tuning only)
   unsigned long long* prof = nullptr;  // measurement: 16 x min block start, 16 x ~max block end (slot = block id & 15: 500
@@ -84,19 +84,12 @@ struct ConvArgs {
 };
 // returns hipSuccess or the launch error; `cfg_out` (optional) receives the tile configuration index used
 hipError_t launch_conv(const ConvArgs& a, int num_cu, hipStream_t stream, int* cfg_out = nullptr);
-// does the kernel behind variant code `cfg` (launch_conv's cfg_out) honour ConvArgs::lens in its epilogue?
-bool conv_masks_rows(int cfg);
 hipError_t init_conv_kernels();  // raises the dynamic-LDS limit of every instantiation
 double direct3_tiles_per_simd(int M, int Nq, int B, int num_cu);  // wave tiles per SIMD of the no-split-K throughput kernel
-// Small-K rate-change conv of the wide levels with the anti-alias FIR fused: y = conv_{k=s=r}(FIR(prelu(x))) + bias
-// (a.fir = taps or null, a.fir_len = 2r + 1; a.act / a.alpha_val = the PReLU).  hipErrorNotSupported = use launch_fir +
-// launch_conv.
-bool rate_down_supported(const ConvArgs& a);
-hipError_t launch_rate_down(const ConvArgs& a, hipStream_t st, int* cfg_out = nullptr);
-// ... and the last up conv: y = FIR(convT_{k=s=r}(prelu(x))) + bias, then the residual (a.fir = taps or null, a.bias = the
-// bias added after the filter)
-bool rate_up_supported(const ConvArgs& a);
-hipError_t launch_rate_up(const ConvArgs& a, hipStream_t st, int* cfg_out = nullptr);
+// (plan_rate_down / plan_rate_up of ou_internal.h:) Small-K rate-change conv of the wide levels with the anti-alias FIR fused:
+// y = conv_{k=s=r}(FIR(prelu(x))) + bias (a.fir = taps or null, a.fir_len = 2r + 1; a.act / a.alpha_val = the PReLU);
+// hipErrorNotSupported = use launch_fir + launch_conv.  ... and the last up conv: y = FIR(convT_{k=s=r}(prelu(x))) + bias, then
+// the residual (a.fir = taps or null, a.bias = the bias added after the filter)
 
 // ---- small VALU kernels ------------------------------------------------------------------------------------
 // Per-step scalars of the sampler / EDM wrapper (universe.py:175-209, 333-343), one row per batch element

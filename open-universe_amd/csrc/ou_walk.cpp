@@ -1,6 +1,8 @@
 // The network walk: what Runner does per conv layer, ConvBlock and GRU layer, the conditioner and the score
 // passes built from them, and the sampler's scalars.  No allocation, no host sync: everything goes through Runner::launch.
 #include "ou_walk.h"
+#include "ou_internal.h"
+#include "ou_variants.h"
 
 #include <algorithm>
 #include <cmath>
@@ -57,25 +59,22 @@ Runner::ConvOut Runner::conv(const ConvL& L, const Tensor& in, const std::string
   // carry the reference's own kernel sizes)
   a.prof = prof_open(2.0 * L.M * (double)a.Nq * L.Cin * L.KW * B,
                      4.0 * ((double)B * ((double)L.Cin * in.T + (double)L.Cout * a.Tout) + (double)L.M * L.Cin * L.KW), -1);
-  int cfg = -1;
-  hipError_t le;
-  if (e.rate_down) {
-    le = launch_rate_down(a, st, &cfg);
-  } else if (e.rate_up) {
-    le = launch_rate_up(a, st, &cfg);
-  } else {
-    le = launch_conv(a, h->num_cu, st, &cfg);
-    if (le == hipErrorNotSupported && a.out_act) {  // the kernel for this layer has no activating epilogue: store y
+  // plan, then launch once (ou_internal.h): nothing is enqueued for a layer that falls back
+  ConvPlan p = e.rate_down ? plan_rate_down(a) : e.rate_up ? plan_rate_up(a) : plan_conv(a, h->num_cu);
+  if (!e.rate_down && !e.rate_up) {
+    if (p.status == hipErrorNotSupported && a.out_act) {  // the kernel for this layer has no activating epilogue: store y
       a.out_act = 0;
-      le = launch_conv(a, h->num_cu, st, &cfg);
+      p = plan_conv(a, h->num_cu);
     }
     o.stored_act = a.out_act != 0;
-    if (le == hipErrorNotSupported && e.fir) {  // not a failure and not counted: the caller falls back to conv + launch_fir
+    if (p.status == hipErrorNotSupported && e.fir) {  // not a failure and not counted: the caller falls back to conv + launch_fir
       prof_drop(a.prof);
       o.supported = false;
       return o;
     }
   }
+  const int cfg = p.variant;
+  const hipError_t le = launch_plan(p, st);
   launch(L.name.c_str(), [le] { return le; });  // (the gate was passed above: this records the launcher's answer)
   prof_close(a.prof, cfg);
   h->last_cfg = cfg;
@@ -90,7 +89,7 @@ Runner::ConvOut Runner::conv(const ConvL& L, const Tensor& in, const std::string
 
 // ---- ConvBlock.forward  (blocks.py:327-412) in three parts: up_path, body, down_path; block() sequences them.
 
-// What rate_up_supported / rate_down_supported ask about the rate-change conv of a block reading Tin frames: the shape and
+// What plan_rate_up / plan_rate_down are asked about the rate-change conv of a block reading Tin frames: the shape and
 // whether a FIR rides along (fir_mode 1: in front of the down conv, 2: behind the up conv).  Pure function of the layer shape.
 ConvArgs Runner::rate_probe(const ConvL& rc, int Tin) {
   ConvArgs a;
@@ -108,7 +107,7 @@ Tensor Runner::up_path(const BlockL& Bk, const Tensor& hin, const std::string& n
   Epi e;
   e.res = res; e.res_scale = kInvSqrt2;  // blocks.py:374-376 fused into the up-conv epilogue
   if (rc.fir_mode == 2) { e.fir = W(rc.fir_off); e.fir_len = rc.fir_len; e.fir_bias = W(rc.fbias_off); }
-  if ((rc.fir_mode == 0 || rc.fir_mode == 2) && env.rate_small != 0 && rate_up_supported(rate_probe(rc, hin.T))) {
+  if ((rc.fir_mode == 0 || rc.fir_mode == 2) && env.rate_small != 0 && plan_rate_up(rate_probe(rc, hin.T)).status == hipSuccess) {
     e.rate_up = true;
     return conv(rc, hin, nm + ".up", e).out;
   }
@@ -268,7 +267,7 @@ Tensor Runner::down_path(const BlockL& Bk, const Tensor& v, const std::string& n
   const ConvL& rc = Bk.rc;
   Epi e;
   // wide levels: FIR + strided conv in one launch
-  if (rc.fir_mode <= 1 && env.rate_small != 0 && rate_down_supported(rate_probe(rc, v.T))) {
+  if (rc.fir_mode <= 1 && env.rate_small != 0 && plan_rate_down(rate_probe(rc, v.T)).status == hipSuccess) {
     e.rate_down = true;
     if (rc.fir_mode == 1) { e.fir = W(rc.fir_off); e.fir_len = rc.fir_len; }
     return conv(rc, v, nm + ".h", e).out;
@@ -342,7 +341,7 @@ Tensor Runner::gru(const GruL& G, const Tensor& in, const std::string& nm, unsig
   // the recurrence proper (the input projection is a conv launch of its own): 2 directions x T steps x (3H x H) MACs;
   // variant code 1000 + steps per pass
   a.prof = prof_open(2.0 * 2.0 * 3.0 * G.H * G.H * (double)in.T * B,
-                     4.0 * ((double)B * (6.0 + 2.0 + (res ? 2.0 : 0.0)) * G.H * in.T + 2.0 * 3.0 * G.H * G.H), 1000 + in.T);
+                     4.0 * ((double)B * (6.0 + 2.0 + (res ? 2.0 : 0.0)) * G.H * in.T + 2.0 * 3.0 * G.H * G.H), kVarRecurrence + in.T);
   if (before && (*before = next_event())) launch("pre-gru record", [&] { return hipEventRecord(*before, st); });
   launch(G.name.c_str(), [&] { return launch_gru(a, h->num_cu, st); });
   mask(out);

@@ -69,6 +69,7 @@ import torch
 import torch.nn.functional as Fn
 
 import small_fp64 as F
+from open_universe_amd.variants import family_of  # noqa: F401  (the one decoder; the body convs use its names as they are)
 from small_fp64 import INV_SQRT2, U, Report, prelu, valid_mask  # noqa: F401  (one convention, one implementation)
 
 # M of the bf16-split bound = ceil(2 x worst measured err / e32) over the split cases of tests/test_gpu_conv_fp64.py on an MI355X
@@ -92,35 +93,24 @@ BT_ROUNDINGS = {3: 1, 5: 4}
 
 
 # ---- which family a variant code names, what its tap holds ------------------------------------------------------------------
+_KIND = {"fused": ("fused",), "split": ("split",), "wino": ("direct2w", "direct3w", "direct4w"),
+         "chain": ("lds", "rate_down", "rate_up", "direct", "direct2", "strided", "direct3", "direct3s")}
+
+
 def kind_of(cfg):
-    """Bound kind of a launch's variant code (kConvFamilies, ou_conv_mfma.hip; launch_conv_direct; launch_chain)."""
-    if 100 <= cfg < 200:
-        return "fused"
-    if 800 <= cfg < 1100:
-        return "split"
-    if 400 <= cfg < 800:
-        return "wino"
-    if 0 <= cfg < 100 or 200 <= cfg < 300:
-        return "chain"
+    """Bound kind of a launch's variant code (open_universe_amd.variants.family_of: the library's own table)."""
+    for kind, fams in _KIND.items():
+        if family_of(cfg) in fams:
+            return kind
     raise AssertionError(f"variant code {cfg} is no body-conv family")
-
-
-def family_of(cfg):
-    """Kernel family of a variant code."""
-    for name, ok in (("lds", 0 <= cfg < 50), ("direct", 50 <= cfg < 100 and cfg not in (66, 67, 76, 77)),
-                     ("direct2", cfg in (66, 67, 76, 77)), ("fused", 100 <= cfg < 200), ("direct3", 200 <= cfg < 300),
-                     ("direct2w", 400 <= cfg < 500), ("direct3w", 500 <= cfg < 600), ("direct4w", 600 <= cfg < 800),
-                     ("split", 800 <= cfg < 1100)):
-        if ok:
-            return name
-    raise AssertionError(cfg)
 
 
 def stores_activated(cfg, requested):
     """Does the tap hold prelu(y; alpha_next)?  `requested`: Runner::body asked for it (option preact, the tensor read by the next
     PReLU_Conv only).  The LDS kernels and the first-generation direct kernels have no activating epilogue (launch_conv /
     launch_conv_direct answer hipErrorNotSupported and the layer is launched again storing y); every other body family has."""
-    return bool(requested) and family_of(cfg) not in ("lds", "direct", "fused")
+    kind_of(cfg)  # (a body-conv family at all)
+    return bool(requested) and family_of(cfg) not in ("lds", "rate_down", "rate_up", "direct", "strided", "fused")
 
 
 # ---- parameters -------------------------------------------------------------------------------------------------------------

@@ -63,22 +63,22 @@ import torch
 import torch.nn.functional as Fn
 
 import conv_fp64 as C
+from open_universe_amd import variants as V
 import small_fp64 as F
 from conv_fp64 import Epi, _epilogue
 from small_fp64 import U, Report, prelu, valid_mask  # noqa: F401  (one convention, one implementation)
 
 
 # ---- which family a variant code names ----------------------------------------------------------------------------------------
+# (the mel conv is a stride-1 k3 layer: the minimal-filtering families of the body convs take it)
+_FAMILIES = ("rate_down", "rate_up", "lds", "direct2", "direct", "strided", "direct3s", "direct4", "direct2w", "direct3w", "direct4w")
+
+
 def family_of(cfg):
-    """Kernel family of a variant code on a rate-change / 1x1 layer (launch_rate_down / launch_rate_up, kConvFamilies)."""
-    for name, ok in (("rate_down", cfg == 42), ("rate_up", cfg == 47), ("lds", 0 <= cfg < 40), ("direct2", cfg in (66, 67, 76, 77)),
-                     ("direct", 60 <= cfg < 80), ("strided", 80 <= cfg < 100), ("direct3s", 260 <= cfg < 270),
-                     ("direct4", 300 <= cfg < 400)):
-        if ok:
-            return name
-    if 400 <= cfg < 800:  # (the mel conv is a stride-1 k3 layer: the minimal-filtering families of the body convs take it)
-        return C.family_of(cfg)
-    raise AssertionError(f"variant code {cfg} is no rate-change / 1x1 family")
+    """Kernel family of a variant code on a rate-change / 1x1 layer: the library's name, which has to be one such a layer can get."""
+    fam = V.family_of(cfg)
+    assert fam in _FAMILIES, f"variant code {cfg} is no rate-change / 1x1 family"
+    return fam
 
 
 def kind_of(cfg, fir_mode, fused_fir):
@@ -424,7 +424,7 @@ def walk_slots(spec):
 
 
 def _is_body(cfg):
-    return cfg < 1000 and not (300 <= cfg < 400) and not (260 <= cfg < 270) and cfg not in (42, 47)
+    return not V.is_recurrence_record(cfg) and V.family_of(cfg) not in ("direct4", "direct3s", "rate_down", "rate_up")
 
 
 def pair_walk(slots, records, flops_of, score_passes=1):
@@ -442,24 +442,24 @@ def pair_walk(slots, records, flops_of, score_passes=1):
         assert i < len(records), (key, "the profile ended before this launch")
         cfg = records[i][3]
         if kind == "rec":
-            assert cfg >= 1000, (key, i, "a recurrence is due here, the record says variant", cfg)
+            assert V.is_recurrence_record(cfg), (key, i, "a recurrence is due here, the record says variant", cfg)
             i += 1
         elif kind == "gruproj":
-            assert cfg < 1000, (key, i, cfg)
+            assert not V.is_recurrence_record(cfg), (key, i, cfg)
             i += 1
         elif kind == "body":
             fl = flops_of[(kind, key)]
             for pat in ([sum(fl)], [fl[0], fl[1] + fl[2]], list(fl)):
                 got = records[i: i + len(pat)]
                 if len(got) == len(pat) and all(_is_body(r[3]) and r[1] == f for r, f in zip(got, pat)) and \
-                        all((100 <= r[3] < 200) == (len(pat) < 3 and k == len(pat) - 1) for k, r in enumerate(got)):
+                        all((V.family_of(r[3]) == "fused") == (len(pat) < 3 and k == len(pat) - 1) for k, r in enumerate(got)):
                     i += len(pat)
                     break
             else:
                 raise AssertionError((key, i, "no body records here", [(r[1], r[3]) for r in records[i: i + 3]], fl))
         else:
             want = flops_of[(kind, key)]
-            assert cfg < 1000 and records[i][1] == want, (key, i, "record", (records[i][1], cfg), "expected FLOPs", want)
+            assert not V.is_recurrence_record(cfg) and records[i][1] == want, (key, i, "record", (records[i][1], cfg), "expected FLOPs", want)
             family_of(cfg)
             out[(pas, key)] = cfg
             i += 1

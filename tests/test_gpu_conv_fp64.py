@@ -20,7 +20,7 @@ import conv_fp64 as C
 import restatement as O
 import small_fp64 as F
 from helpers import synth_mix
-from open_universe_amd import _lib
+from open_universe_amd import _lib, variants as V
 from test_gpu_parity import get_model
 
 pytestmark = pytest.mark.gpu
@@ -53,7 +53,7 @@ def _pair_with_profile(P, records, B, T_of):
     algorithmic FLOPs are those of (c1, c2, c3), (c1, c2 + c3) or (c1 + c2 + c3); everything else (rate-change, 1x1, GRU) is
     passed over.  A block that is not found fails the test."""
     out, i = {}, 0
-    body = lambda cfg: cfg < 1000 and not (300 <= cfg < 400) and not (260 <= cfg < 270)
+    body = lambda cfg: not V.is_recurrence_record(cfg) and V.family_of(cfg) not in ("direct4", "direct3s")
     for p, *_ in P.walk:
         bp = P.blocks[p]
         fl = [2.0 * bp.C * float(T_of[p]) * bp.C * cv.KW * B for cv in bp.c]
@@ -63,7 +63,7 @@ def _pair_with_profile(P, records, B, T_of):
             for depth, pat in pats:
                 got = records[i: i + len(pat)]
                 if len(got) == len(pat) and all(body(r[3]) and r[1] == f for r, f in zip(got, pat)) and \
-                        all((100 <= r[3] < 200) == (depth > 0 and k == len(pat) - 1) for k, r in enumerate(got)):
+                        all((V.family_of(r[3]) == "fused") == (depth > 0 and k == len(pat) - 1) for k, r in enumerate(got)):
                     found = (depth, [r[3] for r in got])
                     i += len(pat)
                     break

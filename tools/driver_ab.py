@@ -16,8 +16,12 @@ calls repeat the batch-1, the ragged and the two-row call with one option off it
 walk that the defaults never take, and one `layout` line per model holds workspace sizes and tensor offsets.  Behind the two
 default models come the models of tests/snake_cases.py with Snake and with mixed ConvBlock activations (ou_enhance and a ragged
 ou_enhance_var each, one `layout` line with the `.act` planes) and PP16s in every level-normalisation mode of
-tests/norm_cases.py (normalization_norm max and 2-max, zero_mean false: ou_enhance and ou_enhance_segments each).  Run it
-once per library and compare the files byte for byte:
+tests/norm_cases.py (normalization_norm max and 2-max, zero_mean false: ou_enhance and ou_enhance_segments each).  Every call
+runs with the per-launch profile on, and its line carries `variants`: the SHA-256 of the variant codes of its profiled launches
+(convs, fused bodies, GRU passes) in launch order -- which kernel took which layer, not how long it took.  Behind the calls of
+the first model come the `forced` lines: `bench_conv` of one layer of each kind (k1, k3, k5, a down and an up rate-change conv)
+at batch 1 and 4, one and five frames of the layer's level, with every code of FORCED as `cfg` -- the status (0, or the
+exception a refusal raises) and the variant answered.  Run it once per library and compare the files byte for byte:
 
     OU_LIBRARY=/path/to/parent/libouniverse.so timeout -k 10 600 python tools/driver_ab.py --out parent.json
     timeout -k 10 600 python tools/driver_ab.py --out branch.json && cmp parent.json branch.json
@@ -45,6 +49,9 @@ from open_universe_amd.noise import CounterNoise  # noqa: E402
 from open_universe_amd.universe import draw_noise  # noqa: E402
 
 N = 3
+# forced `cfg` codes of the `forced` lines: the launcher's choice, every LDS config, the first-generation family's requests, and
+# one code of each register-direct family
+FORCED = [-1] + list(range(8)) + list(range(105, 111)) + [223, 262, 322, 523, 613, 723, 813, 863]
 
 
 def build(name):
@@ -207,6 +214,30 @@ def calls(model, spec):
 WALK_TENSORS = ("mixn", "x", "cond.aux", "cond.latent", "cond.enc0.c1", "score.dec0.v", "score.gru")
 
 
+def forced_lines(model, spec, name):
+    """One line per (layer, B, frames, forced code): what a forced request reaches on a layer of each kind."""
+    plan = json.loads(model._L.ou_plan_json(model._handle).decode())
+    layers = {}
+    for L in plan["convs"]:
+        kind = ("down" if L["stride"] > 1 else "up" if L["up"] > 1 else "k%d" % L["KW"])
+        if kind in ("k1", "k3", "k5", "down", "up") and (kind != "up" or L.get("fir_mode") == 2):
+            layers.setdefault(kind, L)
+    for kind in ("k1", "k3", "k5", "down", "up"):
+        L = layers[kind]
+        for B in (1, 4):
+            for frames in (1, 5):
+                Tin = frames * max(L["stride"], 1)
+                for cfg in FORCED:
+                    try:
+                        _, used = model.bench_conv(L["name"], B, Tin, cfg=cfg, iters=1)
+                        status = 0
+                    except Exception as e:  # a refusal is a recorded answer
+                        status, used = type(e).__name__, -1
+                    torch.cuda.synchronize()
+                    yield json.dumps({"call": f"{name}.forced.{kind}.b{B}.f{frames}.cfg{cfg}", "layer": L["name"], "status": status,
+                                      "variant": used})
+
+
 def layout(model, spec, names=WALK_TENSORS):
     """The workspace layout of a model as one record: ou_workspace_bytes at three shapes, and where `Universe.tensor` finds
     the tensors `names` of the walk after `enhance.b1` -- (byte offset into the workspace, C, T) each."""
@@ -270,12 +301,20 @@ def main():
         model, spec = make()
         for call, seeds, fn in calls_of(model, spec):
             gens = [gen(s) for s in seeds]
+            model.profile(True)
             out = fn(gens)
             torch.cuda.synchronize()
             launches, convs = model.launch_stats()
+            codes = [r[3] for r in model.profile_read(max_records=32768)]
+            model.profile(False)
+            variants = hashlib.sha256(",".join(map(str, codes)).encode()).hexdigest()
             lines.append(json.dumps({"call": f"{name}.{call}", "launches": launches, "convs": convs, "sha256": digest(out),
-                                     "rng": rng_digest(gens)}))
+                                     "rng": rng_digest(gens), "variants": variants, "profiled": len(codes)}))
             print(lines[-1], flush=True)
+        if name == args.models[0]:
+            for line in forced_lines(model, spec, name):
+                lines.append(line)
+                print(line, flush=True)
         if tensors:
             lines.append(json.dumps({"call": f"{name}.layout", **layout(model, spec, tensors)}))
             print(lines[-1], flush=True)

@@ -14,6 +14,7 @@ from helpers import get_spec, synth_mix  # noqa: E402
 from open_universe_amd import UniverseGAN, distributed as D, state_dict as S  # noqa: E402
 from open_universe_amd.universe import Universe as _U; _U.steer_from_env = True  # tools only: OU_<OPTION>=v env vars -> ou_set_option
 from open_universe_amd.lanes import LanePool  # noqa: E402
+from open_universe_amd import variants as V  # noqa: E402
 
 K, n = int(sys.argv[1]), int(sys.argv[2])
 spec = get_spec("PP16")
@@ -31,14 +32,13 @@ dt = time.perf_counter() - t0
 print(f"in_flight={K}: {1e3 * dt / n:.2f} ms per utterance, {n / dt:.1f} utt/s (per-launch stamps on)")
 
 
+_LABEL = {"direct2": "direct2 (k3/k5 deep)", "fused": "chain (C=32/64 bodies)", "direct4": "direct4 (1x1/rate)",
+          "direct": "direct gen1 (1x1/rate)", "strided": "direct gen1 (1x1/rate)", "rate_down": "rate_up/down", "rate_up": "rate_up/down"}
+
+
 def kind(c):
-    if c >= 1000: return "gru"
-    if c in (66, 76): return "direct2 (k3/k5 deep)"
-    if 100 <= c < 200: return "chain (C=32/64 bodies)"
-    if 300 <= c < 400: return "direct4 (1x1/rate)"
-    if 50 <= c < 100: return "direct gen1 (1x1/rate)"
-    if 40 <= c < 50: return "rate_up/down"
-    return "other conv"
+    if V.is_recurrence_record(c): return "gru"
+    return _LABEL.get(V.family_of(c), "other conv")
 
 
 ev = []

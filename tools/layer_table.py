@@ -17,7 +17,7 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
     sys.path.insert(0, p)
 import torch
 from helpers import get_spec, synth_mix
-from open_universe_amd import Universe, UniverseGAN, state_dict as S
+from open_universe_amd import Universe, UniverseGAN, state_dict as S, variants as V
 from open_universe_amd.universe import Universe as _U; _U.steer_from_env = True  # tools only: OU_<OPTION>=v env vars -> ou_set_option
 
 PEAK = 157.3
@@ -53,15 +53,15 @@ finally:
     os.close(saved)
 tmp.seek(0)
 lines = [l.split() for l in tmp.read().decode(errors="replace").splitlines() if l.startswith("OU_TRACE conv") or l.startswith("OU_TRACE chain")]
-conv_recs = [r for r in recs if r[3] < 1000]
+conv_recs = [r for r in recs if not V.is_recurrence_record(r[3])]
 assert len(conv_recs) == len(lines), (len(conv_recs), len(lines))
 
 
 def executed_fraction(cfg, kw, depth=None):
     """MFMA multiply-adds issued / algorithmic ones."""
-    if 400 <= cfg < 800:
+    if V.family_of(cfg) in ("direct2w", "direct3w", "direct4w"):
         return (kw + 1) / (2.0 * kw)
-    if 800 <= cfg < 1000:  # conv_split_kernel: six bf16 products per MAC on the BF16 pipe (2 500 TFLOP/s dense = 16 x the f32 pipe):
+    if V.family_of(cfg) == "split":  # conv_split_kernel: six bf16 products per MAC on the BF16 pipe (2 500 TFLOP/s dense = 16 x the f32 pipe):
         return 6.0 / 16.0  # in units of the f32 pipe's capacity, so that the one assertion below covers both pipes
     if cfg == 193:   # conv_chainw_kernel, depth 3: k5, k3, k3
         return (6 + 4 + 4) / (10 + 6 + 6.0)
@@ -70,12 +70,15 @@ def executed_fraction(cfg, kw, depth=None):
     return 1.0
 
 
+_LABEL = {"direct2": "direct2/2w/4w", "direct2w": "direct2/2w/4w", "direct4w": "direct2/2w/4w", "direct": "direct (dword)",
+          "strided": "direct (dword)", "lds": "lds", "rate_down": "rate", "rate_up": "rate", "fused": "chain", "direct3": "direct3/3w/3s",
+          "direct3s": "direct3/3w/3s", "direct3w": "direct3/3w/3s", "split": "split (bf16 x 6)", "direct4": "direct4"}
 fam = {}
 rows, it = [], iter(lines)
 worst = 0.0
 for ms, fl, by, cfg in recs:
     us = ms * 1e3
-    if cfg >= 1000:
+    if V.is_recurrence_record(cfg):
         rows.append(("gru (recurrence, %d steps)" % (cfg - 1000), "", us, fl / (ms * 1e-3) / 1e12, None, cfg))
         key = "gru"
     else:
@@ -92,8 +95,7 @@ for ms, fl, by, cfg in recs:
         alg = fl / (ms * 1e-3) / 1e12
         rows.append((nm, shape, us, alg, alg * frac, cfg))
         worst = max(worst, alg * frac)
-        key = ("direct2/2w/4w" if cfg in (66, 76, 67, 77) or 400 <= cfg < 500 or 600 <= cfg < 800 else "direct (dword)" if 50 <= cfg < 100 else
-               "lds" if cfg < 40 else "rate" if cfg < 50 else "chain" if cfg < 200 else "direct3/3w/3s" if cfg < 300 or 500 <= cfg < 600 else "split (bf16 x 6)" if cfg >= 800 else "direct4")
+        key = _LABEL[V.family_of(cfg)]
     f = fam.setdefault(key, [0, 0.0, 0.0])
     f[0] += 1; f[1] += us; f[2] += fl
 tot_us = sum(r[2] for r in rows)

@@ -11,6 +11,15 @@
 #include <random>
 #include <vector>
 
+// plan + launch (launch_plan lives with the dispatcher in ou_conv_mfma.hip, which this file does not include)
+static hipError_t launch_conv_split(const ou::ConvArgs& a, int num_cu, hipStream_t st, int* cfg) {
+  const ou::ConvPlan p = ou::plan_conv_split(a, num_cu);
+  if (p.status != hipSuccess) return p.status;
+  if (cfg) *cfg = p.variant;
+  hipLaunchKernelGGL(p.kern, p.grid, p.block, p.smem, st, p.args);
+  return hipGetLastError();
+}
+
 #define CHK(x)                                                                          \
   do {                                                                                  \
     hipError_t e_ = (x);                                                                \
@@ -56,7 +65,7 @@ int main(int argc, char** argv) {
   a.force_cfg = force;
   a.dbg = argc > 8 ? atoi(argv[8]) : 0;  // tuning: 1 = no epilogue (wrong results), 16 / 32 + 256 x us = every second block starts late
   int cfg = 0;
-  CHK(ou::launch_conv_split(a, pr.multiProcessorCount, 0, &cfg));
+  CHK(launch_conv_split(a, pr.multiProcessorCount, 0, &cfg));
   CHK(hipDeviceSynchronize());
   std::vector<float> y(res.size());
   CHK(hipMemcpy(y.data(), dy, y.size() * 4, hipMemcpyDeviceToHost));
@@ -95,9 +104,9 @@ int main(int argc, char** argv) {
          M, Cin, KW, T, B, cfg, act, 10 * std::log10(ref2 / (e_split + 1e-300)), 10 * std::log10(ref2 / (e_f32 + 1e-300)), worst);
   hipEvent_t e0, e1;
   CHK(hipEventCreate(&e0)); CHK(hipEventCreate(&e1));
-  for (int i = 0; i < 3; i++) CHK(ou::launch_conv_split(a, pr.multiProcessorCount, 0, nullptr));
+  for (int i = 0; i < 3; i++) CHK(launch_conv_split(a, pr.multiProcessorCount, 0, nullptr));
   CHK(hipEventRecord(e0, 0));
-  for (int i = 0; i < iters; i++) CHK(ou::launch_conv_split(a, pr.multiProcessorCount, 0, nullptr));
+  for (int i = 0; i < iters; i++) CHK(launch_conv_split(a, pr.multiProcessorCount, 0, nullptr));
   CHK(hipEventRecord(e1, 0));
   CHK(hipEventSynchronize(e1));
   float ms = 0;
@@ -111,7 +120,7 @@ int main(int argc, char** argv) {
     CHK(hipMalloc(&dts, nw * 8 * 8));
     CHK(hipMemset(dts, 0, nw * 8 * 8));
     a.tstamps = dts;
-    CHK(ou::launch_conv_split(a, pr.multiProcessorCount, 0, nullptr));
+    CHK(launch_conv_split(a, pr.multiProcessorCount, 0, nullptr));
     CHK(hipDeviceSynchronize());
     std::vector<long long> ts(nw * 8);
     CHK(hipMemcpy(ts.data(), dts, nw * 8 * 8, hipMemcpyDeviceToHost));
