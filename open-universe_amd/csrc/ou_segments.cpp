@@ -74,6 +74,7 @@ int seg_workspace_bytes(ou_handle* h, int B, long long L, const SegArea& A, size
 struct SegWs {
   size_t walk;  // bytes of the walk's part
   size_t stats_off;  // `stats` in bytes from the workspace's start (ou_tensor "seg.stats")
+  size_t row_scale_off, zbuf_off, carry_off;  // ... and "seg.row_scale", "seg.z", "seg.carry"
   float *stats, *row_scale, *zbuf, *carry;
   double* part;
   int *hist, *lens_b;
@@ -90,6 +91,9 @@ int seg_workspace(ou_handle* h, void* ws, size_t ws_bytes, int B, int L, const S
   w.stats = (float*)(seg + A.stats);
   w.stats_off = w.walk + A.stats;
   w.row_scale = (float*)(seg + A.row_scale);
+  w.row_scale_off = w.walk + A.row_scale;
+  w.zbuf_off = w.walk + A.zbuf;
+  w.carry_off = w.walk + A.carry;
   w.part = (double*)(seg + A.part);
   w.zbuf = (float*)(seg + A.zbuf);
   w.carry = (float*)(seg + A.carry);
@@ -186,6 +190,7 @@ bool seg_row_stats(ou_handle* h, const float* mix, float* esum, const SegWs& w, 
   const Model& m = h->m;
   const float level = (float)std::pow(10.0, (double)m.cfg.level_db / 20.0);
   h->tensors["seg.stats"] = TensorRef{w.stats_off, 4, 1};  // rows 0 .. C - 1: {mean removed, gain, mix_rms, 0} of the input rows
+  h->tensors["seg.row_scale"] = TensorRef{w.row_scale_off, 1, 1};  // rows 0 .. C - 1: the whole-row mel scale of the input rows
   return launched(h, launch_seg_stats(mix, w.part, w.stats, rows, C, level, h->norm, st), "segment stats") &&
          launched(h, launch_seg_mel_energy(mix, w.stats, h->W + m.mel.win_off, h->W + m.mel.tw_off, h->W + m.mel.fb_off, esum, rows,
                                            C, m.mel.n_fft, m.mel.hop, m.mel.pad_left, m.mel.n_freq, m.mel.n_mels, frames_max, st),
@@ -195,6 +200,12 @@ bool seg_row_stats(ou_handle* h, const float* mix, float* esum, const SegWs& w, 
 // slice of the caller's tensor (step_noise words), or -- counter mode -- the same positions come straight from the function, no
 // whole-row noise exists then: `entry(row, stream_row, t0, len)` names the long row whose stream walk row `row` reads, the first
 // position and the length (0 behind it, so x needs no mask).
+// (the names a group leaves behind: "seg.z", E * Bw rows of T: the last step's noise of the last group; "seg.carry", E rows of T:
+// the window in front of the last group that had one)
+void seg_group_taps(ou_handle* h, const SegWs& w, int T) {
+  h->tensors["seg.z"] = TensorRef{w.zbuf_off, 1, T};
+  h->tensors["seg.carry"] = TensorRef{w.carry_off, 1, T};
+}
 template <class Gather, class EntryFn>
 auto seg_noise(ou_handle* h, Runner& r, const float* noise, size_t step_noise, float* zbuf, int T, int n_rows, Gather gather,
                EntryFn entry) {
@@ -292,6 +303,7 @@ int seg_enhance(ou_handle* h, const char* who, const char* sizer, const float* m
                          len = L;
                        });
     sample(r, P, L, tab, 0, nullptr, false, z);
+    seg_group_taps(h, w, L);
     r.launch("segment stitch", [&] { return launch_seg_stitch(P.x.p, w.carry, members, rows, ents, n_real, L, Bw, E, C, st); });
     if (e0 + Bw < g.n_entries) seg_carry(r, w.carry, P.x.p, L, Bw, E, n_real);
     if (const int rc2 = finish(h, r)) return rc2;
@@ -422,6 +434,8 @@ int seg_var_enhance(ou_handle* h, const char* who, const char* sizer, const floa
                          len = en.len;
                        });
     sample(r, P, T, tab, 0, nullptr, false, z);
+    if (full) seg_group_taps(h, w, T);
+    else h->tensors["seg.z"] = TensorRef{w.zbuf_off, 1, T};  // (a SHORT group reads no carry: the name keeps the FULL groups' rows)
     for_blocks(n_real, [&](const SegEntriesList& ents, int n) {
       r.launch("segment stitch", [&] { return launch_seg_stitch(P.x.p, w.carry, members, rows, ents, n, T, Bw, E, C, st); });
     });
