@@ -271,8 +271,23 @@ int ou_segments_workspace_bytes(const ou_handle* h, int32_t C, int64_t T_raw, in
                                 int32_t max_batch, size_t* nbytes, int32_t* batch, int32_t* length);
 /* Universe.enhance of C independent rows of T_raw samples, in windows (see above):
  *   mix, out : (C, T_raw) device (out also serves as scratch for the whole-row mel frame energies before the first window)
- *   noise    : (n_steps, C, T_pad) standard-normal, device, the draw order of ou_enhance (x0, z_0 .. z_{N-2})
- *   flags    : OU_ENH_KEEP_RMS, OU_ENH_NO_PEAK_GUARD; warm_start must be -1 and OU_ENH_USE_AUX_SIGNAL is refused (OU_EINVAL).
+ *   noise    : (n_steps - max(warm_start, 0), C, T_pad) standard-normal, device, the draw order of ou_enhance (x0, z_0 ..
+ *              z_{N-2}): plane 0 is the initial draw, plane d - warm_start is draw d = n + 1 of the absolute step n.  A noise
+ *              source draws 0, warm_start + 1, warm_start + 2, .. at the positions s_k + i.
+ *   flags    : OU_ENH_KEEP_RMS, OU_ENH_NO_PEAK_GUARD, OU_ENH_USE_AUX_SIGNAL
+ *   warm_start: -1, or 0 <= k < n_steps (OU_EINVAL otherwise)
+ * The two cheap modes of ou_enhance, per window.  With wav_k = aux_to_wav(conditioner(xn[s_k : s_k + L])), the decoupling layer
+ * over the window's own aux signal (the whole row's mel scale, as above):
+ *   OU_ENH_USE_AUX_SIGNAL : window k's result is wav_k; no score pass runs, no noise is read (`noise` and a noise source as in
+ *                           ou_enhance under this flag: `noise` may be NULL, a set source still needs n_streams == C).  Same
+ *                           crossfade; unpad, keep_rms and the peak guard over the whole row.
+ *   warm_start = k        : x_k = wav_k + sigma[k] * z0[s_k : s_k + L], then the steps k .. n_steps - 1, stitch and post as above.
+ * Both need the snake signal-decoupling layer (UNIVERSE++): OU_ENOTIMPL otherwise, with the message of ou_enhance, decided on
+ * the host before anything is launched.  The `segment too long` guard then counts the layer's (C0, 2 L) plane as ou_enhance
+ * does.  Workspace: ou_segments_workspace_bytes answers what it answers for a cold start and a buffer of exactly that size runs
+ * both modes (ou_workspace_bytes reserves the layer's scratch for the walk's rows); the aux exit gets no smaller workspace.
+ * A row that fits one window is the ou_enhance call with the same warm_start / flags, bit for bit.  ou_tensor "wav": the last
+ * group's wav rows.  With warm_start == -1 and without the flag the call enqueues what it always has.
  * Everything is enqueued on `stream` (no side streams). */
 int ou_enhance_segments(ou_handle* h, const float* mix, float* out, const float* noise, int32_t C, int64_t T_raw,
                         int32_t segment, int32_t overlap, int32_t max_batch, int32_t n_steps, double epsilon,
@@ -312,9 +327,12 @@ int ou_segments_var_workspace_bytes(const ou_handle* h, int32_t C, const int64_t
 /*   mix, out : (C, T_raw_max) device; row c holds t_raw[c] samples, the rest of a mix row is ignored and the rest of an out row
  *              is zeroed (the ou_enhance_var convention; out also serves as scratch for the mel frame energies)
  *   t_raw    : HOST, C lengths, 1 <= t_raw[c] <= T_raw_max = the longest (OU_EINVAL otherwise, before anything is launched)
- *   noise    : (n_steps, C, T_pad_max) device; row c uses its first T_pad_c columns (what the call on row c alone would draw).
- *              With a noise source: NULL, n_streams == C, window k of row c draws at t = s_k + i from the stream of row c.
- *   flags, warm_start: as ou_enhance_segments.
+ *   noise    : (n_steps - max(warm_start, 0), C, T_pad_max) device; row c uses its first T_pad_c columns (what the call on row c
+ *              alone would draw).  With a noise source: NULL, n_streams == C, window k of row c draws at t = s_k + i from the
+ *              stream of row c.
+ *   flags, warm_start: as ou_enhance_segments, both cheap modes included.  In a ragged group the window's wav is zero behind the
+ *              entry's own length (the decoupling layer takes the entries' lengths), so x_k and the stitched wav are too.  Rows
+ *              of one length are ou_enhance_segments with the same warm_start / flags, bit for bit.
  * Everything is enqueued on `stream`: no allocation, no host synchronisation, no side streams; the per-row geometry and every
  * group's entries reach the device as kernel arguments (capturable). */
 int ou_enhance_segments_var(ou_handle* h, const float* mix, float* out, const float* noise, int32_t C, int64_t T_raw_max,
@@ -334,7 +352,8 @@ int ou_enhance_segments_var(ou_handle* h, const float* mix, float* out, const fl
  *              THAT GROWS WITH THE RECORDING (E x the output); the workspace does not depend on T_raw, as for ou_enhance_segments.
  *   noise    : (n_steps, E * C, T_pad) device; NULL when a noise source is set -- its n_streams must then equal E * C, and stream
  *              e * C + c belongs to that member row.  Window k of a member row reads the positions s_k + i of that row's noise.
- *   stat     : as ou_enhance_ensemble;  flags, warm_start: as ou_enhance_segments.
+ *   stat     : as ou_enhance_ensemble;  flags: OU_ENH_KEEP_RMS, OU_ENH_NO_PEAK_GUARD;  warm_start must be -1 (the cheap modes of
+ *              ou_enhance_segments are not carried into the ensemble forms: OU_EINVAL).
  *
  * Groups (pure host function).  The windows are those of ou_segment_plan, the entry list is row-major (c, k) as in
  * ou_enhance_segments.  Bw = ceil(n / ceil(n / floor(max_batch / E))) entries per group for n = C * n_windows entries, and the
@@ -374,7 +393,7 @@ int ou_enhance_segments_ensemble(ou_handle* h, const float* mix, float* out, flo
  *   t_raw    : HOST, C lengths, 1 <= t_raw[c] <= T_raw_max = the longest
  *   noise    : (n_steps, E * C, T_pad_max) device; member row e * C + c uses its first T_pad_c columns, window k reads the
  *              positions s_k + i.  With a noise source: NULL, n_streams == E * C, stream e * C + c belongs to that member row.
- *   stat     : as ou_enhance_ensemble;  flags, warm_start: as ou_enhance_segments.
+ *   stat     : as ou_enhance_ensemble;  flags, warm_start: as ou_enhance_segments_ensemble.
  *
  * Groups.  Entries, classes (FULL, then SHORT), group boundaries and `ragged` marks are exactly those of ou_segment_groups(tot_ds,
  * C, t_raw, segment, overlap, floor(max_batch / E)); with Bw that call's `batch`, the walk runs batch = E * Bw rows, walk row e *

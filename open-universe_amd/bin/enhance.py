@@ -108,7 +108,9 @@ def build_parser():
     parser.add_argument("--segment-seconds", type=float, default=None,
                         help="Enhance every file longer than this many seconds in overlapping windows of this length "
                              "(Universe.enhance_long: bounded memory for recordings of any length; normalisation, mel scale, "
-                             "noise and output level stay those of the whole file).  Off by default")
+                             "noise and output level stay those of the whole file).  Takes --warm_start and --use_aux_signal "
+                             "(every window starts from, or is, its own conditioner estimate); --segment-ensemble and "
+                             "--segment-files N > 1 refuse them.  Off by default")
     parser.add_argument("--segment-overlap", type=float, default=None,
                         help="With --segment-seconds: overlap of consecutive windows in seconds (default 1.0)")
     parser.add_argument("--segment-files", type=int, default=1,
@@ -189,11 +191,17 @@ def check_segment_args(args, enhance_kwargs):
     if args.batch_size > 1 or args.in_flight > 1:
         raise ValueError("--segment-seconds cannot be combined with --batch-size or --in-flight (--segment-files N puts N "
                          "files into one segmented call)")
-    for key in ("ensemble", "target", "warm_start"):
+    for key in ("ensemble", "target"):
         if enhance_kwargs.get(key) is not None:
             raise ValueError(f"--segment-seconds cannot be combined with --{key}")
-    if enhance_kwargs.get("use_aux_signal"):
-        raise ValueError("--segment-seconds cannot be combined with --use-aux-signal")
+    # --warm_start / --use_aux_signal: taken by the one-file-per-call form without an ensemble (enhance_long); the ensemble
+    # and the multi-file forms of the CLI refuse them
+    if seg_ens is not None or getattr(args, "segment_files", 1) > 1:
+        form = "--segment-ensemble" if seg_ens is not None else "--segment-files > 1"
+        if enhance_kwargs.get("warm_start") is not None:
+            raise ValueError(f"{form} cannot be combined with --warm_start")
+        if enhance_kwargs.get("use_aux_signal"):
+            raise ValueError(f"{form} cannot be combined with --use_aux_signal")
 
 
 def check_noise_args(args, enhance_kwargs):
@@ -227,6 +235,10 @@ def enhance_file(model, audio, args, enhance_kwargs, rng):
     if args.segment_seconds is not None and audio.shape[-1] > args.segment_seconds * model.fs:
         ov = 1.0 if args.segment_overlap is None else args.segment_overlap
         kw = {k: v for k, v in enhance_kwargs.items() if k in ("n_steps", "epsilon", "keep_rms")}
+        if enhance_kwargs.get("warm_start") is not None:
+            kw["warm_start"] = enhance_kwargs["warm_start"]
+        if enhance_kwargs.get("use_aux_signal"):
+            kw["use_aux_signal"] = True
         return model.enhance_long(audio, segment_s=args.segment_seconds, overlap_s=ov, rng=rng, **kw)
     try:
         return model.enhance(audio, **dict(enhance_kwargs, rng=rng))

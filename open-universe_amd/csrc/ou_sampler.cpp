@@ -172,17 +172,6 @@ void post(Runner& r, Persist& P, const float* x, float* out, int rows, int T_raw
                     : launch_post(x, P.stats, out, rows, T_raw, T, (T - T_raw) / 2, f.keep_rms, f.peak, r.st);
   });
 }
-// the signal decoupling layer: P.aux -> P.wav for the rows of r (scratch from the walk's bump allocator)
-void decouple(Runner& r, Persist& P) {
-  const Model& m = r.h->m;
-  const int T = P.wav.T;
-  float* tmp = r.alloc_raw((size_t)r.B * m.C0 * 2 * T);
-  r.launch("decoupling", [&] {
-    return launch_decoupling(P.aux.p, r.W(m.dec.alpha_off), r.W(m.dec.up_off), r.W(m.dec.down_off), r.W(m.dec.conv.w_off),
-                             r.W(m.dec.conv.b_off), tmp, P.wav.p, r.B, m.C0, T, r.st, r.lens_of(T), r.lens_of(2 * T));
-  });
-}
-
 // Noise provider of the calls whose rows are whole signals: draw d is plane (d ? d - n_start : 0) of the caller's tensor, or --
 // counter mode -- filled into plane d & 1 of the scratch right in front of the launch that reads it, on the caller's stream (the
 // simplest place: the launches that read a plane are untouched, and at step n_start the fill runs beside the first score-encoder
@@ -206,6 +195,24 @@ auto row_noise(Runner& r, const float* noise, int n_start, int T, const int32_t*
 }  // namespace
 
 namespace ou {
+// what a call that needs P.wav asks of the model, on the host before anything is launched
+int check_decoupling(ou_handle* h) {
+  const Model& m = h->m;
+  if (!m.dec.present || m.dec.act != OU_ACT_SNAKE)
+    return fail(h, OU_ENOTIMPL, "aux_to_wav needs the snake signal-decoupling layer (UNIVERSE++)");
+  return OU_OK;
+}
+// the signal decoupling layer: P.aux -> P.wav for the rows of r (scratch from the walk's bump allocator)
+void decouple(Runner& r, Persist& P) {
+  const Model& m = r.h->m;
+  const int T = P.wav.T;
+  float* tmp = r.alloc_raw((size_t)r.B * m.C0 * 2 * T);
+  r.launch("decoupling", [&] {
+    return launch_decoupling(P.aux.p, r.W(m.dec.alpha_off), r.W(m.dec.up_off), r.W(m.dec.down_off), r.W(m.dec.conv.w_off),
+                             r.W(m.dec.conv.b_off), tmp, P.wav.p, r.B, m.C0, T, r.st, r.lens_of(T), r.lens_of(2 * T));
+  });
+}
+
 // universe.py:325-327: x = sigma * z_0 (+ the warm start's signal).  `mask`: the plane may hold noise behind a row's own end.
 void init_x(Runner& r, Persist& P, const float* z0, const float* warm, float sigma, int T, bool mask) {
   r.launch("init x", [&] { return launch_init_x(z0, warm, sigma, P.x.p, (size_t)r.B * T, r.st); });
@@ -251,8 +258,8 @@ int enhance_impl(ou_handle* h, const float* mix, float* out, const float* noise,
     upload_row_lengths(r, P.rows, P.lens, t_raw, B);
     r.set_ragged(P.lens, P.rows);
   }
-  if (need_wav && (!m.dec.present || m.dec.act != OU_ACT_SNAKE))
-    return fail(h, OU_ENOTIMPL, "aux_to_wav needs the snake signal-decoupling layer (UNIVERSE++)");
+  if (need_wav)
+    if (const int rc = check_decoupling(h)) return rc;
   const int n_start = warm_start >= 0 ? warm_start : 0;
   auto z = row_noise(r, noise, n_start, T, t_raw);
 
@@ -417,8 +424,8 @@ int ensemble_impl(ou_handle* h, const float* mix, float* out, float* members_out
     return fail(h, OU_EINVAL, "workspace was not prepared by ou_workspace_init for this (E * B, T_raw + pad)");
   if (h->noise_src.on)
     if (const int rc = check_noise_scratch(h, EB, T, "ou_noise_scratch_bytes for E * B rows")) return rc;
-  if (need_wav && (!m.dec.present || m.dec.act != OU_ACT_SNAKE))
-    return fail(h, OU_ENOTIMPL, "aux_to_wav needs the snake signal-decoupling layer (UNIVERSE++)");
+  if (need_wav)
+    if (const int rc = check_decoupling(h)) return rc;
   CallScope scope(h, true);  // one chain on the caller's stream (the conditioner || first-encoder overlap of ou_enhance is dropped)
   hipStream_t st = (hipStream_t)stream;
   const bool share = h->opt.ens_share != 0 && E > 1;

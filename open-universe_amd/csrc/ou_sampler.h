@@ -86,6 +86,8 @@ struct PostFlags {
   explicit PostFlags(uint32_t flags) : keep_rms((flags & OU_ENH_KEEP_RMS) ? 1 : 0), peak((flags & OU_ENH_NO_PEAK_GUARD) ? 0 : 1) {}
 };
 
+int check_decoupling(ou_handle* h);
+void decouple(Runner& r, Persist& P);
 void init_x(Runner& r, Persist& P, const float* z0, const float* warm, float sigma, int T, bool mask);
 // A first score-encoder pass that already ran on side stream 2 (ou_enhance's overlap with the conditioner): its results and
 // where its scratch ends.  Its init_x ran in front of it.

@@ -196,22 +196,32 @@ bool seg_row_stats(ou_handle* h, const float* mix, float* esum, const SegWs& w, 
                                            C, m.mel.n_fft, m.mel.hop, m.mel.pad_left, m.mel.n_freq, m.mel.n_mels, frames_max, st),
                   "segment mel energy");
 }
+// The cheap modes of a call, both from the window's own wav = aux_to_wav(conditioner(window)): `warm` -- the
+// sampler starts at step n_start from wav + sigma[n_start] z_0 --, `aux` -- wav is the window's result, no score pass and no noise.
+struct SegMode {
+  int n_start;
+  bool warm, aux;
+  SegMode(int warm_start, uint32_t flags)
+      : n_start(warm_start >= 0 ? warm_start : 0), warm(warm_start >= 0), aux((flags & OU_ENH_USE_AUX_SIGNAL) != 0) {}
+  bool need_wav() const { return warm || aux; }
+};
 // One step's noise of a group's n_rows walk rows of T columns, in w.zbuf: `gather(slice)` enqueues the gather from one step's
 // slice of the caller's tensor (step_noise words), or -- counter mode -- the same positions come straight from the function, no
 // whole-row noise exists then: `entry(row, stream_row, t0, len)` names the long row whose stream walk row `row` reads, the first
-// position and the length (0 behind it, so x needs no mask).
+// position and the length (0 behind it, so x needs no mask).  Draw d is plane (d ? d - n_start : 0) of the caller's tensor: the
+// convention of ou_enhance (row_noise), (n_steps - n_start) planes.
 // (the names a group leaves behind: "seg.z", E * Bw rows of T: the last step's noise of the last group; "seg.carry", E rows of T:
 // the window in front of the last group that had one)
-void seg_group_taps(ou_handle* h, const SegWs& w, int T) {
-  h->tensors["seg.z"] = TensorRef{w.zbuf_off, 1, T};
+void seg_group_taps(ou_handle* h, const SegWs& w, int T, bool with_z) {
+  if (with_z) h->tensors["seg.z"] = TensorRef{w.zbuf_off, 1, T};  // (the aux exit reads no noise)
   h->tensors["seg.carry"] = TensorRef{w.carry_off, 1, T};
 }
 template <class Gather, class EntryFn>
-auto seg_noise(ou_handle* h, Runner& r, const float* noise, size_t step_noise, float* zbuf, int T, int n_rows, Gather gather,
-               EntryFn entry) {
+auto seg_noise(ou_handle* h, Runner& r, const float* noise, size_t step_noise, int n_start, float* zbuf, int T, int n_rows,
+               Gather gather, EntryFn entry) {
   return [=, &r](int draw) -> const float* {
     if (noise) {
-      gather(noise + (size_t)draw * step_noise);
+      gather(noise + (size_t)(draw ? draw - n_start : 0) * step_noise);
       return zbuf;
     }
     fill_noise_plane(r, zbuf, T, n_rows, h->noise_src.seed, draw, [&](int row, unsigned long long& sid, long long& t0, long long& len) {
@@ -246,8 +256,11 @@ int seg_epilogue(ou_handle* h, float* long_rows, const SegWs& w, const Rows& row
 // `members`, post-processed there and, `reduce`, reduced into `out`.
 int seg_enhance(ou_handle* h, const char* who, const char* sizer, const float* mix, float* out, float* members, const float* noise,
                 int C, int E, bool reduce, int stat, SegGeom g, int Bw, int n_steps, double epsilon, const float* sigma_host,
-                uint32_t flags, void* ws, size_t ws_bytes, ou_stream_t stream) {
-  if (g.L > max_walk_length(h, false)) return fail(h, OU_EINVAL, std::string(who) + ": segment too long for one pass of the walk");
+                SegMode mode, uint32_t flags, void* ws, size_t ws_bytes, ou_stream_t stream) {
+  if (mode.need_wav())
+    if (const int rc = check_decoupling(h)) return rc;
+  if (g.L > max_walk_length(h, mode.need_wav()))
+    return fail(h, OU_EINVAL, std::string(who) + ": segment too long for one pass of the walk");
   const int B = E * Bw;  // rows of the walk
   const int L = (int)g.L;
   SegWs w;
@@ -276,7 +289,8 @@ int seg_enhance(ou_handle* h, const char* who, const char* sizer, const float* m
     r.mel_scale_preset = true;
     Persist P = layout_persist(r, L);
     if (r.oom) return finish(h, r);
-    if (e0 == 0) tab.upload(r, P);  // (the persistent area of the workspace keeps the tables from group to group)
+    // (the persistent area of the workspace keeps the tables from group to group; the aux exit runs no step)
+    if (e0 == 0 && !mode.aux) tab.upload(r, P);
     Runner rc = Runner::conditioner_of(r, Bc);
     // the group's inputs: once into the prefix, or -- the conditioner over all rows -- once per member
     for (int e = 0; e < (share ? 1 : E); e++)
@@ -285,13 +299,15 @@ int seg_enhance(ou_handle* h, const char* who, const char* sizer, const float* m
                                        ents, Bw, L, st);
       });
     run_condition(rc, P, P.mixn.p, L);
-    // (the statistics of the post step are those of the whole long rows, w.stats: P.stats is not written; no warm start)
+    // the window's own wav, its scratch behind the conditioner's (ou_workspace_bytes reserves it for the walk's rows)
+    if (mode.need_wav()) decouple(rc, P);
+    // (the statistics of the post step are those of the whole long rows, w.stats: P.stats is not written)
     if (share) replicate_conditioned(rc, P, Bw, E, false, false);
     if (const int rc2 = finish(h, rc)) return rc2;
     r.off = rc.off;
     // walk row e * Bw + j: window k of long row e * C + c, positions s_k + i of that row's noise.  The filler rows of a short
     // last group repeat their member's last real entry.
-    auto z = seg_noise(h, r, noise, (size_t)E * C * g.T_pad, w.zbuf, L, B,
+    auto z = seg_noise(h, r, noise, (size_t)E * C * g.T_pad, mode.n_start, w.zbuf, L, B,
                        [&](const float* slice) {
                          r.launch("segment noise", [&] { return launch_seg_gather_noise(slice, w.zbuf, rows, ents, Bw, L, Bw, E, C, st); });
                        },
@@ -302,10 +318,11 @@ int seg_enhance(ou_handle* h, const char* who, const char* sizer, const float* m
                          t0 = seg_start_host(g, en.win);
                          len = L;
                        });
-    sample(r, P, L, tab, 0, nullptr, false, z);
-    seg_group_taps(h, w, L);
-    r.launch("segment stitch", [&] { return launch_seg_stitch(P.x.p, w.carry, members, rows, ents, n_real, L, Bw, E, C, st); });
-    if (e0 + Bw < g.n_entries) seg_carry(r, w.carry, P.x.p, L, Bw, E, n_real);
+    if (!mode.aux) sample(r, P, L, tab, mode.n_start, mode.warm ? P.wav.p : nullptr, false, z);
+    const float* y = mode.aux ? P.wav.p : P.x.p;  // what the windows of this group are
+    seg_group_taps(h, w, L, !mode.aux);
+    r.launch("segment stitch", [&] { return launch_seg_stitch(y, w.carry, members, rows, ents, n_real, L, Bw, E, C, st); });
+    if (e0 + Bw < g.n_entries) seg_carry(r, w.carry, y, L, Bw, E, n_real);
     if (const int rc2 = finish(h, r)) return rc2;
   }
   // ---- the post step over every long row (keep_rms: the mix_rms of the member's own input row), then the reduce over e
@@ -323,11 +340,14 @@ int seg_enhance(ou_handle* h, const char* who, const char* sizer, const float* m
 // stitched into the (E * C, T_raw_max) rows `members`, post-processed there and, `reduce`, reduced into `out` at the rows' lengths.
 int seg_var_enhance(ou_handle* h, const char* who, const char* sizer, const float* mix, float* out, float* members,
                     const float* noise, int C, long long T_raw_max, const int64_t* t_raw, int E, bool reduce, int stat,
-                    const SegGroups& G, int n_steps, double epsilon, const float* sigma_host, uint32_t flags, void* ws,
-                    size_t ws_bytes, ou_stream_t stream) {
+                    const SegGroups& G, int n_steps, double epsilon, const float* sigma_host, SegMode mode, uint32_t flags,
+                    void* ws, size_t ws_bytes, ou_stream_t stream) {
   const Model& m = h->m;
   const int tot = m.tot_ds;
-  if (G.length > max_walk_length(h, false)) return fail(h, OU_EINVAL, std::string(who) + ": segment too long for one pass of the walk");
+  if (mode.need_wav())
+    if (const int rc = check_decoupling(h)) return rc;
+  if (G.length > max_walk_length(h, mode.need_wav()))
+    return fail(h, OU_EINVAL, std::string(who) + ": segment too long for one pass of the walk");
   const int Bw = G.batch;  // entries per group
   const int B = E * Bw;    // rows of the walk
   SegWs w;
@@ -391,7 +411,8 @@ int seg_var_enhance(ou_handle* h, const char* who, const char* sizer, const floa
     r.mel_scale_preset = true;
     Persist P = layout_persist(r, T);
     if (r.oom) return finish(h, r);
-    if (gi == 0) tab.upload(r, P);  // (the persistent area keeps the tables from group to group: its layout depends on B alone)
+    // (the persistent area keeps the tables from group to group: its layout depends on B alone; the aux exit runs no step)
+    if (gi == 0 && !mode.aux) tab.upload(r, P);
     const bool ragged = G.group_ragged[gi] != 0;
     if (ragged) {
       // the entries' lengths on every level of the network (as ou_enhance_var; an entry is an already padded window, so its
@@ -415,12 +436,15 @@ int seg_var_enhance(ou_handle* h, const char* who, const char* sizer, const floa
         });
       });
     run_condition(rc, P, P.mixn.p, T);
-    // (the statistics of the post step are those of the whole long rows, w.stats: P.stats is not written; no warm start)
+    // the window's own wav (seg_enhance); in a ragged group the layer writes 0 behind an entry's own length, as the noise gather
+    // does, so x0 = wav + sigma z_0 and the stitched wav keep that invariant without a mask
+    if (mode.need_wav()) decouple(rc, P);
+    // (the statistics of the post step are those of the whole long rows, w.stats: P.stats is not written)
     if (share) replicate_conditioned(rc, P, Bw, E, false, false);
     if (const int rc2 = finish(h, rc)) return rc2;
     r.off = rc.off;
     // walk row e * Bw + j: window k of long row e * C + c, positions s_k + i of that row's noise
-    auto z = seg_noise(h, r, noise, (size_t)E * C * T_pad_max, w.zbuf, T, B,
+    auto z = seg_noise(h, r, noise, (size_t)E * C * T_pad_max, mode.n_start, w.zbuf, T, B,
                        [&](const float* slice) {
                          for_blocks(Bw, [&](const SegEntriesList& ents, int n) {
                            r.launch("segment noise", [&] { return launch_seg_gather_noise(slice, w.zbuf, rows, ents, n, T, Bw, E, C, st); });
@@ -433,13 +457,14 @@ int seg_var_enhance(ou_handle* h, const char* who, const char* sizer, const floa
                          t0 = en.win < G.rows[en.row].n_win - 1 ? en.win * G.hop : G.rows[en.row].T_pad - en.len;
                          len = en.len;
                        });
-    sample(r, P, T, tab, 0, nullptr, false, z);
-    if (full) seg_group_taps(h, w, T);
-    else h->tensors["seg.z"] = TensorRef{w.zbuf_off, 1, T};  // (a SHORT group reads no carry: the name keeps the FULL groups' rows)
+    if (!mode.aux) sample(r, P, T, tab, mode.n_start, mode.warm ? P.wav.p : nullptr, false, z);
+    const float* y = mode.aux ? P.wav.p : P.x.p;  // what the windows of this group are
+    if (full) seg_group_taps(h, w, T, !mode.aux);
+    else if (!mode.aux) h->tensors["seg.z"] = TensorRef{w.zbuf_off, 1, T};  // (a SHORT group reads no carry: the name keeps the FULL groups' rows)
     for_blocks(n_real, [&](const SegEntriesList& ents, int n) {
-      r.launch("segment stitch", [&] { return launch_seg_stitch(P.x.p, w.carry, members, rows, ents, n, T, Bw, E, C, st); });
+      r.launch("segment stitch", [&] { return launch_seg_stitch(y, w.carry, members, rows, ents, n, T, Bw, E, C, st); });
     });
-    if (full && e_end < G.n_full) seg_carry(r, w.carry, P.x.p, T, Bw, E, n_real);  // the window in front of the next group
+    if (full && e_end < G.n_full) seg_carry(r, w.carry, y, T, Bw, E, n_real);  // the window in front of the next group
     if (const int rc2 = finish(h, r)) return rc2;
   }
   // ---- the post step over every long row (keep_rms: the mix_rms of the member's own input row), then the reduce over e
@@ -497,16 +522,15 @@ int ou_enhance_segments(ou_handle* h, const float* mix, float* out, const float*
                         const float* sigma_host, int32_t warm_start, uint32_t flags, void* ws, size_t ws_bytes,
                         ou_stream_t stream) {
   if (!h || !mix || !out || !ws || C < 1 || T_raw < 1 || max_batch < 1) return fail(h, OU_EINVAL, "bad argument");
-  if (const int rc = check_noise_source(h, noise, C, "the rows of the call (", true)) return rc;
-  if (warm_start >= 0 || (flags & OU_ENH_USE_AUX_SIGNAL))
-    return fail(h, OU_EINVAL, "ou_enhance_segments: warm_start and use_aux_signal are not supported");
+  const SegMode mode(warm_start, flags);
+  if (const int rc = check_noise_source(h, noise, C, "the rows of the call (", !mode.aux)) return rc;
   if (const int rc = check_steps(h, n_steps, warm_start)) return rc;
   SegPlan plan;
   if (!seg_plan(h->m.tot_ds, T_raw, segment, overlap, plan)) return fail(h, OU_EINVAL, plan.err);
   SegGeom g = plan.g;
   g.n_entries = (long long)C * g.n_win;
   return seg_enhance(h, "ou_enhance_segments", "ou_segments_workspace_bytes", mix, out, out, noise, C, 1, false, 0, g,
-                     seg_batch(g.n_entries, max_batch), n_steps, epsilon, sigma_host, flags, ws, ws_bytes, stream);
+                     seg_batch(g.n_entries, max_batch), n_steps, epsilon, sigma_host, mode, flags, ws, ws_bytes, stream);
 }
 
 int ou_segments_ensemble_workspace_bytes(const ou_handle* hc, int32_t C, int64_t T_raw, int32_t segment, int32_t overlap,
@@ -538,7 +562,7 @@ int ou_enhance_segments_ensemble(ou_handle* h, const float* mix, float* out, flo
   if (const int rc = check_noise_source(h, noise, E * C, "the member rows of the call (E * C = ", true)) return rc;
   if (const int rc = check_steps(h, n_steps, warm_start)) return rc;
   return seg_enhance(h, who, "ou_segments_ensemble_workspace_bytes", mix, out, members, noise, C, E, true, stat, g, Bw, n_steps,
-                     epsilon, sigma_host, flags, ws, ws_bytes, stream);
+                     epsilon, sigma_host, SegMode(-1, 0), flags, ws, ws_bytes, stream);
 }
 
 int ou_segment_groups(int32_t tot_ds, int32_t C, const int64_t* t_raw, int32_t segment, int32_t overlap, int32_t max_batch,
@@ -583,14 +607,13 @@ int ou_enhance_segments_var(ou_handle* h, const float* mix, float* out, const fl
   if (max_batch < 1) return fail(h, OU_EINVAL, "ou_enhance_segments_var: max_batch must be at least 1");
   if (const int rc = check_rows(h, "ou_enhance_segments_var", 'c', t_raw, C, T_raw_max, false)) return rc;
   if (!h || !mix || !out || !ws) return fail(h, OU_EINVAL, "bad argument");
-  if (const int rc = check_noise_source(h, noise, C, "the rows of the call (", true)) return rc;
-  if (warm_start >= 0 || (flags & OU_ENH_USE_AUX_SIGNAL))
-    return fail(h, OU_EINVAL, "ou_enhance_segments_var: warm_start and use_aux_signal are not supported");
+  const SegMode mode(warm_start, flags);
+  if (const int rc = check_noise_source(h, noise, C, "the rows of the call (", !mode.aux)) return rc;
   if (const int rc = check_steps(h, n_steps, warm_start)) return rc;
   SegGroups G;
   if (!seg_groups(h->m.tot_ds, C, t_raw, segment, overlap, max_batch, G)) return fail(h, OU_EINVAL, G.err);
   return seg_var_enhance(h, "ou_enhance_segments_var", "ou_segments_var_workspace_bytes", mix, out, out, noise, C, T_raw_max, t_raw,
-                         1, false, 0, G, n_steps, epsilon, sigma_host, flags, ws, ws_bytes, stream);
+                         1, false, 0, G, n_steps, epsilon, sigma_host, mode, flags, ws, ws_bytes, stream);
 }
 
 int ou_segments_var_ensemble_workspace_bytes(const ou_handle* hc, int32_t C, const int64_t* t_raw, int32_t segment,
@@ -626,7 +649,7 @@ int ou_enhance_segments_var_ensemble(ou_handle* h, const float* mix, float* out,
   SegGroups G;
   if (!seg_groups(h->m.tot_ds, C, t_raw, segment, overlap, max_batch / E, G)) return fail(h, OU_EINVAL, G.err);
   return seg_var_enhance(h, who, "ou_segments_var_ensemble_workspace_bytes", mix, out, members, noise, C, T_raw_max, t_raw, E, true,
-                         stat, G, n_steps, epsilon, sigma_host, flags, ws, ws_bytes, stream);
+                         stat, G, n_steps, epsilon, sigma_host, SegMode(-1, 0), flags, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -1037,11 +1037,21 @@ class Universe:
         n_noise = 0 if use_aux_signal else n_steps - (0 if warm_start is None else int(warm_start))
         draw_noise(self.tot_ds, [(int(channels), int(length), rng)], n_noise, device=self.device, discard=True)
 
-    def draw_noise_like_enhance(self, rng, channels, length, n_steps=None):
+    def draw_noise_like_enhance(self, rng, channels, length, n_steps=None, planes=None):
         """The noise `enhance` draws for a (channels, length) input -- x0, then one z per noisy step, each (channels, 1, length
-        + pad) -- in ONE (n_steps, channels, length + pad) tensor, drawn in that order from `rng`."""
+        + pad) -- in ONE (n_steps, channels, length + pad) tensor, drawn in that order from `rng`.  `planes`: the number of
+        draws where it is not n_steps (a warm start at step k draws n_steps - k)."""
         n_steps = self.diff_kwargs.n_steps if n_steps is None else int(n_steps)
-        return draw_noise(self.tot_ds, [(int(channels), int(length), rng)], n_steps, device=self.device)[:, :, 0]
+        n = n_steps if planes is None else int(planes)
+        return draw_noise(self.tot_ds, [(int(channels), int(length), rng)], n, device=self.device)[:, :, 0]
+
+    @staticmethod
+    def _long_planes(who, n_steps, warm_start, use_aux_signal):
+        """Noise planes of a segmented call, as `enhance` counts them: n_steps - warm_start, none for the aux exit."""
+        n_start = 0 if warm_start is None else int(warm_start)
+        if not 0 <= n_start < n_steps:
+            raise ValueError(f"{who}: warm_start must lie in [0, n_steps)")
+        return 0 if use_aux_signal else n_steps - n_start
 
     # ---- recordings of any length: segmented enhance (ou_enhance_segments) ---------------------------------------------
     SEGMENT_S = 8.0
@@ -1050,7 +1060,8 @@ class Universe:
     @torch.no_grad()
     def enhance_long(self, mix, segment_s: float = SEGMENT_S, overlap_s: float = OVERLAP_S, max_batch: int = 32,
                      rng: Optional[torch.Generator] = None, n_steps: Optional[int] = None, epsilon: Optional[float] = None,
-                     keep_rms: Optional[bool] = False, **other) -> torch.Tensor:
+                     keep_rms: Optional[bool] = False, warm_start: Optional[int] = None, use_aux_signal: bool = False,
+                     **other) -> torch.Tensor:
         """`enhance` of a recording of any length in bounded memory (extension).  `mix`: (T,) or (C, T); rows are independent
         signals, as channels are everywhere else.  The signal is cut into windows of `segment_s` seconds that overlap by
         `overlap_s` seconds and run `max_batch` at a time through the walk of `enhance`; normalisation, mel scale, noise,
@@ -1059,21 +1070,27 @@ class Universe:
         T_pad) tensor, n_steps times the recording.  `rng=noise.CounterNoise(seed, u)` removes that tensor: every window's noise
         is computed at its offset from the counter-based function (row c: stream id (u << 16) | c), and the memory of the call is
         the workspace plus input and output.  A file that fits into one window gets the `enhance` result.  Workspace: ou_segments_workspace_bytes -- set by max_batch and segment_s.
+        `warm_start=k` / `use_aux_signal=True` (UNIVERSE++ with the snake decoupling layer): every window starts at step k from
+        its own conditioner estimate plus noise, or IS that estimate (no score pass); the draws are those of `enhance` with the
+        same arguments -- n_steps - k planes, none for the aux exit, which leaves the generator where it was.
         Ensembles of long recordings: `enhance_long_ensemble` (`ensemble=` is refused here)."""
         self._refuse_long_options("enhance_long", other)
         n_steps, epsilon, segment, overlap = self._begin(n_steps, epsilon, segment_s, overlap_s)
+        planes = self._long_planes("enhance_long", n_steps, warm_start, use_aux_signal)
         x = self._long_rows(mix, "enhance_long")
         C, T_raw = x.shape
         if is_counter(rng):
             noise, counter = None, (rng.seed, rng.stream_ids(C))
         else:
-            noise, counter = self.draw_noise_like_enhance(rng, C, T_raw, n_steps), None
-        out = self._segments_call(x, segment, overlap, max_batch, n_steps, epsilon, keep_rms, noise, counter)
+            noise, counter = (self.draw_noise_like_enhance(rng, C, T_raw, n_steps, planes) if planes else None), None
+        out = self._segments_call(x, segment, overlap, max_batch, n_steps, epsilon, keep_rms, noise, counter, warm_start,
+                                  use_aux_signal)
         return out if mix.ndim == 2 else out[0]
 
-    def _segments_plan(self, C, T, segment, overlap, max_batch, ensemble=None, t_raw=None):
+    def _segments_plan(self, C, T, segment, overlap, max_batch, ensemble=None, t_raw=None, warm_start=None, use_aux_signal=False):
         """What tells the four segmented entry points apart -- plain, `ensemble` = (E, stat), `t_raw` = a length per row, or both --,
-        sized: -> (library function, its arguments between the noise pointer and n_steps, workspace)."""
+        sized: -> (library function, its arguments between the noise pointer and n_steps, workspace, and the mode of the call:
+        warm_start, use_aux_signal -- the sizers answer the same for every mode)."""
         geo = (segment, overlap, int(max_batch))
         if ensemble is not None and t_raw is not None:
             fn, sizer = self._L.ou_enhance_segments_var_ensemble, self._L.ou_segments_var_ensemble_workspace_bytes
@@ -1087,23 +1104,25 @@ class Universe:
         else:
             fn, sizer = self._L.ou_enhance_segments, self._L.ou_segments_workspace_bytes
             sized, dims = (C, T) + geo, (C, T) + geo
-        return fn, dims, self._segments_sizer(sizer, *sized)[0]
+        return fn, dims, self._segments_sizer(sizer, *sized)[0], warm_start, bool(use_aux_signal)
 
     def _segments_run(self, plan, x, n_steps, epsilon, keep_rms, noise, counter, members=None):
         """The call `plan` (_segments_plan) on the prepared (C, T) rows `x` -> out (C, T); `members`: the (E, C, T) tensor an
         ensemble writes its members to.  Noise as in `_segments_call`; no noise scratch (the library fills window by window)."""
-        fn, dims, ws = plan
+        fn, dims, ws, warm_start, use_aux_signal = plan
         out = torch.empty(x.shape, dtype=torch.float32, device=self.device)
-        self._forward(fn, (x, out, noise) if members is None else (x, out, members, noise), dims, n_steps, epsilon, None,
-                      _lib.OU_ENH_KEEP_RMS if keep_rms else 0, ws, counter if noise is None else None)
+        flags = (_lib.OU_ENH_KEEP_RMS if keep_rms else 0) | (_lib.OU_ENH_USE_AUX_SIGNAL if use_aux_signal else 0)
+        self._forward(fn, (x, out, noise) if members is None else (x, out, members, noise), dims, n_steps, epsilon, warm_start,
+                      flags, ws, counter if noise is None else None)
         return out
 
-    def _segments_call(self, x, segment, overlap, max_batch, n_steps, epsilon, keep_rms, noise, counter):
-        """ou_enhance_segments of the prepared (C, T_raw) rows `x` on `noise` ((n_steps, C, T_pad)) or, with noise None, on the
-        counter source `counter` = (seed, C stream ids).  (Also what the tests of enhance_long_ensemble run a single member row
-        through, on that member's own noise or stream id.)"""
-        return self._segments_run(self._segments_plan(*x.shape, segment, overlap, max_batch), x, n_steps, epsilon, keep_rms,
-                                  noise, counter)
+    def _segments_call(self, x, segment, overlap, max_batch, n_steps, epsilon, keep_rms, noise, counter, warm_start=None,
+                       use_aux_signal=False):
+        """ou_enhance_segments of the prepared (C, T_raw) rows `x` on `noise` ((n_steps - (warm_start or 0), C, T_pad); None for
+        the aux exit) or, with noise None, on the counter source `counter` = (seed, C stream ids).  (Also what the tests of
+        enhance_long_ensemble run a single member row through, on that member's own noise or stream id.)"""
+        plan = self._segments_plan(*x.shape, segment, overlap, max_batch, warm_start=warm_start, use_aux_signal=use_aux_signal)
+        return self._segments_run(plan, x, n_steps, epsilon, keep_rms, noise, counter)
 
     @torch.no_grad()
     def enhance_long_ensemble(self, mix, ensemble: int, ensemble_stat: str = "median", segment_s: float = SEGMENT_S,
@@ -1140,7 +1159,8 @@ class Universe:
     @torch.no_grad()
     def enhance_long_many(self, signals, rngs=None, segment_s: float = SEGMENT_S, overlap_s: float = OVERLAP_S,
                           max_batch: int = 32, n_steps: Optional[int] = None, epsilon: Optional[float] = None,
-                          keep_rms: Optional[bool] = False, **other):
+                          keep_rms: Optional[bool] = False, warm_start: Optional[int] = None, use_aux_signal: bool = False,
+                          **other):
         """`enhance_long` of several independent inputs of ANY lengths in ONE call (extension; ou_enhance_segments_var).
         `signals`: list of (L,) or (C, L) tensors, channels are rows as in `enhance_many`.  Inputs longer than a window are cut
         into windows, shorter ones are one window each, and the windows of all rows share the window groups of `max_batch`;
@@ -1148,18 +1168,22 @@ class Universe:
         guard of its own; to fp32 round-off, since the kernels a group selects differ).  `rngs`: one generator per input, ONE
         shared generator (it advances input by input, as `enhance_long` draws for each), or None -- or `noise.CounterNoise`
         objects as in `enhance_many` (one per input with one seed, or one shared: input i is utterance `stream + i`).
+        `warm_start` / `use_aux_signal`: as in `enhance_long`, for every input.
         Returns the list of enhanced signals, each with the shape of its input."""
         self._refuse_long_options("enhance_long_many", other)
         if not signals:
             return []
         n_steps, epsilon, segment, overlap = self._begin(n_steps, epsilon, segment_s, overlap_s)
+        planes = self._long_planes("enhance_long_many", n_steps, warm_start, use_aux_signal)
         pk = pack_rows(signals, "enhance_long_many", self._prep)
         C, l_max = pk.batch.shape
-        plan = self._segments_plan(C, l_max, segment, overlap, max_batch, t_raw=(ctypes.c_int64 * C)(*pk.row_lens))
+        plan = self._segments_plan(C, l_max, segment, overlap, max_batch, t_raw=(ctypes.c_int64 * C)(*pk.row_lens),
+                                   warm_start=warm_start, use_aux_signal=use_aux_signal)
         counter = self._counter_plan(rngs, pk.chans)
         noise = None
-        if counter is None:  # the draws of `enhance_long` on every input alone, input by input: (C_i, 1, T_i) per step, x0 first
-            noise = draw_noise(self.tot_ds, pk.entries(rngs), n_steps, device=self.device)
+        if counter is None and planes:  # the draws of `enhance_long` on every input alone, input by input: (C_i, 1, T_i) per
+            # step, x0 first
+            noise = draw_noise(self.tot_ds, pk.entries(rngs), planes, device=self.device)
         return unpack_rows(pk, self._segments_run(plan, pk.batch, n_steps, epsilon, keep_rms, noise, counter))[0]
 
     @torch.no_grad()
