@@ -46,10 +46,16 @@ enum { OU_ACT_NONE = 0, OU_ACT_PRELU = 1, OU_ACT_SNAKE = 2, OU_ACT_SNAKEBETA = 3
 /* normalization_norm (utils/norm.py:31-44) for ou_set_normalization: 2 | "max" | "2-max" */
 enum { OU_NORM_2 = 0, OU_NORM_MAX = 1, OU_NORM_2MAX = 2 };
 
-#define OU_MAX_RATES 8
+#define OU_MAX_RATES 8 /* size of ou_net_config.rate_factors (the ABI's layout); a model may have at most 4, see below */
 
 /* One network's hyper-parameters == the constructor arguments of
- * ScoreNetwork (networks/universe/score.py:214-232) / ConditionerNetwork (condition.py:274-293). */
+ * ScoreNetwork (networks/universe/score.py:214-232) / ConditionerNetwork (condition.py:274-293).
+ * Accepted (ou_packed_bytes / ou_packer_create / ou_create answer OU_ENOTIMPL with a message naming the field otherwise):
+ *   n_rates 1 .. 4, every factor in [2, 8], prod(rate_factors) <= 496 with more than one factor; fb_kernel_size 1, 3, 5, 7;
+ *   n_channels even, <= 64, with n_channels * 2^n_rates / 2 (the GRU's hidden size) a multiple of 64; noise_cond_dim a
+ *   multiple of 64 in [64, 1024]; n_rff 1 .. 64 (random Fourier features); n_mels even, <= 256;
+ *   n_mel_oversample * prod(rate_factors) (= n_fft) <= 2048; rate_factors, n_channels, fb_kernel_size and extra_conv_block the
+ *   same in the score and the condition network. */
 typedef struct ou_net_config {
   int32_t n_rates;
   int32_t rate_factors[OU_MAX_RATES];

@@ -784,7 +784,8 @@ __global__ __launch_bounds__(64 * MT * NWN) void rate_down_kernel(ConvArgs p) {
       const float* xr = xb + (size_t)ci * Tin;
       if (ts >= 0 && ts + nwin <= Tin) {
         if (!fir) {
-          const f32x4 q = *reinterpret_cast<const f32x4*>(xr + ts);
+          // (dword-aligned type: ts is a multiple of 4, but a row starts at ci * Tin, 8 bytes off for odd ci when Tin % 4 == 2)
+          const f32x4 q = *reinterpret_cast<const f32x4u*>(xr + ts);
           v[u][0] = q.x; v[u][1] = q.y; v[u][2] = q.z; v[u][3] = q.w;
         } else {
 #pragma unroll

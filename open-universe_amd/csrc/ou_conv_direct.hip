@@ -172,6 +172,8 @@ struct DirectEpilogue {
         case 3: fir_up<3>(p, Es, tid, m0, n0, ybase, insc); break;
         case 4: fir_up<4>(p, Es, tid, m0, n0, ybase, insc); break;
         case 5: fir_up<5>(p, Es, tid, m0, n0, ybase, insc); break;
+        // (up == 8 and nothing else: plan_conv_direct gates the fused up-FIR form to up in {2, 3, 4, 5, 8}, so 6 and 7 never get
+        // here -- tests/test_gpu_offlist.py holds those layers on whatever family takes them instead)
         default: fir_up<8>(p, Es, tid, m0, n0, ybase, insc); break;
       }
       return;

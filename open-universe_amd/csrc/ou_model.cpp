@@ -174,21 +174,28 @@ std::string build_model(const ou_config& cfg, Model& m) {
   g_no_split = cfg.no_split_copy != 0;
   const ou_net_config& s = cfg.score;
   const ou_net_config& c = cfg.cond;
-  if (s.n_rates < 1 || s.n_rates > OU_MAX_RATES) return "bad n_rates";
-  if (c.n_rates != s.n_rates || c.n_channels != s.n_channels) return "score/cond topology mismatch";
+  // (the conditioner's encoder sum, sum_kernel, takes the mel block and four more operands: n - 1 st convs and the encoder's
+  // output -- a fifth rate factor used to pass here and fail in the walk with "too many encoder outputs")
+  constexpr int kMaxRatesWalk = 4;
+  static_assert(kMaxRatesWalk <= OU_MAX_RATES, "ou_net_config.rate_factors");
+  if (s.n_rates < 1 || s.n_rates > kMaxRatesWalk) return "n_rates (the number of rate_factors) must lie in [1," + std::to_string(kMaxRatesWalk) + "]";
+  if (c.n_rates != s.n_rates || c.n_channels != s.n_channels) return "score/cond mismatch: rate_factors (their number) and n_channels must be the same";
   for (int i = 0; i < s.n_rates; i++)
     if (c.rate_factors[i] != s.rate_factors[i] || s.rate_factors[i] < 2 || s.rate_factors[i] > 8)
       return "rate factors must match between score/cond and lie in [2,8]";
-  if (s.fb_kernel_size % 2 == 0 || s.fb_kernel_size > 7) return "fb_kernel_size must be odd and <= 7";
+  if (s.fb_kernel_size < 1 || s.fb_kernel_size % 2 == 0 || s.fb_kernel_size > 7) return "fb_kernel_size must be odd and <= 7";
   if (c.fb_kernel_size != s.fb_kernel_size) return "fb_kernel_size mismatch";
-  if (s.n_channels % 2 || s.n_channels > 64) return "n_channels must be even and <= 64";
-  if (s.noise_cond_dim % 64 || s.noise_cond_dim > 1024) return "noise_cond_dim must be a multiple of 64";
+  if (s.n_channels < 2 || s.n_channels % 2 || s.n_channels > 64) return "n_channels must be even and <= 64";
+  if (s.noise_cond_dim < 64 || s.noise_cond_dim % 64 || s.noise_cond_dim > 1024) return "noise_cond_dim must be a multiple of 64 in [64,1024]";
   if (!s.time_embedding_simple && (s.n_rff < 1 || s.n_rff > 64)) return "n_rff out of range";
   if (s.extra_conv_block != c.extra_conv_block) return "extra_conv_block mismatch";
 
   const int n = s.n_rates, C0 = s.n_channels;
   int tot = 1;
   for (int i = 0; i < n; i++) tot *= s.rate_factors[i];
+  // (s2d_kernel stages 32 quotients of R samples in LDS, R up to prod(rate_factors) for the first st conv: 33 R + 1 floats have
+  // to fit the 64 KiB a launch gets without asking for more)
+  if (n > 1 && 33 * tot + 1 > 16384) return "prod(rate_factors) = " + std::to_string(tot) + " must be <= 496 with more than one rate factor";
   m.tot_ds = tot;
   m.n_levels = n + 1;
   m.n_blocks = n + (s.extra_conv_block ? 1 : 0);
@@ -255,7 +262,9 @@ std::string build_model(const ou_config& cfg, Model& m) {
   m.mel.n_freq = m.mel.n_fft / 2 + 1;
   m.mel.n_mels = c.n_mels;
   m.mel.pad_left = (m.mel.n_fft - tot) / 2;
-  if (m.mel.n_fft > 2048 || c.n_mels > 256 || c.n_mels % 2) return "mel front-end size out of range";
+  if (c.n_mel_oversample < 1 || m.mel.n_fft > 2048)
+    return "mel front-end: n_fft = n_mel_oversample * prod(rate_factors) = " + std::to_string(m.mel.n_fft) + " must lie in [1,2048]";
+  if (c.n_mels < 2 || c.n_mels > 256 || c.n_mels % 2) return "mel front-end: n_mels must be even and <= 256";
   m.mel.win_off = a.take(m.mel.n_fft);
   m.mel.fb_off = a.take((size_t)m.mel.n_freq * c.n_mels);
   m.mel.tw_off = a.take((size_t)2 * m.mel.n_fft);

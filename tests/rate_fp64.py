@@ -54,8 +54,14 @@ one wrong FIR tap by a few u hides; a wrong halo frame, padding mode or phase or
 folded: one folded weight off by an ulp is invisible to the output bound (u sum |W| |a| is allowed for it) -- that is what the blob
 identity holds instead.
 
-Not reached by any seam: rate_up_kernel's scalar store loop (Tout % 4 != 0; padded lengths are multiples of tot_ds, itself a
-multiple of 4).  conv_direct_strided_kernel with folded weights (G = 3) is not built: folded layers run on the LDS kernel.
+Not reached by the shipped topologies: rate_up_kernel's scalar store loop (Tout % 4 != 0; padded lengths are multiples of tot_ds,
+itself a multiple of 4).  rate_down_kernel / rate_up_kernel are built for R = 2 at 32 -> 64 and 48 -> 96 channels only, so an
+odd tot_ds (no factor 2) or another width never reaches them: the loop runs in case r27 of tests/offlist_cases.py alone (rates
+[2, 7] at 32 channels, T = 14, 42, 182: 2 modulo 4), where tests/test_gpu_offlist.py asserts that both kernels took the outermost
+level of both networks -- with the FIR (score) and without (conditioner) -- and holds them with the bounds of this module; there
+rate_down_kernel's rows also start 8 bytes off a 16-byte boundary.  The other off-list models (tot_ds 21, 63; rate factors 6, 7)
+are held on whichever family takes their layers (tests/golden/offlist_variants.json).
+conv_direct_strided_kernel with folded weights (G = 3) is not built: folded layers run on the LDS kernel.
 
 No element is excluded: `excluded == 0` is asserted of every report.
 """

@@ -36,10 +36,13 @@ gru_tail_fill_kernel is held exactly by tests/test_gpu_gru_fp64.py
 places.  out_conv_kernel's OUT_UPDATE WITH the noise term is never a call's last step and earlier steps leave no taps: the same
 arithmetic is held through sampler_step_kernel.  init_x_kernel is held through score.in of a warm-started call (its x0 is
 overwritten by the update).
-Branches no public seam reaches: fir_kernel (the scalar form takes only tap counts without a fir4_kernel instantiation; the
-shipped topologies have 5, 7, 9, 11, 17, all instantiated), out_conv_kernel's scalar path (T % 4 != 0: padded lengths are
-multiples of tot_ds, itself a multiple of 4), in_conv_kernel / out_conv_kernel with KW > 3 (every shipped topology has
-fb_kernel_size 3), film_kernel with D / 64 != 8."""
+Branches the shipped topologies (the cases of this module) do not reach, and where they are held instead -- the off-list
+topologies of tests/offlist_cases.py, run by tests/test_gpu_offlist.py with the functions of this module: fir_kernel (the scalar
+form takes only tap counts without a fir4_kernel instantiation; shipped: 5, 7, 9, 11, 17, all instantiated) at 13 and 15 taps on
+both paths (cases r67, odd_pp, r27); out_conv_kernel's scalar path (T % 4 != 0) on whole rows of the models whose tot_ds is 21,
+63 and 14 (odd_pp with KW 5, odd_or, r27); in_conv_kernel / out_conv_kernel with KW 1, 5 and 7 (one, odd_pp, kw7), OUT_SCORE and OUT_UPDATE;
+film_kernel and sigma_embed_kernel with D / 64 = 1 and 16 (kw7, d1024) and the random-Fourier-feature MLP at n_rff 16 (odd_or);
+sum_kernel with 2, 3 and 4 operands (one, odd_pp, r67 / odd_or)."""
 import math
 
 import torch
