@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define OU_ABI_VERSION 7 /* 7: level normalisation modes (ou_set_normalization, OU_NORM_*: additive, the number stays -- a handle nobody sets is normalization_norm 2 with zero_mean, and ou_config is what it was); Snake activations of the ConvBlock body convs (ou_config tail score_enc_act .. cond_dec_act, OU_ACT_SNAKEBETA, ou_snake_act, ou_snake_tile: additive, the number stays -- a zeroed tail is the PReLU model); ensembles of segmented rows (ou_segments_ensemble_workspace_bytes, ou_enhance_segments_ensemble: additive, the number stays); segmented enhance of rows with lengths of their own (ou_segment_groups, ou_segments_var_workspace_bytes, ou_enhance_segments_var: additive, the number stays); ensembles in the library (ou_enhance_ensemble, ou_ensemble_workspace_bytes, ou_ensemble_reduce, ou_ensemble_reduce_scratch_bytes; option ens_share); existing entry points unchanged; 6: counter-based sampler noise (ou_set_noise_source, ou_noise_scratch_bytes, ou_noise_fill); existing entry points unchanged; 5: ou_enhance_var (batches whose rows have lengths of their own), workspace header carries the per-row geometry; ou_set_option / ou_get_option replace every OU_* environment switch (the library reads no environment variable), ou_config.fir_fold; 4: the packed blob carries a bf16-split weight copy (conv_split_kernel); 3: a Winograd-domain copy (round 5), ou_set_lane_batch, ou_lane_capacity */
+#define OU_ABI_VERSION 7 /* 7: the bottleneck of the score encoder (ou_config.score.seq_bottleneck, OU_SEQ_*, in the slot the score network never used: additive, the number stays and so does the size of ou_config -- 0 there is the plain GRU model, blob, plan and launches bit for bit); level normalisation modes (ou_set_normalization, OU_NORM_*: additive, the number stays -- a handle nobody sets is normalization_norm 2 with zero_mean, and ou_config is what it was); Snake activations of the ConvBlock body convs (ou_config tail score_enc_act .. cond_dec_act, OU_ACT_SNAKEBETA, ou_snake_act, ou_snake_tile: additive, the number stays -- a zeroed tail is the PReLU model); ensembles of segmented rows (ou_segments_ensemble_workspace_bytes, ou_enhance_segments_ensemble: additive, the number stays); segmented enhance of rows with lengths of their own (ou_segment_groups, ou_segments_var_workspace_bytes, ou_enhance_segments_var: additive, the number stays); ensembles in the library (ou_enhance_ensemble, ou_ensemble_workspace_bytes, ou_ensemble_reduce, ou_ensemble_reduce_scratch_bytes; option ens_share); existing entry points unchanged; 6: counter-based sampler noise (ou_set_noise_source, ou_noise_scratch_bytes, ou_noise_fill); existing entry points unchanged; 5: ou_enhance_var (batches whose rows have lengths of their own), workspace header carries the per-row geometry; ou_set_option / ou_get_option replace every OU_* environment switch (the library reads no environment variable), ou_config.fir_fold; 4: the packed blob carries a bf16-split weight copy (conv_split_kernel); 3: a Winograd-domain copy (round 5), ou_set_lane_batch, ou_lane_capacity */
 
 enum {
   OU_OK = 0,
@@ -43,6 +43,10 @@ enum { OU_KIND_UNIVERSE = 0, OU_KIND_UNIVERSE_GAN = 1 };
 enum { OU_ACT_NONE = 0, OU_ACT_PRELU = 1, OU_ACT_SNAKE = 2, OU_ACT_SNAKEBETA = 3 };
 /* act_type "none" in the four *_act fields at the end of ou_config, where 0 has to mean "not set" = PReLU */
 #define OU_ACT_IDENTITY (-1)
+/* ou_config.score.seq_bottleneck: seq_model / encoder_gru_conv_sandwich of ScoreNetwork */
+/* (1 is taken: a caller that filled `score` from its conditioner block left encoder_gru_residual = 1 there, which never meant
+ * anything and still means the plain GRU) */
+enum { OU_SEQ_GRU = 0, OU_SEQ_NONE = 2, OU_SEQ_GRU_SANDWICH = 3 };
 /* normalization_norm (utils/norm.py:31-44) for ou_set_normalization: 2 | "max" | "2-max" */
 enum { OU_NORM_2 = 0, OU_NORM_MAX = 1, OU_NORM_2MAX = 2 };
 
@@ -69,7 +73,17 @@ typedef struct ou_net_config {
   int32_t time_embedding_simple; /* 1: SimpleTimeEmbedding (sigma_block.py:60-78), 0: SigmaBlock RFF (:36-57) */
   int32_t n_mels;                /* conditioner only */
   int32_t n_mel_oversample;      /* conditioner only */
-  int32_t encoder_gru_residual;  /* conditioner only */
+  /* One slot, two readings.  ou_config.cond: encoder_gru_residual of ConditionerNetwork.  ou_config.score, where that argument does
+   * not exist and every caller so far left 0 (or 1, copied from its conditioner block; ignored then, the plain GRU now): what sits in the bottleneck of the score encoder (seq_model and
+   * encoder_gru_conv_sandwich of ScoreNetwork, score.py:32-36, 81-102, 113-123) -- OU_SEQ_GRU (0; also 1) the bidirectional GRU, OU_SEQ_NONE
+   * nothing at all (no GRU tensor of the score network is asked for or packed), OU_SEQ_GRU_SANDWICH a ConvBlock(oc) in front of
+   * that GRU and one behind it (encoder.conv_block1 / conv_block2; the reference knows the sandwich in its gru branch only, so
+   * there is no fourth state).  Any other value is OU_ENOTIMPL naming the field.  The plan and the blob depend on it: same value
+   * for the packer and ou_create.  sizeof(ou_config) is what it was. */
+  union {
+    int32_t encoder_gru_residual; /* conditioner */
+    int32_t seq_bottleneck;       /* score network: OU_SEQ_* */
+  };
 } ou_net_config;
 
 /* == config.model of the reference (the yaml files under config/model/), inference-relevant part;

@@ -19,6 +19,7 @@ OU_ACT_IDENTITY = -1  # act_type "none" in the four *_act fields of ou_config, w
 # normalization_norm -> the mode of ou_set_normalization
 OU_NORM_2, OU_NORM_MAX, OU_NORM_2MAX = 0, 1, 2
 NORM_MODES = {"2": OU_NORM_2, "max": OU_NORM_MAX, "2-max": OU_NORM_2MAX}
+OU_SEQ_GRU, OU_SEQ_NONE, OU_SEQ_GRU_SANDWICH = 0, 2, 3  # ou_config.score.seq_bottleneck (1: a legacy spelling of the plain GRU)
 BODY_ACTS = {"prelu": 0, "snake": OU_ACT_SNAKE, "snakebeta": OU_ACT_SNAKEBETA, "none": OU_ACT_IDENTITY}
 OU_ENH_KEEP_RMS, OU_ENH_USE_AUX_SIGNAL, OU_ENH_NO_PEAK_GUARD, OU_ENH_SERIAL = 1, 2, 4, 8
 OU_MAX_ENSEMBLE = 32
@@ -26,7 +27,13 @@ OU_ENS_MEAN, OU_ENS_MEDIAN, OU_ENS_SIGNAL_MEDIAN = 0, 1, 2
 ENSEMBLE_STATS = {"mean": OU_ENS_MEAN, "median": OU_ENS_MEDIAN, "signal_median": OU_ENS_SIGNAL_MEDIAN}
 
 
+class _NetConfigLast(ctypes.Union):
+    """The last slot of ou_net_config: encoder_gru_residual in ou_config.cond, seq_bottleneck (OU_SEQ_*) in ou_config.score."""
+    _fields_ = [("encoder_gru_residual", c_int32), ("seq_bottleneck", c_int32)]
+
+
 class NetConfig(Structure):
+    _anonymous_ = ("_last",)
     _fields_ = [
         ("n_rates", c_int32),
         ("rate_factors", c_int32 * OU_MAX_RATES),
@@ -40,7 +47,7 @@ class NetConfig(Structure):
         ("time_embedding_simple", c_int32),
         ("n_mels", c_int32),
         ("n_mel_oversample", c_int32),
-        ("encoder_gru_residual", c_int32),
+        ("_last", _NetConfigLast),
     ]
 
 
@@ -395,6 +402,12 @@ def make_config(spec, fir_fold=0, split_copy=True):
     cfg.score_dec_act = body_act(spec.score, "decoder_act_type")
     cfg.cond_enc_act = body_act(spec.cond, "encoder_act_type")
     cfg.cond_dec_act = body_act(spec.cond, "decoder_act_type")
+    # (ScoreNetwork has no encoder_gru_residual: in ou_config.score that slot says what sits in the encoder's bottleneck)
+    seq = getattr(spec.score, "seq_model", "gru")
+    if seq not in ("gru", "none"):
+        raise NotImplementedError(f"score_model.seq_model={seq!r}: gru | none")
+    sandwich = bool(getattr(spec.score, "encoder_gru_conv_sandwich", False))
+    cfg.score.seq_bottleneck = OU_SEQ_NONE if seq == "none" else OU_SEQ_GRU_SANDWICH if sandwich else OU_SEQ_GRU
     norm_args(spec)  # (an unknown norm is refused here, where every other key is; the values travel by ou_set_normalization)
     return cfg
 

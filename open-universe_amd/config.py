@@ -38,7 +38,10 @@ class NetSpec:
     use_weight_norm: bool = False
     use_antialiasing: bool = False
     time_embedding: Optional[str] = None
+    # score network only (score.py:81-102, 113-123): what sits in the encoder's bottleneck.  seq_model gru | none; the sandwich
+    # (a ConvBlock in front of the GRU and one behind it) exists in the gru branch alone and is ignored with none
     encoder_gru_conv_sandwich: bool = False
+    seq_model: str = "gru"
     # act_type of conv1 .. conv3 of every ConvBlock of the encoder / decoder half (score.py:223-224, condition.py:283-284,
     # blocks.py:176-187): prelu | snake | snakebeta | none
     encoder_act_type: str = "prelu"
@@ -144,8 +147,23 @@ def _net_spec(d, is_cond):
     for k in ("encoder_act_type", "decoder_act_type"):
         if kw.get(k, "prelu") not in ACT_TYPES:
             raise ValueError(f"{k}={kw[k]!r}: 'act_type' should be one of [{' | '.join(ACT_TYPES)}]")  # blocks.py:187
-    if d.get("seq_model", "gru") != "gru":
-        raise NotImplementedError("only seq_model=gru is supported (all shipped configs)")
+    seq = d.get("seq_model", "gru")
+    if seq is None:
+        seq = "gru"
+    if is_cond:
+        # condition.py refuses anything but gru with ValueError; so a `none` score model cannot hand its value on through the
+        # ${model.score_model.seq_model} interpolation of universe_original.yaml
+        if seq != "gru":
+            raise NotImplementedError(f"condition_model.seq_model={seq!r}: the conditioner runs seq_model=gru only (the reference "
+                                      "refuses every other value); a model with score_model.seq_model=none has to say "
+                                      "condition_model.seq_model: gru instead of interpolating the score network's value")
+    elif seq == "attention":
+        raise NotImplementedError("score_model.seq_model='attention': the reference has no such module (ScoreEncoder.forward "
+                                  "reads a self.att that nobody creates); gru | none")
+    elif seq not in ("gru", "none"):
+        raise ValueError(f"score_model.seq_model={seq!r}: Values for 'seq_model' can be gru|attention|none")  # score.py:102
+    kw["seq_model"] = str(seq)
+    kw["encoder_gru_conv_sandwich"] = bool(kw.get("encoder_gru_conv_sandwich", False)) and seq == "gru"
     if d.get("precoding"):
         raise NotImplementedError("precoding is not used by any shipped config")
     if is_cond and d.get("output_channels") is not None:

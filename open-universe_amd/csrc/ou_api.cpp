@@ -278,6 +278,7 @@ int ou_create(const ou_config* cfg, const void* weights_dev, size_t nbytes, int3
     const Model& m = h->m;
     for (auto& b : m.s_enc) addb(b);
     for (auto& b : m.s_dec) addb(b);
+    if (m.s_sandwich) { addb(m.s_cb1); addb(m.s_cb2); }
     addb(m.c_melblock);
     for (auto& b : m.c_enc) addb(b);
     for (auto& l : m.c_st) all.push_back(&l);
@@ -484,7 +485,9 @@ int ou_bench_conv(ou_handle* h, const char* layer, int32_t B, int32_t Tin, int32
   for (auto& b : m.s_enc) addb(b);
   for (auto& b : m.s_dec) addb(b);
   for (auto& l : m.s_sig) all.push_back(&l);
-  all.push_back(&m.s_gru.proj); all.push_back(&m.c_melconv); addb(m.c_melblock);
+  if (m.s_has_gru) all.push_back(&m.s_gru.proj);
+  if (m.s_sandwich) { addb(m.s_cb1); addb(m.s_cb2); }
+  all.push_back(&m.c_melconv); addb(m.c_melblock);
   for (auto& b : m.c_enc) addb(b);
   for (auto& l : m.c_st) all.push_back(&l);
   all.push_back(&m.c_gru0.proj); all.push_back(&m.c_gru1.proj);

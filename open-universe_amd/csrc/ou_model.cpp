@@ -170,6 +170,9 @@ std::string build_model(const ou_config& cfg, Model& m) {
   for (int v : {cfg.score_enc_act, cfg.score_dec_act, cfg.cond_enc_act, cfg.cond_dec_act})
     if (v != 0 && v != OU_ACT_PRELU && v != OU_ACT_SNAKE && v != OU_ACT_SNAKEBETA && v != OU_ACT_IDENTITY)
       return "ou_config.*_act must be 0, OU_ACT_PRELU, OU_ACT_SNAKE, OU_ACT_SNAKEBETA or OU_ACT_IDENTITY";
+  // (1: encoder_gru_residual copied over from a conditioner block, which the score network always ignored: the plain GRU)
+  if (cfg.score.seq_bottleneck < 0 || cfg.score.seq_bottleneck > OU_SEQ_GRU_SANDWICH)
+    return "ou_config.score.seq_bottleneck must be OU_SEQ_GRU (0), OU_SEQ_NONE (2) or OU_SEQ_GRU_SANDWICH (3)";
   g_fir_fold = cfg.fir_fold;
   g_no_split = cfg.no_split_copy != 0;
   const ou_net_config& s = cfg.score;
@@ -235,7 +238,15 @@ std::string build_model(const ou_config& cfg, Model& m) {
     m.film.enc_off.push_back(frow);
     frow += 2 * C;
   }
-  if (!(e = make_gru(m.s_gru, a, sp + ".encoder.gru", 0, OC, OC / 2)).empty()) return e;
+  // score.py:81-102: the GRU, and -- sandwich -- a ConvBlock(oc) on either side of it; a model with 0 there takes
+  // exactly the slots it always took
+  m.s_has_gru = s.seq_bottleneck != OU_SEQ_NONE;  // (0, 1 and OU_SEQ_GRU_SANDWICH)
+  m.s_sandwich = s.seq_bottleneck == OU_SEQ_GRU_SANDWICH;
+  if (m.s_has_gru && !(e = make_gru(m.s_gru, a, sp + ".encoder.gru", 0, OC, OC / 2)).empty()) return e;
+  if (m.s_sandwich) {
+    if (!(e = make_block(m.s_cb1, a, sp + ".encoder.conv_block1", OC, 0, 1, false, cfg.score_enc_act)).empty()) return e;
+    if (!(e = make_block(m.s_cb2, a, sp + ".encoder.conv_block2", OC, 0, 1, false, cfg.score_enc_act)).empty()) return e;
+  }
   m.s_dec.resize(m.n_blocks);
   m.s_sig.resize(m.n_blocks);
   for (int j = 0; j < m.n_blocks; j++) {
@@ -313,6 +324,7 @@ std::string build_model(const ou_config& cfg, Model& m) {
   {
     std::vector<BlockL*> blocks;
     for (auto& b : m.s_enc) blocks.push_back(&b);
+    if (m.s_sandwich) { blocks.push_back(&m.s_cb1); blocks.push_back(&m.s_cb2); }
     for (auto& b : m.s_dec) blocks.push_back(&b);
     for (auto& b : m.c_enc) blocks.push_back(&b);
     blocks.push_back(&m.c_cb1); blocks.push_back(&m.c_cb2); blocks.push_back(&m.c_decin);
@@ -331,10 +343,15 @@ std::string build_model(const ou_config& cfg, Model& m) {
   std::ostringstream os;
   os << "{\"total_floats\":" << m.total_floats << ",\"tot_ds\":" << m.tot_ds << ",\"film_rows\":" << m.film.rows
      << ",\"film_w_off\":" << m.film.w_off << ",\"film_b_off\":" << m.film.b_off << ",\"n_snake\":" << m.n_snake
-     << ",\"snake_up_off\":" << m.snake_up_off << ",\"snake_down_off\":" << m.snake_down_off << ",\n\"convs\":[\n";
+     << ",\"snake_up_off\":" << m.snake_up_off << ",\"snake_down_off\":" << m.snake_down_off;
+  // (only a model with another bottleneck than the plain GRU says so: the plan of every other model is the text it always was)
+  if (!m.s_has_gru || m.s_sandwich)
+    os << ",\"score_seq_model\":\"" << (m.s_has_gru ? "gru" : "none") << "\",\"score_gru_sandwich\":" << (m.s_sandwich ? 1 : 0);
+  os << ",\n\"convs\":[\n";
   bool first = true;
   for (auto& b : m.s_enc) json_block(os, b, first);
-  json_conv(os, m.s_gru.proj, first);
+  if (m.s_has_gru) json_conv(os, m.s_gru.proj, first);
+  if (m.s_sandwich) { json_block(os, m.s_cb1, first); json_block(os, m.s_cb2, first); }
   for (auto& b : m.s_dec) json_block(os, b, first);
   for (auto& l : m.s_sig) json_conv(os, l, first);
   json_conv(os, m.c_melconv, first);
@@ -727,7 +744,8 @@ std::string pack_weights(const Model& m, const std::map<std::string, HostTensor>
   }
   P.pack_small_in(m.s_in, false);
   for (auto& b : m.s_enc) P.pack_block(b);
-  P.pack_gru(m.s_gru);
+  if (m.s_has_gru) P.pack_gru(m.s_gru);
+  if (m.s_sandwich) { P.pack_block(m.s_cb1); P.pack_block(m.s_cb2); }
   for (auto& b : m.s_dec) P.pack_block(b);
   for (auto& l : m.s_sig) P.pack_conv(l);
   // FiLM projections: encoder.cond_proj.i / decoder.noise_cond_proj.j (Linear D -> 2C, maybe weight-normed)

@@ -131,6 +131,10 @@ struct Model {
   std::vector<ConvL> s_sig;  // signal_cond_proj 1x1
   FilmL film;
   GruL s_gru;
+  // the bottleneck of the score encoder (score.py:81-102): ou_config.score.seq_bottleneck.  s_has_gru false: no
+  // s_gru (OU_SEQ_NONE); s_sandwich: s_cb1 in front of the GRU and s_cb2 behind it (encoder.conv_block1 / conv_block2)
+  bool s_has_gru = true, s_sandwich = false;
+  BlockL s_cb1, s_cb2;
   // conditioner
   MelL mel;
   ConvL c_melconv;

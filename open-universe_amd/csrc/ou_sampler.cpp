@@ -284,7 +284,7 @@ int enhance_impl(ou_handle* h, const float* mix, float* out, const float* noise,
     // (only when two GRU layers fit on the machine side by side: their clusters spin on each other's publishes and must
     // all be resident)
     const int share2 = Runner::gru_share_of(h->lanes, B, true);
-    const bool gru_fit = gru_ring_batch_cap(m.s_gru.H, h->num_cu, share2, 0, B, h->lanes) >= 1 &&
+    const bool gru_fit = (!m.s_has_gru || gru_ring_batch_cap(m.s_gru.H, h->num_cu, share2, 0, B, h->lanes) >= 1) &&
                          gru_ring_batch_cap(m.c_gru0.H, h->num_cu, share2, 0, B, h->lanes) >= 1;
     if (warm_start < 0 && h->overlap && gru_fit) {
       r.gru_shared = true;

@@ -362,7 +362,8 @@ Persist layout_persist(Runner& r, int T) {
   P.rows = (RowInfo*)r.alloc_raw((size_t)r.B * 4);
   P.lens = (int*)r.alloc_raw((size_t)r.B * kMaxLenLevels);
   P.xchg = (unsigned long long*)r.alloc_raw(gru_granules(r.B, m.OC / 2) * 2);
-  P.xchg2 = (unsigned long long*)r.alloc_raw(gru_granules(r.B, m.OC / 2) * 2);
+  // (a score network without a GRU, OU_SEQ_NONE, has no second exchange area)
+  P.xchg2 = m.s_has_gru ? (unsigned long long*)r.alloc_raw(gru_granules(r.B, m.OC / 2) * 2) : nullptr;
   r.h->tensors["mel_scale"] = TensorRef{r.off, 1, 1};  // (B, 1, 1): the conditioner's mel normalisation of each row
   P.mel_scale = r.alloc_raw(r.B);
   r.h->tensors["sigma.g"] = TensorRef{r.off, m.film.D, 1};  // (B, D, 1): the noise-level embedding of the first B coefficient rows
@@ -487,10 +488,18 @@ ScoreEnc run_score_enc(Runner& r, Persist& P, const float* x, const StepCoef* co
     E.residuals.push_back(bo.v);
     hcur = bo.h_next;
   }
-  // GRU bottleneck; when decoder block 0 has no rate change its residual add (blocks.py:374-376) is fused here
-  E.fuse_res = m.s_dec[0].dir == 0;
+  // The bottleneck (score.py:113-123).  Plain GRU model: when decoder block 0 has no rate change its residual add
+  // (blocks.py:374-376) is fused into the GRU's epilogue.  Sandwich (conv_block1 -> GRU -> conv_block2): that add belongs behind
+  // conv_block2, and with seq_model none there is no GRU to carry it: decoder block 0 then takes the residual itself
+  // (run_score_dec), as the models without extra_conv_block do.
+  E.fuse_res = m.s_has_gru && !m.s_sandwich && m.s_dec[0].dir == 0;
+  if (!m.s_has_gru) { E.hg = hcur; return E; }
+  // (conv_block1 is masked like any block; conv_block2 reads exact zeros behind a row's own end: Runner::gru masks what the
+  // tail fill left there, as between cond.gru and cond.cb2)
+  if (m.s_sandwich) hcur = r.block(m.s_cb1, hcur, "score.cb1", nullptr, 0, nullptr, nullptr).v;
   E.hg = r.gru(m.s_gru, hcur, "score.gru", P.xchg2, P.status, P.status + 4,
                E.fuse_res && !r.dry ? E.residuals[m.n_blocks - 1].p : nullptr, kInvSqrt2, pre_gru);
+  if (m.s_sandwich) E.hg = r.block(m.s_cb2, E.hg, "score.cb2", nullptr, 0, nullptr, nullptr).v;
   return E;
 }
 void run_score_dec(Runner& r, Persist& P, const ScoreEnc& E, const float* x, const float* noise, float* out, int mode,
@@ -502,6 +511,17 @@ void run_score_dec(Runner& r, Persist& P, const ScoreEnc& E, const float* x, con
     const float* fr = film_row ? film_row + m.film.dec_off[j] : nullptr;
     const Tensor& res = E.residuals[m.n_blocks - 1 - j];
     const float* resp = (j == 0 && E.fuse_res) ? nullptr : res.p;
+    if (!(j == 0 && E.fuse_res) && m.s_dec[j].dir == 0) {  // (not `resp`: a dry walk has no pointers, and has to see the plane)
+      // a block without a rate change has no up conv whose epilogue could add its residual (up_path), and here no GRU took it
+      // either (sandwich, seq_model none): (y + res) / sqrt(2) as one sum_kernel pass over OC x T / tot_ds.  Both operands are
+      // zero behind a ragged row's end, so the sum is.
+      const Tensor in0 = r.alloc("score.dec" + std::to_string(j) + ".in", y.C, y.T);
+      r.launch("dec res", [&] {
+        return launch_sum(y.p, res.p, nullptr, nullptr, nullptr, kInvSqrt2, in0.p, (size_t)r.B * y.C * y.T, r.st);
+      });
+      y = in0;
+      resp = nullptr;
+    }
     auto bo = r.block(m.s_dec[j], y, "score.dec" + std::to_string(j), fr, film_bs, P.sc[j].p, resp);
     y = bo.v;
   }
@@ -510,7 +530,11 @@ void run_score_dec(Runner& r, Persist& P, const ScoreEnc& E, const float* x, con
                            m.cfg.has_edm, mode, r.B, m.C0, T, m.s_out.KW, r.st, ln);
   });
 }
-static bool m_blocks_ok(const Runner& r) { return r.h->m.n_blocks >= 1 && r.h->m.s_dec[0].dir == 0; }
+// (the plain GRU model only: with the sandwich conv_block2 sits between the GRU and decoder block 0, with none there is no GRU)
+static bool m_blocks_ok(const Runner& r) {
+  const Model& m = r.h->m;
+  return m.n_blocks >= 1 && m.s_dec[0].dir == 0 && m.s_has_gru && !m.s_sandwich;
+}
 void run_score(Runner& r, Persist& P, const float* x, const float* noise, float* out, int mode,
                const StepCoef* coef, int coef_bs, const float* film_row, int film_bs, int T) {
   // OU_DBG_DEC0=1 -- MEASUREMENT ONLY, RESULTS INVALID: the first decoder block is launched on a side stream that waits for

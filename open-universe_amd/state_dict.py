@@ -110,7 +110,13 @@ def score_schema(p: str, s: NetSpec) -> List[Entry]:
         out += _linear(f"{p}.encoder.cond_proj.{i}", c0 * 2 ** (i + 1), D, wn)
     if s.extra_conv_block:
         out += _linear(f"{p}.encoder.cond_proj.{n}", 2 * oc, D, wn)
-    out += _gru(p + ".encoder.gru", oc, oc // 2, 1)
+    # score.py:81-102: seq_model gru registers the GRU, then -- encoder_gru_conv_sandwich -- conv_block1 and conv_block2 (plain
+    # ConvBlock(oc): no rate change, no anti-aliasing); seq_model none registers nothing
+    if getattr(s, "seq_model", "gru") == "gru":
+        out += _gru(p + ".encoder.gru", oc, oc // 2, 1)
+        if getattr(s, "encoder_gru_conv_sandwich", False):
+            out += _conv_block(p + ".encoder.conv_block1", oc, wn, act=ea)
+            out += _conv_block(p + ".encoder.conv_block2", oc, wn, act=ea)
     chans = [c0 * 2 ** (n - i - 1) for i in range(n)]
     up = rates[::-1]
     blocks = ([(oc, None, "none")] if s.extra_conv_block else []) + [(c, r, "up") for c, r in zip(chans, up)]
