@@ -553,6 +553,56 @@ int ou_snake_act(const float* x, float* y, int32_t B, int32_t C, int32_t T, int6
 /* Consecutive outputs of one (row, channel) that one workgroup of ou_snake_act owns (tests sit on its edges). */
 int32_t ou_snake_tile(void);
 
+/* ---- scoring: how close an estimate is to a reference, for batches whose rows have lengths of their own ------------------
+ * The four scores of the reference's inference tooling that are arithmetic on two waveforms: the log-spectral distance and its
+ * scale-invariant form (metrics/lsd.py as metrics/wrapper.py:130-153 calls it), SI-SDR (wrapper.py:197-213), the plain SNR
+ * beside it, and the time-domain + multi-resolution spectral L1 (losses/multires_stft.py).  Stateless: no handle.
+ *   est, ref : (B, stride) device; row b holds len[b] samples of each, nothing behind them is read
+ *   len_host : B entries on the HOST, 1 <= len[b] <= min(stride, 2^31 - 1)
+ *   out      : B floats on the device, one score per row
+ *   scratch  : device, at least ou_metrics_scratch_bytes(B, longest len, the call's specs) bytes (OU_ESHAPE otherwise); no
+ *              contents are kept between calls
+ * Every row is scored as if it were alone at its own length: its frame count is ou_metrics_frames(len[b], hop), its own last
+ * sample is the reflection point of the centred STFT, and the result is bit for bit that of a B = 1 call on the row.  Sums
+ * run in one fixed order (no atomics): two runs of a call are bit-identical.
+ * The STFT is centred, one-sided (n_fft / 2 + 1 bins), with the periodic Hann window of n_fft points (win_length = n_fft);
+ * the DFT is a product with a cos / sin basis on the matrix pipe, in double (window, basis and sums; the samples are the
+ * caller's fp32).  No spectrogram is
+ * stored.  n_fft must be even, at least 2 and at most OU_METRICS_MAX_NFFT: a workgroup keeps 16 frames of both
+ * signals, 128 * n_fft bytes, in the 160 KiB of LDS.  hop >= 1.  Anything else: OU_EINVAL with a message, decided on the host
+ * before the first HIP call, like every other refusal below.  Enqueued on `stream`: no allocation, no host synchronisation. */
+#define OU_METRICS_MAX_NFFT 1024
+#define OU_METRICS_MAX_SPECS 8
+#define OU_MET_SCALE_INVARIANT 1 /* rescale by alpha = sum(est ref) / (sum(est^2) + eps) first (lsd.py:95-98, multires_stft.py:97-100) */
+#define OU_MET_NATURAL_LOG 2     /* ou_lsd: ln instead of 10 log10 (`db = False`) */
+typedef struct ou_metrics_spec {
+  int32_t n_fft, hop;
+  float eps;     /* ou_lsd: inside the logarithm and in alpha.  Not read by ou_spectral_mae */
+  int32_t flags; /* ou_lsd: OU_MET_*.  Not read by ou_spectral_mae */
+} ou_metrics_spec;
+/* 1 + T / hop: the frames of the centred STFT of T samples (n_fft even); -1 for T < 0 or hop < 1 */
+int64_t ou_metrics_frames(int64_t T, int32_t hop);
+/* Scratch of a call with B rows, the longest T_max samples, and these resolutions (n_spec = 0: ou_si_sdr). */
+int ou_metrics_scratch_bytes(int32_t B, int64_t T_max, const ou_metrics_spec* spec, int32_t n_spec, size_t* nbytes);
+/* Log-spectral distance, p = 2:  with X, Y the STFTs of est and alpha * ref (reflect padding), W = sum of window^2,
+ *     out[b] = sqrt(mean over frames and bins of (L(|X|^2 / W + eps) - L(|Y|^2 / W + eps))^2),   L = 10 log10 (or ln)
+ * OU_EINVAL also for len[b] <= n_fft / 2, where the reflect padding is undefined. */
+int ou_lsd(const float* est, const float* ref, int64_t stride, const int64_t* len_host, int32_t B, const ou_metrics_spec* spec,
+           float* out, void* scratch, size_t scratch_bytes, ou_stream_t stream);
+/* out[b] = w * mean_t |alpha est - ref| + (1 - w) / n_spec * sum over specs of mean over frames and bins of | |X| - |Y| |,
+ * X, Y the STFTs of alpha * est and ref with zero padding, w = time_domain_weight; n_spec = 0: the time-domain mean alone.
+ * flags: OU_MET_SCALE_INVARIANT or 0; eps is the one in alpha. */
+int ou_spectral_mae(const float* est, const float* ref, int64_t stride, const int64_t* len_host, int32_t B,
+                   const ou_metrics_spec* spec, int32_t n_spec, float time_domain_weight, float eps, int32_t flags, float* out,
+                   void* scratch, size_t scratch_bytes, ou_stream_t stream);
+/* With c = (sum est ref)^2 / (sum est^2 * sum ref^2) for out_si_sdr (no mean removed) and c = sum ref^2 / (sum ref^2 +
+ * sum (est - ref)^2) for out_snr, both 0 where the denominator is 0, and e = 10^(-clamp_db / 10) / (1 + 10^(-clamp_db / 10)):
+ *     out = 10 log10(c' / (1 - c')),   c' = min(max(c, e), 1 - e)
+ * i.e. the ratio clamped to [-clamp_db, clamp_db] (the reference passes 100).  The sums are taken in double.  Either output
+ * may be NULL.  OU_EINVAL for a clamp_db that is not positive and finite. */
+int ou_si_sdr(const float* est, const float* ref, int64_t stride, const int64_t* len_host, int32_t B, float clamp_db,
+              float* out_si_sdr, float* out_snr, void* scratch, size_t scratch_bytes, ou_stream_t stream);
+
 /* ---- level normalisation: normalization_norm and normalization_kwargs.zero_mean / .eps of the model yaml (utils/norm.py:22-87):
  * how every enhance entry point (ou_enhance, _var, _ensemble, the four ou_enhance_segments*) levels a row before the networks
  * see it.  With m the mean of the padded row, sd its unbiased std (around m) and mx = max |x - mu| over the padded row,

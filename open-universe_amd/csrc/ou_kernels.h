@@ -465,4 +465,37 @@ hipError_t launch_snake_act(const float* x, float* y, int B, int C, int T, long 
                             const SnakeRows* rows, const float* exp_alpha, const float* exp_beta, const float* up_k,
                             const float* down_k, hipStream_t st);
 
+// Scoring (ou_metrics.hip; "scoring" in include/ouniverse.h).  Rows of lengths of their own travel as kernel arguments, 64 per
+// launch; row0 is the first row of the launch in the call's batch (scratch and results are indexed by row0 + b).
+constexpr int kMetRowsPerLaunch = 64;
+constexpr int kMetMaxNfft = 1024;  // = OU_METRICS_MAX_NFFT: 32 frames x n_fft floats of LDS
+constexpr int kMetMaxSpecs = 8;    // = OU_METRICS_MAX_SPECS
+struct MetRows {
+  long long len[kMetRowsPerLaunch];
+};
+struct MetSpecs {  // what met_final_l1_kernel needs of every resolution: partial + offset[i] is (B, tile_stride[i]) doubles
+  int n;
+  int hop[kMetMaxSpecs], nbins[kMetMaxSpecs];
+  long long offset[kMetMaxSpecs], tile_stride[kMetMaxSpecs];
+};
+inline int met_k4(int n_fft) { return (n_fft + 3) / 4; }                   // k-steps of 4
+inline int met_bin_tiles(int n_fft) { return (n_fft / 2 + 1 + 15) / 16; }  // 16-bin tiles (the last one partial)
+inline long long met_frame_tiles(long long len, int hop) { return (1 + len / hop + 15) / 16; }
+inline size_t met_basis_words(int n_fft) { return (size_t)met_bin_tiles(n_fft) * 2 * met_k4(n_fft) * 64; }
+hipError_t launch_met_time(const float* est, const float* ref, long long stride, const MetRows& rows, int n_rows, int row0,
+                           float eps, bool scale_invariant, double* tsum, hipStream_t st);
+// basis: met_basis_words(n_fft) doubles, window: 4 * met_k4(n_fft) doubles
+hipError_t launch_met_basis(double* basis, double* window, int n_fft, hipStream_t st);
+// tsum: 8 doubles per row (sum xy, x^2, y^2, (x - y)^2, |alpha x - y|, alpha, -, -), written by launch_met_time.
+// l1: | |alpha X| - |Y| | with zero padding; else the squared log-spectral difference with reflect padding.  w2 = sum of window^2
+hipError_t launch_met_stft(bool l1, const float* est, const float* ref, long long stride, const MetRows& rows, int n_rows, int row0,
+                           long long len_max, const double* basis, const double* window, const double* tsum, int n_fft, int hop,
+                           double w2, float eps, bool natural_log, double* partial, long long tile_stride, hipStream_t st);
+hipError_t launch_met_final_lsd(const MetRows& rows, int n_rows, int row0, const double* partial, long long tile_stride, int hop,
+                                int n_fft, float* out, hipStream_t st);
+hipError_t launch_met_final_l1(const MetRows& rows, int n_rows, int row0, const double* partial, const MetSpecs& specs,
+                               const double* tsum, float tdw, float* out, hipStream_t st);
+hipError_t launch_met_final_sdr(int n_rows, int row0, const double* tsum, float clamp_db, float* out_si_sdr, float* out_snr,
+                                hipStream_t st);
+
 }  // namespace ou

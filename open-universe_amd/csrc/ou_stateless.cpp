@@ -1,4 +1,4 @@
-// Entry points that take no handle: the STFT pair, the resampler (plan, table, call) and the Snake activation.
+// Entry points that take no handle: the STFT pair, the resampler (plan, table, call), the Snake activation and the scores.
 #include <cmath>
 #include <string>
 #include <vector>
@@ -230,6 +230,233 @@ int ou_snake_act(const float* x, float* y, int32_t B, int32_t C, int32_t T, int6
     const hipError_t e = launch_snake_act(x + skip, y + skip, n, C, T, row_stride, nullptr, &blk, exp_alpha, exp_beta, up_kernel,
                                           down_kernel, (hipStream_t)stream);
     if (e != hipSuccess) return fail(nullptr, OU_EHIP, std::string("ou_snake_act: ") + hipGetErrorString(e));
+  }
+  return OU_OK;
+}
+
+}  // extern "C"
+
+// ---- scoring: ou_lsd, ou_spectral_mae, ou_si_sdr (include/ouniverse.h, "scoring"; kernels: ou_metrics.hip) -------------------
+namespace {
+constexpr long long kMetMaxLen = 0x7fffffffll;
+inline size_t met_align(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// scratch of one call: | tsum (B, 8) double | window | basis (the largest n_fft) | partial of every spec |
+struct MetLayout {
+  size_t tsum = 0, window = 0, basis = 0, bytes = 0;
+  size_t partial[kMetMaxSpecs] = {};
+  long long tile_stride[kMetMaxSpecs] = {};
+};
+
+// the message of a bad spec, or empty
+std::string met_spec_error(const ou_metrics_spec& s) {
+  if (s.n_fft < 2 || (s.n_fft & 1))
+    return "n_fft = " + std::to_string(s.n_fft) + " must be even and at least 2";
+  if (s.n_fft > OU_METRICS_MAX_NFFT)
+    return "n_fft = " + std::to_string(s.n_fft) + " exceeds OU_METRICS_MAX_NFFT = " + std::to_string(OU_METRICS_MAX_NFFT) +
+           " (the 32 frames of a workgroup are kept in LDS)";
+  if (s.hop < 1) return "hop = " + std::to_string(s.hop) + " must be at least 1";
+  return std::string();
+}
+
+MetLayout met_layout(int B, long long T_max, const ou_metrics_spec* spec, int n_spec) {
+  MetLayout L;
+  size_t at = 0;
+  L.tsum = at; at = met_align(at + (size_t)B * 8 * sizeof(double));
+  int nmax = 0;
+  for (int i = 0; i < n_spec; i++) nmax = spec[i].n_fft > nmax ? spec[i].n_fft : nmax;
+  L.window = at; at = met_align(at + (size_t)4 * met_k4(nmax) * sizeof(double));
+  L.basis = at; at = met_align(at + (nmax ? met_basis_words(nmax) : 0) * sizeof(double));
+  for (int i = 0; i < n_spec; i++) {
+    L.tile_stride[i] = met_frame_tiles(T_max, spec[i].hop);
+    L.partial[i] = at; at = met_align(at + (size_t)B * (size_t)L.tile_stride[i] * sizeof(double));
+  }
+  L.bytes = at;
+  return L;
+}
+
+// sum of the squares of the periodic Hann window
+double met_window_power(int n_fft) {
+  double s = 0.0;
+  for (int k = 0; k < n_fft; k++) {
+    const double w = 0.5 - 0.5 * std::cos(2.0 * M_PI * (double)k / (double)n_fft);
+    s += w * w;
+  }
+  return s;
+}
+
+// the checks every score shares; len_max <- the longest row
+int met_check_rows(const char* who, const float* est, const float* ref, int64_t stride, const int64_t* len_host, int32_t B,
+                   long long* len_max) {
+  const std::string w(who);
+  if (!est || !ref || !len_host) return fail(nullptr, OU_EINVAL, w + ": null argument");
+  if (B < 1) return fail(nullptr, OU_EINVAL, w + ": B must be at least 1");
+  if (stride < 1 || (long long)stride > (1ll << 60) / B)
+    return fail(nullptr, OU_EINVAL, w + ": stride must be at least 1 and B * stride at most 2^60");
+  long long mx = 0;
+  for (int b = 0; b < B; b++) {
+    const long long n = len_host[b];
+    if (n < 1 || n > stride || n > kMetMaxLen)
+      return fail(nullptr, OU_EINVAL, w + ": 1 <= len[" + std::to_string(b) + "] <= min(stride, 2^31 - 1), got " + std::to_string(n));
+    mx = n > mx ? n : mx;
+  }
+  *len_max = mx;
+  return OU_OK;
+}
+
+inline void met_rows_of(const int64_t* len_host, int B, int off, MetRows& rows, int& n, long long& len_max) {
+  n = B - off < kMetRowsPerLaunch ? B - off : kMetRowsPerLaunch;
+  len_max = 0;
+  for (int i = 0; i < kMetRowsPerLaunch; i++) {
+    rows.len[i] = i < n ? len_host[off + i] : 0;
+    len_max = rows.len[i] > len_max ? rows.len[i] : len_max;
+  }
+}
+
+inline int met_hip(const char* who, hipError_t e) {
+  return e == hipSuccess ? OU_OK : fail(nullptr, OU_EHIP, std::string(who) + ": " + hipGetErrorString(e));
+}
+}  // namespace
+
+extern "C" {
+
+int64_t ou_metrics_frames(int64_t T, int32_t hop) {
+  if (T < 0 || hop < 1) return -1;
+  return 1 + T / hop;
+}
+
+int ou_metrics_scratch_bytes(int32_t B, int64_t T_max, const ou_metrics_spec* spec, int32_t n_spec, size_t* nbytes) {
+  if (!nbytes || B < 1 || T_max < 1 || T_max > kMetMaxLen || n_spec < 0 || n_spec > OU_METRICS_MAX_SPECS || (n_spec && !spec))
+    return fail(nullptr, OU_EINVAL, "ou_metrics_scratch_bytes: B >= 1, 1 <= T_max <= 2^31 - 1, 0 <= n_spec <= OU_METRICS_MAX_SPECS");
+  for (int i = 0; i < n_spec; i++) {
+    const std::string m = met_spec_error(spec[i]);
+    if (!m.empty()) return fail(nullptr, OU_EINVAL, "ou_metrics_scratch_bytes: spec " + std::to_string(i) + ": " + m);
+  }
+  *nbytes = met_layout(B, T_max, spec, n_spec).bytes;
+  return OU_OK;
+}
+
+int ou_lsd(const float* est, const float* ref, int64_t stride, const int64_t* len_host, int32_t B, const ou_metrics_spec* spec,
+           float* out, void* scratch, size_t scratch_bytes, ou_stream_t stream) {
+  long long len_max = 0;
+  if (int rc = met_check_rows("ou_lsd", est, ref, stride, len_host, B, &len_max)) return rc;
+  if (!spec || !out || !scratch) return fail(nullptr, OU_EINVAL, "ou_lsd: null argument");
+  const std::string m = met_spec_error(*spec);
+  if (!m.empty()) return fail(nullptr, OU_EINVAL, "ou_lsd: " + m);
+  if (spec->flags & ~(OU_MET_SCALE_INVARIANT | OU_MET_NATURAL_LOG)) return fail(nullptr, OU_EINVAL, "ou_lsd: unknown flag");
+  if (!(spec->eps >= 0.0f)) return fail(nullptr, OU_EINVAL, "ou_lsd: eps must not be negative");
+  for (int b = 0; b < B; b++)
+    if (len_host[b] <= spec->n_fft / 2)
+      return fail(nullptr, OU_EINVAL, "ou_lsd: len[" + std::to_string(b) + "] = " + std::to_string((long long)len_host[b]) +
+                                          " must exceed n_fft / 2 = " + std::to_string(spec->n_fft / 2) +
+                                          " (the reflect padding of the centred STFT is undefined otherwise)");
+  const MetLayout L = met_layout(B, len_max, spec, 1);
+  if (scratch_bytes < L.bytes)
+    return fail(nullptr, OU_ESHAPE, "ou_lsd: scratch of " + std::to_string(scratch_bytes) + " bytes, ou_metrics_scratch_bytes asks for " +
+                                        std::to_string(L.bytes));
+  char* base = static_cast<char*>(scratch);
+  double* tsum = reinterpret_cast<double*>(base + L.tsum);
+  double* window = reinterpret_cast<double*>(base + L.window);
+  double* basis = reinterpret_cast<double*>(base + L.basis);
+  double* partial = reinterpret_cast<double*>(base + L.partial[0]);
+  const hipStream_t st = (hipStream_t)stream;
+  const bool si = spec->flags & OU_MET_SCALE_INVARIANT;
+  if (int rc = met_hip("ou_lsd", launch_met_basis(basis, window, spec->n_fft, st))) return rc;
+  const double w2 = met_window_power(spec->n_fft);
+  for (int off = 0; off < B; off += kMetRowsPerLaunch) {
+    MetRows rows;
+    int n;
+    long long lm;
+    met_rows_of(len_host, B, off, rows, n, lm);
+    if (int rc = met_hip("ou_lsd", launch_met_time(est, ref, stride, rows, n, off, spec->eps, si, tsum, st))) return rc;
+    if (int rc = met_hip("ou_lsd", launch_met_stft(false, est, ref, stride, rows, n, off, lm, basis, window, tsum, spec->n_fft,
+                                                   spec->hop, w2, spec->eps, spec->flags & OU_MET_NATURAL_LOG, partial,
+                                                   L.tile_stride[0], st)))
+      return rc;
+    if (int rc = met_hip("ou_lsd", launch_met_final_lsd(rows, n, off, partial, L.tile_stride[0], spec->hop, spec->n_fft, out, st)))
+      return rc;
+  }
+  return OU_OK;
+}
+
+int ou_spectral_mae(const float* est, const float* ref, int64_t stride, const int64_t* len_host, int32_t B,
+                   const ou_metrics_spec* spec, int32_t n_spec, float time_domain_weight, float eps, int32_t flags, float* out,
+                   void* scratch, size_t scratch_bytes, ou_stream_t stream) {
+  long long len_max = 0;
+  if (int rc = met_check_rows("ou_spectral_mae", est, ref, stride, len_host, B, &len_max)) return rc;
+  if (!out || !scratch || (n_spec && !spec)) return fail(nullptr, OU_EINVAL, "ou_spectral_mae: null argument");
+  if (n_spec < 0 || n_spec > OU_METRICS_MAX_SPECS)
+    return fail(nullptr, OU_EINVAL, "ou_spectral_mae: 0 <= n_spec <= OU_METRICS_MAX_SPECS = " + std::to_string(OU_METRICS_MAX_SPECS));
+  for (int i = 0; i < n_spec; i++) {
+    const std::string m = met_spec_error(spec[i]);
+    if (!m.empty()) return fail(nullptr, OU_EINVAL, "ou_spectral_mae: spec " + std::to_string(i) + ": " + m);
+  }
+  if (flags & ~OU_MET_SCALE_INVARIANT) return fail(nullptr, OU_EINVAL, "ou_spectral_mae: the only flag is OU_MET_SCALE_INVARIANT");
+  if (!(eps >= 0.0f) || !std::isfinite(time_domain_weight))
+    return fail(nullptr, OU_EINVAL, "ou_spectral_mae: eps must not be negative and time_domain_weight must be finite");
+  const MetLayout L = met_layout(B, len_max, spec, n_spec);
+  if (scratch_bytes < L.bytes)
+    return fail(nullptr, OU_ESHAPE, "ou_spectral_mae: scratch of " + std::to_string(scratch_bytes) +
+                                        " bytes, ou_metrics_scratch_bytes asks for " + std::to_string(L.bytes));
+  char* base = static_cast<char*>(scratch);
+  double* tsum = reinterpret_cast<double*>(base + L.tsum);
+  double* window = reinterpret_cast<double*>(base + L.window);
+  double* basis = reinterpret_cast<double*>(base + L.basis);
+  double* partial = reinterpret_cast<double*>(base);  // (MetSpecs.offset counts doubles from here)
+  const hipStream_t st = (hipStream_t)stream;
+  MetSpecs specs;
+  specs.n = n_spec;
+  for (int i = 0; i < kMetMaxSpecs; i++) {
+    specs.hop[i] = i < n_spec ? spec[i].hop : 1;
+    specs.nbins[i] = i < n_spec ? spec[i].n_fft / 2 + 1 : 1;
+    specs.offset[i] = i < n_spec ? (long long)(L.partial[i] / sizeof(double)) : 0;
+    specs.tile_stride[i] = L.tile_stride[i];
+  }
+  std::vector<MetRows> rows((size_t)(B + kMetRowsPerLaunch - 1) / kMetRowsPerLaunch);
+  std::vector<int> cnt(rows.size());
+  std::vector<long long> lm(rows.size());
+  for (size_t c = 0; c < rows.size(); c++) {
+    met_rows_of(len_host, B, (int)c * kMetRowsPerLaunch, rows[c], cnt[c], lm[c]);
+    if (int rc = met_hip("ou_spectral_mae", launch_met_time(est, ref, stride, rows[c], cnt[c], (int)c * kMetRowsPerLaunch, eps,
+                                                           flags & OU_MET_SCALE_INVARIANT, tsum, st)))
+      return rc;
+  }
+  for (int i = 0; i < n_spec; i++) {  // one basis at a time in the same words: the stream orders build, use, rebuild
+    if (int rc = met_hip("ou_spectral_mae", launch_met_basis(basis, window, spec[i].n_fft, st))) return rc;
+    for (size_t c = 0; c < rows.size(); c++)
+      if (int rc = met_hip("ou_spectral_mae",
+                           launch_met_stft(true, est, ref, stride, rows[c], cnt[c], (int)c * kMetRowsPerLaunch, lm[c], basis, window,
+                                           tsum, spec[i].n_fft, spec[i].hop, 1.0, 0.0f, false, partial + specs.offset[i],
+                                           L.tile_stride[i], st)))
+        return rc;
+  }
+  for (size_t c = 0; c < rows.size(); c++)
+    if (int rc = met_hip("ou_spectral_mae", launch_met_final_l1(rows[c], cnt[c], (int)c * kMetRowsPerLaunch, partial, specs, tsum,
+                                                               time_domain_weight, out, st)))
+      return rc;
+  return OU_OK;
+}
+
+int ou_si_sdr(const float* est, const float* ref, int64_t stride, const int64_t* len_host, int32_t B, float clamp_db,
+              float* out_si_sdr, float* out_snr, void* scratch, size_t scratch_bytes, ou_stream_t stream) {
+  long long len_max = 0;
+  if (int rc = met_check_rows("ou_si_sdr", est, ref, stride, len_host, B, &len_max)) return rc;
+  if (!scratch || (!out_si_sdr && !out_snr)) return fail(nullptr, OU_EINVAL, "ou_si_sdr: null argument");
+  if (!(clamp_db > 0.0f) || !std::isfinite(clamp_db)) return fail(nullptr, OU_EINVAL, "ou_si_sdr: clamp_db must be positive and finite");
+  const MetLayout L = met_layout(B, len_max, nullptr, 0);
+  if (scratch_bytes < L.bytes)
+    return fail(nullptr, OU_ESHAPE, "ou_si_sdr: scratch of " + std::to_string(scratch_bytes) +
+                                        " bytes, ou_metrics_scratch_bytes asks for " + std::to_string(L.bytes));
+  char* base = static_cast<char*>(scratch);
+  double* tsum = reinterpret_cast<double*>(base + L.tsum);
+  const hipStream_t st = (hipStream_t)stream;
+  for (int off = 0; off < B; off += kMetRowsPerLaunch) {
+    MetRows rows;
+    int n;
+    long long lm;
+    met_rows_of(len_host, B, off, rows, n, lm);
+    if (int rc = met_hip("ou_si_sdr", launch_met_time(est, ref, stride, rows, n, off, 0.0f, false, tsum, st))) return rc;
+    if (int rc = met_hip("ou_si_sdr", launch_met_final_sdr(n, off, tsum, clamp_db, out_si_sdr, out_snr, st))) return rc;
   }
   return OU_OK;
 }
