@@ -10,7 +10,17 @@ profiles/metrics_observed.json is a committed copy.
 
 Lengths: 201 = the shortest the reflect padding allows at n_fft 400 (2 frames: a frame tile of two); 479 / 480 / 481 around
 3 hops (480: 4 frames, the last one centred on the sample behind the row); 16000: 101 frames = 6 tiles of 16 and a last tile of
-ONE frame; 201 bins = 12 tiles of 16 and a tile of 9."""
+FIVE frames; 201 bins = 12 tiles of 16 and a tile of 9.
+
+The shapes of test_g / test_h / test_i reach what those lengths and n_fft 400 / 600 / 64 / 256 / 512 do not: n_fft % 4 == 2
+(Kpad != n_fft: the zero words of the frames, window and basis behind n_fft are live), n_fft / 4 rounded up = 1, 2, 3 mod 4
+(the remainder loop behind the 4-deep MFMA pipeline), n_fft 2 (one k-step, two bins) and 1024 (the cap: all of the dynamic
+LDS), hop 1, a hop above n_fft, hops that do not divide n_fft, rows of exactly 16 and 17 frames (a full frame tile; a full tile
+and a tile of one), and 130 rows in one call (launches of 64, 64 and 2 rows, the longest row in the last one).
+
+Measured on an MI355X (profiles/metrics_observed.json, `worst_ratio` = err / max(|f32 - f64|, 1 ulp), gate 4): test_g 0.025 ..
+0.483 (worst: LSD at n_fft 1022), test_h 0.338 and 0.324, test_i 0.141 .. 0.498 (worst: the L1 of row 63), every one of the
+130 rows equal to the row scored alone -- no higher than the 0.5 of the shapes above."""
 import json
 import os
 import statistics
@@ -60,16 +70,22 @@ def pairs():
     return R.signals(LENGTHS, seed=0)
 
 
+def _pack_nan(prs):
+    """Pairs as a ragged batch on the device: one (B, stride) buffer each, filled with NaN behind every row -> (x, y, lengths)"""
+    lens = [e.shape[0] for e, _ in prs]
+    stride = max(lens) + 4
+    x = torch.full((len(prs), stride), float("nan"), device=DEV)
+    y = torch.full((len(prs), stride), float("nan"), device=DEV)
+    for b, (e, r) in enumerate(prs):
+        x[b, :e.shape[0]] = e.to(DEV)
+        y[b, :r.shape[0]] = r.to(DEV)
+    return x, y, lens
+
+
 @pytest.fixture(scope="module")
 def ragged(pairs):
     """The ragged batch on the device: rows of LENGTHS in one (B, stride) buffer filled with NaN behind every row."""
-    stride = max(LENGTHS) + 4
-    x = torch.full((len(pairs), stride), float("nan"), device=DEV)
-    y = torch.full((len(pairs), stride), float("nan"), device=DEV)
-    for b, (e, r) in enumerate(pairs):
-        x[b, :e.shape[0]] = e.to(DEV)
-        y[b, :r.shape[0]] = r.to(DEV)
-    return x, y, list(LENGTHS)
+    return _pack_nan(pairs)
 
 
 def _lsd_case(case, pairs, ragged, n_fft, hop, eps, si, db, keep=lambda T: True):
@@ -180,6 +196,95 @@ def test_evaluate_many_and_metrics_agree(pairs):
         assert m(16000, est[b], ref[b]) == many[b]  # one pair alone: padded to the longer, scored the same, bit for bit
     two = M.Metrics(metrics=["si-sdr", "lsd"])(16000, torch.stack([est[5], est[5]]), torch.stack([pairs[5][1].to(DEV)] * 2))
     assert len(two) == 2 and two[0] == two[1] and list(two[0]) == ["si-sdr", "lsd"]
+
+
+# (n_fft, hop): n_fft / 4 rounded up = 1, 2, 8, 101, 256, 256, 101, 103, 16; 2, 6, 30, 402 and 1022 leave zero words behind n_fft
+G_SHAPES = [(2, 1), (6, 1), (30, 7), (402, 160), (1022, 256), (1024, 256), (404, 101), (412, 103), (64, 100)]
+
+
+def _shape_lengths(n_fft, hop):
+    """Ragged rows for one (n_fft, hop), every one above n_fft / 2: the shortest the reflect padding allows, exactly 16 frames,
+    exactly 17 frames, and a few hops."""
+    lens = [n_fft // 2 + 1, 15 * hop + hop // 2, 16 * hop, max(3 * hop + 1, n_fft // 2 + 3)]
+    assert M.frames(lens[1], hop) == 16 and M.frames(lens[2], hop) == 17 and min(lens) > n_fft // 2
+    return lens
+
+
+@pytest.mark.parametrize("si", [False, True])
+@pytest.mark.parametrize("n_fft,hop", G_SHAPES)
+def test_g_lsd_at_the_edges_of_the_accepted_resolutions(n_fft, hop, si):
+    prs = R.signals(_shape_lengths(n_fft, hop), seed=10 + n_fft)
+    lib = _lsd_case(f"g_{'si_' if si else ''}lsd_{n_fft}_{hop}", prs, _pack_nan(prs), n_fft, hop, 1e-7, si, True)
+    assert torch.isfinite(lib).all()
+
+
+H_WINDOWS, H_HOPS = [2, 30, 1022, 1024], [1, 7, 256, 300]  # 7 does not divide 30, 256 not 1022, 300 not 1024
+H_LENGTHS = (300, 1022, 4001)  # 300: shorter than half the largest window
+
+
+@pytest.mark.parametrize("si", [False, True])
+def test_h_multires_l1_smallest_and_largest_windows(si):
+    prs = R.signals(H_LENGTHS, seed=4)
+    x, y, lens = _pack_nan(prs)
+    lib = M._l1_rows(x, y, lens, H_WINDOWS, H_HOPS, 1e-8, 0.5, si).cpu()
+    rows = []
+    for b, (e, r) in enumerate(prs):
+        f64 = R.spectral_l1(e, r, H_WINDOWS, H_HOPS, 1e-8, 0.5, si, torch.float64)
+        f32 = R.spectral_l1(e, r, H_WINDOWS, H_HOPS, 1e-8, 0.5, si, torch.float32)
+        rows.append((f"T={lens[b]}", lib[b], f64, f32))
+    _gate(f"h_l1_2_30_1022_1024_si{int(si)}", rows)
+
+
+I_ROWS, I_GATED = 130, (0, 63, 64, 127, 128, 129)
+I_LSD = (400, 43)  # hop 43: the rows of the first launch have one frame tile, the longest row of the call two
+I_L1_HOPS = [43, 128, 1]  # of L1_WINDOWS; hop 1 at 512: 43 frame tiles in the first launch, 44 in the call
+
+
+@pytest.fixture(scope="module")
+def many():
+    """130 rows in one call (launches of 64, 64 and 2 rows): lengths drawn from 201 ... 700, the longest row moved into the last
+    launch and the shortest into the first, so the launches' grids differ from one another and from the call's tile stride."""
+    lens = torch.randint(201, 701, (I_ROWS,), generator=torch.Generator().manual_seed(5)).tolist()
+    i = lens.index(max(lens))
+    lens[i], lens[I_ROWS - 1] = lens[I_ROWS - 1], lens[i]
+    i = lens.index(min(lens))
+    lens[i], lens[0] = lens[0], lens[i]
+    tiles = lambda T, hop: (M.frames(T, hop) + 15) // 16
+    for hop in (I_LSD[1], I_L1_HOPS[0], I_L1_HOPS[2]):
+        assert tiles(max(lens[:64]), hop) < tiles(max(lens[128:]), hop) == tiles(max(lens), hop)
+    assert min(lens[:64]) == min(lens) and min(lens) > I_LSD[0] // 2
+    prs = R.signals(lens, seed=3)
+    return prs, _pack_nan(prs)
+
+
+_I_CALLS = {
+    "lsd": lambda x, y, l: M._lsd_rows(x, y, l, I_LSD[0], I_LSD[1], 1e-7, False, True),
+    "si-lsd": lambda x, y, l: M._lsd_rows(x, y, l, I_LSD[0], I_LSD[1], 1e-7, True, True),
+    "l1": lambda x, y, l: M._l1_rows(x, y, l, L1_WINDOWS, I_L1_HOPS, 1e-8, 0.5, True),
+    "si-sdr": lambda x, y, l: M._sdr_rows(x, y, l, 100.0)[0],
+    "snr": lambda x, y, l: M._sdr_rows(x, y, l, 100.0)[1],
+}
+_I_REFS = {
+    "lsd": lambda e, r, dt: R.lsd(e, r, I_LSD[0], I_LSD[1], 1e-7, False, True, dt),
+    "si-lsd": lambda e, r, dt: R.lsd(e, r, I_LSD[0], I_LSD[1], 1e-7, True, True, dt),
+    "l1": lambda e, r, dt: R.spectral_l1(e, r, L1_WINDOWS, I_L1_HOPS, 1e-8, 0.5, True, dt),
+    "si-sdr": lambda e, r, dt: R.si_sdr(e, r, 100.0, dt),
+    "snr": lambda e, r, dt: R.snr(e, r, 100.0, dt),
+}
+
+
+@pytest.mark.parametrize("name", list(_I_CALLS))
+def test_i_130_rows_in_one_call_equal_every_row_alone(many, name):
+    prs, (x, y, lens) = many
+    call = _I_CALLS[name]
+    whole = call(x, y, lens)
+    alone = torch.cat([call(e.to(DEV)[None], r.to(DEV)[None], [lens[b]]) for b, (e, r) in enumerate(prs)])
+    whole, alone = whole.cpu(), alone.cpu()
+    _gate(f"i_130_rows_{name}", [(f"row {b} T={lens[b]}", whole[b], _I_REFS[name](*prs[b], torch.float64),
+                                  _I_REFS[name](*prs[b], torch.float32)) for b in I_GATED])
+    assert torch.isfinite(whole).all()  # NaN behind every row's len: never read
+    differ = [(b, lens[b], float(whole[b]), float(alone[b])) for b in range(I_ROWS) if whole[b] != alone[b]]
+    assert not differ, (name, differ[:8])  # every row = the same row alone, bit for bit
 
 
 def _median_ms(fn, warmup=3, reps=15):

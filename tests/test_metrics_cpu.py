@@ -22,6 +22,17 @@ def test_frames_match_torch_stft(built_lib, T):
     assert built_lib.ou_metrics_frames(T, 0) == -1 and built_lib.ou_metrics_frames(-1, 160) == -1
 
 
+@pytest.mark.parametrize("n_fft,hop", [(2, 1), (6, 1), (30, 7), (402, 160), (1022, 256), (1024, 256), (404, 101), (412, 103),
+                                       (64, 100), (1024, 300), (400, 43), (512, 1)])
+def test_edge_resolutions_are_accepted_and_frames_match_torch_stft(built_lib, n_fft, hop):
+    """The resolutions test_gpu_metrics.py adds (test_g / test_h / test_i), at rows of 16 and 17 frames and the shortest row."""
+    assert M.scratch_bytes(130, 16 * hop, [_lib.MetricsSpec(n_fft, hop, 0.0, 0)]) > M.scratch_bytes(130, 16 * hop)
+    for T in (n_fft // 2 + 1, 15 * hop + hop // 2, 16 * hop):
+        spec = torch.stft(torch.zeros(T), n_fft, hop_length=hop, window=torch.hann_window(n_fft), center=True,
+                          pad_mode="constant", return_complex=True)
+        assert M.frames(T, hop) == spec.shape[-1]
+
+
 def test_symbols_are_bound(built_lib):
     for name in ("ou_metrics_frames", "ou_metrics_scratch_bytes", "ou_lsd", "ou_spectral_mae", "ou_si_sdr"):
         assert name in _lib.EXPORTED_SYMBOLS and hasattr(built_lib, name)
