@@ -365,7 +365,8 @@ def norm_args(spec):
     eps = float(spec.norm_eps)
     if not eps > 0.0:
         raise ValueError(f"normalization_kwargs.eps={eps!r} must be positive")
-    return NORM_MODES[norm], 1 if spec.zero_mean else 0, 0.0 if eps == 1e-5 else eps
+    # utils/norm.py:31-39 hands eps to the 2-max branch alone: the other two are sent 0 (= their 1e-5) whatever the key says
+    return NORM_MODES[norm], 1 if spec.zero_mean else 0, eps if norm == "2-max" and eps != 1e-5 else 0.0
 
 
 def make_config(spec, fir_fold=0, split_copy=True):

@@ -1,18 +1,22 @@
 """
 Golden vectors of the REAL reference for models with another level normalisation than every shipped config's
-(normalization_norm max | 2-max, normalization_kwargs.zero_mean false: utils/norm.py:22-87).  Needs the reference checkout
-(oracle/ref_import.py); run on a CPU, no GPU test uses this script:
+(normalization_norm max | 2-max, normalization_kwargs.zero_mean false, normalization_kwargs.eps: utils/norm.py:22-87).  Needs
+the reference checkout (oracle/ref_import.py); run on a CPU, no GPU test uses this script:
 
-    python tests/golden/make_golden_norm.py
+    python tests/golden/make_golden_norm.py [mode ...]      (no mode: every mode of tests/norm_cases.py)
 
-Writes norm_<model>_<mode>.npz per case of tests/norm_cases.py (PP16s and OR16s x max | 2max | keepmean; seeded synthetic
-weights), 3 steps, fixed noise planes:
+Writes norm_<model>_<mode>.npz per case of tests/norm_cases.py (PP16s and OR16s x max | 2max | keepmean | max_keepmean |
+2max_keepmean | 2max_eps; seeded synthetic weights), 3 steps, fixed noise planes:
     mix, noise, enh                  a batch of two rows of a ragged length (T % tot_ds != 0) on a DC offset: row 0 smooth (2-max
-                                     takes its std branch), row 1 with one spike of crest factor > 1 / level (its max branch)
+                                     takes its std branch), row 1 with one spike of crest factor > 1 / level (its max branch);
+                                     2max_eps (eps = 1e-3): a third, quiet row (sd about 1e-4, maximum about 4e-4) whose gain
+                                     the key decides -- level / eps where eps = 1e-5 would give 1 / mx
     norm_mean, norm_std              what the reference's normalize_batch returns for the padded batch (mean, 1 / gain)
     noise_warm, enh_warm             PP16s: the same batch with warm_start = 1
     mix_f<i>, noise_f<i>, enh_f<i>, norm_mean_f<i>, norm_std_f<i>    three files of different lengths, each enhanced ALONE
     self_db                          SI-SDR of the reference in fp32 against the reference in float64 on the batch
+The quiet row stays in the 2max_eps batch: on it too the reference agrees with its own float64 evaluation well above the 60 dB
+floor of the tests (asserted row by row below; printed).
 """
 import os
 import sys
@@ -56,13 +60,17 @@ def reference_stats(m, mix):
     return mean.reshape(-1).numpy().astype(np.float32), std.reshape(-1).numpy().astype(np.float32)
 
 
-def main():
+def main(modes=()):
     for model, mode in K.CASES:
+        if modes and mode not in modes:
+            continue
         m = reference_model(model, mode)
         spec = K.spec_of(model, mode)
         td = spec.tot_ds
         out = {}
-        mix = K.batch_mix(spec)
+        mix = K.batch_mix(spec, mode)
+        rows = K.batch_rows(mode)
+        assert mix.shape[0] == rows and (spec.norm, spec.zero_mean, spec.norm_eps) == K.MODE_ARGS[mode]
         T = mix.shape[-1]
         Tp = T + (td - T % td)
         # which branch of 2-max each row takes (float64): the smooth row its std, the spiked row its max
@@ -70,12 +78,15 @@ def main():
             st = K.norm_stats(K.padded(mix[b], td), "2-max", spec.level_db)
             assert st["branch"] == want, (b, st)
             assert (st["mx"] / st["sd"] > K.crest_needed(spec.level_db)) == (want == "max")
-        nz = K.noise_planes(K.NOISE_SEED, K.N_STEPS, K.B, Tp)
+        if mode == "2max_eps":  # the quiet row: both norms between 1e-5 and eps
+            st = K.norm_stats(K.padded(mix[2], td), "2-max", spec.level_db, True, spec.norm_eps)
+            assert 1e-5 < st["sd"] < st["mx"] < spec.norm_eps and st["gain"] == st["level"] / spec.norm_eps, st
+        nz = K.noise_planes(K.NOISE_SEED, K.N_STEPS, rows, Tp)
         out["mix"], out["noise"] = mix.numpy(), torch.stack(nz).numpy()
         out["enh"] = enhance_with_noise(m, mix, nz, n_steps=K.N_STEPS).numpy()
         out["norm_mean"], out["norm_std"] = reference_stats(m, mix)
         if model == "PP16s":
-            nzw = K.noise_planes(K.NOISE_SEED + 100, K.N_STEPS - 1, K.B, Tp)
+            nzw = K.noise_planes(K.NOISE_SEED + 100, K.N_STEPS - 1, rows, Tp)
             out["noise_warm"] = torch.stack(nzw).numpy()
             out["enh_warm"] = enhance_with_noise(m, mix, nzw, n_steps=K.N_STEPS, warm_start=1).numpy()
         for i, L in enumerate(K.FILE_LENGTHS):
@@ -89,12 +100,15 @@ def main():
         e64 = enhance_with_noise(m.double(), mix.double(), [z.double() for z in nz], n_steps=K.N_STEPS)
         out["self_db"] = float(si_sdr(e64.float(), torch.from_numpy(out["enh"])))
         assert out["self_db"] > 80.0, (model, mode, out["self_db"])
+        per_row = [float(si_sdr(e64[b].float(), torch.from_numpy(out["enh"])[b])) for b in range(rows)]
+        assert min(per_row) > 80.0, (model, mode, per_row)
         np.savez_compressed(K.golden_path(model, mode), **out)
         size = os.path.getsize(K.golden_path(model, mode))
         assert size < 1 << 20, size
-        print(model, mode, "self_db %.1f" % out["self_db"], "std", out["norm_std"], "mean", out["norm_mean"], size, "bytes")
+        print(model, mode, "self_db %.1f" % out["self_db"], "per row", ["%.1f" % v for v in per_row], "std", out["norm_std"], "mean",
+              out["norm_mean"], size, "bytes")
 
 
 if __name__ == "__main__":
     torch.set_num_threads(8)
-    main()
+    main(tuple(sys.argv[1:]))

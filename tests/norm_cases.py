@@ -18,11 +18,17 @@ MODES = {
     "max": {"normalization_norm": "max"},
     "2max": {"normalization_norm": "2-max"},
     "keepmean": {"normalization_norm": 2, "normalization_kwargs.zero_mean": False},
+    "max_keepmean": {"normalization_norm": "max", "normalization_kwargs.zero_mean": False},
+    "2max_keepmean": {"normalization_norm": "2-max", "normalization_kwargs.zero_mean": False},
+    "2max_eps": {"normalization_norm": "2-max", "normalization_kwargs.eps": 1e-3},
 }
+# mode -> (norm, zero_mean, eps) as ModelSpec holds them
+MODE_ARGS = {"max": ("max", True, 1e-5), "2max": ("2-max", True, 1e-5), "keepmean": ("2", False, 1e-5),
+             "max_keepmean": ("max", False, 1e-5), "2max_keepmean": ("2-max", False, 1e-5), "2max_eps": ("2-max", True, 1e-3)}
 CASES = [(m, mode) for m in MODELS for mode in MODES]
 SEED = 0          # of the synthetic weights
 N_STEPS = 3
-B = 2
+B = 2             # rows of the batch; 2max_eps has a third, the quiet row (batch_rows)
 FILE_LENGTHS = (2731, 1600, 977)  # a ragged length, a multiple of tot_ds, a short one; file 1 carries the spike
 NOISE_SEED = 41
 DC = 0.02         # offset of every input: what zero_mean false leaves in the row
@@ -70,12 +76,28 @@ def with_spike(x, at):
     return x
 
 
-def batch_mix(spec):
-    """(B, T): row 0 smooth (2-max takes its std branch), row 1 with one spike (2-max takes its max branch), both on a DC offset."""
+def batch_rows(mode):
+    return B + 1 if mode == "2max_eps" else B
+
+
+def batch_mix(spec, mode=None):
+    """(B, T): row 0 smooth (2-max takes its std branch), row 1 with one spike (2-max takes its max branch), both on a DC offset.
+    Mode 2max_eps: a third row, the quiet one (quiet_row: sd above 1e-5, mx below the mode's eps 1e-3 -- the row on which
+    normalization_kwargs.eps decides the gain)."""
     T = batch_length(spec)
     mix = synth_mix(spec, B, T) + DC
     mix[1] = with_spike(mix[1], T // 3)
+    if mode == "2max_eps":
+        mix = torch.cat([mix, quiet_row(spec, T)[None, :]])
     return mix
+
+
+QUIET = 2e-3      # scale of the quiet row: synth_mix has sd 0.05 and peak 0.2 -> sd about 1e-4, mx about 4e-4
+
+
+def quiet_row(spec, T, seed=77):
+    """A smooth row without offset whose sd lies above the 1e-5 clamp and whose maximum below an eps of 1e-3."""
+    return synth_mix(spec, 1, T, seed=seed)[0] * QUIET
 
 
 def file_mix(spec, i):
@@ -163,6 +185,63 @@ def gain32(norm, level_db, sd32, mx32, eps=1e-5):
     if norm == "2-max":
         return min(level / max(f(sd32), f(eps)), f(1) / max(f(mx32), f(eps)))
     return level / max(f(sd32), f(1e-5))
+
+
+def undetermined(st, norm, rho, eps=1e-5):
+    """Why rounding, not the input, would decide the gain of the row with the float64 statistics `st` (norm_stats) on a device
+    that forms them within the relative `rho` of stats_bounds -- or None.  A norm within rho of its clamp (1e-5; eps under
+    2-max) may or may not be clamped; under 2-max two candidate gains within rho of each other leave the branch open."""
+    c = eps if norm == "2-max" else 1e-5
+    if norm in ("2", "2-max") and abs(st["sd"] - c) <= rho * c:
+        return f"sd {st['sd']!r} within {rho:.2e} of its clamp {c!r}"
+    if norm in ("max", "2-max") and abs(st["mx"] - c) <= rho * c:
+        return f"mx {st['mx']!r} within {rho:.2e} of its clamp {c!r}"
+    if norm == "2-max":
+        g2, gm = st["level"] / max(st["sd"], eps), 1.0 / max(st["mx"], eps)
+        if abs(g2 - gm) <= rho * max(g2, gm):
+            return f"level / sd = {g2!r} and 1 / mx = {gm!r} within {rho:.2e} of each other"
+    return None
+
+
+# ---- the rows the element tests hold (tests/test_norm_cpu.py, tests/test_gpu_norm_fp64.py) ---------------------------------------
+ALL_MODES = [(n, z) for n in ("2", "max", "2-max") for z in (True, False)]   # every (norm, zero_mean) of ou_set_normalization
+ROW_KINDS = ("smooth", "spike0", "spike_last", "spike_1029", "zero", "const", "quiet")
+EDGE = 1024 + 5   # the third spike: past the first 1024 samples, thread 5's second sample
+
+
+def mode_overrides(model, norm, zero_mean, eps=None):
+    ov = dict(SMALL[model][1], **{"normalization_norm": int(norm) if norm == "2" else norm,
+                                   "normalization_kwargs.zero_mean": bool(zero_mean)})
+    if eps is not None:
+        ov["normalization_kwargs.eps"] = eps
+    return ov
+
+
+def mode_spec(model, norm, zero_mean, eps=None):
+    return C.spec_from_config(C.builtin_config(SMALL[model][0], **mode_overrides(model, norm, zero_mean, eps)))
+
+
+def lengths(td):
+    """pad_normalize_kernel's register window from one sample to its end (65 536), the first length of its loops, and both
+    sides of a multiple of tot_ds."""
+    return {"1": 1, "td-1": td - 1, "td": td, "td+1": td + 1, "65536": 65536, "65537": 65537}
+
+
+def element_rows(spec, T):
+    """{kind: row (T,)} of the kinds that exist at T samples: a smooth row on the DC offset; that row with the spike at the
+    first sample, the last, and past the 1024th (needs T > 1029; a spike needs a standard deviation to be measured in: T > 3);
+    all zero; the constant DC alone; the quiet row."""
+    base = synth_mix(spec, 1, T, seed=77)[0] + DC
+    rows = {"smooth": base}
+    if T > 3:
+        rows["spike0"] = with_spike(base, 0)
+        rows["spike_last"] = with_spike(base, T - 1)
+    if T > EDGE:
+        rows["spike_1029"] = with_spike(base, EDGE)
+    rows["zero"] = torch.zeros(T)
+    rows["const"] = torch.full((T,), DC)
+    rows["quiet"] = quiet_row(spec, T)
+    return rows
 
 
 def crest_needed(level_db):

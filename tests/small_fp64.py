@@ -398,14 +398,47 @@ def mel_scale(mel_tap, n_frames=None):
 
 
 # ---- statistics kernels ----------------------------------------------------------------------------------------------------
-def pad_normalize(mix, t_raw, T_pad_max, level, tot_ds, dtype=torch.float64, std_den_off=1):
+def norm_gain(level, sd, mx, norm, eps, dtype):
+    """NormMode::gain (ou_kernels.h) of the unclamped 0-d tensors sd and mx, every operation once in `dtype`."""
+    c = lambda v: torch.tensor(v, dtype=torch.float64).to(dtype)
+    level = level.to(dtype)
+    if norm == "max":
+        return level / torch.maximum(mx, c(1e-5))
+    if norm == "2-max":
+        return torch.minimum(level / torch.maximum(sd, c(eps)), c(1.0) / torch.maximum(mx, c(eps)))
+    return level / torch.maximum(sd, c(1e-5))
+
+
+def pad_normalize(mix, t_raw, T_pad_max, level, tot_ds, dtype=torch.float64, std_den_off=1, norm="2", zero_mean=True, eps=1e-5):
     """pad_normalize_kernel / pad_normalize_var_kernel.  Row b: T_pad = t_raw + (tot_ds - t_raw % tot_ds), the samples at
     pad_left = (T_pad - t_raw) / 2, y = (x_padded - mean) * level / sd with mean over the PADDED signal and the unbiased sd
     (T_pad - 1) of it; zero from T_pad on (ragged batches).
     Device: sums in double (n 2^-53: negligible against u), mean rounded to fp32 (|d mean| <= u |mean|), d = fl(x - mean_f)
     (u |d|), sd from the d's in double: by the triangle inequality in l2 its relative error is at most u + u |mean| / sd
     sqrt(N / (N - 1)); then (float) sd, gain = fl(level / sd): rho = (3 u + 1.01 u |mean| / sd); y = fl(d * gain):
-    |y - ref| <= G (u |mean| + |x - mean| (u + rho)) + 1/2 ulp(y),  G = level / sd."""
+    |y - ref| <= G (u |mean| + |x - mean| (u + rho)) + 1/2 ulp(y),  G = level / sd.
+
+    The other modes (NormMode, ou_kernels.h; `norm` "2" | "max" | "2-max", `zero_mean`, `eps` of the 2-max branch), as
+    norm_cases.norm_stats states utils/norm.py: mu = mean if zero_mean else 0; sd unbiased around the row's own mean whatever
+    zero_mean says; mx = max |x_padded - mu|; G = NormMode::gain(level, sd, mx); y = (x_padded - mu) G.  The same three
+    sources of error, with rho the relative error of the device's gain as norm_cases.stats_bounds derives it:
+      unclamped std branch   rho = rho_sd (there with one more u for fl(level), which this function is handed exactly: kept)
+      max branch             rho = rho_max: the fp32 maximum of the d's is one of them (u, and the mean's u |mean| / mx), the
+                             division u
+      a clamp in force       the gain is fl(fl(level) / fl(clamp)), clamp = 1e-5, or eps under 2-max: rho = 3 u
+      2-max                  the larger of its two candidates' rho, whichever the device took
+      zero_mean true         |y - ref| <= G (u |mean| + |x - mean| (u + rho)) + 1/2 ulp(y)   as above
+      zero_mean false        d = fl(x - 0) = x exactly and the padding is exactly 0:  |y - ref| <= |x| G rho + 1/2 ulp(y)
+    (norm 2 with zero_mean keeps its own arithmetic and its 3 u above where the sd is not clamped.)
+    Determinacy, asserted of the inputs in float64 from the reference alone (norm_cases.undetermined with the row's rho): no
+    norm within rho of its clamp, and under 2-max the two candidate gains not within rho of each other -- elsewhere rounding
+    would pick the branch (choose other inputs).
+    With another dtype the arithmetic is the device's in that precision: the sums in double, every scalar rounded once."""
+    import norm_cases as K
+
+    norm = str(norm)
+    plain = norm == "2" and zero_mean
+    level_db = 20.0 * math.log10(float(level))  # (norm_stats takes dB; what it makes of this is fl(level) within 2^-52)
     B = mix.shape[0]
     ref = torch.zeros(B, 1, T_pad_max, dtype=dtype)
     bound = torch.zeros(B, 1, T_pad_max, dtype=torch.float64)
@@ -417,16 +450,40 @@ def pad_normalize(mix, t_raw, T_pad_max, level, tot_ds, dtype=torch.float64, std
         lens.append(Tp)
         xp = torch.zeros(Tp, dtype=dtype)
         xp[pl: pl + n] = mix[b].reshape(-1)[:n].to(dtype)
-        mean = xp.sum() / Tp
-        if dtype != torch.float64:
-            mean = mean.float()
-        d = xp - mean
-        sd = (d.double().pow(2).sum() / (Tp - std_den_off)).sqrt().to(dtype).clamp(min=1e-5)
-        assert float(sd) > 2e-5, "the sd clamp is not what this reference is written for"
-        G = level.to(dtype) / sd
+        st = K.norm_stats(xp, norm, level_db, zero_mean, eps)
+        rho = K.stats_bounds(xp, st, norm, zero_mean)[1]
+        why = K.undetermined(st, norm, rho, eps)
+        assert why is None, f"row {b}: {why}: the gain's branch is not determined (choose other inputs)"
+        if plain:
+            mean = xp.double().sum() / Tp  # (the sum in double, as on the device; float64: the very sum this always was)
+            if dtype != torch.float64:
+                mean = mean.float()
+            d = xp - mean
+            sd = (d.double().pow(2).sum() / (Tp - std_den_off)).sqrt().to(dtype)
+            if float(sd) > 1e-5:
+                rho = 3 * U + 1.01 * U * float(mean.abs() / sd)
+            G = level.to(dtype) / sd.clamp(min=1e-5)
+            ref[b, 0, :Tp] = d * G
+            bound[b, 0, :Tp] = float(G) * (U * float(mean.abs()) + d.double().abs() * (U + rho))
+            continue
+        if dtype == torch.float64:
+            mean = torch.tensor(float(xp.mean()), dtype=dtype)
+            mu = torch.tensor(st["mean"], dtype=dtype)
+            sd, mx = torch.tensor(st["sd"], dtype=dtype), torch.tensor(st["mx"], dtype=dtype)
+            if std_den_off != 1:
+                sd = sd * math.sqrt((Tp - 1) / (Tp - std_den_off))
+        else:
+            mean = (xp.double().sum() / Tp).to(dtype)
+            mu = mean if zero_mean else torch.zeros((), dtype=dtype)
+            sd = ((xp - mean).double().pow(2).sum() / (Tp - std_den_off)).sqrt().to(dtype)
+            mx = (xp - mu).abs().max()
+        G = norm_gain(level, sd, mx, norm, eps, dtype)
+        d = xp - mu
         ref[b, 0, :Tp] = d * G
-        rho = 3 * U + 1.01 * U * float(mean.abs() / sd)
-        bound[b, 0, :Tp] = float(G) * (U * float(mean.abs()) + d.double().abs() * (U + rho))
+        if zero_mean:
+            bound[b, 0, :Tp] = float(G) * (U * float(mean.abs()) + d.double().abs() * (U + rho))
+        else:
+            bound[b, 0, :Tp] = float(G) * d.double().abs() * rho
     return ref, bound, lens
 
 

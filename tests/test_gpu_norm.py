@@ -31,7 +31,7 @@ from test_gpu_ensemble import _members_by_enhance, _share
 pytestmark = pytest.mark.gpu
 
 _models = {}
-NORM_OF = {"max": ("max", True), "2max": ("2-max", True), "keepmean": ("2", False)}
+NORM_OF = {mode: K.MODE_ARGS[mode][:2] for mode in K.MODES}
 
 
 def get_model(model, mode, tmp_path_factory):
@@ -74,13 +74,15 @@ def _variants(spec, T, edge):
 
 
 def _hold_stats(tag, stats, rows, t_pad, spec, mode):
-    """stats: (n, 4) of the device; rows: the raw rows; t_pad: each row's padded length."""
-    norm, zero_mean = NORM_OF[mode]
+    """stats: (n, 4) of the device; rows: the raw rows; t_pad: each row's padded length; mode: a key of norm_cases.MODES or
+    (norm, zero_mean).  The clamp of the 2-max branch is the spec's normalization_kwargs.eps."""
+    norm, zero_mean = NORM_OF.get(mode, mode)
+    eps = float(spec.norm_eps)
     td = spec.tot_ds
     for i, (x, Tp) in enumerate(zip(rows, t_pad)):
         xp = K.padded(x, td)
         assert xp.numel() == Tp
-        st = K.norm_stats(xp, norm, spec.level_db, zero_mean)
+        st = K.norm_stats(xp, norm, spec.level_db, zero_mean, eps)
         b_mean, rho = K.stats_bounds(xp, st, norm, zero_mean)
         mean_g, gain_g = float(stats[i, 0]), float(stats[i, 1])
         err_m, err_g = abs(mean_g - st["mean"]), abs(gain_g / st["gain"] - 1.0)
@@ -95,7 +97,7 @@ def _hold_stats(tag, stats, rows, t_pad, spec, mode):
             mx = K.exact_max(x, Tp, np.float32(mean_g) if zero_mean else np.float32(0))
             if norm == "max":
                 assert np.float32(gain_g) == K.gain32("max", spec.level_db, 0.0, mx), (tag, i, "max is not exact")
-            elif st["branch"] == "max" and st["mx"] > 1e-5:
+            elif st["branch"] == "max" and st["mx"] > eps:
                 assert np.float32(gain_g) == np.float32(1) / mx, (tag, i, "max is not exact")
 
 
@@ -198,6 +200,7 @@ def test_enhance_vs_reference_golden(model_name, mode, tmp_path_factory):
     assert (model.spec.norm, model.spec.zero_mean) == NORM_OF[mode]
     plan = json.loads(model._L.ou_plan_json(model._handle).decode())
     assert (plan["norm"], plan["zero_mean"]) == (NORM_OF[mode][0], int(NORM_OF[mode][1]))
+    assert np.float32(plan["norm_eps"]) == np.float32(K.MODE_ARGS[mode][2]) and model.spec.norm_eps == K.MODE_ARGS[mode][2]
     self_db = float(gold["self_db"])
     mix = torch.from_numpy(gold["mix"])
     out = _enhance(model, mix, torch.from_numpy(gold["noise"]))

@@ -262,21 +262,26 @@ def test_multi_block_reductions(ragged):
 _norm_models = {}
 
 
-@pytest.mark.parametrize("norm,zero_mean", G.NORM_MODES)
-def test_statistics_in_every_norm_mode(norm, zero_mean):
+@pytest.mark.parametrize("norm,zero_mean,eps", [pytest.param(n, z, None, id=f"{n}-{z}") for n, z in G.NORM_MODES]
+                         + [pytest.param("2-max", True, 1e-3, id="2-max-True-eps0.001")])
+def test_statistics_in_every_norm_mode(norm, zero_mean, eps):
     """Every NormMode of ou_set_normalization, zero_mean on and off, at the smallest cases (1 sample; one window): the plain and
-    the GEN statistics kernels."""
-    key = (norm, zero_mean)
+    the GEN statistics kernels -- and 2-max with normalization_kwargs.eps = 1e-3, which seg_stats_finish_kernel and
+    seg_gather_input_kernel then see routed (the one-sample rows have both norms under it)."""
+    key = (norm, zero_mean, eps)
     if key not in _norm_models:
         base, over = SMALL["PP16s"]
         over = dict(over, **{"normalization_norm": int(norm) if norm == "2" else norm, "normalization_kwargs.zero_mean": zero_mean})
+        if eps is not None:
+            over["normalization_kwargs.eps"] = eps
         spec = Cfg.spec_from_config(Cfg.builtin_config(base, **over))
         sd = S.synthetic_state_dict(spec, seed=0)
         cls = UniverseGAN if spec.kind == "universe_gan" else Universe
         _norm_models[key] = (cls(spec, state_dict=sd, device="cuda:0"), spec, sd)
     ms = _norm_models[key]
-    assert (str(ms[1].norm), bool(ms[1].zero_mean)) == key
+    assert (str(ms[1].norm), bool(ms[1].zero_mean), float(ms[1].norm_eps)) == (norm, zero_mean, 1e-5 if eps is None else eps)
     td = ms[1].tot_ds
     Sg, Ov = G.seg_so(td)
     for n in (1, 16 * td - 1):
-        _run_case(f"norm.{norm}.zm{int(zero_mean)}.T{n}", "PP16s", [n, n], Sg, Ov, stitch=False, post=False, model_spec=ms)
+        _run_case(f"norm.{norm}.zm{int(zero_mean)}{'' if eps is None else '.eps%g' % eps}.T{n}", "PP16s", [n, n], Sg, Ov, stitch=False,
+                  post=False, model_spec=ms)
