@@ -106,19 +106,12 @@ def _condition_reports(reps, model, spec, P, xin, lens_T=None, frames=None):
     reps["enc_sum"] = F.Report("enc_sum", _tap(model, "cond.enc_sum"), ref, bound, frames)
 
 
-@pytest.mark.parametrize("name,B,frames", F.CASES)
-def test_conditioner_and_score_seams(name, B, frames):
-    t0 = time.time()
-    model, spec, sd = get_model(name)
-    P = _P(name, spec, sd)
-    T = spec.tot_ds * frames
-    xin = O.normalize(synth_mix(spec, B, T, seed=1000 + frames)[:, None, :], spec.level_db).float().contiguous()
-    model.condition_model(xin.cuda(), train=True)
-    reps = {}
-    _condition_reports(reps, model, spec, P, xin)
-
-    sig = torch.tensor([0.3, 1.7, 0.05, 4.0])[:B]
-    xs = (torch.randn(xin.shape, generator=torch.Generator().manual_seed(5 + frames)) * sig[:, None, None]).float().contiguous()
+def _score_reports(reps, model, spec, P, shape, sig, seed):
+    """ou_score on x = sig[b] * N(0, 1) of `shape` with the per-row sigmas `sig` (any number of rows), behind a conditioner pass
+    of the same shape: score.in, sigma.g, sigma.film and the returned score, every row."""
+    B = shape[0]
+    assert sig.numel() == B
+    xs = (torch.randn(shape, generator=torch.Generator().manual_seed(seed)) * sig[:, None, None]).float().contiguous()
     score = model.score_model(xs.cuda(), sig).cpu()
     coef = F.edm_coef(spec, sig)
     ref, bound = F.in_conv(xs, P.s_in_w, P.s_in_b, coef["w_in"] if P.edm else None)
@@ -130,6 +123,20 @@ def test_conditioner_and_score_seams(name, B, frames):
     last = len(spec.score.rate_factors) + int(spec.score.extra_conv_block) - 1
     ref, bound = F.out_conv_score(_tap(model, f"score.dec{last}.v"), xs, P, coef)
     reps["out_conv"] = F.Report("out_conv", score, ref, bound)
+
+
+@pytest.mark.parametrize("name,B,frames", F.CASES)
+def test_conditioner_and_score_seams(name, B, frames):
+    t0 = time.time()
+    model, spec, sd = get_model(name)
+    P = _P(name, spec, sd)
+    T = spec.tot_ds * frames
+    xin = O.normalize(synth_mix(spec, B, T, seed=1000 + frames)[:, None, :], spec.level_db).float().contiguous()
+    model.condition_model(xin.cuda(), train=True)
+    reps = {}
+    _condition_reports(reps, model, spec, P, xin)
+
+    _score_reports(reps, model, spec, P, xin.shape, torch.tensor([0.3, 1.7, 0.05, 4.0])[:B], 5 + frames)
     _finish(f"seams.{name}.b{B}.f{frames}", reps, t0, "CASES")
 
 
