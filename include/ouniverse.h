@@ -556,7 +556,8 @@ int32_t ou_snake_tile(void);
 /* ---- scoring: how close an estimate is to a reference, for batches whose rows have lengths of their own ------------------
  * The four scores of the reference's inference tooling that are arithmetic on two waveforms: the log-spectral distance and its
  * scale-invariant form (metrics/lsd.py as metrics/wrapper.py:130-153 calls it), SI-SDR (wrapper.py:197-213), the plain SNR
- * beside it, and the time-domain + multi-resolution spectral L1 (losses/multires_stft.py).  Stateless: no handle.
+ * beside it, and the time-domain + multi-resolution spectral L1 (losses/multires_stft.py); and a fifth, the BSS-eval SDR
+ * (wrapper.py:179-195), which the reference takes from a package but is arithmetic all the same (ou_sdr).  Stateless: no handle.
  *   est, ref : (B, stride) device; row b holds len[b] samples of each, nothing behind them is read
  *   len_host : B entries on the HOST, 1 <= len[b] <= min(stride, 2^31 - 1)
  *   out      : B floats on the device, one score per row
@@ -602,6 +603,23 @@ int ou_spectral_mae(const float* est, const float* ref, int64_t stride, const in
  * may be NULL.  OU_EINVAL for a clamp_db that is not positive and finite. */
 int ou_si_sdr(const float* est, const float* ref, int64_t stride, const int64_t* len_host, int32_t B, float clamp_db,
               float* out_si_sdr, float* out_snr, void* scratch, size_t scratch_bytes, ou_stream_t stream);
+/* The BSS-eval SDR with a distortion filter of L = filter_length taps (metrics/wrapper.py:179-195 asks the fast_bss_eval
+ * package for it with filter_length 512, zero_mean False, clamp_db 100).  For one row of T = len[b] samples, with s_l = ref
+ * delayed by l samples (l = 0 .. L - 1), every signal zero-extended to T + L - 1, and P the orthogonal projection onto
+ * span{s_0 .. s_{L-1}}:
+ *     c = ||P est||^2 / ||est||^2,  0 where est or ref is all zero;   out = 10 log10(c' / (1 - c')),  c' clamped as above
+ * i.e. with r[l] = sum_t ref[t] ref[t + l], x[l] = sum_t ref[t] est[t + l], R = toeplitz(r) and R h = x: c = x.h / sum est^2.
+ * R is positive definite for every non-zero ref (T < L included).  L = 1 is out_si_sdr of ou_si_sdr; either signal may be
+ * rescaled without changing the score.  The correlations are sums of exact products of the caller's fp32 samples, taken in
+ * double on the matrix pipe; the solve (Levinson recursion) is in double; no zero-extended copy of a signal is stored.  The
+ * package itself is not a dependency and not part of the reference tree: the definition above is the contract.
+ * Rows, lengths, out and stream as for the other scores; scratch at least ou_sdr_scratch_bytes(B, longest len, L) bytes
+ * (OU_ESHAPE otherwise).  OU_EINVAL for filter_length outside 1 .. OU_SDR_MAX_FILTER and for a clamp_db that is not positive
+ * and finite.  Not done: zero_mean, load_diag, permutation solving, the conjugate-gradient solver. */
+#define OU_SDR_MAX_FILTER 512
+int ou_sdr_scratch_bytes(int32_t B, int64_t T_max, int32_t filter_length, size_t* nbytes);
+int ou_sdr(const float* est, const float* ref, int64_t stride, const int64_t* len_host, int32_t B, int32_t filter_length,
+           float clamp_db, float* out, void* scratch, size_t scratch_bytes, ou_stream_t stream);
 
 /* ---- level normalisation: normalization_norm and normalization_kwargs.zero_mean / .eps of the model yaml (utils/norm.py:22-87):
  * how every enhance entry point (ou_enhance, _var, _ensemble, the four ou_enhance_segments*) levels a row before the networks

@@ -1,10 +1,12 @@
 """
-`python -m open_universe_amd.bin.eval_metrics REF_DIR DEG_DIR --metrics lsd si-lsd si-sdr snr [--batch-size N] --result-dir OUT`
+`python -m open_universe_amd.bin.eval_metrics REF_DIR DEG_DIR --metrics lsd si-lsd si-sdr snr [sdr] [--batch-size N] --result-dir OUT`
 
 The scoring half of the reference's inference tooling (open_universe/bin/eval_metrics.py) for the metrics this library
 computes on the device (open_universe_amd.metrics): every .wav / .flac below DEG_DIR is scored against the file with the same
 relative path below REF_DIR.  Up to --batch-size pairs of one sample rate -- of any lengths -- share one library call per
 metric (`metrics.evaluate_many`); every pair is scored as if it were alone.
+
+`sdr` (the BSS-eval SDR, filter length 512) is computed when it is named; it is not among the defaults.
 
 Nothing is resampled: a pair whose two sample rates differ is an error naming the pair.  Files are mono.
 
@@ -84,7 +86,7 @@ def save_results(results, result_dir, name):
 
 def evaluate_pairs(pairs, metric_names, batch_size=16, device="cuda:0"):
     """Score the pairs in batches of one sample rate -> {label: {metric: value}} in the order of `pairs`."""
-    names = M.check_metric_names(metric_names)
+    names = M.check_score_names(metric_names)
     results = {label: None for label, _, _ in pairs}
     pending = {}  # fs -> [(label, deg, ref)]
 
@@ -109,14 +111,15 @@ def main(argv=None):
     parser = argparse.ArgumentParser(description="Score enhanced files against their references on the device")
     parser.add_argument("ref_path", type=Path, help="Path to the reference (clean) audio folder")
     parser.add_argument("enhanced_path", type=Path, help="Path to the enhanced (degraded) audio folder")
-    parser.add_argument("--metrics", nargs="+", default=list(M.AVAILABLE_METRICS), help="Metrics to compute")
+    parser.add_argument("--metrics", nargs="+", default=list(M.AVAILABLE_METRICS),
+                        help=f"Metrics to compute (default: {' '.join(M.AVAILABLE_METRICS)}; also: {' '.join(M.OPTIONAL_METRICS)})")
     parser.add_argument("--batch-size", type=int, default=16, help="pairs per library call")
     parser.add_argument("--result-dir", "--result_dir", type=Path, default=None, help="where the two JSON files go")
     parser.add_argument("--device", default="cuda:0")
     args = parser.parse_args(argv)
     if args.batch_size < 1:
         parser.error("--batch-size must be at least 1")
-    names = M.check_metric_names(args.metrics)
+    names = M.check_score_names(args.metrics)
     pairs = find_pairs(args.ref_path, args.enhanced_path)
     results = evaluate_pairs(pairs, names, args.batch_size, args.device)
     result_dir = args.enhanced_path.resolve().parent if args.result_dir is None else args.result_dir

@@ -498,4 +498,15 @@ hipError_t launch_met_final_l1(const MetRows& rows, int n_rows, int row0, const 
 hipError_t launch_met_final_sdr(int n_rows, int row0, const double* tsum, float clamp_db, float* out_si_sdr, float* out_snr,
                                 hipStream_t st);
 
+// BSS-eval SDR (ou_sdr.hip; ou_sdr of include/ouniverse.h).  partial: (B, tile_stride, 2, L) doubles -- the L autocorrelation
+// lags of ref, then the L cross-correlation lags, of every tile of kSdrTile samples; tile_stride >= sdr_tiles(len_max).
+// launch_sdr_solve reads tsum word 1 (sum est^2) of launch_met_time.
+constexpr int kSdrTile = 2064;     // + 240 = 36 * 64 (ou_sdr.hip)
+constexpr int kSdrMaxFilter = 512;  // = OU_SDR_MAX_FILTER: two accumulator tiles of 256 lags
+inline long long sdr_tiles(long long len) { return (len + kSdrTile - 1) / kSdrTile; }
+hipError_t launch_sdr_corr(const float* est, const float* ref, long long stride, const MetRows& rows, int n_rows, int row0,
+                           long long len_max, int L, double* partial, long long tile_stride, hipStream_t st);
+hipError_t launch_sdr_solve(const MetRows& rows, int n_rows, int row0, const double* partial, long long tile_stride,
+                            const double* tsum, int L, float clamp_db, float* out, hipStream_t st);
+
 }  // namespace ou

@@ -462,3 +462,67 @@ int ou_si_sdr(const float* est, const float* ref, int64_t stride, const int64_t*
 }
 
 }  // extern "C"
+
+// ---- ou_sdr: the BSS-eval SDR (kernels: ou_sdr.hip) ---------------------------------------------------------------------
+namespace {
+// scratch of one call: | tsum (B, 8) double | partial (B, tiles of the longest row, 2, L) double |
+struct SdrLayout {
+  size_t tsum = 0, partial = 0, bytes = 0;
+  long long tile_stride = 0;
+};
+SdrLayout sdr_layout(int B, long long T_max, int L) {
+  SdrLayout s;
+  size_t at = 0;
+  s.tsum = at; at = met_align(at + (size_t)B * 8 * sizeof(double));
+  s.tile_stride = sdr_tiles(T_max);
+  s.partial = at; at = met_align(at + (size_t)B * (size_t)s.tile_stride * 2 * (size_t)L * sizeof(double));
+  s.bytes = at;
+  return s;
+}
+std::string sdr_filter_error(int L) {
+  return "filter_length = " + std::to_string(L) + " must lie in 1 .. OU_SDR_MAX_FILTER = " + std::to_string(OU_SDR_MAX_FILTER);
+}
+}  // namespace
+
+extern "C" {
+
+int ou_sdr_scratch_bytes(int32_t B, int64_t T_max, int32_t filter_length, size_t* nbytes) {
+  if (!nbytes || B < 1 || T_max < 1 || T_max > kMetMaxLen)
+    return fail(nullptr, OU_EINVAL, "ou_sdr_scratch_bytes: B >= 1, 1 <= T_max <= 2^31 - 1");
+  if (filter_length < 1 || filter_length > OU_SDR_MAX_FILTER)
+    return fail(nullptr, OU_EINVAL, "ou_sdr_scratch_bytes: " + sdr_filter_error(filter_length));
+  *nbytes = sdr_layout(B, T_max, filter_length).bytes;
+  return OU_OK;
+}
+
+int ou_sdr(const float* est, const float* ref, int64_t stride, const int64_t* len_host, int32_t B, int32_t filter_length,
+           float clamp_db, float* out, void* scratch, size_t scratch_bytes, ou_stream_t stream) {
+  static_assert(OU_SDR_MAX_FILTER == kSdrMaxFilter, "the header's cap is the kernels'");
+  long long len_max = 0;
+  if (int rc = met_check_rows("ou_sdr", est, ref, stride, len_host, B, &len_max)) return rc;
+  if (!scratch || !out) return fail(nullptr, OU_EINVAL, "ou_sdr: null argument");
+  if (filter_length < 1 || filter_length > OU_SDR_MAX_FILTER) return fail(nullptr, OU_EINVAL, "ou_sdr: " + sdr_filter_error(filter_length));
+  if (!(clamp_db > 0.0f) || !std::isfinite(clamp_db)) return fail(nullptr, OU_EINVAL, "ou_sdr: clamp_db must be positive and finite");
+  const SdrLayout L = sdr_layout(B, len_max, filter_length);
+  if (scratch_bytes < L.bytes)
+    return fail(nullptr, OU_ESHAPE, "ou_sdr: scratch of " + std::to_string(scratch_bytes) + " bytes, ou_sdr_scratch_bytes asks for " +
+                                        std::to_string(L.bytes));
+  char* base = static_cast<char*>(scratch);
+  double* tsum = reinterpret_cast<double*>(base + L.tsum);
+  double* partial = reinterpret_cast<double*>(base + L.partial);
+  const hipStream_t st = (hipStream_t)stream;
+  for (int off = 0; off < B; off += kMetRowsPerLaunch) {
+    MetRows rows;
+    int n;
+    long long lm;
+    met_rows_of(len_host, B, off, rows, n, lm);
+    if (int rc = met_hip("ou_sdr", launch_met_time(est, ref, stride, rows, n, off, 0.0f, false, tsum, st))) return rc;
+    if (int rc = met_hip("ou_sdr", launch_sdr_corr(est, ref, stride, rows, n, off, lm, filter_length, partial, L.tile_stride, st)))
+      return rc;
+    if (int rc = met_hip("ou_sdr", launch_sdr_solve(rows, n, off, partial, L.tile_stride, tsum, filter_length, clamp_db, out, st)))
+      return rc;
+  }
+  return OU_OK;
+}
+
+}  // extern "C"

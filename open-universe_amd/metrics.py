@@ -1,6 +1,7 @@
 """
-Scores of enhanced speech on the device: log-spectral distance (LSD, SI-LSD), SI-SDR, SNR and the time-domain +
-multi-resolution spectral L1, through ou_lsd / ou_si_sdr / ou_spectral_mae of the C ABI (include/ouniverse.h, "scoring").
+Scores of enhanced speech on the device: log-spectral distance (LSD, SI-LSD), SI-SDR, SNR, the BSS-eval SDR and the time-domain
++ multi-resolution spectral L1, through ou_lsd / ou_si_sdr / ou_sdr / ou_spectral_mae of the C ABI (include/ouniverse.h,
+"scoring").
 
 Names and defaults follow the reference: `log_spectral_distance` / `LogSpectralDistance` (open_universe/metrics/lsd.py),
 `Metrics` (metrics/wrapper.py), `MultiResL1SpecLoss` (losses/multires_stft.py).  Every function takes tensors on a HIP device
@@ -8,8 +9,9 @@ Names and defaults follow the reference: `log_spectral_distance` / `LogSpectralD
 per metric, every row scored as if it were alone.  These are scores: nothing here is differentiable.
 
 What the kernels do not cover raises NotImplementedError naming the argument (p != 2, a custom window, win_length != n_fft,
-pad != 0); the metrics of the reference that need a model or a package (pesq-*, stoi*, lps, dnsmos, plcmos, sdr) are refused by
-name.
+pad != 0); the metrics of the reference that need a model or a package (pesq-*, stoi*, lps, dnsmos, plcmos) are refused by
+name.  `sdr` is computed here (`sdr`, and `evaluate_many` / bin/eval_metrics when it is named) from its definition: the package
+the reference asks for it (fast_bss_eval) is not a dependency.  `Metrics` keeps the four names it had and refuses `sdr`.
 """
 import ctypes
 
@@ -19,8 +21,12 @@ from . import _lib
 
 #: metrics this module computes ("snr" is an extension: the plain signal-to-noise ratio with the clamp of si-sdr)
 AVAILABLE_METRICS = ("lsd", "si-lsd", "si-sdr", "snr")
-#: metrics of the reference (metrics/wrapper.py) that need an external model or package
+#: metrics `evaluate_many` and bin/eval_metrics compute when they are named explicitly (never by default, never by `Metrics`)
+OPTIONAL_METRICS = ("sdr",)
+#: metrics of the reference (metrics/wrapper.py) that `Metrics` refuses: all but `sdr` need an external model or package
 EXTERNAL_METRICS = ("pesq-wb", "pesq-nb", "stoi", "stoi-ext", "lps", "dnsmos", "plcmos", "sdr")
+#: the filter length and clamp of the reference's `Metrics.sdr` (metrics/wrapper.py:179-195)
+SDR_FILTER_LENGTH, SDR_CLAMP_DB = 512, 100.0
 
 
 def _spec(n_fft, hop, eps=0.0, flags=0):
@@ -71,12 +77,12 @@ def _device_rows(x, y, who):
 class _Call:
     """Pointers of one ABI call on rows x, y (B, stride) with the lengths `lens`."""
 
-    def __init__(self, x, y, lens, specs):
+    def __init__(self, x, y, lens, specs, nbytes=None):
         self.B = x.shape[0]
         self.lens = (ctypes.c_int64 * self.B)(*[int(n) for n in lens])
         self.x, self.y = ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(y.data_ptr())
         self.stride = int(x.stride(0)) if self.B > 1 else max(int(x.stride(0)), int(x.shape[1]))
-        self.nbytes = scratch_bytes(self.B, max(int(n) for n in lens), specs)
+        self.nbytes = scratch_bytes(self.B, max(int(n) for n in lens), specs) if nbytes is None else nbytes
         self.scratch = torch.empty(self.nbytes, dtype=torch.uint8, device=x.device)
         self.stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
 
@@ -114,6 +120,29 @@ def _sdr_rows(x, y, lens, clamp_db):
                                ctypes.c_void_p(b.data_ptr()), ctypes.c_void_p(c.scratch.data_ptr()), ctypes.c_size_t(c.nbytes),
                                c.stream))
     return a, b
+
+
+def sdr_scratch_bytes(B, T_max, filter_length=SDR_FILTER_LENGTH):
+    """ou_sdr_scratch_bytes: pure host code; ValueError for a filter_length outside 1 .. 512."""
+    n = ctypes.c_size_t()
+    _lib.check(_lib.load().ou_sdr_scratch_bytes(int(B), int(T_max), int(filter_length), ctypes.byref(n)))
+    return n.value
+
+
+def _bss_sdr_rows(x, y, lens, filter_length, clamp_db):
+    if int(filter_length) != filter_length:
+        raise ValueError(f"sdr: filter_length = {filter_length!r} must be an integer")
+    sdr_scratch_bytes(1, 1, filter_length)  # the refusal of the filter length, before anything else
+    if not (float(clamp_db) > 0.0 and float(clamp_db) < float("inf")):
+        raise ValueError(f"sdr: clamp_db = {clamp_db!r} must be positive and finite")
+    x, y = _device_rows(x, y, "sdr")
+    L = _lib.load()
+    with torch.cuda.device(x.device):
+        c = _Call(x, y, lens, [], sdr_scratch_bytes(x.shape[0], max(int(n) for n in lens), filter_length))
+        out = c.out(x.device)
+        _lib.check(L.ou_sdr(c.x, c.y, c.stride, c.lens, c.B, int(filter_length), float(clamp_db), ctypes.c_void_p(out.data_ptr()),
+                            ctypes.c_void_p(c.scratch.data_ptr()), ctypes.c_size_t(c.nbytes), c.stream))
+    return out
 
 
 def _l1_rows(x, y, lens, window_sz, hop_sz, eps, time_domain_weight, scale_invariant):
@@ -218,10 +247,21 @@ def snr(input, target, clamp_db=100.0):
     return _sdr_rows(x, y, [x.shape[1]] * x.shape[0], clamp_db)[1].reshape(batch)
 
 
+def sdr(input, target, filter_length=SDR_FILTER_LENGTH, clamp_db=SDR_CLAMP_DB):
+    """BSS-eval SDR of `input` against `target` [..., T] -> [...] with a distortion filter of `filter_length` taps (1 .. 512), as
+    metrics/wrapper.py:179-195 asks fast_bss_eval for it (zero_mean=False, clamped to +-clamp_db): the share of `input` that lies
+    in the span of `target` delayed by 0 .. filter_length - 1 samples, against the rest.  filter_length=1 is `si_sdr`."""
+    x, y, batch = _flatten(input, target, "sdr")
+    return _bss_sdr_rows(x, y, [x.shape[1]] * x.shape[0], filter_length, clamp_db).reshape(batch)
+
+
 def check_metric_names(metrics):
     """The names `Metrics` accepts, in order; NotImplementedError for any other (metrics/wrapper.py:76-79)."""
     out = []
     for met in AVAILABLE_METRICS if metrics is None else metrics:
+        if met in OPTIONAL_METRICS:
+            raise NotImplementedError(f"Metric {met} is not supported by Metrics, which keeps to {', '.join(AVAILABLE_METRICS)}: "
+                                      f"call metrics.{met}, or name it in evaluate_many(metrics=[...]) / eval_metrics --metrics")
         if met in EXTERNAL_METRICS:
             raise NotImplementedError(f"Metric {met} is not supported: it needs a model or a package that this library does not "
                                       f"carry (available: {', '.join(AVAILABLE_METRICS)})")
@@ -229,6 +269,14 @@ def check_metric_names(metrics):
             raise NotImplementedError(f"Metric {met} is not supported")
         out.append(met)
     return out
+
+
+def check_score_names(metrics):
+    """The names `evaluate_many` and bin/eval_metrics accept, in order: those of `Metrics` and, named explicitly, OPTIONAL_METRICS
+    (None: the defaults of `Metrics`)."""
+    if metrics is None:
+        return check_metric_names(None)
+    return [met if met in OPTIONAL_METRICS else check_metric_names([met])[0] for met in metrics]
 
 
 def stft_setting(fs):
@@ -273,13 +321,16 @@ def _score_rows(names, x, y, lens, fs):
     if "si-sdr" in names or "snr" in names:
         a, b = _sdr_rows(x, y, lens, 100.0)
         cols["si-sdr"], cols["snr"] = a, b
+    if "sdr" in names:
+        cols["sdr"] = _bss_sdr_rows(x, y, lens, SDR_FILTER_LENGTH, SDR_CLAMP_DB)
     return {k: v.tolist() for k, v in cols.items() if k in names}  # (the one host synchronisation per metric)
 
 
 def evaluate_many(est_list, ref_list, fs, metrics=None):
     """Score pairs (estimate, reference) of 1-D signals of any lengths at rate fs: ONE library call per metric over all pairs,
-    every pair scored as `Metrics(metrics)(fs, est, ref)` scores it alone.  -> one dict per pair."""
-    names = check_metric_names(metrics)
+    every pair scored as `Metrics(metrics)(fs, est, ref)` scores it alone.  -> one dict per pair.  `metrics` may also name
+    "sdr" (OPTIONAL_METRICS): the BSS-eval SDR as `sdr` computes it, one ou_sdr call over all pairs."""
+    names = check_score_names(metrics)
     x, y, lens = pack_pairs(est_list, ref_list)
     return unpack_scores(names, _score_rows(names, x, y, lens, fs), len(lens))
 
