@@ -620,6 +620,42 @@ int ou_si_sdr(const float* est, const float* ref, int64_t stride, const int64_t*
 int ou_sdr_scratch_bytes(int32_t B, int64_t T_max, int32_t filter_length, size_t* nbytes);
 int ou_sdr(const float* est, const float* ref, int64_t stride, const int64_t* len_host, int32_t B, int32_t filter_length,
            float clamp_db, float* out, void* scratch, size_t scratch_bytes, ou_stream_t stream);
+/* STOI (Taal et al. 2011) and extended STOI (Jensen & Taal 2016) of est against the clean signal ref, both at rate fs, with
+ * the constants of the authors' MATLAB code (metrics/wrapper.py:116-128 asks the pystoi package for them).  The package is not
+ * a dependency and nothing is compared against it: the definition below is the contract.  EPS = 2^-52.
+ *   1. fs != 10000: both signals to 10 kHz.  p = 10000 / g, q = fs / g, g = gcd; fc = 1 / (2 max(p, q)),
+ *      L = ceil(52 / (28.714 fc / 10)), h[t] = 2 p fc sinc(2 fc t) kaiser(2 L + 1, 0.1102 (60 - 8.7))[t + L] for t = -L .. L,
+ *      normalised to sum 1 and multiplied by p; output j = sum_k h[k] xup[j q + L - k], xup[i p] = x[i] and zero elsewhere
+ *      (outside the row too); ceil(T p / q) outputs.
+ *   2. Frames of 256 at hop 128 starting at range(0, n - 256, 128) -- end exclusive: a frame that would start exactly at
+ *      n - 256 is NOT counted (the MATLAB rule; one function in the library) --, window w = hanning(258)[1:-1].
+ *      E_f = 20 log10(||w ref_f|| + EPS); the frames with E_f > max E - 40 are kept, and the kept windowed frames of both
+ *      signals are overlap-added at hop 128 in their order (K frames: 128 (K - 1) + 256 samples).
+ *   3. Same frames, window and hop on both results; bins 0 .. 256 of the 512-point DFT of the zero-padded frame.
+ *   4. Fifteen one-third-octave bands: the square root of the sum of |X|^2 over bins [lo, hi) = (7,9) (9,11) (11,14) (14,17)
+ *      (17,22) (22,27) (27,34) (34,43) (43,55) (55,69) (69,87) (87,109) (109,138) (138,174) (174,219).
+ *   5. Fewer than 30 frames after step 3: the score is 1e-5.  That is a result, not an error -- a row too short to have a
+ *      single frame scores 1e-5 too.
+ *   6. Segment m = 30 .. frames is band values [:, m - 30 : m], M = frames - 29 of them.
+ *      extended == 0: per segment and band c = ||x|| / (||y|| + EPS), y' = min(c y, x (1 + 10^(15/20))), both with their mean
+ *        over the 30 frames removed and divided by their norm + EPS; the score is sum x y' / (15 M).
+ *      extended != 0: per segment and band mean removed and divided by norm + EPS over the 30 frames, then per segment and
+ *        frame the same over the 15 bands, for x and y; the score is sum x y / (30 M).       (x: ref, y: est)
+ * The samples enter as fp32; the filter table, the resampled and overlap-added signals, the DFT (on the f64 matrix
+ * instruction), the band values and every sum are double, and out is rounded to fp32 once.
+ * Rows, lengths, out and stream as for the other scores; scratch at least ou_stoi_scratch_bytes(B, longest len, fs) bytes
+ * (OU_ESHAPE otherwise).  The filter table is built on the host from fs and copied into the scratch on the stream.
+ * OU_EINVAL, before the first HIP call, for fs < 1, for an fs whose filter needs more than OU_STOI_MAX_TAPS taps per output
+ * (ceil((2 L + 1) / p)) or a table (p ints, taps x p doubles) above OU_STOI_MAX_TABLE_BYTES -- 8000, 10000, 16000, 22050,
+ * 24000, 32000, 44100, 48000, 96000 pass; a rate coprime to 10000 above about 7000 does not --, for a row with more than
+ * 2^31 - 1 samples at 10 kHz, and for B < 1 or bad lengths.  ou_stoi_frame_tile: STFT frames per workgroup (for tests).
+ * Not done: other internal rates, a differentiable form. */
+#define OU_STOI_MAX_TAPS 2048
+#define OU_STOI_MAX_TABLE_BYTES (4 << 20)
+int ou_stoi_scratch_bytes(int32_t B, int64_t T_max, int32_t fs, size_t* nbytes);
+int ou_stoi(const float* est, const float* ref, int64_t stride, const int64_t* len_host, int32_t B, int32_t fs, int32_t extended,
+            float* out, void* scratch, size_t scratch_bytes, ou_stream_t stream);
+int32_t ou_stoi_frame_tile(void);
 
 /* ---- level normalisation: normalization_norm and normalization_kwargs.zero_mean / .eps of the model yaml (utils/norm.py:22-87):
  * how every enhance entry point (ou_enhance, _var, _ensemble, the four ou_enhance_segments*) levels a row before the networks

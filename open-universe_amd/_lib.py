@@ -202,6 +202,9 @@ def load():
         "ou_si_sdr": (i32, [vp, vp, c_int64, POINTER(c_int64), i32, c_float, vp, vp, vp, sz, vp]),
         "ou_sdr_scratch_bytes": (i32, [i32, c_int64, i32, POINTER(sz)]),
         "ou_sdr": (i32, [vp, vp, c_int64, POINTER(c_int64), i32, i32, c_float, vp, vp, sz, vp]),
+        "ou_stoi_scratch_bytes": (i32, [i32, c_int64, i32, POINTER(sz)]),
+        "ou_stoi": (i32, [vp, vp, c_int64, POINTER(c_int64), i32, i32, i32, vp, vp, sz, vp]),
+        "ou_stoi_frame_tile": (i32, []),
         "ou_transform_frames": (i32, [i32, i32, i32]),
         "ou_transform_forward": (i32, [vp, i32, i32, vp, i32, i32, i32, c_float, c_float, vp, vp]),
         "ou_transform_inverse": (i32, [vp, i32, i32, vp, i32, i32, i32, c_float, c_float, i32, vp, vp, vp]),
@@ -235,7 +238,7 @@ EXPORTED_SYMBOLS = [
     "ou_resample_plan", "ou_resample_table", "ou_resample_length", "ou_resample_tile", "ou_resample",
     "ou_snake_act", "ou_snake_tile", "ou_set_normalization",
     "ou_metrics_frames", "ou_metrics_scratch_bytes", "ou_lsd", "ou_spectral_mae", "ou_si_sdr",
-    "ou_sdr_scratch_bytes", "ou_sdr",
+    "ou_sdr_scratch_bytes", "ou_sdr", "ou_stoi_scratch_bytes", "ou_stoi", "ou_stoi_frame_tile",
     "ou_set_option", "ou_get_option", "ou_reset_options", "ou_option_count", "ou_option_name", "ou_option_doc", "ou_option_default", "ou_plan_json",
     "ou_packer_plan_json", "ou_tensor", "ou_launch_stats", "ou_workspace_init", "ou_sampler_step",
     "ou_set_gru_publish_mode", "ou_get_gru_publish_mode", "ou_set_lanes", "ou_set_lane_batch", "ou_lane_capacity",

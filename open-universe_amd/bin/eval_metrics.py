@@ -1,5 +1,5 @@
 """
-`python -m open_universe_amd.bin.eval_metrics REF_DIR DEG_DIR --metrics lsd si-lsd si-sdr snr [sdr] [--batch-size N] --result-dir OUT`
+`python -m open_universe_amd.bin.eval_metrics REF_DIR DEG_DIR --metrics lsd si-lsd si-sdr snr [sdr] [--intelligibility stoi stoi-ext] [--batch-size N] --result-dir OUT`
 
 The scoring half of the reference's inference tooling (open_universe/bin/eval_metrics.py) for the metrics this library
 computes on the device (open_universe_amd.metrics): every .wav / .flac below DEG_DIR is scored against the file with the same
@@ -7,6 +7,8 @@ relative path below REF_DIR.  Up to --batch-size pairs of one sample rate -- of 
 metric (`metrics.evaluate_many`); every pair is scored as if it were alone.
 
 `sdr` (the BSS-eval SDR, filter length 512) is computed when it is named; it is not among the defaults.
+`--intelligibility stoi stoi-ext` adds STOI and / or extended STOI (`metrics.stoi`; default: neither): their columns follow
+those of --metrics in the same two files.  `--metrics stoi` stays refused.
 
 Nothing is resampled: a pair whose two sample rates differ is an error naming the pair.  Files are mono.
 
@@ -84,16 +86,18 @@ def save_results(results, result_dir, name):
     return results_path, summary_path
 
 
-def evaluate_pairs(pairs, metric_names, batch_size=16, device="cuda:0"):
+def evaluate_pairs(pairs, metric_names, batch_size=16, device="cuda:0", intelligibility=()):
     """Score the pairs in batches of one sample rate -> {label: {metric: value}} in the order of `pairs`."""
     names = M.check_score_names(metric_names)
+    extra = M.check_intelligibility_names(intelligibility)
     results = {label: None for label, _, _ in pairs}
     pending = {}  # fs -> [(label, deg, ref)]
 
     def flush(fs):
         batch = pending.pop(fs, [])
         if batch:
-            scores = M.evaluate_many([d.to(device) for _, d, _ in batch], [r.to(device) for _, _, r in batch], fs, names)
+            scores = M.evaluate_many([d.to(device) for _, d, _ in batch], [r.to(device) for _, _, r in batch], fs, names,
+                                     intelligibility=extra)
             for (label, _, _), s in zip(batch, scores):
                 results[label] = s
 
@@ -113,6 +117,8 @@ def main(argv=None):
     parser.add_argument("enhanced_path", type=Path, help="Path to the enhanced (degraded) audio folder")
     parser.add_argument("--metrics", nargs="+", default=list(M.AVAILABLE_METRICS),
                         help=f"Metrics to compute (default: {' '.join(M.AVAILABLE_METRICS)}; also: {' '.join(M.OPTIONAL_METRICS)})")
+    parser.add_argument("--intelligibility", nargs="*", default=[], choices=list(M.INTELLIGIBILITY_METRICS),
+                        help="STOI scores to add (default: none)")
     parser.add_argument("--batch-size", type=int, default=16, help="pairs per library call")
     parser.add_argument("--result-dir", "--result_dir", type=Path, default=None, help="where the two JSON files go")
     parser.add_argument("--device", default="cuda:0")
@@ -121,7 +127,7 @@ def main(argv=None):
         parser.error("--batch-size must be at least 1")
     names = M.check_score_names(args.metrics)
     pairs = find_pairs(args.ref_path, args.enhanced_path)
-    results = evaluate_pairs(pairs, names, args.batch_size, args.device)
+    results = evaluate_pairs(pairs, names, args.batch_size, args.device, args.intelligibility)
     result_dir = args.enhanced_path.resolve().parent if args.result_dir is None else args.result_dir
     paths = save_results(results, result_dir, args.enhanced_path.resolve().name)
     print(f"{len(results)} files scored: {paths[0]}, {paths[1]}")

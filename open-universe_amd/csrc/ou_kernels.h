@@ -509,4 +509,53 @@ hipError_t launch_sdr_corr(const float* est, const float* ref, long long stride,
 hipError_t launch_sdr_solve(const MetRows& rows, int n_rows, int row0, const double* partial, long long tile_stride,
                             const double* tsum, int L, float clamp_db, float* out, hipStream_t st);
 
+// STOI / ESTOI (ou_stoi.hip; ou_stoi of include/ouniverse.h).  Everything behind the caller's fp32 samples is double.  Rows of
+// a launch carry two lengths by value: len (samples at fs) and n10 (samples at 10 kHz, = len when fs is 10 kHz).  Scratch of
+// row r = row0 + b, F = stoi_frames(longest n10 of the CALL):
+//   res     (2, B, res_stride) doubles   est, ref at 10 kHz (absent at fs = 10 kHz: the kernels read the caller's rows)
+//   energy  (B, F) doubles               20 log10(||w ref_f|| + eps) of frame f
+//   src     (B, F) ints, count (B) ints  the kept frames in order, and how many
+//   bands   (B, 2, 15, F) doubles        one-third-octave band values of est, ref over the frames of the compacted signals
+//   partial (B, stoi_seg_tiles(F))       sums over kStoiSegTile segments
+constexpr int kStoiRowsPerLaunch = 64;
+constexpr int kStoiFrame = 256, kStoiHop = 128, kStoiSegment = 30, kStoiBands = 15;
+constexpr int kStoiFrameTile = 16;  // STFT frames of both signals per workgroup (= ou_stoi_frame_tile())
+constexpr int kStoiSegTile = 16;    // segments per workgroup of stoi_seg_kernel
+constexpr int kStoiBinTiles = 14;   // 16-bin tiles of the DFT: 7 from bin 7 (bands 0 .. 11), 7 from bin 109 (bands 12 .. 14)
+constexpr size_t kStoiBasisWords = (size_t)kStoiBinTiles * 2 * (kStoiFrame / 4) * 64;
+struct StoiRows {
+  long long len[kStoiRowsPerLaunch], n10[kStoiRowsPerLaunch];
+};
+struct StoiSignals {  // est / ref: (B, stride) fp32 at fs; res_est / res_ref: (B, res_stride) doubles at 10 kHz, or null
+  const float *est, *ref;
+  long long stride;
+  const double *res_est, *res_ref;
+  long long res_stride;
+};
+// THE frame rule: frames of 256 at hop 128 start at range(0, n - 256, 128), end exclusive -- a frame that would
+// start exactly at n - 256 is not counted.  Both the silent-frame stage and the STFT of the compacted signals count with this.
+__host__ __device__ inline long long stoi_frames(long long n) {
+  return n > kStoiFrame ? (n - kStoiFrame + kStoiHop - 1) / kStoiHop : 0;
+}
+// samples of the overlap-add of K kept frames, and the STFT frames it has
+__host__ __device__ inline long long stoi_compacted_len(long long K) { return K > 0 ? kStoiHop * (K - 1) + kStoiFrame : 0; }
+inline long long stoi_seg_tiles(long long frames) {
+  return frames >= kStoiSegment ? (frames - kStoiSegment + 1 + kStoiSegTile - 1) / kStoiSegTile : 0;
+}
+// table: int first[p] (padded to a multiple of 2), then double coef[taps][p]; output j = f p + ph reads x[f q + first[ph] + t]
+hipError_t launch_stoi_resample(const StoiSignals& sig, const StoiRows& rows, int n_rows, int row0, long long n10_max, int p, int q,
+                                int taps, const void* table, double* res_est, double* res_ref, hipStream_t st);
+// basis: kStoiBasisWords doubles, window: kStoiFrame doubles
+hipError_t launch_stoi_basis(double* basis, double* window, hipStream_t st);
+hipError_t launch_stoi_energy(const StoiSignals& sig, const StoiRows& rows, int n_rows, int row0, long long n10_max,
+                              const double* window, double* energy, long long F, hipStream_t st);
+hipError_t launch_stoi_mask(const StoiRows& rows, int n_rows, int row0, const double* energy, long long F, int* src, int* count,
+                            hipStream_t st);
+hipError_t launch_stoi_stft(const StoiSignals& sig, const StoiRows& rows, int n_rows, int row0, long long n10_max,
+                            const double* basis, const double* window, const int* src, const int* count, long long F,
+                            double* bands, hipStream_t st);
+hipError_t launch_stoi_segments(bool extended, const StoiRows& rows, int n_rows, int row0, long long n10_max, const double* bands,
+                                const int* count, long long F, double clip, double* partial, long long seg_stride, float* out,
+                                hipStream_t st);
+
 }  // namespace ou

@@ -526,3 +526,208 @@ int ou_sdr(const float* est, const float* ref, int64_t stride, const int64_t* le
 }
 
 }  // extern "C"
+
+// ---- ou_stoi: STOI and extended STOI (kernels: ou_stoi.hip) --------------------------------------------------------------
+namespace {
+// What a sample rate asks of the 10 kHz resampler (include/ouniverse.h, step 1 of the definition): a pure host function of fs.
+struct StoiPlan {
+  int fs = 0;
+  int p = 1, q = 1, L = 0, taps = 0;  // taps per output (0: fs is 10 kHz, nothing is resampled)
+  size_t table_bytes = 0;
+  std::vector<char> table;            // int first[p] padded to an even count, double coef[taps][p]
+  std::string error;                  // why this fs is refused, or empty
+};
+
+// I0 by its power series sum_k ((x / 2)^k / k!)^2; the terms fall below 2^-53 of the sum after about 25 of them at beta = 5.65
+double stoi_i0(double x) {
+  const double h = 0.5 * x;
+  double term = 1.0, sum = 1.0;
+  for (int k = 1; k < 500; k++) {
+    term *= (h / (double)k) * (h / (double)k);
+    sum += term;
+    if (term < 1e-18 * sum) break;
+  }
+  return sum;
+}
+inline long long floor_div(long long a, long long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }  // b > 0
+inline long long ceil_div(long long a, long long b) { return -floor_div(-a, b); }
+
+const StoiPlan& stoi_plan(int fs) {
+  thread_local StoiPlan pl;
+  thread_local bool cached = false;
+  if (cached && pl.fs == fs) return pl;
+  pl = StoiPlan();
+  pl.fs = fs;
+  cached = true;
+  if (fs < 1) {
+    pl.error = "fs = " + std::to_string(fs) + " must be at least 1";
+    return pl;
+  }
+  if (fs == 10000) return pl;
+  const long long g = gcd_ll(10000, fs);
+  const long long p = 10000 / g, q = fs / g, mx = p > q ? p : q;
+  const double fc = 1.0 / (2.0 * (double)mx);
+  const double Ld = std::ceil(52.0 / (28.714 * fc / 10.0));
+  const double taps_d = std::ceil((2.0 * Ld + 1.0) / (double)p);
+  const double bytes_d = ((double)((p + 1) & ~1ll)) * 4.0 + taps_d * (double)p * 8.0;
+  if (taps_d > (double)OU_STOI_MAX_TAPS || bytes_d > (double)OU_STOI_MAX_TABLE_BYTES) {
+    pl.error = "fs = " + std::to_string(fs) + ": the 10 kHz resampling filter (10000 / " + std::to_string(fs) + " = " +
+               std::to_string(p) + " / " + std::to_string(q) + ") needs " + std::to_string((long long)taps_d) +
+               " taps per output and a table of " + std::to_string((long long)bytes_d) + " bytes; the caps are OU_STOI_MAX_TAPS = " +
+               std::to_string(OU_STOI_MAX_TAPS) + " and OU_STOI_MAX_TABLE_BYTES = " + std::to_string(OU_STOI_MAX_TABLE_BYTES);
+    return pl;
+  }
+  const long long L = (long long)Ld;
+  pl.p = (int)p; pl.q = (int)q; pl.L = (int)L;
+  // h[t + L] = 2 p fc sinc(2 fc t) kaiser(2 L + 1, beta)[t + L], normalised to sum 1, times p
+  const double beta = 0.1102 * (60.0 - 8.7), i0b = stoi_i0(beta);
+  std::vector<double> h((size_t)(2 * L + 1));
+  double sum = 0.0;
+  for (long long k = 0; k <= 2 * L; k++) {
+    const double t = (double)(k - L), u = t / (double)L;
+    const double x = M_PI * (2.0 * fc * t);
+    const double sinc = k == L ? 1.0 : std::sin(x) / x;
+    const double kaiser = stoi_i0(beta * std::sqrt(1.0 - u * u)) / i0b;
+    h[(size_t)k] = 2.0 * (double)p * fc * sinc * kaiser;
+    sum += h[(size_t)k];
+  }
+  for (double& v : h) v = v / sum * (double)p;
+  // output j = f p + ph: sum_k h[k] xup[j q + L - k], xup[i p] = x[i]  ->  i = f q + i', k = ph q + L - i' p in [0, 2 L]:
+  // i' from ceil((ph q - L) / p) to floor((ph q + L) / p), ascending
+  long long taps = 0;
+  for (long long ph = 0; ph < p; ph++) {
+    const long long n = floor_div(ph * q + L, p) - ceil_div(ph * q - L, p) + 1;
+    taps = n > taps ? n : taps;
+  }
+  pl.taps = (int)taps;
+  const size_t first_words = (size_t)((p + 1) & ~1ll);
+  pl.table_bytes = first_words * 4 + (size_t)taps * (size_t)p * 8;
+  pl.table.assign(pl.table_bytes, 0);
+  int32_t* first = reinterpret_cast<int32_t*>(pl.table.data());
+  double* coef = reinterpret_cast<double*>(pl.table.data() + first_words * 4);
+  for (long long ph = 0; ph < p; ph++) {
+    const long long a = ceil_div(ph * q - L, p);
+    first[ph] = (int32_t)a;
+    for (long long t = 0; t < taps; t++) {
+      const long long k = ph * q + L - (a + t) * p;
+      coef[(size_t)t * (size_t)p + (size_t)ph] = (k >= 0 && k <= 2 * L) ? h[(size_t)k] : 0.0;
+    }
+  }
+  return pl;
+}
+
+inline long long stoi_len10(long long T, const StoiPlan& pl) { return (T * pl.p + pl.q - 1) / pl.q; }  // ceil(T p / q)
+
+// scratch of one call: | table | window | basis | res (2, B, n10) | energy (B, F) | src (B, F) | count (B) | bands (B, 2, 15, F) |
+// partial (B, segment tiles) |, F = stoi_frames(n10 of the longest row)
+struct StoiLayout {
+  size_t table = 0, window = 0, basis = 0, res = 0, energy = 0, src = 0, count = 0, bands = 0, partial = 0, bytes = 0;
+  long long n10 = 0, F = 0, seg_stride = 0;
+};
+StoiLayout stoi_layout(int B, long long T_max, const StoiPlan& pl) {
+  StoiLayout s;
+  s.n10 = stoi_len10(T_max, pl);
+  s.F = stoi_frames(s.n10);
+  s.seg_stride = stoi_seg_tiles(s.F);
+  const size_t nb = (size_t)B, F = (size_t)s.F;
+  size_t at = 0;
+  s.table = at; at = met_align(at + pl.table_bytes);
+  s.window = at; at = met_align(at + kStoiFrame * sizeof(double));
+  s.basis = at; at = met_align(at + kStoiBasisWords * sizeof(double));
+  s.res = at; at = met_align(at + (pl.taps ? 2 * nb * (size_t)s.n10 * sizeof(double) : 0));
+  s.energy = at; at = met_align(at + nb * F * sizeof(double));
+  s.src = at; at = met_align(at + nb * F * sizeof(int));
+  s.count = at; at = met_align(at + nb * sizeof(int));
+  s.bands = at; at = met_align(at + nb * 2 * kStoiBands * F * sizeof(double));
+  s.partial = at; at = met_align(at + nb * (size_t)s.seg_stride * sizeof(double));
+  s.bytes = at;
+  return s;
+}
+// the message of a T_max this fs cannot take, or empty
+std::string stoi_length_error(long long T_max, const StoiPlan& pl) {
+  if (stoi_len10(T_max, pl) > kMetMaxLen)  // (T_max p fits 64 bits: T_max < 2^31, p <= 10000)
+    return "a row of " + std::to_string(T_max) + " samples at fs = " + std::to_string(pl.fs) + " has more than 2^31 - 1 samples at 10 kHz";
+  return std::string();
+}
+}  // namespace
+
+extern "C" {
+
+int32_t ou_stoi_frame_tile(void) { return kStoiFrameTile; }
+
+int ou_stoi_scratch_bytes(int32_t B, int64_t T_max, int32_t fs, size_t* nbytes) {
+  if (!nbytes || B < 1 || T_max < 1 || T_max > kMetMaxLen)
+    return fail(nullptr, OU_EINVAL, "ou_stoi_scratch_bytes: B >= 1, 1 <= T_max <= 2^31 - 1");
+  const StoiPlan& pl = stoi_plan(fs);
+  if (!pl.error.empty()) return fail(nullptr, OU_EINVAL, "ou_stoi_scratch_bytes: " + pl.error);
+  const std::string m = stoi_length_error(T_max, pl);
+  if (!m.empty()) return fail(nullptr, OU_EINVAL, "ou_stoi_scratch_bytes: " + m);
+  *nbytes = stoi_layout(B, T_max, pl).bytes;
+  return OU_OK;
+}
+
+int ou_stoi(const float* est, const float* ref, int64_t stride, const int64_t* len_host, int32_t B, int32_t fs, int32_t extended,
+            float* out, void* scratch, size_t scratch_bytes, ou_stream_t stream) {
+  static_assert(kStoiRowsPerLaunch == kMetRowsPerLaunch, "one launch group per 64 rows, as the other scores");
+  // everything is decided here, on the host, before the first HIP call
+  if (fs < 1) return fail(nullptr, OU_EINVAL, "ou_stoi: " + stoi_plan(fs).error);
+  long long len_max = 0;
+  if (int rc = met_check_rows("ou_stoi", est, ref, stride, len_host, B, &len_max)) return rc;
+  if (!scratch || !out) return fail(nullptr, OU_EINVAL, "ou_stoi: null argument");
+  const StoiPlan& pl = stoi_plan(fs);
+  if (!pl.error.empty()) return fail(nullptr, OU_EINVAL, "ou_stoi: " + pl.error);
+  const std::string m = stoi_length_error(len_max, pl);
+  if (!m.empty()) return fail(nullptr, OU_EINVAL, "ou_stoi: " + m);
+  const StoiLayout L = stoi_layout(B, len_max, pl);
+  if (scratch_bytes < L.bytes)
+    return fail(nullptr, OU_ESHAPE, "ou_stoi: scratch of " + std::to_string(scratch_bytes) + " bytes, ou_stoi_scratch_bytes asks for " +
+                                        std::to_string(L.bytes));
+  char* base = static_cast<char*>(scratch);
+  double* window = reinterpret_cast<double*>(base + L.window);
+  double* basis = reinterpret_cast<double*>(base + L.basis);
+  double* energy = reinterpret_cast<double*>(base + L.energy);
+  int* src = reinterpret_cast<int*>(base + L.src);
+  int* count = reinterpret_cast<int*>(base + L.count);
+  double* bands = reinterpret_cast<double*>(base + L.bands);
+  double* partial = reinterpret_cast<double*>(base + L.partial);
+  StoiSignals sig{est, ref, stride, nullptr, nullptr, 0};
+  double *res_est = nullptr, *res_ref = nullptr;
+  const hipStream_t st = (hipStream_t)stream;
+  if (pl.taps) {
+    res_est = reinterpret_cast<double*>(base + L.res);
+    res_ref = res_est + (size_t)B * (size_t)L.n10;
+    sig.res_stride = L.n10;
+    // the plan's table outlives the call (it is the thread's cache, and a pageable source is staged before the copy returns)
+    if (int rc = met_hip("ou_stoi", hipMemcpyAsync(base + L.table, pl.table.data(), pl.table_bytes, hipMemcpyHostToDevice, st)))
+      return rc;
+  }
+  if (int rc = met_hip("ou_stoi", launch_stoi_basis(basis, window, st))) return rc;
+  const double clip = 1.0 + std::pow(10.0, 15.0 / 20.0);  // the estimate is clipped 15 dB above the clean band value
+  for (int off = 0; off < B; off += kStoiRowsPerLaunch) {
+    StoiRows rows;
+    const int n = B - off < kStoiRowsPerLaunch ? B - off : kStoiRowsPerLaunch;
+    long long n10_max = 0;
+    for (int i = 0; i < kStoiRowsPerLaunch; i++) {
+      rows.len[i] = i < n ? len_host[off + i] : 0;
+      rows.n10[i] = i < n ? stoi_len10(rows.len[i], pl) : 0;
+      n10_max = rows.n10[i] > n10_max ? rows.n10[i] : n10_max;
+    }
+    StoiSignals s = sig;  // the resampler reads the caller's rows; everything behind it the rows at 10 kHz
+    if (pl.taps) {
+      if (int rc = met_hip("ou_stoi", launch_stoi_resample(s, rows, n, off, n10_max, pl.p, pl.q, pl.taps, base + L.table, res_est,
+                                                           res_ref, st)))
+        return rc;
+      s.res_est = res_est;
+      s.res_ref = res_ref;
+    }
+    if (int rc = met_hip("ou_stoi", launch_stoi_energy(s, rows, n, off, n10_max, window, energy, L.F, st))) return rc;
+    if (int rc = met_hip("ou_stoi", launch_stoi_mask(rows, n, off, energy, L.F, src, count, st))) return rc;
+    if (int rc = met_hip("ou_stoi", launch_stoi_stft(s, rows, n, off, n10_max, basis, window, src, count, L.F, bands, st))) return rc;
+    if (int rc = met_hip("ou_stoi", launch_stoi_segments(extended != 0, rows, n, off, n10_max, bands, count, L.F, clip, partial,
+                                                         L.seg_stride, out, st)))
+      return rc;
+  }
+  return OU_OK;
+}
+
+}  // extern "C"

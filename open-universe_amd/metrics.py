@@ -1,7 +1,7 @@
 """
-Scores of enhanced speech on the device: log-spectral distance (LSD, SI-LSD), SI-SDR, SNR, the BSS-eval SDR and the time-domain
-+ multi-resolution spectral L1, through ou_lsd / ou_si_sdr / ou_sdr / ou_spectral_mae of the C ABI (include/ouniverse.h,
-"scoring").
+Scores of enhanced speech on the device: log-spectral distance (LSD, SI-LSD), SI-SDR, SNR, the BSS-eval SDR, STOI and extended
+STOI, and the time-domain + multi-resolution spectral L1, through ou_lsd / ou_si_sdr / ou_sdr / ou_stoi / ou_spectral_mae of
+the C ABI (include/ouniverse.h, "scoring").
 
 Names and defaults follow the reference: `log_spectral_distance` / `LogSpectralDistance` (open_universe/metrics/lsd.py),
 `Metrics` (metrics/wrapper.py), `MultiResL1SpecLoss` (losses/multires_stft.py).  Every function takes tensors on a HIP device
@@ -9,9 +9,15 @@ Names and defaults follow the reference: `log_spectral_distance` / `LogSpectralD
 per metric, every row scored as if it were alone.  These are scores: nothing here is differentiable.
 
 What the kernels do not cover raises NotImplementedError naming the argument (p != 2, a custom window, win_length != n_fft,
-pad != 0); the metrics of the reference that need a model or a package (pesq-*, stoi*, lps, dnsmos, plcmos) are refused by
-name.  `sdr` is computed here (`sdr`, and `evaluate_many` / bin/eval_metrics when it is named) from its definition: the package
-the reference asks for it (fast_bss_eval) is not a dependency.  `Metrics` keeps the four names it had and refuses `sdr`.
+pad != 0); the metrics of the reference that need a model or a package (pesq-*, lps, dnsmos, plcmos) are refused by name.
+`sdr` is computed here (`sdr`, and `evaluate_many` / bin/eval_metrics when it is named) from its definition: the package the
+reference asks for it (fast_bss_eval) is not a dependency.  `Metrics` keeps the four names it had and refuses `sdr`.
+
+`stoi` and `stoi-ext` are computed here too, from their definition (include/ouniverse.h; pystoi, which the reference asks, is
+not a dependency): by `stoi(input, target, fs, extended)`, and by `evaluate_many(..., intelligibility=[...])` /
+`eval_metrics --intelligibility` when they are named there (INTELLIGIBILITY_METRICS).  As names of `Metrics`, of
+`check_metric_names` / `check_score_names` and of the `metrics=` argument they remain refused, with the message they always
+had: one list of names for all scores is left to a later change.
 """
 import ctypes
 
@@ -23,7 +29,11 @@ from . import _lib
 AVAILABLE_METRICS = ("lsd", "si-lsd", "si-sdr", "snr")
 #: metrics `evaluate_many` and bin/eval_metrics compute when they are named explicitly (never by default, never by `Metrics`)
 OPTIONAL_METRICS = ("sdr",)
-#: metrics of the reference (metrics/wrapper.py) that `Metrics` refuses: all but `sdr` need an external model or package
+#: the scores `stoi` computes; `evaluate_many(intelligibility=...)` and `eval_metrics --intelligibility` take these names
+INTELLIGIBILITY_METRICS = ("stoi", "stoi-ext")
+#: metrics of the reference (metrics/wrapper.py) that `Metrics` and `metrics=` refuse by name.  pesq-*, lps, dnsmos and plcmos
+#: need an external model or package; `sdr` (OPTIONAL_METRICS) and `stoi` / `stoi-ext` (INTELLIGIBILITY_METRICS) are computed by
+#: this module through entry points of their own and stay in this list only because those two callers keep their refusals
 EXTERNAL_METRICS = ("pesq-wb", "pesq-nb", "stoi", "stoi-ext", "lps", "dnsmos", "plcmos", "sdr")
 #: the filter length and clamp of the reference's `Metrics.sdr` (metrics/wrapper.py:179-195)
 SDR_FILTER_LENGTH, SDR_CLAMP_DB = 512, 100.0
@@ -145,6 +155,28 @@ def _bss_sdr_rows(x, y, lens, filter_length, clamp_db):
     return out
 
 
+def stoi_scratch_bytes(B, T_max, fs):
+    """ou_stoi_scratch_bytes: pure host code; ValueError for fs < 1 and for an fs whose 10 kHz resampling filter exceeds the caps
+    of include/ouniverse.h (OU_STOI_MAX_TAPS, OU_STOI_MAX_TABLE_BYTES)."""
+    n = ctypes.c_size_t()
+    _lib.check(_lib.load().ou_stoi_scratch_bytes(int(B), int(T_max), int(fs), ctypes.byref(n)))
+    return n.value
+
+
+def _stoi_rows(x, y, lens, fs, extended):
+    if int(fs) != fs:
+        raise ValueError(f"stoi: fs = {fs!r} must be an integer")
+    stoi_scratch_bytes(1, 1, fs)  # the refusal of the rate, before anything else
+    x, y = _device_rows(x, y, "stoi")
+    L = _lib.load()
+    with torch.cuda.device(x.device):
+        c = _Call(x, y, lens, [], stoi_scratch_bytes(x.shape[0], max(int(n) for n in lens), fs))
+        out = c.out(x.device)
+        _lib.check(L.ou_stoi(c.x, c.y, c.stride, c.lens, c.B, int(fs), 1 if extended else 0, ctypes.c_void_p(out.data_ptr()),
+                             ctypes.c_void_p(c.scratch.data_ptr()), ctypes.c_size_t(c.nbytes), c.stream))
+    return out
+
+
 def _l1_rows(x, y, lens, window_sz, hop_sz, eps, time_domain_weight, scale_invariant):
     specs = [_spec(w, h) for w, h in zip(window_sz, hop_sz)]
     if len(specs) > _lib.OU_METRICS_MAX_SPECS:
@@ -255,6 +287,24 @@ def sdr(input, target, filter_length=SDR_FILTER_LENGTH, clamp_db=SDR_CLAMP_DB):
     return _bss_sdr_rows(x, y, [x.shape[1]] * x.shape[0], filter_length, clamp_db).reshape(batch)
 
 
+def stoi(input, target, fs, extended=False):
+    """STOI (extended=False) or extended STOI of the estimate `input` against the clean `target` [..., T] -> [...], both at rate
+    `fs`, from the definition in include/ouniverse.h (resampling to 10 kHz, silent-frame removal, one-third-octave bands,
+    30-frame segments), as metrics/wrapper.py:116-128 asks pystoi for them.  A signal that ends with fewer than 30 frames
+    scores 1e-5."""
+    x, y, batch = _flatten(input, target, "stoi")
+    return _stoi_rows(x, y, [x.shape[1]] * x.shape[0], fs, extended).reshape(batch)
+
+
+def check_intelligibility_names(names):
+    """The names `evaluate_many(intelligibility=...)` accepts, in order; ValueError for any other."""
+    out = list(names or ())
+    for n in out:
+        if n not in INTELLIGIBILITY_METRICS:
+            raise ValueError(f"intelligibility: {n!r} is not one of {', '.join(INTELLIGIBILITY_METRICS)}")
+    return out
+
+
 def check_metric_names(metrics):
     """The names `Metrics` accepts, in order; NotImplementedError for any other (metrics/wrapper.py:76-79)."""
     out = []
@@ -326,13 +376,19 @@ def _score_rows(names, x, y, lens, fs):
     return {k: v.tolist() for k, v in cols.items() if k in names}  # (the one host synchronisation per metric)
 
 
-def evaluate_many(est_list, ref_list, fs, metrics=None):
+def evaluate_many(est_list, ref_list, fs, metrics=None, intelligibility=()):
     """Score pairs (estimate, reference) of 1-D signals of any lengths at rate fs: ONE library call per metric over all pairs,
     every pair scored as `Metrics(metrics)(fs, est, ref)` scores it alone.  -> one dict per pair.  `metrics` may also name
-    "sdr" (OPTIONAL_METRICS): the BSS-eval SDR as `sdr` computes it, one ou_sdr call over all pairs."""
+    "sdr" (OPTIONAL_METRICS): the BSS-eval SDR as `sdr` computes it, one ou_sdr call over all pairs.  `intelligibility` names
+    scores of INTELLIGIBILITY_METRICS ("stoi", "stoi-ext"): their columns follow the others, one ou_stoi call per name over all
+    pairs; anything else there is a ValueError."""
     names = check_score_names(metrics)
+    extra = check_intelligibility_names(intelligibility)
     x, y, lens = pack_pairs(est_list, ref_list)
-    return unpack_scores(names, _score_rows(names, x, y, lens, fs), len(lens))
+    cols = _score_rows(names, x, y, lens, fs)
+    for name in extra:
+        cols[name] = _stoi_rows(x, y, lens, fs, name == "stoi-ext").tolist()
+    return unpack_scores(names + [n for n in extra if n not in names], cols, len(lens))
 
 
 class Metrics:
