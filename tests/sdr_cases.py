@@ -10,7 +10,11 @@ reads them.  COLOURED is the same at L = 64, T = 4097 with a one-pole low-passed
 A case is `gated` when the accuracy gate of test_gpu_sdr.py applies to it: cond(R) <= 1e8 and the restatement inside [-40, 60]
 dB, so that neither the clamp nor hopeless conditioning is what the gate measures -- both are asserted by test_sdr_cpu.py.
 The cases with T = 1 cannot be: one sample of the estimate is always a multiple of one sample of the reference, the
-projection is the estimate itself and the SDR is infinite.  They stay in the table and must score +clamp_db."""
+projection is the estimate itself and the SDR is infinite.  They stay in the table and must score +clamp_db.
+
+`edge` holds what that table stops short of: filter lengths either side of the switch between one and two accumulator tiles
+of the correlation kernel (255, 256, 257) and 511, a coloured reference at 257 taps, a row of 32 correlation tiles.  MANY are
+ragged calls of 130 rows -- three launch groups -- with the one longest row last or first."""
 import functools
 
 import numpy as np
@@ -95,3 +99,62 @@ assert len(RAGGED) == 5
 
 def by_name(name):
     return next(c for c in CASES + [COLOURED] if c.name == name)
+
+
+# ---- the edges the table above stops short of ----
+#: filter lengths either side of the switch between one accumulator tile of 256 lags and two, and one below the cap
+EDGE_FILTER_LENGTHS = (255, 256, 257, 511)
+#: every edge case by name; "T+" stands for the first length with a second correlation tile, which the caller finds from the
+#: scratch sizer (the `_tile()` of test_gpu_sdr.py) and hands to `edge`
+EDGE_NAMES = tuple(f"edge-L{L}-T{T}" for L in EDGE_FILTER_LENGTHS for T in ("L+1", "tile+1")) + (
+    "edge-coloured-L257-T4097", "edge-L64-T65537")
+
+
+def tile_from(scratch_bytes):
+    """Samples per correlation tile, from the scratch sizer (pure host code): the last T that costs what T = 1 costs."""
+    lo, hi, base = 1, 1 << 20, scratch_bytes(1, 1, 512)
+    assert scratch_bytes(1, hi, 512) > base
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        lo, hi = (mid, hi) if scratch_bytes(1, mid, 512) == base else (lo, mid - 1)
+    return lo
+
+
+@functools.lru_cache(maxsize=None)
+def edge(tile):
+    """{name: Case} of EDGE_NAMES for a correlation tile of `tile` samples: L in EDGE_FILTER_LENGTHS at T = L + 1 (one tile,
+    barely more samples than lags) and T = tile + 1 (one sample in a second tile); a coloured reference (pole 0.9) on the
+    two-accumulator-tile path; and a row of 32 correlation tiles at L = 64 (the shift matrix of `sdr_lstsq` is 34 MB)."""
+    out, i = {}, 0
+    for L in EDGE_FILTER_LENGTHS:
+        for label, T in (("L+1", L + 1), ("tile+1", tile + 1)):
+            out[f"edge-L{L}-T{label}"] = Case(f"edge-L{L}-T{T}", L, T, TARGET_DB[i % len(TARGET_DB)], 2000 + i)
+            i += 1
+    out["edge-coloured-L257-T4097"] = Case("edge-coloured-L257-T4097", 257, 4097, 20.0, 78, pole=0.9)
+    out["edge-L64-T65537"] = Case("edge-L64-T65537", 64, 65537, 10.0, 2010)
+    assert tuple(out) == EDGE_NAMES
+    return out
+
+
+class Many:
+    """A ragged call of 130 rows -- launch groups of 64, 64 and 2 -- at one filter length.  The lengths cycle over a short list,
+    so the rows reuse a few pairs and every distinct pair has its references computed once; rows 63, 64, 127 and 128 -- the
+    last and first rows of the groups -- hold one sample; `longest_at` (0 or 129) holds the one row of `longest` samples, so
+    either the first group or the last is the one whose grid is as large as the call's strides."""
+    ROWS, DEGENERATE = 130, (63, 64, 127, 128)
+
+    def __init__(self, L, cycle, longest, longest_at, seed):
+        assert longest > max(cycle) and longest_at in (0, self.ROWS - 1)
+        self.L, self.longest_at = L, longest_at
+        pool = {T: Case(f"many-L{L}-T{T}", L, T, TARGET_DB[k % len(TARGET_DB)], seed + k)
+                for k, T in enumerate(list(cycle) + [1, longest])}
+        self.cases = [pool[1] if b in self.DEGENERATE else pool[longest] if b == longest_at else pool[cycle[b % len(cycle)]]
+                      for b in range(self.ROWS)]
+
+    def __repr__(self):
+        return f"many-L{self.L}-longest-at-{self.longest_at}"
+
+
+#: the 130-row calls: L = 64 and L = 257 (one and two accumulator tiles), the longest row last and first
+MANY = [Many(L, (5, L - 1, L + 1, 700), 4097, at, 3000 + 100 * k + 10 * j)
+        for k, L in enumerate((64, 257)) for j, at in enumerate((129, 0))]

@@ -14,7 +14,11 @@ overlapping by half, "every other frame silent" cannot be made from samples (a k
 a hop with each): the `alternate` case removes every third frame, the densest pattern there is.
 
 A case is `gated` when the restatements' threshold margin is at least 1e-6 dB and it has at least 30 frames: a condition on the
-inputs, not a measurement.  The cases built to have fewer than 30 frames carry `short`: they must score float32(1e-5)."""
+inputs, not a measurement.  The cases built to have fewer than 30 frames carry `short`: they must score float32(1e-5).
+
+EDGE holds what those tables stop short of: rows of more than 1024 energy frames (the chunk of the kernel's kept-frame scan),
+45 and 46 frames (its segment tile), 48, 22.05, 6 and 12 kHz, and 14 s at 48 kHz.  MANY are ragged calls of 130 rows -- three
+launch groups -- with the one longest row last or first, at 10 and at 16 kHz."""
 import functools
 
 import numpy as np
@@ -146,3 +150,68 @@ def by_name(name, tile=16):
 
 #: the ragged batch: six rows at 10 kHz mixing the above
 RAGGED = [by_name(n) for n in ("frames-29", "start-k30+1", "silent-leading", "T-255", "silent-alternate", "frames-31")]
+
+
+# ---- the edges the tables above stop short of ----
+MASK_CHUNK = 1024  # frames per pass of the kept-frame scan (stoi_mask_kernel)
+SEG_TILE_FRAMES = 45  # 16 segments of 30 frames: one segment tile (stoi_seg_kernel); 46 frames start a second
+
+
+def _edge():
+    n = length_for
+    out = [
+        # energy frames round one and two chunks of the kept-frame scan, no silent frame: length_for(J) has J + 1 of them
+        *(Case(f"mask-{e}", n(e - 1), 300 + i) for i, e in enumerate((1023, 1024, 1025, 2048, 2049))),
+        # 2101 energy frames, a silent stretch across frame 1024 and one across frame 2048: the running base of chunks 2 and 3
+        # is not the chunk's first frame, and kept frames are missing on both sides of each border
+        Case("mask-silent-2100", n(2100), 310, silent_hops=list(range(1000, 1040)) + list(range(2040, 2060))),
+        # exactly one segment tile, and the first segment of a second
+        Case("segtile-45", n(SEG_TILE_FRAMES), 320), Case("segtile-46", n(SEG_TILE_FRAMES + 1), 321),
+        # rates: one second each, an interior stretch of five hops removed; 6 kHz up-samples by 5 / 3
+        Case("fs-48000", 48000, 330, fs=48000, silent_hops=range(30, 35)), Case("fs-22050", 22050, 331, fs=22050, silent_hops=range(40, 45)),
+        Case("fs-6000", 6000, 332, fs=6000, silent_hops=range(20, 25)), Case("fs-12000", 12000, 333, fs=12000, silent_hops=range(50, 55)),
+        # 14 s at 48 kHz: the resampler feeds a second chunk of the scan, a silent stretch across energy frame 1024
+        Case("long-48000", 14 * 48000, 334, fs=48000, silent_hops=range(1010, 1040)),
+    ]
+    return out
+
+
+EDGE = _edge()
+
+
+def edge_by_name(name):
+    return next(c for c in EDGE if c.name == name)
+
+
+class Many:
+    """A ragged call of 130 rows -- launch groups of 64, 64 and 2 -- at one rate.  The rows cycle over a short list of cases, so
+    every distinct pair has its references computed once; rows 63, 64, 127 and 128 -- the last and first rows of the groups --
+    hold one sample and a row of fewer than 30 frames; `longest_at` (0 or 129) holds the one longest row, so either the first
+    group or the last is the one whose grid is as large as the call's strides."""
+    ROWS, DEGENERATE = 130, (63, 64, 127, 128)
+
+    def __init__(self, fs, cycle, degenerate, longest, longest_at):
+        assert longest.T > max(c.T for c in cycle) and longest_at in (0, self.ROWS - 1) and {c.fs for c in cycle + [longest]} == {fs}
+        self.fs, self.longest_at = fs, longest_at
+        self.cases = [degenerate[self.DEGENERATE.index(b) % len(degenerate)] if b in self.DEGENERATE else
+                      longest if b == longest_at else cycle[b % len(cycle)] for b in range(self.ROWS)]
+
+    def __repr__(self):
+        return f"many-fs{self.fs}-longest-at-{self.longest_at}"
+
+
+def _many():
+    n = by_name
+    cycle = [n("frames-29"), n("frames-30"), n("start-k31+1"), n("silent-leading"), n("silent-leaves-30"), n("tile-33"),
+             edge_by_name("segtile-46")]
+    short = [n("one-sample"), n("T-255"), n("frames-28"), n("one-sample")]
+    out = [Many(R.FS, cycle, short, n("silent-alternate"), at) for at in (129, 0)]  # the longest row: length_for(60)
+    # 16 kHz: rows of 41 and 43 frames before removal and one below the cut, one sample at the group borders, 1.2 s the longest
+    cycle16 = [n("fs-16000"), Case("fs-16000-b", 9300, 340, fs=16000, silent_hops=range(20, 24)),
+               Case("fs-16000-short", 6000, 341, fs=16000, short=True)]
+    short16 = [Case("fs-16000-one-sample", 1, 342, fs=16000, short=True), Case("fs-16000-T-300", 300, 343, fs=16000, short=True)]
+    longest16 = Case("fs-16000-long", 19200, 344, fs=16000, silent_hops=range(60, 66))
+    return out + [Many(16000, cycle16, short16, longest16, at) for at in (129, 0)]
+
+
+MANY = _many()

@@ -11,10 +11,15 @@ against a recording of it.
 
 Shapes: every (L, T) of the case table -- T below, at and above L, one sample, rows of two to four correlation tiles, both
 accumulator plans (L <= 256: one tile of 256 lags, L = 512: two) --, T around the correlation tile (found from the scratch
-sizer), a ragged batch of five rows, and the clamp.
+sizer), a ragged batch of five rows, and the clamp.  The edges (sdr_cases.edge): L = 255, 256, 257 and 511 -- either side of
+the switch between the accumulator plans, and one below the cap -- at T = L + 1 and T = tile + 1, a coloured reference at
+L = 257, T = 4097, and L = 64 at T = 65537 (32 correlation tiles).  Ragged calls of 130 rows (sdr_cases.MANY: launch groups
+of 64, 64 and 2) at L = 64 and 257, one sample at rows 63, 64, 127 and 128, the one row of two tiles last or first.
 
 Measured on an MI355X (DESIGN 4.21 has the table): distance / bound 0.007 .. 0.50 over the 33 gated cases and the 8 tile
-cases -- the rounding of `out` to fp32 -- and every row of the ragged batch equal to the row scored alone."""
+cases -- the rounding of `out` to fp32 -- and every row of the ragged batch equal to the row scored alone; 0.02 .. 0.49 over
+the 10 edge cases, 0.04 .. 0.45 over the rows of the 130-row calls, each of their rows equal to the row scored alone."""
+import functools
 import json
 
 import numpy as np
@@ -113,6 +118,60 @@ def test_tile_boundaries(L):
         case = C.Case(f"tile-L{L}-T{T}", L, T, 10.0, 500 + T % 7)
         assert case.cond <= C.COND_MAX and C.DB_MIN <= case.lstsq <= C.DB_MAX
         _check(case, _score(case))
+
+
+@pytest.mark.parametrize("name", C.EDGE_NAMES)
+def test_edge_accuracy_gate(name):
+    """The accumulator-tile switch of sdr_corr_kernel -- L = 255 and 256 on one tile of 256 lags, 257 and 511 on two, where the
+    `lag < L` guard of the write-out drops 255 and 1 lags of the second tile -- at T = L + 1 and one sample into a second
+    correlation tile; a coloured reference on the two-tile path; and an SDR row of many tiles (32 at T = 65537), where the
+    solver's ascending sum over tiles is long.  The gate of every other case."""
+    case = C.edge(_tile())[name]
+    _check(case, _score(case))
+
+
+@functools.lru_cache(maxsize=None)
+def _many_rows(k):
+    """The 130 rows of C.MANY[k] in one (130, stride) buffer each, NaN behind every row; every distinct pair uploaded once."""
+    many = C.MANY[k]
+    lens = [c.T for c in many.cases]
+    x = torch.full((len(lens), max(lens) + 4), float("nan"), device=DEV)
+    y = torch.full_like(x, float("nan"))
+    dev = {c.name: (_dev(c.pair[0]), _dev(c.pair[1])) for c in many.cases}
+    for b, c in enumerate(many.cases):
+        x[b, :c.T], y[b, :c.T] = dev[c.name]
+    return x, y, lens
+
+
+@pytest.mark.parametrize("k", range(len(C.MANY)), ids=[repr(m) for m in C.MANY])
+def test_130_rows_in_one_call(k):
+    """Rows 64 and up: 130 ragged rows are launch groups of 64, 64 and 2, so the second and third run with row0 = 64 and 128
+    (signals, tsum, partial and out at row0 + block, the by-value lengths at the block), one sample at rows 63, 64, 127, 128.
+    Per-group grid against per-call strides: with the longest row last, groups 0 and 1 run grids of one tile inside a tile
+    stride of two; with it first, groups 1 and 2 do.  At L = 64 and at L = 257 (one and two accumulator tiles).  Two runs are
+    bit-identical, zeros for the NaN behind the rows change nothing, EVERY row is bit for bit its own B = 1 call, and every
+    row holds the gate or, at one sample, scores the clamp."""
+    many = C.MANY[k]
+    x, y, lens = _many_rows(k)
+    assert _tile() < max(lens) and sorted(lens)[-2] <= _tile()  # the longest row alone reaches a second tile
+    a = M._bss_sdr_rows(x, y, lens, many.L, 100.0)
+    assert a.shape == (130,) and bool(torch.isfinite(a).all())
+    assert torch.equal(a, M._bss_sdr_rows(x, y, lens, many.L, 100.0))
+    assert torch.equal(a, M._bss_sdr_rows(torch.nan_to_num(x, nan=0.0), torch.nan_to_num(y, nan=0.0), lens, many.L, 100.0))
+    alone = torch.stack([M.sdr(x[i, :n], y[i, :n], filter_length=many.L) for i, n in enumerate(lens)])
+    a, alone = a.cpu(), alone.cpu()
+    differ = [(i, lens[i], float(a[i]), float(alone[i])) for i in range(len(lens)) if a[i] != alone[i]]
+    assert not differ, (many, differ[:8])
+    seen = set()
+    for i, c in enumerate(many.cases):
+        lib = float(a[i])
+        if not c.gated:
+            assert lib == pytest.approx(100.0, abs=R.ulp32(100.0)), (many, i, lib)
+        elif c.name in seen:
+            assert abs(lib - c.lstsq) <= c.bound(), (many, i, c, lib, c.lstsq)
+        else:
+            _check(c, lib)
+            seen.add(c.name)
 
 
 def test_clamp_and_degenerate_inputs():

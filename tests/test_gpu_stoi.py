@@ -12,12 +12,17 @@ recording of it.
 Shapes: the frame count round the cut of 30 and one sample either side of a frame start, frame counts round one, two and three
 STFT frame tiles of the kernel (ou_stoi_frame_tile), silent stretches (leading, trailing, interior, every third frame, leaving
 exactly 30 and 29 frames), 8, 16, 24 and 44.1 kHz, one sample, 255 samples, an all-zero clean signal, 3 s at 16 kHz, and a
-ragged batch of six rows.
+ragged batch of six rows.  The edges (stoi_cases.EDGE): 1023, 1024, 1025, 2048 and 2049 energy frames with none silent and 2101
+with silent stretches across frames 1024 and 2048 (the chunks of the kept-frame scan), 45 and 46 frames (the segment tile),
+one second at 48, 22.05, 6 and 12 kHz, and 14 s at 48 kHz.  Ragged calls of 130 rows (stoi_cases.MANY: launch groups of 64, 64
+and 2) at 10 and 16 kHz, one sample or a row below 30 frames at rows 63, 64, 127 and 128, the one longest row last or first;
+`evaluate_many` on 70 pairs.
 
 Measured on an MI355X (DESIGN 4.22 has the table): distance / bound 0.00 .. 0.49 over the 22 gated cases in both forms -- the
 rounding of `out` to fp32 --, every below-30 case exactly float32(1e-5), and every row of the ragged batch equal to the row
-scored alone."""
+scored alone; 0.01 .. 0.47 over the 13 edge cases in both forms, and each of the 130 rows equal to the row scored alone."""
 import ctypes
+import functools
 import json
 
 import numpy as np
@@ -116,6 +121,81 @@ def test_rows_in_a_batch_at_another_rate():
     for i, c in enumerate(cases):
         assert torch.equal(both[i], M.stoi(est[i], ref[i], 16000)), c
         _check(c, False, float(both[i]))
+
+
+@pytest.mark.parametrize("extended", FORMS, ids=("stoi", "estoi"))
+@pytest.mark.parametrize("case", C.EDGE, ids=repr)
+def test_edge_accuracy_gate(case, extended):
+    """mask-*: more than 1024 energy frames in stoi_mask_kernel -- 1023, 1024, 1025, 2048 and 2049 frames with none silent,
+    and 2101 with silent stretches across frames 1024 and 2048, so the scan's second and third chunks run with a carried base
+    that is not the chunk's first frame and `src` is written past the first chunk.  segtile-*: the segment-tile border of
+    stoi_seg_kernel, 45 frames (exactly one tile of 16 segments) and 46 (the first segment of a second).  fs-*: the resampling
+    ratios 5/24 (48 kHz), 200/441 (22.05 kHz), 5/3 (6 kHz, up-sampling) and 5/6 (12 kHz); long-48000: 14 s at 48 kHz, a
+    resampled row that needs a second mask chunk.  The gate of every other case."""
+    _check(case, extended, _score(case, extended))
+
+
+@functools.lru_cache(maxsize=None)
+def _many_rows(k):
+    """The 130 rows of C.MANY[k] in one (130, stride) buffer each, NaN behind every row; every distinct pair uploaded once."""
+    many = C.MANY[k]
+    lens = [c.T for c in many.cases]
+    x = torch.full((len(lens), max(lens) + 4), float("nan"), device=DEV)
+    y = torch.full_like(x, float("nan"))
+    dev = {c.name: (_dev(c.pair[0]), _dev(c.pair[1])) for c in many.cases}
+    for b, c in enumerate(many.cases):
+        x[b, :c.T], y[b, :c.T] = dev[c.name]
+    return x, y, lens
+
+
+#: (index into C.MANY, extended): 10 kHz in both forms and both arrangements, 16 kHz in one form per arrangement
+MANY_CALLS = [(0, False), (0, True), (1, False), (1, True), (2, False), (3, True)]
+
+
+@pytest.mark.parametrize("k,extended", MANY_CALLS, ids=[f"{C.MANY[k]}-{'estoi' if e else 'stoi'}" for k, e in MANY_CALLS])
+def test_130_rows_in_one_call(k, extended):
+    """Rows 64 and up: 130 ragged rows are launch groups of 64, 64 and 2, so the second and third run with row0 = 64 and 128
+    in every kernel (signals, res_*, energy, src, count, bands, partial and out at row0 + block, the by-value lengths at the
+    block), one sample and a row below 30 frames at rows 63, 64, 127, 128.  Per-group grid against per-call strides: with the
+    longest row last, groups 0 and 1 run grids sized by their own rows inside F, seg_stride and n10 of the call; with it first,
+    groups 1 and 2 do.  At 16 kHz stoi_resample_kernel has its own row0 and res_* the call-wide n10 stride.  Two runs are
+    bit-identical, zeros for the NaN behind the rows change nothing, EVERY row is bit for bit its own B = 1 call, and every row
+    holds the gate or scores the constant."""
+    many = C.MANY[k]
+    x, y, lens = _many_rows(k)
+    a = M._stoi_rows(x, y, lens, many.fs, extended)
+    assert a.shape == (130,) and bool(torch.isfinite(a).all())
+    assert torch.equal(a, M._stoi_rows(x, y, lens, many.fs, extended))
+    assert torch.equal(a, M._stoi_rows(torch.nan_to_num(x, nan=0.0), torch.nan_to_num(y, nan=0.0), lens, many.fs, extended))
+    alone = torch.stack([M.stoi(x[i, :n], y[i, :n], many.fs, extended=extended) for i, n in enumerate(lens)])
+    a, alone = a.cpu(), alone.cpu()
+    differ = [(i, lens[i], float(a[i]), float(alone[i])) for i in range(len(lens)) if a[i] != alone[i]]
+    assert not differ, (many, extended, differ[:8])
+    seen = set()
+    for i, c in enumerate(many.cases):
+        lib = float(a[i])
+        if c.short:
+            assert np.float32(lib) == np.float32(1e-5), (many, i, c, lib)
+        elif c.name in seen:
+            assert c.gated and abs(lib - c.vec(extended).score) <= c.bound(extended), (many, i, c, lib)
+        else:
+            _check(c, extended, lib)
+            seen.add(c.name)
+
+
+def test_evaluate_many_on_70_pairs_is_the_per_pair_functions():
+    """The wiring past one launch group: pack_pairs and the column unpacking are the only Python between `evaluate_many` and
+    the calls, and 70 pairs put six of them behind row 64 (rows 64 and up of ou_si_sdr, ou_sdr and ou_stoi in one go)."""
+    cases = C.MANY[0].cases[:70]
+    dev = {c.name: (_dev(c.pair[0]), _dev(c.pair[1])) for c in cases}
+    est, ref = [dev[c.name][0] for c in cases], [dev[c.name][1] for c in cases]
+    rows = M.evaluate_many(est, ref, R.FS, metrics=["si-sdr", "sdr"], intelligibility=("stoi",))
+    assert len(rows) == 70
+    want = {name: {"si-sdr": float(M.si_sdr(e, r)), "sdr": float(M.sdr(e, r)), "stoi": float(M.stoi(e, r, R.FS))}
+            for name, (e, r) in dev.items()}
+    for i, (c, row) in enumerate(zip(cases, rows)):
+        assert list(row) == ["si-sdr", "sdr", "stoi"]
+        assert row == want[c.name], (i, c, row, want[c.name])
 
 
 def test_identity_gain_and_shape():

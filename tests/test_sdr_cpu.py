@@ -37,6 +37,54 @@ def test_restatements_agree_and_the_case_can_be_gated(case):
     assert case.d_ref <= 0.01 * R.ulp32(case.lstsq)
 
 
+def _can_be_gated(case):
+    print(f"{case}: lstsq {case.lstsq:.12f} normal {case.normal:.12f} d_ref {case.d_ref:.3g} cond {case.cond:.4g} "
+          f"ulp32 {R.ulp32(case.lstsq):.3g}")
+    assert np.isfinite(case.lstsq) and np.isfinite(case.normal)
+    assert case.cond <= C.COND_MAX
+    assert C.DB_MIN <= case.lstsq <= C.DB_MAX
+    assert case.d_ref <= 1e-6 * max(1.0, abs(case.lstsq))
+    assert case.d_ref <= 0.01 * R.ulp32(case.lstsq)
+
+
+@pytest.mark.parametrize("name", C.EDGE_NAMES)
+def test_edge_cases_can_be_gated(built_lib, name):
+    """The edge table (L = 255, 256, 257, 511 at T = L + 1 and one sample into a second correlation tile; a coloured reference
+    at L = 257; 32 tiles at L = 64): every case is well conditioned and away from the clamp, as the table cases are."""
+    tile = C.tile_from(M.sdr_scratch_bytes)
+    case = C.edge(tile)[name]
+    assert case.gated and case.L in C.EDGE_FILTER_LENGTHS + (64,)
+    if name.endswith("tile+1"):
+        assert case.T == tile + 1 and M.sdr_scratch_bytes(1, case.T, 512) > M.sdr_scratch_bytes(1, case.T - 1, 512)
+    _can_be_gated(case)
+
+
+def test_edge_table_is_the_one_asked_for(built_lib):
+    tile = C.tile_from(M.sdr_scratch_bytes)
+    E = C.edge(tile)
+    assert {(c.L, c.T) for c in E.values()} == {(L, T) for L in (255, 256, 257, 511) for T in (L + 1, tile + 1)} | {
+        (257, 4097), (64, 65537)}
+    assert E["edge-coloured-L257-T4097"].pole == 0.9 and E["edge-coloured-L257-T4097"].cond > 100.0
+    assert -(-65537 // tile) >= 32  # many tiles: the solver's ascending sum is long
+    assert not {c.name for c in E.values()} & {c.name for c in C.CASES + [C.COLOURED]}
+
+
+@pytest.mark.parametrize("many", C.MANY, ids=repr)
+def test_rows_of_the_130_row_calls_can_be_gated(many):
+    """130 rows: groups of 64, 64 and 2; one sample at the group borders; the one longest row first or last; every other row
+    has a restatement the gate can be held against."""
+    assert len(many.cases) == 130 and [many.cases[b].T for b in (63, 64, 127, 128)] == [1] * 4
+    lens = [c.T for c in many.cases]
+    assert lens.index(max(lens)) == many.longest_at and lens.count(max(lens)) == 1 and max(lens) == 4097
+    assert {c.L for c in many.cases} == {many.L}
+    distinct = {c.name: c for c in many.cases}
+    assert len(distinct) <= 8  # the references are computed once per distinct pair
+    for c in distinct.values():
+        if c.gated:
+            _can_be_gated(c)
+    assert {(m.L, m.longest_at) for m in C.MANY} == {(64, 129), (64, 0), (257, 129), (257, 0)}
+
+
 def test_target_ratios_are_covered():
     got = [c.lstsq for c in C.GATED]
     assert min(got) < -15.0 and max(got) > 33.0  # about -20 .. +35 dB

@@ -44,6 +44,55 @@ def test_restatements_agree(case):
             assert case.d_ref(ext) <= 0.01 * max(R.ulp32(v.score), 1e-9)
 
 
+def _many_only():
+    """The cases the 130-row calls add to the tables (the 16 kHz rows), once each."""
+    known = {c.name for c in TABLE + C.EDGE}
+    return list({c.name: c for m in C.MANY for c in m.cases if c.name not in known}.values())
+
+
+@pytest.mark.parametrize("case", C.EDGE + _many_only(), ids=repr)
+def test_edge_restatements_agree_and_the_case_can_be_gated(case):
+    """The edge table and the rows of the 130-row calls, as test_restatements_agree holds the case table; and every case not
+    built short is gated -- margin, at least 30 frames, both restatements on one frame count."""
+    test_restatements_agree(case)
+    assert case.gated == (not case.short), (case, case.margin, case.frames, case.direct().frames)
+    if not case.short:
+        assert case.margin >= C.MARGIN_MIN_DB and case.frames >= R.SEGMENT and case.direct().frames == case.frames
+
+
+def test_edge_table_is_the_one_asked_for():
+    E = {c.name: c for c in C.EDGE}
+    assert len(E) == len(C.EDGE) and not set(E) & {c.name for c in TABLE}
+    energy = lambda c: len(R.frame_starts(-(-c.T * R.ratio(c.fs)[0] // R.ratio(c.fs)[1])))  # frames before the silent ones go
+    # the kept-frame scan walks chunks of 1024 energy frames: one short of a chunk, a chunk, one more, two chunks, one more
+    assert [energy(E[f"mask-{e}"]) for e in (1023, 1024, 1025, 2048, 2049)] == [1023, 1024, 1025, 2048, 2049]
+    assert [E[f"mask-{e}"].frames for e in (1023, 1024, 1025, 2048, 2049)] == [1022, 1023, 1024, 2047, 2048]  # none silent
+    s = E["mask-silent-2100"]
+    assert energy(s) == 2101 and s.T == C.length_for(2100) and s.frames < 2100 - 50
+    for border in (C.MASK_CHUNK, 2 * C.MASK_CHUNK):  # silent hops on both sides of each chunk border
+        assert {border - 2, border - 1, border, border + 1} <= set(s.silent_hops)
+    # the segment tile: 45 frames are 16 segments, 46 are 17
+    assert (E["segtile-45"].frames, E["segtile-46"].frames) == (C.SEG_TILE_FRAMES, C.SEG_TILE_FRAMES + 1) == (45, 46)
+    assert not E["segtile-45"].silent_hops and not E["segtile-46"].silent_hops
+    assert [R.ratio(E[f"fs-{fs}"].fs) for fs in (48000, 22050, 6000, 12000)] == [(5, 24), (200, 441), (5, 3), (5, 6)]
+    assert all(E[f"fs-{fs}"].silent_hops and 60 <= E[f"fs-{fs}"].frames <= 75 for fs in (48000, 22050, 6000, 12000))
+    lg = E["long-48000"]
+    assert lg.fs == 48000 and lg.T == 14 * 48000 and energy(lg) > C.MASK_CHUNK + 30 and lg.frames > 1024
+    assert {C.MASK_CHUNK - 1, C.MASK_CHUNK, C.MASK_CHUNK + 1} <= set(lg.silent_hops)
+
+
+def test_the_130_row_calls_are_the_ones_asked_for():
+    assert [(m.fs, m.longest_at) for m in C.MANY] == [(R.FS, 129), (R.FS, 0), (16000, 129), (16000, 0)]
+    for m in C.MANY:
+        lens = [c.T for c in m.cases]
+        assert len(lens) == 130 and lens.index(max(lens)) == m.longest_at and lens.count(max(lens)) == 1
+        assert {c.fs for c in m.cases} == {m.fs} and len({c.name for c in m.cases}) <= 12
+        border = [m.cases[b] for b in (63, 64, 127, 128)]
+        assert all(c.short for c in border) and 1 in {c.T for c in border} and {c.T for c in border} - {1}
+        assert sum(not c.short for c in m.cases) > 80 and sum(c.short for c in m.cases) > 4
+    assert max(c.T for c in C.MANY[0].cases) == C.length_for(60)
+
+
 def test_the_cases_that_cannot_be_gated_are_the_ones_built_short():
     """`gated` is a condition on the inputs: a threshold margin of at least 1e-6 dB and at least 30 frames.  Every case that
     fails it was built to have fewer than 30 frames; no case fails it on the margin (they clear it by decibels)."""
