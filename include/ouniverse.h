@@ -778,6 +778,37 @@ int ou_flac_info(const uint8_t* data, size_t bytes, int32_t* sample_rate, int32_
                  int64_t* total_samples, uint8_t* md5 /* 16 bytes, all zero = not recorded */);
 int ou_flac_decode(const uint8_t* data, size_t bytes, int32_t* out, int64_t capacity_per_channel, int64_t* decoded);
 
+/* ---- output files of the CLI ------------------------------------------------------------------------------ */
+/* FLAC encoder for fp32 rows that live on the device (extension; the reference writes its results with torchaudio.save,
+ * bin/enhance.py:77-80).  The stream is byte for byte the one audio.flac_encode of the Python package writes for the samples
+ * q = clip(rint(x * 2^(bps - 1)), -2^(bps - 1), 2^(bps - 1) - 1) (round half to even; NaN -> 0): fixed blocks of 4096 samples,
+ * independent channels, per channel and block the fixed predictor of order 2 with one Rice partition (k from the mean of the
+ * folded residual) or a verbatim subframe where that is not longer, STREAMINFO with the MD5 of the samples.  Three calls:
+ *   ou_flac_encode_sizes  : pure host.  frames_bytes / pcm_bytes: the device buffers of the next call (and their host copies);
+ *                           n_frames: blocks of all files = entries of frame_bytes; stream_capacity[f] (may be NULL): an upper
+ *                           bound of file f's stream, their sum always suffices as out_capacity.
+ *   ou_flac_encode_frames : file f owns channels[f] consecutive rows of x (row_stride floats apart), each len[f] long; nothing
+ *                           behind a row's length is read.  One workgroup per (file, block) quantises, codes and packs; all
+ *                           files of a call go in launches of 64 files.  Writes, file after file and block after block, one
+ *                           frame per slot of 16 + ceil(channels * (8 + 4096 * bps) / 8) + 2 bytes rounded up to 16 (frames), its
+ *                           byte count (frame_bytes, the CRC-16 included, whose two bytes are left zero), and per file the
+ *                           interleaved little-endian samples at bps / 8 bytes, rounded up to 16 bytes (pcm).  What the buffers
+ *                           held before does not matter.  frames and pcm 16-byte aligned.  Enqueued on `stream`: no allocation,
+ *                           no host synchronisation, capturable.
+ *   ou_flac_assemble      : pure host, on host copies of the three buffers once the stream has been synchronised: CRC-16 of
+ *                           every frame, MD5, STREAMINFO; stream f is out[offsets[f] .. offsets[f + 1]).
+ * OU_EINVAL with a message (ou_flac_last_error), before any HIP call: files < 1, channels outside 1 .. 8, bps not 16 or 24, fs
+ * outside 1 .. 2^20 - 1, a length below 1 or above 2^36 - 1, row_stride below the longest length, a null or misaligned buffer, a
+ * frame size the kernel cannot have written.  OU_ESHAPE: frames_bytes, pcm_bytes or out_capacity too small. */
+int ou_flac_encode_sizes(int32_t files, const int32_t* channels_host, const int64_t* len_host, int32_t bps, size_t* frames_bytes,
+                         int64_t* n_frames, size_t* pcm_bytes, int64_t* stream_capacity);
+int ou_flac_encode_frames(const float* x, int64_t row_stride, int32_t files, const int32_t* channels_host,
+                          const int64_t* len_host, int32_t bps, void* frames, size_t frames_bytes, int32_t* frame_bytes,
+                          void* pcm, size_t pcm_bytes, ou_stream_t stream);
+int ou_flac_assemble(const uint8_t* frames_host, const int32_t* frame_bytes_host, const uint8_t* pcm_host, int32_t files,
+                     const int32_t* channels_host, const int64_t* len_host, int32_t fs, int32_t bps, uint8_t* out,
+                     size_t out_capacity, int64_t* offsets);
+
 /* Measurement / tuning entry points (ou_profile_*, ou_bench_conv) are declared in ouniverse_tuning.h. */
 
 #ifdef __cplusplus

@@ -478,3 +478,116 @@ def save_flac(path, audio, fs, bits_per_sample=24):
     full = float(1 << (bits_per_sample - 1))
     q = np.clip(np.rint(x * full), -full, full - 1).astype(np.int64)
     Path(path).write_bytes(flac_encode(q, int(fs), bits_per_sample))
+
+
+# ---- the same stream from the device (ou_flac_encode_frames, csrc/ou_flac_encode.hip): quantisation, residuals, Rice codes and
+# bit packing of all files of a call in one kernel per 64 files, CRC-16 / MD5 / STREAMINFO in the library's host stage
+# (ou_flac_assemble).  Byte for byte what `flac_encode` writes for the samples `save_flac` would quantise (a NaN sample, which
+# numpy leaves undefined, encodes as 0).
+_pinned = {}
+
+
+def _pinned_bytes(key, nbytes):
+    """a pinned uint8 host buffer of at least `nbytes`, kept and grown per purpose"""
+    buf = _pinned.get(key)
+    if buf is None or buf.numel() < nbytes:
+        buf = torch.empty(max(nbytes, 1), dtype=torch.uint8, pin_memory=True)
+        _pinned[key] = buf
+    return buf[:nbytes]
+
+
+def _flac_encode_device(x, stride, channels, lens, bits_per_sample):
+    """ONE ou_flac_encode_frames call over the rows of x (file f: channels[f] consecutive rows of lens[f] samples) ->
+    (frames, frame_bytes, pcm) uint8 / int32 / uint8 tensors on the device.  No synchronisation."""
+    from . import _lib
+
+    L = _lib.load()
+    files = len(channels)
+    ch = (ctypes.c_int32 * files)(*channels)
+    ln = (ctypes.c_int64 * files)(*lens)
+    fb, nf, pb = ctypes.c_size_t(), ctypes.c_int64(), ctypes.c_size_t()
+    if L.ou_flac_encode_sizes(files, ch, ln, int(bits_per_sample), ctypes.byref(fb), ctypes.byref(nf), ctypes.byref(pb), None) != 0:
+        raise ValueError((L.ou_flac_last_error() or b"ou_flac_encode_sizes failed").decode())
+    frames = torch.empty(fb.value, dtype=torch.uint8, device=x.device)
+    sizes = torch.empty(nf.value, dtype=torch.int32, device=x.device)
+    pcm = torch.empty(pb.value, dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = L.ou_flac_encode_frames(ctypes.c_void_p(x.data_ptr()), int(stride), files, ch, ln, int(bits_per_sample),
+                                     ctypes.c_void_p(frames.data_ptr()), ctypes.c_size_t(fb.value),
+                                     ctypes.c_void_p(sizes.data_ptr()), ctypes.c_void_p(pcm.data_ptr()), ctypes.c_size_t(pb.value),
+                                     ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
+    if rc != 0:
+        msg = (L.ou_flac_last_error() or b"ou_flac_encode_frames failed").decode()
+        raise (RuntimeError if rc == _lib.OU_EHIP else ValueError)(msg)
+    return frames, sizes, pcm
+
+
+def _flac_assemble(frames, sizes, pcm, channels, lens, fs, bits_per_sample):
+    """host copies of the three buffers (numpy uint8 / int32 / uint8) -> list of streams (ou_flac_assemble)"""
+    from . import _lib
+
+    L = _lib.load()
+    files = len(channels)
+    ch = (ctypes.c_int32 * files)(*channels)
+    ln = (ctypes.c_int64 * files)(*lens)
+    cap = (ctypes.c_int64 * files)()
+    if L.ou_flac_encode_sizes(files, ch, ln, int(bits_per_sample), None, None, None, cap) != 0:
+        raise ValueError((L.ou_flac_last_error() or b"ou_flac_encode_sizes failed").decode())
+    out = np.empty(sum(cap), dtype=np.uint8)
+    off = (ctypes.c_int64 * (files + 1))()
+    rc = L.ou_flac_assemble(frames.ctypes.data_as(ctypes.c_void_p), sizes.ctypes.data_as(ctypes.c_void_p),
+                            pcm.ctypes.data_as(ctypes.c_void_p), files, ch, ln, int(fs), int(bits_per_sample),
+                            out.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(out.nbytes), off)
+    if rc != 0:
+        raise ValueError((L.ou_flac_last_error() or b"ou_flac_assemble failed").decode())
+    return [out[off[f]:off[f + 1]].tobytes() for f in range(files)]
+
+
+def flac_encode_many(signals, fs, bits_per_sample=24):
+    """signals: list of (T_i,) or (C_i, T_i) float tensors on one HIP device, in [-1, 1] -> list of `bytes`, the FLAC streams
+    `save_flac` would write (round to nearest even, clipped; 16 or 24 bits).  One device call over all channel rows of all
+    signals, one device-to-host copy per buffer (into pinned memory), one ou_flac_assemble.  There is no CPU path and no
+    fallback: ValueError for a CPU tensor."""
+    signals = list(signals)
+    if not signals:
+        return []
+    for s in signals:
+        if s.device.type != "cuda":
+            raise ValueError("flac_encode_many runs on a HIP device only: move the tensors there or use save_flac")
+        if s.ndim not in (1, 2):
+            raise ValueError("flac_encode_many: signals are (T,) or (C, T) tensors")
+        if s.device != signals[0].device:
+            raise ValueError("flac_encode_many: all signals must live on one device")
+    device = signals[0].device
+    channels = [1 if s.ndim == 1 else int(s.shape[0]) for s in signals]
+    lens = [int(s.shape[-1]) for s in signals]
+    if min(channels) < 1 or min(lens) < 1:
+        raise ValueError("flac_encode_many: every signal needs at least one channel and one sample")
+    if len(signals) == 1 and signals[0].dtype == torch.float32 and signals[0].stride(-1) == 1 and \
+            (signals[0].ndim == 1 or channels[0] == 1 or signals[0].stride(0) >= lens[0]):
+        x = signals[0].detach()  # the rows as they lie: no gather
+        stride = lens[0] if x.ndim == 1 or channels[0] == 1 else x.stride(0)
+    else:
+        stride = (max(lens) + 3) // 4 * 4
+        x = torch.empty((sum(channels), stride), dtype=torch.float32, device=device)
+        r = 0
+        for s, c in zip(signals, channels):
+            x[r:r + c, :s.shape[-1]] = s.detach().to(torch.float32).reshape(c, -1)
+            r += c
+    frames, sizes, pcm = _flac_encode_device(x, stride, channels, lens, bits_per_sample)
+    host = []
+    for key, t in (("frames", frames), ("sizes", sizes), ("pcm", pcm)):
+        h = _pinned_bytes(key, t.numel() * t.element_size())
+        h.copy_(t.view(torch.uint8), non_blocking=True)
+        host.append(h)
+    torch.cuda.current_stream(device).synchronize()
+    return _flac_assemble(host[0].numpy(), host[1].numpy().view(np.int32), host[2].numpy(), channels, lens, fs, bits_per_sample)
+
+
+def save_flac_many(paths, signals, fs, bits_per_sample=24):
+    """`save_flac(path, signal, fs, bits_per_sample)` for every pair, encoded by ONE `flac_encode_many` call."""
+    paths, signals = list(paths), list(signals)
+    if len(paths) != len(signals):
+        raise ValueError("save_flac_many: one path per signal")
+    for path, data in zip(paths, flac_encode_many(signals, fs, bits_per_sample)):
+        Path(path).write_bytes(data)

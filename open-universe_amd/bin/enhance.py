@@ -33,7 +33,7 @@ from pathlib import Path
 import torch
 
 from .. import inference_utils
-from ..audio import AUDIO_SUFFIXES, can_decode, channels, load, resample, resample_many, save
+from ..audio import AUDIO_SUFFIXES, can_decode, channels, load, resample, resample_many, save, save_flac_many
 
 
 def handle_help(argv):
@@ -94,6 +94,11 @@ def build_parser():
                              "dense windowed-sinc kernel.  library: the library's own kernel (ou_resample; an extension), the "
                              "same filter evaluated over the window's support only -- with --batch-size one launch per "
                              "window of files and per enhanced group instead of one chain of torch calls per file")
+    parser.add_argument("--encoder", choices=("numpy", "library"), default="numpy",
+                        help="What encodes a .flac output.  numpy (default): the host encoder, file by file.  library: the "
+                             "library's own kernel (ou_flac_encode_frames; an extension) -- the results stay on the device, "
+                             "every .flac output of a window, group or file is encoded in one call, and the files are byte "
+                             "for byte those of the default.  .wav outputs are written as before")
     parser.add_argument("--batch-size", type=int, default=1,
                         help="Enhance up to this many consecutive files of equal sample rate (any lengths) in one call; "
                              "every file gets the result it would get alone")
@@ -314,6 +319,21 @@ def main(argv=None, model=None):
         return args.output
 
     done = []
+
+    def write(outputs):
+        """outputs: list of (output_path, enhanced tensor on the device, fs), written in this order"""
+        if args.encoder == "library":
+            flac = [o for o in outputs if Path(o[0]).suffix.lower() == ".flac"]
+            for fs in dict.fromkeys(o[2] for o in flac):  # one encoder call per sample rate
+                grp = [o for o in flac if o[2] == fs]
+                save_flac_many([o[0] for o in grp], [o[1] for o in grp], fs)
+            outputs_host = [o for o in outputs if Path(o[0]).suffix.lower() != ".flac"]
+        else:
+            outputs_host = outputs
+        for output_path, enh, fs in outputs_host:
+            save(output_path, enh.cpu(), fs)
+        done.extend(o[0] for o in outputs)
+
     if args.batch_size <= 1 and args.in_flight > 1 and enhance_kwargs.get("target") is None \
             and getattr(model, "fork", None) is not None:
         # The serial loop below with K calls in flight: file k + K is read, resampled and enqueued while files k .. k + K - 1
@@ -324,8 +344,7 @@ def main(argv=None, model=None):
         def finish(item):
             lane, output_path, enh, fs = item
             pool.wait(lane)
-            save(output_path, enh.cpu(), fs)
-            done.append(output_path)
+            write([(output_path, enh, fs)])
 
         # one call per file, batch size = its channel count: files that differ there put calls of different sizes in flight,
         # and the lanes then have to agree on how their GRU clusters share the device (headers only are read here)
@@ -381,10 +400,7 @@ def main(argv=None, model=None):
                         rngs.append(file_rng)
                 enhs = model.enhance_long_many(sigs, rngs if rngs else rng, segment_s=args.segment_seconds, overlap_s=ov, **kw)
                 outs = [resample(e, model.fs, fs, backend=args.resampler) for e, fs in zip(enhs, rates)]
-            for (k, path), enh, fs in zip(grp, outs, rates):
-                output_path = out_path(path)
-                save(output_path, enh.cpu(), fs)
-                done.append(output_path)
+            write([(out_path(path), enh, fs) for (k, path), enh, fs in zip(grp, outs, rates)])
         return done
     if args.segment_seconds is not None and getattr(args, "segment_ensemble_files", 1) > 1:
         # --segment-ensemble-files N: up to N consecutive files of one sample rate per enhance_long_many_ensemble call.  Every file
@@ -409,10 +425,7 @@ def main(argv=None, model=None):
                                                         rngs=rngs if rngs else rng, segment_s=args.segment_seconds,
                                                         overlap_s=ov, **kw)
                 outs = [resample(e, model.fs, fs, backend=args.resampler) for e, (_, _, _, fs) in zip(enhs, grp)]
-            for (_, path, _, fs), enh in zip(grp, outs):
-                output_path = out_path(path)
-                save(output_path, enh.cpu(), fs)
-                done.append(output_path)
+            write([(out_path(path), enh, fs) for (_, path, _, fs), enh in zip(grp, outs)])
 
         grp = []
         for k, path in todo:
@@ -436,8 +449,7 @@ def main(argv=None, model=None):
                 audio = resample(audio, fs, model.fs, backend=args.resampler)
                 enh = enhance_file(model, audio, args, enhance_kwargs, file_noise(args, k) if counter else rng)
                 enh = resample(enh, model.fs, fs, backend=args.resampler)
-            save(output_path, enh.cpu(), fs)
-            done.append(output_path)
+            write([(output_path, enh, fs)])
         return done
 
     # --batch-size: files are read in processing order into a window (one sample rate, --batch-window files), sorted by length
@@ -493,10 +505,7 @@ def main(argv=None, model=None):
                 outs = resample_many(list(enhs), model.fs, fs, backend=args.resampler)
                 for (k, _, _, _), e in zip(grp, outs):
                     results[k] = e
-        for k, path, _, _ in window:  # written in processing order
-            output_path = out_path(path)
-            save(output_path, results[k].cpu(), fs)
-            done.append(output_path)
+        write([(out_path(path), results[k], fs) for k, path, _, _ in window])  # written in processing order
 
     window = []
     for k, path in todo:

@@ -6,12 +6,15 @@
 // (constant, verbatim, fixed predictors of order 0-4, LPC of order 1-32 with wasted bits), partitioned Rice residuals (4- and
 // 5-bit parameters, escaped partitions), the three stereo decorrelation modes, frame CRC-16.  Every checksum is verified: a
 // stream this decoder misreads is refused, not passed on; the MD5 of the decoded audio is checked by the caller (audio.py).
+// Behind it, the host side of the device encoder (ou_flac_encode.hip): buffer sizes, and the stage that turns the frames and
+// packed samples a kernel left into streams (CRC-16 per frame, MD5, STREAMINFO).
 #include <cstdint>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "../../include/ouniverse.h"
+#include "ou_flac_layout.h"
 
 namespace {
 
@@ -290,11 +293,162 @@ int decode(const uint8_t* d, size_t n, const Info& I, int32_t* out, int64_t cap,
   return OU_OK;
 }
 
+// ---- the host stage of the encoder (ou_flac_assemble): the kernel of ou_flac_encode.hip leaves frames without their CRC-16
+// and the packed samples; what is left is serial per file and touches every byte once
+
+const uint16_t* crc16_table() {
+  static const struct Table {
+    uint16_t t[256];
+    Table() {
+      for (int i = 0; i < 256; i++) {
+        uint16_t c = (uint16_t)(i << 8);
+        for (int b = 0; b < 8; b++) c = (uint16_t)((c & 0x8000) ? (c << 1) ^ 0x8005 : (c << 1));
+        t[i] = c;
+      }
+    }
+  } table;
+  return table.t;
+}
+uint16_t crc16_fast(const uint8_t* p, size_t n) {
+  const uint16_t* t = crc16_table();
+  uint16_t c = 0;
+  for (size_t i = 0; i < n; i++) c = (uint16_t)((c << 8) ^ t[(c >> 8) ^ p[i]]);
+  return c;
+}
+
+// MD5 (RFC 1321), restated from the RFC's description: STREAMINFO carries the MD5 of the unencoded samples
+struct Md5 {
+  uint32_t a = 0x67452301u, b = 0xefcdab89u, c = 0x98badcfeu, d = 0x10325476u;
+  static uint32_t rol(uint32_t v, int s) { return (v << s) | (v >> (32 - s)); }
+  void block(const uint8_t* p) {
+    static const uint32_t K[64] = {
+        0xd76aa478, 0xe8c7b756, 0x242070db, 0xc1bdceee, 0xf57c0faf, 0x4787c62a, 0xa8304613, 0xfd469501, 0x698098d8, 0x8b44f7af, 0xffff5bb1,
+        0x895cd7be, 0x6b901122, 0xfd987193, 0xa679438e, 0x49b40821, 0xf61e2562, 0xc040b340, 0x265e5a51, 0xe9b6c7aa, 0xd62f105d, 0x02441453,
+        0xd8a1e681, 0xe7d3fbc8, 0x21e1cde6, 0xc33707d6, 0xf4d50d87, 0x455a14ed, 0xa9e3e905, 0xfcefa3f8, 0x676f02d9, 0x8d2a4c8a, 0xfffa3942,
+        0x8771f681, 0x6d9d6122, 0xfde5380c, 0xa4beea44, 0x4bdecfa9, 0xf6bb4b60, 0xbebfbc70, 0x289b7ec6, 0xeaa127fa, 0xd4ef3085, 0x04881d05,
+        0xd9d4d039, 0xe6db99e5, 0x1fa27cf8, 0xc4ac5665, 0xf4292244, 0x432aff97, 0xab9423a7, 0xfc93a039, 0x655b59c3, 0x8f0ccc92, 0xffeff47d,
+        0x85845dd1, 0x6fa87e4f, 0xfe2ce6e0, 0xa3014314, 0x4e0811a1, 0xf7537e82, 0xbd3af235, 0x2ad7d2bb, 0xeb86d391};
+    static const int S[64] = {7, 12, 17, 22, 7, 12, 17, 22, 7, 12, 17, 22, 7, 12, 17, 22, 5, 9,  14, 20, 5, 9,  14, 20, 5, 9,  14, 20, 5, 9,  14, 20,
+                              4, 11, 16, 23, 4, 11, 16, 23, 4, 11, 16, 23, 4, 11, 16, 23, 6, 10, 15, 21, 6, 10, 15, 21, 6, 10, 15, 21, 6, 10, 15, 21};
+    uint32_t m[16];
+    for (int i = 0; i < 16; i++)
+      m[i] = (uint32_t)p[4 * i] | ((uint32_t)p[4 * i + 1] << 8) | ((uint32_t)p[4 * i + 2] << 16) | ((uint32_t)p[4 * i + 3] << 24);
+    uint32_t A = a, B = b, C = c, D = d;
+    for (int i = 0; i < 64; i++) {
+      uint32_t f;
+      int g;
+      if (i < 16) { f = (B & C) | (~B & D); g = i; }
+      else if (i < 32) { f = (D & B) | (~D & C); g = (5 * i + 1) & 15; }
+      else if (i < 48) { f = B ^ C ^ D; g = (3 * i + 5) & 15; }
+      else { f = C ^ (B | ~D); g = (7 * i) & 15; }
+      const uint32_t next = B + rol(A + f + K[i] + m[g], S[i]);
+      A = D; D = C; C = B; B = next;
+    }
+    a += A; b += B; c += C; d += D;
+  }
+  void digest(const uint8_t* p, uint64_t n, uint8_t* out) {
+    uint64_t i = 0;
+    for (; i + 64 <= n; i += 64) block(p + i);
+    uint8_t tail[128] = {0};
+    const size_t rest = (size_t)(n - i);
+    std::memcpy(tail, p + i, rest);
+    tail[rest] = 0x80;
+    const size_t total = rest < 56 ? 64 : 128;
+    const uint64_t nbits = n * 8;
+    for (int k = 0; k < 8; k++) tail[total - 8 + k] = (uint8_t)(nbits >> (8 * k));
+    block(tail);
+    if (total == 128) block(tail + 64);
+    const uint32_t v[4] = {a, b, c, d};
+    for (int k = 0; k < 16; k++) out[k] = (uint8_t)(v[k >> 2] >> (8 * (k & 3)));
+  }
+};
+
+constexpr size_t kStreamHead = 4 + 4 + 34;  // fLaC, the metadata block header, STREAMINFO
+
 }  // namespace
+
+namespace ou {
+int flac_fail(int code, const std::string& msg) {
+  g_flac_error = msg;
+  return code;
+}
+}  // namespace ou
 
 extern "C" {
 
 const char* ou_flac_last_error(void) { return g_flac_error.c_str(); }
+
+int ou_flac_encode_sizes(int32_t files, const int32_t* channels_host, const int64_t* len_host, int32_t bps, size_t* frames_bytes,
+                         int64_t* n_frames, size_t* pcm_bytes, int64_t* stream_capacity) {
+  const std::string m = ou::flac_shape_error(files, channels_host, len_host, bps);
+  if (!m.empty()) return ou::flac_fail(OU_EINVAL, "ou_flac_encode_sizes: " + m);
+  ou::FlacTotals tot;
+  if (!ou::flac_totals(files, channels_host, len_host, bps, tot))
+    return ou::flac_fail(OU_EINVAL, "ou_flac_encode_sizes: the buffers exceed 2^62 bytes");
+  if (frames_bytes) *frames_bytes = (size_t)tot.frames_bytes;
+  if (n_frames) *n_frames = tot.frames;
+  if (pcm_bytes) *pcm_bytes = (size_t)tot.pcm_bytes;
+  if (stream_capacity)
+    for (int f = 0; f < files; f++)
+      stream_capacity[f] = (int64_t)kStreamHead + ou::flac_blocks(len_host[f]) * ou::flac_frame_max(channels_host[f], bps);
+  return OU_OK;
+}
+
+int ou_flac_assemble(const uint8_t* frames_host, const int32_t* frame_bytes_host, const uint8_t* pcm_host, int32_t files,
+                     const int32_t* channels_host, const int64_t* len_host, int32_t fs, int32_t bps, uint8_t* out,
+                     size_t out_capacity, int64_t* offsets) {
+  const std::string who = "ou_flac_assemble: ";
+  const std::string m = ou::flac_shape_error(files, channels_host, len_host, bps);
+  if (!m.empty()) return ou::flac_fail(OU_EINVAL, who + m);
+  if (!(fs > 0 && fs < (1 << 20))) return ou::flac_fail(OU_EINVAL, who + "fs = " + std::to_string(fs) + ": 1 to 2^20 - 1");
+  if (!frames_host || !frame_bytes_host || !pcm_host || !out || !offsets) return ou::flac_fail(OU_EINVAL, who + "null argument");
+  ou::FlacTotals tot;
+  if (!ou::flac_totals(files, channels_host, len_host, bps, tot)) return ou::flac_fail(OU_EINVAL, who + "the buffers exceed 2^62 bytes");
+  const uint8_t* slot = frames_host;
+  const int32_t* size = frame_bytes_host;
+  const uint8_t* pcm = pcm_host;
+  size_t at = 0;
+  for (int f = 0; f < files; f++) {
+    const int ch = channels_host[f];
+    const long long n = len_host[f], blocks = ou::flac_blocks(n);
+    const long long slot_bytes = ou::flac_slot_bytes(ch, bps), frame_max = ou::flac_frame_max(ch, bps);
+    offsets[f] = (int64_t)at;
+    if (out_capacity - at < kStreamHead) return ou::flac_fail(OU_ESHAPE, who + "out_capacity is too small for file " + std::to_string(f));
+    uint8_t* head = out + at;
+    at += kStreamHead;
+    long long smin = 0, smax = 0;
+    for (long long b = 0; b < blocks; b++, slot += slot_bytes, size++) {
+      const long long sz = *size;
+      if (sz < 3 || sz > frame_max)
+        return ou::flac_fail(OU_EINVAL, who + "frame " + std::to_string(b) + " of file " + std::to_string(f) + " has " +
+                                            std::to_string(sz) + " bytes: not what ou_flac_encode_frames wrote");
+      if (out_capacity - at < (size_t)sz) return ou::flac_fail(OU_ESHAPE, who + "out_capacity is too small for file " + std::to_string(f));
+      std::memcpy(out + at, slot, (size_t)sz - 2);
+      const uint16_t c = crc16_fast(out + at, (size_t)sz - 2);
+      out[at + sz - 2] = (uint8_t)(c >> 8);
+      out[at + sz - 1] = (uint8_t)c;
+      at += (size_t)sz;
+      smin = b == 0 || sz < smin ? sz : smin;
+      smax = sz > smax ? sz : smax;
+    }
+    std::memcpy(head, "fLaC", 4);
+    head[4] = 0x80;  // last metadata block, type 0
+    head[5] = 0; head[6] = 0; head[7] = 34;
+    uint8_t* s = head + 8;
+    s[0] = s[2] = (uint8_t)(ou::kFlacBlock >> 8);
+    s[1] = s[3] = (uint8_t)(ou::kFlacBlock & 0xFF);
+    for (int k = 0; k < 3; k++) {
+      s[4 + k] = (uint8_t)(smin >> (8 * (2 - k)));
+      s[7 + k] = (uint8_t)(smax >> (8 * (2 - k)));
+    }
+    const uint64_t v = ((uint64_t)fs << 44) | ((uint64_t)(ch - 1) << 41) | ((uint64_t)(bps - 1) << 36) | (uint64_t)n;
+    for (int k = 0; k < 8; k++) s[10 + k] = (uint8_t)(v >> (8 * (7 - k)));
+    Md5().digest(pcm, (uint64_t)ch * (uint64_t)n * (uint64_t)((bps + 7) / 8), s + 18);
+    pcm += ou::flac_pcm_bytes(ch, n, bps);
+  }
+  offsets[files] = (int64_t)at;
+  return OU_OK;
+}
 
 int ou_flac_info(const uint8_t* data, size_t bytes, int32_t* sample_rate, int32_t* channels, int32_t* bits_per_sample,
                  int64_t* total_samples, uint8_t* md5) {
