@@ -808,6 +808,31 @@ int ou_flac_encode_frames(const float* x, int64_t row_stride, int32_t files, con
 int ou_flac_assemble(const uint8_t* frames_host, const int32_t* frame_bytes_host, const uint8_t* pcm_host, int32_t files,
                      const int32_t* channels_host, const int64_t* len_host, int32_t fs, int32_t bps, uint8_t* out,
                      size_t out_capacity, int64_t* offsets);
+/* Compression levels.  Level 0 is the stream above, bit for bit, from the same kernel.  Level 1: per channel
+ * and block the cheapest of a constant subframe and the fixed predictors of order 0 .. 4, priced exactly, then the best Rice
+ * partition order 0 .. 6 (2^po divides the block, a partition keeps 16 samples); verbatim where that is not shorter.  Level 2
+ * adds one LPC candidate of order 8 (precision 14, shift 0 .. 15; Welch window, autocorrelation and Levinson-Durbin in double,
+ * in one fixed order: two runs are bit-identical).  Levels 0 and 1 are byte for byte audio.flac_encode(level=...); a level-2
+ * stream is the one audio.flac_encode writes when it is handed the coefficients the device chose (lpc_override).  Blocks, frame
+ * headers, slots, frame_bytes, pcm and ou_flac_assemble are those of ou_flac_encode_frames, and so is the call's contract.
+ *   ou_flac_encode_choices_bytes: pure host.  Bytes of the choices buffer: one record per subframe in stream order (file, block,
+ *                                 channel).
+ *   choices (may be NULL)       : device, 4-byte aligned.  A record is OU_FLAC_CHOICE_WORDS int32:
+ *                                 [0] kind (OU_FLAC_KIND_*)  [1] predictor order  [2] partition order  [3] coefficient precision
+ *                                 [4] shift  [5] bits of the subframe  [6 ..] OU_FLAC_CHOICE_COEFS coefficients; what a kind does
+ *                                 not use is 0.  Level 0 writes fixed / order 2 / partition order 0, or verbatim.
+ * OU_EINVAL also for a level outside 0 .. 2 and a misaligned choices buffer; OU_ESHAPE for one that is too small. */
+#define OU_FLAC_CHOICE_WORDS 18
+#define OU_FLAC_CHOICE_COEFS 12
+#define OU_FLAC_KIND_CONSTANT 0
+#define OU_FLAC_KIND_VERBATIM 1
+#define OU_FLAC_KIND_FIXED 2
+#define OU_FLAC_KIND_LPC 3
+int ou_flac_encode_choices_bytes(int32_t files, const int32_t* channels_host, const int64_t* len_host, size_t* bytes);
+int ou_flac_encode_frames_level(const float* x, int64_t row_stride, int32_t files, const int32_t* channels_host,
+                                const int64_t* len_host, int32_t bps, int32_t level, void* frames, size_t frames_bytes,
+                                int32_t* frame_bytes, void* pcm, size_t pcm_bytes, int32_t* choices, size_t choices_bytes,
+                                ou_stream_t stream);
 
 /* Measurement / tuning entry points (ou_profile_*, ou_bench_conv) are declared in ouniverse_tuning.h. */
 

@@ -215,6 +215,9 @@ def load():
                                        POINTER(c_int64)]),
         "ou_flac_encode_frames": (i32, [vp, c_int64, i32, POINTER(i32), POINTER(c_int64), i32, vp, sz, vp, vp, sz, vp]),
         "ou_flac_assemble": (i32, [vp, vp, vp, i32, POINTER(i32), POINTER(c_int64), i32, i32, vp, sz, POINTER(c_int64)]),
+        "ou_flac_encode_choices_bytes": (i32, [i32, POINTER(i32), POINTER(c_int64), POINTER(sz)]),
+        "ou_flac_encode_frames_level": (i32, [vp, c_int64, i32, POINTER(i32), POINTER(c_int64), i32, i32, vp, sz, vp, vp, sz, vp, sz,
+                                              vp]),
         "ou_profile_enable": (i32, [vp, i32]),
         "ou_variant_family": (c_char_p, [i32]),
         "ou_bench_conv": (i32, [vp, c_char_p, i32, i32, i32, i32, i32, i32, vp, sz, vp, POINTER(c_float), POINTER(i32)]),
@@ -249,6 +252,7 @@ EXPORTED_SYMBOLS = [
     "ou_transform_frames", "ou_transform_forward", "ou_transform_inverse",
     "ou_flac_last_error", "ou_flac_info", "ou_flac_decode",
     "ou_flac_encode_sizes", "ou_flac_encode_frames", "ou_flac_assemble",
+    "ou_flac_encode_choices_bytes", "ou_flac_encode_frames_level",
 ]
 TUNING_SYMBOLS = ["ou_profile_enable", "ou_profile_read", "ou_profile_read_ticks", "ou_bench_conv", "ou_set_stamp_layer",
                   "ou_variant_family",

@@ -181,14 +181,15 @@ def channels(path):
             f.seek(size + (size & 1), 1)
 
 
-def save(path, audio, fs):
-    """audio: float tensor (channels, T).  Written as 32-bit float WAV (what torchaudio.save does for float32)."""
+def save(path, audio, fs, flac_level=0):
+    """audio: float tensor (channels, T).  Written as 32-bit float WAV (what torchaudio.save does for float32).  flac_level > 0:
+    a .flac file comes from `save_flac` at that compression level, with or without torchaudio."""
     ta = _torchaudio()
-    if ta is not None:
+    if ta is not None and not (flac_level and Path(path).suffix.lower() == ".flac"):
         return ta.save(str(path), audio, fs)
     path = Path(path)
     if path.suffix.lower() == ".flac":
-        return save_flac(path, audio, fs)
+        return save_flac(path, audio, fs, level=flac_level)
     if path.suffix.lower() != ".wav":
         raise RuntimeError(f"{path}: only .wav and .flac can be encoded without torchaudio")
     x = audio.detach().to(torch.float32).cpu().numpy()
@@ -435,12 +436,217 @@ def _subframe_bits(x, bps):
     return np.concatenate([head, body])
 
 
-def flac_encode(samples, fs, bps=24, block=4096):
-    """samples: int array (channels, T), values within bps bits -> the bytes of a FLAC stream."""
+# ---- compression levels 1 and 2: per subframe the cheapest of constant / fixed 0-4 / (level 2) one LPC
+# candidate of order 8, priced exactly in integers, then the best Rice partition order 0..6 for the winner; verbatim where that
+# is not shorter.  Level 0 is `_subframe_bits` above.  A choice record is FLAC_CHOICE_WORDS int32: kind, order, partition order,
+# precision, shift, subframe bits, then FLAC_CHOICE_COEFS coefficients (OU_FLAC_CHOICE_* of include/ouniverse.h).
+FLAC_CHOICE_WORDS = 18
+FLAC_CHOICE_COEFS = 12
+FLAC_CONSTANT, FLAC_VERBATIM, FLAC_FIXED, FLAC_LPC = 0, 1, 2, 3
+_FIXED = ((), (1,), (2, -1), (3, -3, 1), (4, -6, 4, -1))
+_LPC_ORDER, _LPC_PRECISION, _LPC_MIN_BLOCK, _RICE_MAX_QUOTIENT = 8, 14, 64, 4096
+
+
+def _rice_k(total, cnt):
+    """the largest k <= 14 with (2^k - 1) cnt <= total"""
+    k = 0
+    while k < 14 and ((2 << k) - 1) * cnt <= total:
+        k += 1
+    return k
+
+
+def _lpc_analysis(x):
+    """one channel of one block (int64, n >= 64) -> (coefs, shift) or None.  Welch window, autocorrelation lags 0..8 and
+    Levinson-Durbin in float64; the sums run in the order of the kernel (16 consecutive samples, a 64-wide butterfly, four
+    partial sums), so the two usually agree to the last bit, which nothing depends on."""
+    n = len(x)
+    i = np.arange(4096, dtype=np.float64)
+    z = (2.0 * i - float(n - 1)) / float(n + 1)
+    xw = np.zeros(4096 + _LPC_ORDER, np.float64)
+    xw[_LPC_ORDER:_LPC_ORDER + n] = x.astype(np.float64) * (1.0 - z * z)[:n]
+    lane = np.arange(256)
+    r = []
+    for lag in range(_LPC_ORDER + 1):
+        prod = (xw[_LPC_ORDER:] * xw[_LPC_ORDER - lag:4096 + _LPC_ORDER - lag]).reshape(256, 16)
+        acc = np.zeros(256, np.float64)
+        for j in range(16):
+            acc = acc + prod[:, j]
+        for o in (32, 16, 8, 4, 2, 1):
+            acc = acc + acc[lane ^ o]
+        t = 0.0
+        for w in range(4):
+            t = t + float(acc[64 * w])
+        r.append(t)
+    if not (math.isfinite(r[0]) and r[0] > 0.0):
+        return None
+    a, err = [0.0] * _LPC_ORDER, r[0]
+    with np.errstate(all="ignore"):
+        for m in range(_LPC_ORDER):
+            acc = np.float64(r[m + 1])
+            for j in range(m):
+                acc = acc - np.float64(a[j]) * np.float64(r[m - j])
+            kk = acc / np.float64(err)
+            prev = list(a)
+            for j in range(m):
+                a[j] = float(np.float64(prev[j]) - kk * np.float64(prev[m - 1 - j]))
+            a[m] = float(kk)
+            err = float(np.float64(err) * (np.float64(1.0) - kk * kk))
+            if not (math.isfinite(err) and err > 0.0):
+                return None
+    if not all(math.isfinite(v) for v in a):
+        return None
+    cmax = max(abs(v) for v in a)
+    if cmax == 0.0:
+        return None
+    shift = min(15, max(0, (_LPC_PRECISION - 1) - math.frexp(cmax)[1]))
+    return [int(np.rint(np.float64(v) * np.float64(2.0 ** shift))) for v in a], shift  # (a value of +-2^13 is refused later)
+
+
+def _fold(r):
+    return np.where(r >= 0, 2 * r, -2 * r - 1)
+
+
+def _subframe_level(x, bps, level, override=None):
+    """one channel of one block (int64) -> (bit array, choice record) at compression level 1 or 2"""
+    n = len(x)
+    two = 1 << bps
+    rec = [0] * FLAC_CHOICE_WORDS
+    # candidates in tie-break order: (kind, order, coefs, shift, residuals)
+    cands = []
+    for p in range(5):
+        if n > p:
+            r = x[p:].copy()
+            for j, c in enumerate(_FIXED[p]):
+                r = r - c * x[p - 1 - j:n - 1 - j]
+            cands.append((FLAC_FIXED, p, (), 0, r))
+    if level >= 2:
+        lpc = None
+        if override is not None:
+            lpc = ([int(v) for v in override[0]], int(override[1]))
+        elif n >= _LPC_MIN_BLOCK:
+            lpc = _lpc_analysis(x)
+        if lpc is not None:
+            coefs, shift = lpc
+            p = len(coefs)
+            half = 1 << (_LPC_PRECISION - 1)
+            if 1 <= p <= FLAC_CHOICE_COEFS and n > p and 0 <= shift <= 15 and all(-half <= c < half for c in coefs):
+                pred = np.zeros(n - p, np.int64)
+                for j, c in enumerate(coefs):
+                    pred = pred + c * x[p - 1 - j:n - 1 - j]
+                r = x[p:] - (pred >> shift)
+                if int(np.abs(r).max(initial=0)) < (1 << 31):
+                    cands.append((FLAC_LPC, p, tuple(coefs), shift, r))
+    # stage 1 and stage 2, once for the candidates of level 1 and once for the lpc candidate, which wins only when it is
+    # strictly shorter after its own partition search (so a level-2 subframe is never longer than the level-1 one)
+    best, po, ks = None, 0, None  # best: (bits, candidate, u, head bits)
+    for group in ([c for c in cands if c[0] == FLAC_FIXED], [c for c in cands if c[0] == FLAC_LPC]):
+        gbest, gpo, gks = None, 0, None
+        if group and group[0][0] == FLAC_FIXED and np.all(x == x[0]):
+            gbest = (8 + bps, None, None, 0)
+        for cand in group:
+            kind, p, coefs, shift, r = cand
+            u = _fold(r)
+            cnt = n - p
+            k = _rice_k(int(u.sum()), cnt)
+            if int((u >> k).max(initial=0)) > _RICE_MAX_QUOTIENT:
+                continue
+            head = 8 + p * bps + (4 + 5 + p * _LPC_PRECISION if kind == FLAC_LPC else 0) + 2 + 4
+            bits = head + 4 + cnt * (k + 1) + int((u >> k).sum())
+            if gbest is None or bits < gbest[0]:
+                gbest, gpo, gks = (bits, cand, u, head), 0, [k]
+        if gbest is not None and gbest[1] is not None:
+            bits, cand, u, head = gbest
+            p = cand[1]
+            for cpo in range(1, 7):
+                if n % (1 << cpo) or (n >> cpo) < 16:
+                    break
+                size = n >> cpo
+                total, kk = 4 << cpo, []
+                for j in range(1 << cpo):
+                    seg = u[max(j * size - p, 0):(j + 1) * size - p]
+                    k = _rice_k(int(seg.sum()), len(seg))
+                    if int((seg >> k).max(initial=0)) > _RICE_MAX_QUOTIENT:
+                        break
+                    kk.append(k)
+                    total += len(seg) * (k + 1) + int((seg >> k).sum())
+                if len(kk) == 1 << cpo and head + total < bits:
+                    bits, gpo, gks = head + total, cpo, kk
+            gbest = (bits, cand, u, head)
+        if gbest is not None and (best is None or gbest[0] < best[0]):
+            best, po, ks = gbest, gpo, gks
+    wrapped = (x.astype(np.int64) % two).astype(np.uint64)
+    if best is None or best[0] >= 8 + n * bps:
+        rec[0], rec[5] = FLAC_VERBATIM, 8 + n * bps
+        return np.concatenate([np.array([0, 0, 0, 0, 0, 0, 1, 0], np.uint8), _bits_of(wrapped, bps).ravel()]), rec
+    bits, cand, u, head = best
+    if cand is None:
+        rec[0], rec[5] = FLAC_CONSTANT, bits
+        return np.concatenate([np.zeros(8, np.uint8), _bits_of(wrapped[:1], bps).ravel()]), rec
+    kind, p, coefs, shift, _ = cand
+    rec[:6] = [kind, p, po, _LPC_PRECISION if kind == FLAC_LPC else 0, shift, bits]
+    rec[6:6 + len(coefs)] = coefs
+    parts = [_bits_of([(8 + p if kind == FLAC_FIXED else 31 + p) << 1], 8).ravel(), _bits_of(wrapped[:p], bps).ravel()]
+    if kind == FLAC_LPC:
+        parts += [_bits_of([_LPC_PRECISION - 1], 4).ravel(), _bits_of([shift], 5).ravel(),
+                  _bits_of([c % (1 << _LPC_PRECISION) for c in coefs], _LPC_PRECISION).ravel()]
+    parts.append(_bits_of([po], 6).ravel())  # coding method 0, the partition order
+    size = n >> po
+    idx = np.arange(p, n)
+    part = idx // size
+    kv = np.asarray(ks, np.int64)[part]
+    pre = np.where((idx % size == 0) | (idx == p), 4, 0)
+    pre[0] = 4
+    lens = pre + (u >> kv) + 1 + kv
+    ends = np.cumsum(lens)
+    body = np.zeros(int(ends[-1]), np.uint8)
+    body[ends - kv - 1] = 1
+    for k in set(ks):
+        if k:
+            sel = kv == k
+            at = (ends[sel] - k)[:, None] + np.arange(k)[None, :]
+            body[at.ravel()] = _bits_of((u[sel] & ((1 << k) - 1)).astype(np.uint64), k).ravel()
+    first = pre == 4
+    at = (ends[first] - lens[first])[:, None] + np.arange(4)[None, :]
+    body[at.ravel()] = _bits_of(kv[first].astype(np.uint64), 4).ravel()
+    out = np.concatenate(parts + [body])
+    assert len(out) == bits, (len(out), bits)
+    return out, rec
+
+
+def _level0_record(bits, n, bps):
+    """the choice record of a level-0 subframe, read off its first byte"""
+    rec = [0] * FLAC_CHOICE_WORDS
+    rec[0], rec[5] = (FLAC_FIXED if bits[3] else FLAC_VERBATIM), len(bits)
+    if bits[3]:
+        rec[1] = 2
+    return rec
+
+
+def flac_encode(samples, fs, bps=24, block=4096, level=0, lpc_override=None, return_choices=False):
+    """samples: int array (channels, T), values within bps bits -> the bytes of a FLAC stream.
+    level: 0 (fixed order 2, one Rice parameter: the stream of earlier versions), 1 (constant, fixed orders 0-4, partitioned
+    Rice) or 2 (level 1 plus an LPC candidate of order 8).  lpc_override: {(frame number, channel): (coefs, shift)} replaces
+    the level-2 analysis of those subframes.  return_choices: also return one record per subframe in stream order, an int32
+    array (subframes, FLAC_CHOICE_WORDS)."""
     x = np.asarray(samples, dtype=np.int64)
     ch, n = x.shape
+    if level not in (0, 1, 2):
+        raise ValueError("flac_encode: level is 0, 1 or 2")
+    if level and block != 4096:
+        raise ValueError("flac_encode: levels 1 and 2 use blocks of 4096")
     if not (1 <= ch <= 8) or bps not in (8, 16, 24) or not (0 < fs < (1 << 20)):
         raise ValueError("flac_encode: 1-8 channels, 8 / 16 / 24 bits per sample")
+    records = []
+
+    def sub(c, blk, fno):
+        if level == 0:
+            bits = _subframe_bits(blk, bps)
+            records.append(_level0_record(bits, len(blk), bps))
+            return bits
+        bits, rec = _subframe_level(blk, bps, level, (lpc_override or {}).get((fno, c)))
+        records.append(rec)
+        return bits
+
     nb = (bps + 7) // 8
     inter = np.ascontiguousarray(x.T).astype("<i4").view(np.uint8).reshape(-1, 4)[:, :nb]
     md5 = hashlib.md5(np.ascontiguousarray(inter).tobytes()).digest()
@@ -455,7 +661,7 @@ def flac_encode(samples, fs, bps=24, block=4096):
         hdr += _utf8_number(fno)
         hdr += (bs - 1).to_bytes(2, "big")
         hdr.append(_crc8(hdr))
-        bits = np.concatenate([_subframe_bits(blk[c], bps) for c in range(ch)])
+        bits = np.concatenate([sub(c, blk[c], fno) for c in range(ch)])
         body = np.packbits(bits).tobytes()
         fr = bytes(hdr) + body
         fr += _crc16(fr).to_bytes(2, "big")
@@ -467,17 +673,20 @@ def flac_encode(samples, fs, bps=24, block=4096):
     si += (min(sizes) if sizes else 0).to_bytes(3, "big") + (max(sizes) if sizes else 0).to_bytes(3, "big")
     v = (int(fs) << 44) | ((ch - 1) << 41) | ((bps - 1) << 36) | n
     si += v.to_bytes(8, "big") + md5
-    return b"fLaC" + bytes([0x80]) + len(si).to_bytes(3, "big") + bytes(si) + b"".join(frames)
+    out = b"fLaC" + bytes([0x80]) + len(si).to_bytes(3, "big") + bytes(si) + b"".join(frames)
+    if return_choices:
+        return out, np.array(records, dtype=np.int32).reshape(-1, FLAC_CHOICE_WORDS)
+    return out
 
 
-def save_flac(path, audio, fs, bits_per_sample=24):
+def save_flac(path, audio, fs, bits_per_sample=24, level=0):
     """audio: float tensor (channels, T) in [-1, 1] -> FLAC with `bits_per_sample` bits (round to nearest, clipped)."""
     x = audio.detach().to(torch.float64).cpu().numpy()
     if x.ndim == 1:
         x = x[None]
     full = float(1 << (bits_per_sample - 1))
     q = np.clip(np.rint(x * full), -full, full - 1).astype(np.int64)
-    Path(path).write_bytes(flac_encode(q, int(fs), bits_per_sample))
+    Path(path).write_bytes(flac_encode(q, int(fs), bits_per_sample, level=level))
 
 
 # ---- the same stream from the device (ou_flac_encode_frames, csrc/ou_flac_encode.hip): quantisation, residuals, Rice codes and
@@ -496,9 +705,9 @@ def _pinned_bytes(key, nbytes):
     return buf[:nbytes]
 
 
-def _flac_encode_device(x, stride, channels, lens, bits_per_sample):
-    """ONE ou_flac_encode_frames call over the rows of x (file f: channels[f] consecutive rows of lens[f] samples) ->
-    (frames, frame_bytes, pcm) uint8 / int32 / uint8 tensors on the device.  No synchronisation."""
+def _flac_encode_device(x, stride, channels, lens, bits_per_sample, level=0, want_choices=False):
+    """ONE ou_flac_encode_frames_level call over the rows of x (file f: channels[f] consecutive rows of lens[f] samples) ->
+    (frames, frame_bytes, pcm, choices or None) uint8 / int32 / uint8 / int32 tensors on the device.  No synchronisation."""
     from . import _lib
 
     L = _lib.load()
@@ -511,15 +720,22 @@ def _flac_encode_device(x, stride, channels, lens, bits_per_sample):
     frames = torch.empty(fb.value, dtype=torch.uint8, device=x.device)
     sizes = torch.empty(nf.value, dtype=torch.int32, device=x.device)
     pcm = torch.empty(pb.value, dtype=torch.uint8, device=x.device)
+    choices, cb = None, ctypes.c_size_t(0)
+    if want_choices:
+        if L.ou_flac_encode_choices_bytes(files, ch, ln, ctypes.byref(cb)) != 0:
+            raise ValueError((L.ou_flac_last_error() or b"ou_flac_encode_choices_bytes failed").decode())
+        choices = torch.empty(cb.value // 4, dtype=torch.int32, device=x.device)
     with torch.cuda.device(x.device):
-        rc = L.ou_flac_encode_frames(ctypes.c_void_p(x.data_ptr()), int(stride), files, ch, ln, int(bits_per_sample),
-                                     ctypes.c_void_p(frames.data_ptr()), ctypes.c_size_t(fb.value),
-                                     ctypes.c_void_p(sizes.data_ptr()), ctypes.c_void_p(pcm.data_ptr()), ctypes.c_size_t(pb.value),
-                                     ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
+        rc = L.ou_flac_encode_frames_level(ctypes.c_void_p(x.data_ptr()), int(stride), files, ch, ln, int(bits_per_sample),
+                                           int(level), ctypes.c_void_p(frames.data_ptr()), ctypes.c_size_t(fb.value),
+                                           ctypes.c_void_p(sizes.data_ptr()), ctypes.c_void_p(pcm.data_ptr()),
+                                           ctypes.c_size_t(pb.value),
+                                           ctypes.c_void_p(choices.data_ptr()) if want_choices else None, cb,
+                                           ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
     if rc != 0:
-        msg = (L.ou_flac_last_error() or b"ou_flac_encode_frames failed").decode()
+        msg = (L.ou_flac_last_error() or b"ou_flac_encode_frames_level failed").decode()
         raise (RuntimeError if rc == _lib.OU_EHIP else ValueError)(msg)
-    return frames, sizes, pcm
+    return frames, sizes, pcm, choices
 
 
 def _flac_assemble(frames, sizes, pcm, channels, lens, fs, bits_per_sample):
@@ -543,14 +759,18 @@ def _flac_assemble(frames, sizes, pcm, channels, lens, fs, bits_per_sample):
     return [out[off[f]:off[f + 1]].tobytes() for f in range(files)]
 
 
-def flac_encode_many(signals, fs, bits_per_sample=24):
+def flac_encode_many(signals, fs, bits_per_sample=24, level=0, return_choices=False):
     """signals: list of (T_i,) or (C_i, T_i) float tensors on one HIP device, in [-1, 1] -> list of `bytes`, the FLAC streams
     `save_flac` would write (round to nearest even, clipped; 16 or 24 bits).  One device call over all channel rows of all
     signals, one device-to-host copy per buffer (into pinned memory), one ou_flac_assemble.  There is no CPU path and no
-    fallback: ValueError for a CPU tensor."""
+    fallback: ValueError for a CPU tensor.  level: 0, 1 or 2 as in `flac_encode` (levels 0 and 1 give its bytes; a level-2 stream
+    is the one it writes with the device's coefficients as lpc_override).  return_choices: -> (streams, list of int32 arrays
+    (subframes of the file, FLAC_CHOICE_WORDS))."""
     signals = list(signals)
+    if level not in (0, 1, 2):
+        raise ValueError("flac_encode_many: level is 0, 1 or 2")
     if not signals:
-        return []
+        return ([], []) if return_choices else []
     for s in signals:
         if s.device.type != "cuda":
             raise ValueError("flac_encode_many runs on a HIP device only: move the tensors there or use save_flac")
@@ -574,20 +794,25 @@ def flac_encode_many(signals, fs, bits_per_sample=24):
         for s, c in zip(signals, channels):
             x[r:r + c, :s.shape[-1]] = s.detach().to(torch.float32).reshape(c, -1)
             r += c
-    frames, sizes, pcm = _flac_encode_device(x, stride, channels, lens, bits_per_sample)
+    frames, sizes, pcm, choices = _flac_encode_device(x, stride, channels, lens, bits_per_sample, level, return_choices)
     host = []
     for key, t in (("frames", frames), ("sizes", sizes), ("pcm", pcm)):
         h = _pinned_bytes(key, t.numel() * t.element_size())
         h.copy_(t.view(torch.uint8), non_blocking=True)
         host.append(h)
     torch.cuda.current_stream(device).synchronize()
-    return _flac_assemble(host[0].numpy(), host[1].numpy().view(np.int32), host[2].numpy(), channels, lens, fs, bits_per_sample)
+    streams = _flac_assemble(host[0].numpy(), host[1].numpy().view(np.int32), host[2].numpy(), channels, lens, fs, bits_per_sample)
+    if not return_choices:
+        return streams
+    rec = choices.cpu().numpy().reshape(-1, FLAC_CHOICE_WORDS)
+    cuts = np.cumsum([0] + [c * ((n + 4095) // 4096) for c, n in zip(channels, lens)])
+    return streams, [rec[cuts[i]:cuts[i + 1]].copy() for i in range(len(channels))]
 
 
-def save_flac_many(paths, signals, fs, bits_per_sample=24):
-    """`save_flac(path, signal, fs, bits_per_sample)` for every pair, encoded by ONE `flac_encode_many` call."""
+def save_flac_many(paths, signals, fs, bits_per_sample=24, level=0):
+    """`save_flac(path, signal, fs, bits_per_sample, level)` for every pair, encoded by ONE `flac_encode_many` call."""
     paths, signals = list(paths), list(signals)
     if len(paths) != len(signals):
         raise ValueError("save_flac_many: one path per signal")
-    for path, data in zip(paths, flac_encode_many(signals, fs, bits_per_sample)):
+    for path, data in zip(paths, flac_encode_many(signals, fs, bits_per_sample, level)):
         Path(path).write_bytes(data)

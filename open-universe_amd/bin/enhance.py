@@ -99,6 +99,12 @@ def build_parser():
                              "library's own kernel (ou_flac_encode_frames; an extension) -- the results stay on the device, "
                              "every .flac output of a window, group or file is encoded in one call, and the files are byte "
                              "for byte those of the default.  .wav outputs are written as before")
+    parser.add_argument("--flac-level", type=int, choices=(0, 1, 2), default=0,
+                        help="Compression level of every .flac output, with either --encoder; .wav outputs ignore it.  0 "
+                             "(default): fixed predictor of order 2, one Rice parameter per block.  1: constant subframes, "
+                             "fixed orders 0-4, partitioned Rice.  2: level 1 plus an LPC candidate of order 8.  At levels 0 "
+                             "and 1 the two encoders write identical files; at level 2 they may differ in the LPC subframes "
+                             "(the last bits of the analysis), and both decode to the same samples")
     parser.add_argument("--batch-size", type=int, default=1,
                         help="Enhance up to this many consecutive files of equal sample rate (any lengths) in one call; "
                              "every file gets the result it would get alone")
@@ -326,12 +332,12 @@ def main(argv=None, model=None):
             flac = [o for o in outputs if Path(o[0]).suffix.lower() == ".flac"]
             for fs in dict.fromkeys(o[2] for o in flac):  # one encoder call per sample rate
                 grp = [o for o in flac if o[2] == fs]
-                save_flac_many([o[0] for o in grp], [o[1] for o in grp], fs)
+                save_flac_many([o[0] for o in grp], [o[1] for o in grp], fs, level=args.flac_level)
             outputs_host = [o for o in outputs if Path(o[0]).suffix.lower() != ".flac"]
         else:
             outputs_host = outputs
         for output_path, enh, fs in outputs_host:
-            save(output_path, enh.cpu(), fs)
+            save(output_path, enh.cpu(), fs, flac_level=args.flac_level)
         done.extend(o[0] for o in outputs)
 
     if args.batch_size <= 1 and args.in_flight > 1 and enhance_kwargs.get("target") is None \
