@@ -834,6 +834,92 @@ int ou_flac_encode_frames_level(const float* x, int64_t row_stride, int32_t file
                                 int32_t* frame_bytes, void* pcm, size_t pcm_bytes, int32_t* choices, size_t choices_bytes,
                                 ou_stream_t stream);
 
+/* ---- streaming enhance: push chunks, get finished audio (extension; the reference, and every entry point above, needs the whole
+ * recording before it starts) ------------------------------------------------------------------------------------------------
+ * A stream has C rows that advance in lockstep, a window length S (`segment` rounded down to a multiple of tot_ds, S >= 2 tot_ds),
+ * an overlap V (`overlap` rounded down to a multiple of tot_ds, 0 <= V <= S / 2) and the stride S - V.  Nothing in its definition
+ * needs a statistic of the whole row.  After T samples per row have been pushed and the stream is flushed:
+ *
+ *   Padded length.  T_pad = ceil(T / tot_ds) * tot_ds: zeros are appended at the END only (a stream does not know its length when
+ *     it starts, so there is no front padding and a multiple of tot_ds gets no extra block).
+ *   Windows (ou_stream_plan, pure host function).  T_pad <= S: one window [0, T_pad).  Else window k is [k (S - V), k (S - V) + S)
+ *     for every k for which that fits into T_pad, and if the last of them ends before T_pad one more window follows at
+ *     [T_pad - S, T_pad).  The crossfade between windows k and k + 1 covers [s_k + S - V, s_k + S); core k runs from the middle of
+ *     one crossfade to the middle of the next, and the cores tile [0, T_pad).
+ *     Relation to ou_segment_plan: for T_pad >= tot_ds, ou_stream_plan(tot_ds, T, segment, overlap) returns the windows, cores,
+ *     overlap_used and T_pad of ou_segment_plan(tot_ds, T_pad - 1, segment, overlap) -- the segmented plan of any row whose padded
+ *     length (which there always grows, T_raw + tot_ds - T_raw % tot_ds) is this T_pad.  The stream accepts less: S >= 2 tot_ds
+ *     where the segmented calls take S >= tot_ds.
+ *   Per-window result.  Window k is, by definition, ou_enhance(B = C, T_raw = the window's length) on the window's samples alone --
+ *     the reference's `enhance` of that excerpt as if it were a file: its own pad, normalisation and mel scale, keep_rms too with
+ *     OU_ENH_KEEP_RMS -- with the stream's n_steps, epsilon, sigma table, warm_start and OU_ENH_USE_AUX_SIGNAL, always with
+ *     OU_ENH_NO_PEAK_GUARD and OU_ENH_SERIAL, on counter-based noise: window k of row c draws from the noise stream ids[c] + k of
+ *     `seed`, at the positions of its own ou_enhance call (the Python layer spaces the ids of the rows by 2^32).  A noise tensor
+ *     makes no sense for a call whose length is unknown: there is none.
+ *   NO PEAK GUARD.  A whole-row maximum is not causal, so a stream never rescales; OU_STREAM_CLIP clamps the emitted samples to
+ *     [-1, 1] instead (off by default: the samples are then what the windows gave).
+ *   Stitching.  Outside the crossfade regions an output sample is the sample of the one window that covers it; where the shifted
+ *     last window overlaps earlier windows beyond its crossfade region, the earlier window's samples are already emitted and stay.
+ *     Inside [s_k + S - V, s_k + S), at offset i: (1 - a(i)) y_k + a(i) y_{k+1} with a(i) = 0.5 - 0.5 cos(pi (i + 0.5) / V), the
+ *     fp32 weight of ou_enhance_segments' stitch (one shared device function); the expression is evaluated in fp32 with its
+ *     rounding errors carried along, so the stored sample is its real value rounded once.
+ *   Emission (ou_stream_emitted, pure host function of how much was pushed).  Once window k has run everything below s_k + S - V
+ *     is final and is emitted: after P pushed samples that is 0 for P < S, else floor((P - S) / (S - V)) (S - V) + S - V.  The last
+ *     V samples of the newest window are carried on the device (raw).  A flush runs the windows that are left, with zeros behind
+ *     T -- one that would emit nothing below T is not run --, and emits up to T.
+ * So the result of a stream differs from ou_enhance_segments of the same row (whose pad split, mean, gain, mix_rms, mel scale and
+ * peak guard are those of the whole row); the worst-case delay between a sample's arrival and its emission is S samples.
+ *
+ * Workspace (ou_stream_workspace_bytes): the walk's workspace for (C, S + tot_ds), a ring of the last S input samples per row, one
+ * assembled window, one window result, the carry (C, V) and the two (C, S + tot_ds) planes of the noise.  It depends on C, S and V,
+ * never on the stream's length.  The caller owns it; the stream prepares the walk's part itself (ou_workspace_init, on the stream
+ * of the first call that runs a window) and needs nothing in it initialised.
+ *
+ * Calls.  Every push and flush enqueues on the caller's stream only: no host synchronisation, no allocation on the device, no side
+ * streams, no graphs; n_out comes from the plan alone and is known before anything is launched.  While a call runs the handle's
+ * noise source is the stream's; when the call returns it is what it was before.  A handle is not re-entrant, and neither are the
+ * streams on it; several streams may take turns on one handle, each on a workspace of its own.
+ *   ou_stream_push : chunk (C, n) device, rows chunk_stride apart, n >= 0 samples per row (n may span several windows; NULL for
+ *                    n = 0); out (C, out_capacity) device, rows out_stride apart, receives *n_out = ou_stream_emitted(P + n) -
+ *                    ou_stream_emitted(P) samples per row, nothing behind them is written.  OU_EINVAL, before anything is
+ *                    launched, when out_capacity is below that.
+ *   ou_stream_flush: the same output arguments; *n_out = T - ou_stream_emitted(T).  Afterwards the stream is at position 0 with
+ *                    window counter 0 again: a second identical run gives identical bytes.
+ * Refused on the host with a message, before any HIP call: C < 1, S < 2 tot_ds, V > S / 2, n_steps / warm_start that ou_enhance
+ * refuses, a window too long for one pass of ou_enhance, warm_start / OU_ENH_USE_AUX_SIGNAL on a model without the snake
+ * decoupling layer (OU_ENOTIMPL, the message of ou_enhance), enhance flags other than OU_ENH_KEEP_RMS | OU_ENH_USE_AUX_SIGNAL, a
+ * workspace that is too small (OU_ENOMEM) or not 256-byte aligned, and a push, flush or destroy on a pointer that is not a live
+ * stream (destroyed, or never returned by ou_stream_create).  After a call that failed with OU_EHIP the stream refuses every call
+ * but ou_stream_destroy. */
+#define OU_STREAM_CLIP 1u
+typedef struct ou_stream_session ou_stream_session;
+typedef struct ou_stream_spec {
+  int32_t C;               /* rows */
+  int32_t segment;         /* samples; S = segment rounded down to a multiple of tot_ds */
+  int32_t overlap;         /* samples; V likewise */
+  int32_t n_steps;
+  double epsilon;
+  const float* sigma_host; /* n_steps floats or NULL, as ou_enhance (copied by ou_stream_create) */
+  int32_t warm_start;      /* -1, or as ou_enhance */
+  uint32_t enh_flags;      /* OU_ENH_KEEP_RMS | OU_ENH_USE_AUX_SIGNAL */
+  uint32_t stream_flags;   /* OU_STREAM_CLIP */
+  uint64_t seed;           /* key of the counter-based noise */
+  const uint64_t* ids;     /* HOST, C noise stream ids (copied); window k of row c draws from ids[c] + k */
+} ou_stream_spec;
+/* `capacity`: entries of the four arrays (all four may be NULL: then only n_windows / overlap_used / T_pad are returned).  T >= 0;
+ * T = 0 has no window. */
+int ou_stream_plan(int32_t tot_ds, int64_t T, int32_t segment, int32_t overlap, int32_t capacity, int64_t* starts,
+                   int32_t* lengths, int64_t* core_begin, int64_t* core_end, int32_t* n_windows, int32_t* overlap_used,
+                   int64_t* T_pad);
+/* Samples per row that are emitted once P have been pushed (before a flush); -1 for a bad argument (message in ou_last_error). */
+int64_t ou_stream_emitted(int32_t tot_ds, int64_t P, int32_t segment, int32_t overlap);
+int ou_stream_workspace_bytes(const ou_handle* h, int32_t C, int32_t segment, int32_t overlap, size_t* nbytes);
+int ou_stream_create(ou_handle* h, const ou_stream_spec* spec, void* ws, size_t ws_bytes, ou_stream_session** out);
+void ou_stream_destroy(ou_stream_session* s);
+int ou_stream_push(ou_stream_session* s, const float* chunk, int64_t chunk_stride, int64_t n, float* out, int64_t out_stride,
+                   int64_t out_capacity, int64_t* n_out, ou_stream_t stream);
+int ou_stream_flush(ou_stream_session* s, float* out, int64_t out_stride, int64_t out_capacity, int64_t* n_out, ou_stream_t stream);
+
 /* Measurement / tuning entry points (ou_profile_*, ou_bench_conv) are declared in ouniverse_tuning.h. */
 
 #ifdef __cplusplus

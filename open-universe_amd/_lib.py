@@ -87,6 +87,26 @@ class NoiseSpec(Structure):
     ]
 
 
+class StreamSpec(Structure):
+    """ou_stream_spec: what a streaming enhance session is created with (include/ouniverse.h, "streaming enhance")."""
+    _fields_ = [
+        ("C", c_int32),
+        ("segment", c_int32),
+        ("overlap", c_int32),
+        ("n_steps", c_int32),
+        ("epsilon", c_double),
+        ("sigma_host", POINTER(c_float)),
+        ("warm_start", c_int32),
+        ("enh_flags", c_uint32),
+        ("stream_flags", c_uint32),
+        ("seed", c_uint64),
+        ("ids", POINTER(c_uint64)),
+    ]
+
+
+OU_STREAM_CLIP = 1
+
+
 class MetricsSpec(Structure):
     """ou_metrics_spec: one STFT resolution of the scores (include/ouniverse.h, "scoring")."""
     _fields_ = [("n_fft", c_int32), ("hop", c_int32), ("eps", c_float), ("flags", c_int32)]
@@ -162,6 +182,14 @@ def load():
                                                            POINTER(i32), POINTER(i32)]),
         "ou_enhance_segments_var_ensemble": (i32, [vp, vp, vp, vp, vp, i32, c_int64, POINTER(c_int64), i32, i32, i32, i32, i32,
                                                    i32, c_double, POINTER(c_float), i32, c_uint32, vp, sz, vp]),
+        "ou_stream_plan": (i32, [i32, c_int64, i32, i32, i32, POINTER(c_int64), POINTER(i32), POINTER(c_int64),
+                                 POINTER(c_int64), POINTER(i32), POINTER(i32), POINTER(c_int64)]),
+        "ou_stream_emitted": (c_int64, [i32, c_int64, i32, i32]),
+        "ou_stream_workspace_bytes": (i32, [vp, i32, i32, i32, POINTER(sz)]),
+        "ou_stream_create": (i32, [vp, POINTER(StreamSpec), vp, sz, POINTER(vp)]),
+        "ou_stream_destroy": (None, [vp]),
+        "ou_stream_push": (i32, [vp, vp, c_int64, c_int64, vp, c_int64, c_int64, POINTER(c_int64), vp]),
+        "ou_stream_flush": (i32, [vp, vp, c_int64, c_int64, POINTER(c_int64), vp]),
         "ou_set_noise_source": (i32, [vp, POINTER(NoiseSpec)]),
         "ou_noise_scratch_bytes": (i32, [vp, i32, i32, POINTER(sz)]),
         "ou_noise_fill": (i32, [vp, c_int64, c_int64, i32, POINTER(c_uint64), POINTER(c_int64), POINTER(c_int64), c_uint64,
@@ -242,6 +270,8 @@ EXPORTED_SYMBOLS = [
     "ou_segments_ensemble_workspace_bytes", "ou_enhance_segments_ensemble",
     "ou_segments_var_ensemble_workspace_bytes", "ou_enhance_segments_var_ensemble",
     "ou_set_noise_source", "ou_noise_scratch_bytes", "ou_noise_fill",
+    "ou_stream_plan", "ou_stream_emitted", "ou_stream_workspace_bytes", "ou_stream_create", "ou_stream_destroy",
+    "ou_stream_push", "ou_stream_flush",
     "ou_resample_plan", "ou_resample_table", "ou_resample_length", "ou_resample_tile", "ou_resample",
     "ou_snake_act", "ou_snake_tile", "ou_set_normalization",
     "ou_metrics_frames", "ou_metrics_scratch_bytes", "ou_lsd", "ou_spectral_mae", "ou_si_sdr",
@@ -303,6 +333,34 @@ def segment_plan(tot_ds, T_raw, segment, overlap):
     return {"starts": np.ctypeslib.as_array(starts).copy(), "lengths": np.ctypeslib.as_array(lens).copy(),
             "core_begin": np.ctypeslib.as_array(ce0).copy(), "core_end": np.ctypeslib.as_array(ce1).copy(),
             "overlap": ov.value, "T_pad": tp.value}
+
+
+def stream_plan(tot_ds, T, segment, overlap):
+    """The library's window plan of a stream flushed after T samples (ou_stream_plan): the dict of `segment_plan`.  Pure host
+    code."""
+    import numpy as np
+
+    L = load()
+    n, ov, tp = c_int32(), c_int32(), c_int64()
+    check(L.ou_stream_plan(int(tot_ds), int(T), int(segment), int(overlap), 0, None, None, None, None, byref(n), byref(ov),
+                           byref(tp)))
+    k = n.value
+    starts, ce0, ce1 = (c_int64 * max(k, 1))(), (c_int64 * max(k, 1))(), (c_int64 * max(k, 1))()
+    lens = (c_int32 * max(k, 1))()
+    if k:
+        check(L.ou_stream_plan(int(tot_ds), int(T), int(segment), int(overlap), k, starts, lens, ce0, ce1, byref(n), byref(ov),
+                               byref(tp)))
+    return {"starts": np.ctypeslib.as_array(starts)[:k].copy(), "lengths": np.ctypeslib.as_array(lens)[:k].copy(),
+            "core_begin": np.ctypeslib.as_array(ce0)[:k].copy(), "core_end": np.ctypeslib.as_array(ce1)[:k].copy(),
+            "overlap": ov.value, "T_pad": tp.value}
+
+
+def stream_emitted(tot_ds, P, segment, overlap):
+    """Samples per row a stream has emitted once P are pushed, before a flush (ou_stream_emitted).  Pure host code."""
+    n = load().ou_stream_emitted(int(tot_ds), int(P), int(segment), int(overlap))
+    if n < 0:
+        check(OU_EINVAL)
+    return n
 
 
 def segment_groups(tot_ds, t_raw, segment, overlap, max_batch):

@@ -138,6 +138,13 @@ def build_parser():
                              "list in one call (Universe.enhance_long_many_ensemble: the windows of all files share the window "
                              "groups, all E members of a window in one group; every file gets the noise and, to round-off, the "
                              "result of the one-file-per-call loop).  Default 1: one file per call.  Not with --segment-files > 1")
+    parser.add_argument("--stream", type=float, default=None, metavar="CHUNK_SECONDS",
+                        help="With --segment-seconds: read every file in chunks of this many seconds and push them through a "
+                             "streaming session (Universe.stream: every window of --segment-seconds is enhanced as an excerpt "
+                             "of its own, crossfaded over --segment-overlap, on counter-based noise of --seed + file index; no "
+                             "whole-file normalisation and no peak guard, so the result differs from the file-at-once forms).  "
+                             "Not with --batch-size, --in-flight, --ensemble, --segment-ensemble, --segment-ensemble-files or "
+                             "--segment-files > 1.  Off by default")
     parser.add_argument("--pad-batch", action="store_true",
                         help="With --batch-size: files of different lengths are zero-padded to the longest WITHOUT a mask "
                              "(the reference's batch semantics: the padding changes every result)")
@@ -213,6 +220,41 @@ def check_segment_args(args, enhance_kwargs):
             raise ValueError(f"{form} cannot be combined with --warm_start")
         if enhance_kwargs.get("use_aux_signal"):
             raise ValueError(f"{form} cannot be combined with --use_aux_signal")
+
+
+def check_stream_args(args, enhance_kwargs):
+    """--stream: refused with what it cannot be combined with."""
+    if getattr(args, "stream", None) is None:
+        return
+    if args.segment_seconds is None:
+        raise ValueError("--stream needs --segment-seconds (the window of the stream)")
+    if not args.stream > 0:
+        raise ValueError("--stream must be a positive number of seconds")
+    if args.batch_size > 1 or args.in_flight > 1:
+        raise ValueError("--stream cannot be combined with --batch-size or --in-flight (a stream is one file at a time)")
+    if enhance_kwargs.get("ensemble") is not None:
+        raise ValueError("--stream cannot be combined with --ensemble")
+    if getattr(args, "segment_ensemble", None) is not None or getattr(args, "segment_ensemble_files", 1) != 1:
+        raise ValueError("--stream cannot be combined with --segment-ensemble or --segment-ensemble-files")
+    if getattr(args, "segment_files", 1) > 1:
+        raise ValueError("--stream cannot be combined with --segment-files > 1")
+    if enhance_kwargs.get("target") is not None:
+        raise ValueError("--stream cannot be combined with --target")
+
+
+def stream_file(model, audio, args, enhance_kwargs, k):
+    """One file through a streaming session in chunks of --stream seconds: what comes out of the pushes and the flush, joined."""
+    ov = 1.0 if args.segment_overlap is None else args.segment_overlap
+    kw = {key: v for key, v in enhance_kwargs.items()
+          if key in ("n_steps", "epsilon", "keep_rms", "warm_start", "use_aux_signal") and v is not None}
+    rows = audio if audio.ndim == 2 else audio[None, :]
+    n = max(1, int(round(args.stream * model.fs)))
+    with model.stream(channels=rows.shape[0], segment_s=args.segment_seconds, overlap_s=ov,
+                      seed=(args.seed + k) & ((1 << 63) - 1), **kw) as st:
+        parts = [st.push(rows[:, i:i + n]) for i in range(0, rows.shape[1], n)]
+        parts.append(st.flush(flat=False))
+    enh = torch.cat(parts, dim=1)
+    return enh if audio.ndim == 2 else enh[0]
 
 
 def check_noise_args(args, enhance_kwargs):
@@ -296,6 +338,7 @@ def main(argv=None, model=None):
         if group.title == "enhance":
             enhance_kwargs = {a.dest: getattr(args, a.dest, None) for a in group._group_actions}
 
+    check_stream_args(args, enhance_kwargs)
     check_segment_args(args, enhance_kwargs)
     check_noise_args(args, enhance_kwargs)
     if args.pad_batch and enhance_kwargs.get("ensemble") is not None:
@@ -340,6 +383,15 @@ def main(argv=None, model=None):
             save(output_path, enh.cpu(), fs, flac_level=args.flac_level)
         done.extend(o[0] for o in outputs)
 
+    if args.stream is not None:
+        # --stream: one streaming session per file, fed in chunks; what the pushes and the flush return is the file's output
+        for k, path in todo:
+            audio, fs = load(path)
+            with torch.no_grad():
+                x = resample(audio.to(device), fs, model.fs, backend=args.resampler)
+                enh = resample(stream_file(model, x, args, enhance_kwargs, k), model.fs, fs, backend=args.resampler)
+            write([(out_path(path), enh, fs)])
+        return done
     if args.batch_size <= 1 and args.in_flight > 1 and enhance_kwargs.get("target") is None \
             and getattr(model, "fork", None) is not None:
         # The serial loop below with K calls in flight: file k + K is read, resampled and enqueued while files k .. k + K - 1

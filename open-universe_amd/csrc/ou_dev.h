@@ -35,6 +35,16 @@ __device__ __forceinline__ void dma_b128(__amdgpu_buffer_rsrc_t r, float* lds, i
   __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void*)lds, 16, voff, soff, 0, 0);
 }
 
+// The complementary raised-cosine crossfade of the window stitches (ou_segment.hip, ou_stream.hip): sample i of an overlap of
+// `overlap` samples gives the later window the weight a(i) = 0.5 - 0.5 cos(pi (i + 0.5) / overlap) and the earlier one 1 - a(i).
+__device__ __forceinline__ float crossfade_weight(long long i, long long overlap) {
+  return 0.5f - 0.5f * cosf(3.14159265358979f * ((float)i + 0.5f) / (float)overlap);
+}
+__device__ __forceinline__ float crossfade(long long i, long long overlap, float earlier, float later) {
+  const float a = crossfade_weight(i, overlap);
+  return (1.f - a) * earlier + a * later;
+}
+
 // s_waitcnt vmcnt(n) for a wave-uniform run-time n (the instruction takes an immediate): vmcnt = bits [3:0] | [15:14],
 // expcnt / lgkmcnt left at their maxima.
 #define OU_VMCNT_CASE(n) case n: __builtin_amdgcn_s_waitcnt(((n) & 0xF) | (((n) >> 4) << 14) | 0x0F70); break;

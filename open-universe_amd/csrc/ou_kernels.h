@@ -320,6 +320,24 @@ hipError_t launch_seg_upload_rows(SegRow* rows, const SegRowBlock& blk, int n, i
 hipError_t launch_seg_upload_lens(int* lens, const SegEntryBlock& blk, int n, int j0, int Bw, int E, const LevelSpec& lv,
                                   hipStream_t st);
 
+// Streaming enhance (ou_stream.hip; ou_stream_* in include/ouniverse.h).  All C rows of the stream advance in lockstep, so one
+// set of numbers, passed by value, describes every row of a launch.
+//   gather: the window [s, s + L) of the stream -> win (C, L), from the ring (C, S) of the last S samples of the P0 pushed before
+//           this call and the call's chunk (C, n; rows chunk_stride apart); 0 from T_valid on.  write_ring: the ring then takes
+//           the chunk in (L = 0: nothing else happens).  L <= S, s >= P0 - S, T_valid <= P0 + n.
+//   emit:   res (C, L)[i0 .. i0 + n_emit) -> out (rows out_stride apart), the first xf <= V samples crossfaded with carry (C, V),
+//           clamped to [-1, 1] with `clip`; V_store = V: carry <- the last V samples of res (0: the carry stays).
+struct StreamGather {
+  long long S, s, L, P0, n, chunk_stride, T_valid;
+  int write_ring;
+};
+struct StreamEmit {
+  long long L, V, i0, n_emit, xf, V_store, out_stride;
+  int clip;
+};
+hipError_t launch_stream_gather(const float* chunk, float* ring, float* win, const StreamGather& g, int C, hipStream_t st);
+hipError_t launch_stream_emit(const float* res, float* carry, float* out, const StreamEmit& e, int C, hipStream_t st);
+
 // Counter-based sampler noise (ou_noise.hip; the function z(seed, stream, draw, t) is defined in include/ouniverse.h).
 // One launch fills up to 64 rows: out[j][col] = col < len[j] ? z(seed, stream[j], draw, t0[j] + col) : 0 for col < cols.
 // The per-row values travel as kernel arguments (capturable, no host memory involved).

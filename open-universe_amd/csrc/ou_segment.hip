@@ -8,6 +8,7 @@
 // come from a device table, a group's entries (row, window, length) from the kernel arguments, and every row reduces over the
 // block partition of the call on that row alone.  Grids are sized by the longest row; a block beyond the row's own share returns
 // before it touches memory (with rows alike there is none).
+#include "ou_dev.h"
 #include "ou_internal.h"
 
 namespace ou {
@@ -60,10 +61,7 @@ struct SegWindow {
   }
   // the sample at position u of the padded row: v from window k, crossfaded with window k - 1 (yp) where they overlap
   __device__ float value(long long u, float v, const float* yp) const {
-    if (u < e_prev) {
-      const float a = 0.5f - 0.5f * cosf(3.14159265358979f * ((float)(u - w0) + 0.5f) / (float)overlap);
-      v = (1.f - a) * yp[u - s_prev] + a * v;
-    }
+    if (u < e_prev) v = crossfade(u - w0, overlap, yp[u - s_prev], v);
     return v;
   }
 };

@@ -1236,6 +1236,18 @@ class Universe:
         self._adopt_workspace(cur[1], B, L)
         return cur[1]
 
+    # ---- streaming enhance --------------------------------------------------------------------
+    def stream(self, channels=1, segment_s: float = SEGMENT_S, overlap_s: float = OVERLAP_S, seed=0, n_steps=None, epsilon=None,
+               keep_rms=False, warm_start=None, use_aux_signal=False, clip=False):
+        """An `EnhanceStream`: push chunks of a live signal of `channels` rows, get finished audio back (ou_stream_*).  Every
+        window of `segment_s` seconds is the `enhance` call on that excerpt alone, with no peak guard, on counter-based noise of
+        key `seed` (row c: stream ids from c << 32 on, one per window); consecutive windows are crossfaded over `overlap_s`.
+        A stream is NOT `enhance_long` in pieces: it has no whole-row normalisation, mel scale or peak guard, so its result
+        differs from that call's; `clip=True` clamps the output to [-1, 1]."""
+        n_steps, epsilon, segment, overlap = self._begin(n_steps, epsilon, segment_s, overlap_s)
+        return EnhanceStream(self, int(channels), segment, overlap, int(seed), n_steps, epsilon, bool(keep_rms), warm_start,
+                             bool(use_aux_signal), bool(clip))
+
     # ---- hipGraph replay of the hot path ------------------------------------------------------------------------
     def graphed_enhance(self, batch, length, n_steps=None, epsilon=None, keep_rms=False, serial=True):
         """-> callable `run(mix, rng=None)` equivalent to `enhance(mix, n_steps, epsilon, rng=rng, keep_rms=keep_rms)`
@@ -1360,6 +1372,110 @@ class Universe:
         x = x + sigma[:, -1, None, None] ** 2 * score_wrapper(x, sigma[:, -1])
         x = x[..., pad // 2: -(pad - pad // 2)]
         return torch.nn.functional.pad(x, (0, mix.shape[-1] - x.shape[-1]))
+
+
+class EnhanceStream:
+    """A streaming enhance session on a model (`Universe.stream`): `.push(chunk)` returns the samples that became final with
+    that chunk (possibly none), `.flush()` the rest, after which the stream starts over at position 0.  `latency_samples` = the
+    window length S: the worst-case delay between a sample's arrival and its emission.  Usable as a context manager; the
+    session owns its workspace (its size depends on the channels and the window, not on how long the stream runs).  The model's
+    handle is not re-entrant: a stream and other calls on the model take turns."""
+
+    ROW_ID_SPACING = 1 << 32  # noise stream id of row c: c * 2^32, + k for window k
+
+    def __init__(self, model, channels, segment, overlap, seed, n_steps, epsilon, keep_rms, warm_start, use_aux_signal, clip):
+        self._model = model
+        self._session = c_void_p()
+        L = self._L = model._L
+        self.channels = channels
+        self._segment, self._overlap = segment, overlap
+        need = c_size_t()
+        _lib.check(L.ou_stream_workspace_bytes(model._handle, channels, segment, overlap, byref(need)), model._handle)
+        # (zeroed: `flush` reads the status word in front of it, also of a stream that never ran a window)
+        self._ws = torch.zeros(need.value, dtype=torch.uint8, device=model.device)
+        sigma = model._sigma_table(n_steps)
+        spec = _lib.StreamSpec()
+        spec.C, spec.segment, spec.overlap = channels, segment, overlap
+        spec.n_steps, spec.epsilon = int(n_steps), float(epsilon)
+        spec.sigma_host = ctypes.cast(sigma.data_ptr(), ctypes.POINTER(c_float))
+        spec.warm_start = -1 if warm_start is None else int(warm_start)
+        spec.enh_flags = (_lib.OU_ENH_KEEP_RMS if keep_rms else 0) | (_lib.OU_ENH_USE_AUX_SIGNAL if use_aux_signal else 0)
+        spec.stream_flags = _lib.OU_STREAM_CLIP if clip else 0
+        spec.seed = seed
+        spec.ids = (ctypes.c_uint64 * channels)(*[c * self.ROW_ID_SPACING for c in range(channels)])
+        _lib.check(L.ou_stream_create(model._handle, byref(spec), c_void_p(self._ws.data_ptr()), c_size_t(need.value),
+                                      byref(self._session)), model._handle)
+        tot = model.tot_ds
+        self.latency_samples = segment - segment % tot
+        self._pushed = 0
+
+    def _out(self, n, flat):
+        return torch.empty((self.channels, n) if not flat else (n,), dtype=torch.float32, device=self._model.device)
+
+    def _live(self):
+        if not self._session.value:
+            raise ValueError("this EnhanceStream is closed")
+
+    @torch.no_grad()
+    def push(self, chunk):
+        """chunk: (n,) for one channel or (channels, n), on the model's device -> the (.., n_out) samples that are final now."""
+        self._live()
+        m = self._model
+        flat = chunk.ndim == 1
+        x = as_rows(chunk, "EnhanceStream.push", m._prep, "n")
+        if x.shape[0] != self.channels:
+            raise ValueError(f"EnhanceStream.push: {x.shape[0]} rows for a stream of {self.channels} channels")
+        n = x.shape[1]
+        tot = m.tot_ds
+        cap = (_lib.stream_emitted(tot, self._pushed + n, self._segment, self._overlap)
+               - _lib.stream_emitted(tot, self._pushed, self._segment, self._overlap))
+        out = self._out(cap, False)
+        n_out = ctypes.c_int64()
+        with torch.cuda.device(m.device):
+            _lib.check(self._L.ou_stream_push(self._session, c_void_p(x.data_ptr()) if n else None, x.stride(0), n,
+                                              c_void_p(out.data_ptr()) if cap else None, max(out.stride(0), cap), cap,
+                                              byref(n_out), m._stream()), m._handle)
+        m._cond_key = None  # (the handle ran other windows since any ou_condition)
+        self._pushed += n
+        assert n_out.value == cap
+        return out[0] if flat else out
+
+    @torch.no_grad()
+    def flush(self, flat=None):
+        """The rest of the stream, (channels, n_out) -- `(n_out,)` for one channel unless flat=False --; the stream then starts
+        over.  Waits for the device and raises if a kernel of the stream's calls flagged a timeout."""
+        self._live()
+        m = self._model
+        cap = self._pushed - _lib.stream_emitted(m.tot_ds, self._pushed, self._segment, self._overlap)
+        out = self._out(cap, False)
+        n_out = ctypes.c_int64()
+        with torch.cuda.device(m.device):
+            _lib.check(self._L.ou_stream_flush(self._session, c_void_p(out.data_ptr()) if cap else None, max(out.stride(0), cap),
+                                               cap, byref(n_out), m._stream()), m._handle)
+            m._cond_key = None
+            self._pushed = 0
+            torch.cuda.current_stream(m.device).synchronize()
+            _lib.check(self._L.ou_check_device_status(m._handle, c_void_p(self._ws.data_ptr())), m._handle)
+        assert n_out.value == cap
+        return out[0] if (self.channels == 1 if flat is None else flat) else out
+
+    def close(self):
+        if self._session.value:
+            self._L.ou_stream_destroy(self._session)
+            self._session = c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class UniverseGAN(Universe):
